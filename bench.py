@@ -25,6 +25,13 @@ aggregate one (36 B x cells / wall against N x 8 TB/s, the fill kernels' device 
 the oracle on rank 0's host.  Rank 0 also times the same walk alone on its GPU (value_one_gpu_same_workload) so that a
 speed-up can be read off one line.  Without torchrun, `--gpus N` runs the in-process work queue over N devices of this
 process instead (one feeder thread per device, pagan_msa_align with n_devices = N).
+
+A plain run does only what `value` needs: inputs, one untimed walk, the resident batches, the warm-up and the timed steps,
+then the line (metric, value, unit, ms_per_step, dtype, config, ...).  Everything else described above -- the second walk
+(e2e_*), value_resident_batch, roofline, kernels_ms, parity_self_check, cpu_baseline, and at N > 1 the one-GPU walk, `also`
+and the sharded walk's check against it -- runs only with --full.  --dump-outputs DIR writes what the last timed step
+computed as DIR/<name>.npy (float32 where that is exact, float64 otherwise; at most 64 MB in all, larger arrays as a fixed,
+seeded sample of their rows with <name>_rows.npy beside them).
 """
 import argparse
 import json
@@ -83,14 +90,70 @@ def make_inputs(workload):
                                  seed=20240807 + cfg, alphabet=alphabet)
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6         # (under 64 MB, headers of the .npy files included)
+
+
+def alignment_outputs(results):
+    """What a caller of the hot path receives for each node (abi.Result: score, status, end corner, alignment columns,
+    used sites, cells), as arrays: the per-node fields one row per node, the variable-length ones concatenated in node
+    order with their lengths beside them."""
+    import numpy as np
+    return {
+        "score": np.array([r.score for r in results], np.float64),
+        "status": np.array([r.status for r in results], np.float64),
+        "end": np.array([r.end for r in results], np.float64).reshape(len(results), 5),
+        "cells": np.array([r.cells for r in results], np.float64),
+        "n_cols": np.array([len(r.cols) for r in results], np.float64),
+        "cols": np.concatenate([r.cols for r in results]).reshape(-1, 3),
+        "n_left_used": np.array([len(r.left_used) for r in results], np.float64),
+        "left_used": np.concatenate([r.left_used for r in results]),
+        "n_right_used": np.array([len(r.right_used) for r in results], np.float64),
+        "right_used": np.concatenate([r.right_used for r in results]),
+    }
+
+
+def write_outputs(outdir, arrays):
+    """--dump-outputs: DIR/<name>.npy for every array, float32 where every value is exact in it, float64 otherwise.  Past
+    DUMP_LIMIT_BYTES in all, the arrays of more than 2^20 rows keep the same number of rows each, a sample drawn with a fixed
+    seed per name (sorted), and <name>_rows.npy holds the indices of the rows kept."""
+    import zlib
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a32 = a.astype(np.float32)
+        conv[name] = a32 if a.dtype != np.float64 and np.array_equal(a32, a) else a.astype(np.float64)
+    big = [n for n, a in conv.items() if a.ndim > 0 and a.shape[0] > (1 << 20)]
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES and big:
+        rest = sum(a.nbytes for n, a in conv.items() if n not in big)
+        per_row = sum(conv[n].nbytes // conv[n].shape[0] + 8 for n in big)     # (+ the float64 index of the row)
+        keep = max(1, (DUMP_LIMIT_BYTES - rest) // per_row)
+        for n in big:
+            if conv[n].shape[0] > keep:
+                rows = np.sort(np.random.default_rng(zlib.crc32(n.encode())).choice(conv[n].shape[0], keep, replace=False))
+                conv[n] = conv[n][rows]
+                conv[n + "_rows"] = rows.astype(np.float64)
+    if sum(a.nbytes for a in conv.values()) > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write more than %d bytes" % DUMP_LIMIT_BYTES)
+    for name, a in conv.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (rank 0, N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also every figure and check beyond the headline: second walk, side-by-side batch, roofline, parity, "
+                         "cpu_baseline, and at N > 1 the one-GPU walk and cfg5 under `also`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (--full; rank 0, N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="N > 1 under torchrun: nccl (= RCCL, the default) or gloo (rehearsal on a box with fewer GPUs than ranks)")
     ap.add_argument("--fb-one-by-one", action="store_true",
@@ -194,7 +257,10 @@ def bench_forward_backward(args, device):
     fwd_ms = float(np.mean([a[0] for a in acc])); bwd_ms = float(np.mean([a[1] for a in acc]))
     cells, totals = acc[-1][2], acc[-1][3]
     dev_s = float(np.mean([a[4] for a in acc]))       # wall-clock of a pass: every pair's two sweeps side by side (one workgroup each), uploads included
-    ok = all(abs(f - b) <= 1e-7 * max(1.0, abs(f)) for f, b in totals)       # the reference's own check (VA:351-355): forward total = backward total
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"log_forward": np.array([f for f, _b in totals], np.float64),
+                                          "log_backward": np.array([b for _f, b in totals], np.float64),
+                                          "cells": np.array(acc[-1][5], np.float64)})
     out = {
         "metric": "DP cells/sec of the forward + backward sweeps (--full-probability), %s node pairs" % workload,
         "value": cells / dev_s, "unit": "cells/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -205,13 +271,19 @@ def bench_forward_backward(args, device):
                    "hip_hw_queues_in_environment_at_start": os.environ.get("PAGAN_BENCH_HW_QUEUES_AT_START"),
                    "call": "one pagan_fb_run per pair from a thread pool" if args.fb_one_by_one else "one pagan_fb_run_batch for all pairs (the wide pairs' forward sweeps in one launch, their backward sweeps in another)",
                    "note": "value = cells / wall-clock of a pass with all node pairs in flight at once (wide pairs: block-scheduled sweeps of one-wave workgroups, each pair its share of the device's workgroup slots); the per-kernel ms are the launches' own durations (one by one: their sums); wall per pass incl. allocation and upload: %.1f ms" % (1e3 * elapsed / args.steps)},
+    }
+    if not args.full:
+        print(json.dumps(out))
+        return
+    ok = all(abs(f - b) <= 1e-7 * max(1.0, abs(f)) for f, b in totals)       # the reference's own check (VA:351-355): forward total = backward total
+    out.update({
         "roofline": {"bound": "hbm", "achieved": 48 * cells / dev_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": 48 * cells / dev_s / 1e9 / HBM_PEAK_GBS, "kernel": "pg_fb_forward + pg_fb_backward",
                      "algorithmic_bytes_per_cell": 48, "traffic": None,
                      "kernels": [{"kernel": "pg_fb_forward", "ms_per_step": fwd_ms, "achieved": 24 * cells / (fwd_ms * 1e-3) / 1e9},
                                  {"kernel": "pg_fb_backward", "ms_per_step": bwd_ms, "achieved": 24 * cells / (bwd_ms * 1e-3) / 1e9}]},
         "parity_self_check": bool(ok),
-    }
+    })
     # HBM bytes per pass from the committed PMC passes of this same command (tools/profile_fb_band.sh), when they describe this run
     try:
         prof = json.load(open(os.path.join(ROOT, PMC_FB_PROFILE)))
@@ -257,19 +329,20 @@ def bench_one_gpu(args, device):
     L.pagan_dp_select_device(device)
     names, seqs, newick = make_inputs(workload)
 
-    # ---- untimed setup: whole progressive alignment on the GPU (twice: the first walk also pays the process's
-    # one-off costs -- code object load, first hipMalloc, staging buffers) ----
+    # ---- untimed setup: whole progressive alignment on the GPU (--full: twice, the first walk also pays the process's
+    # one-off costs -- code object load, first hipMalloc, staging buffers -- and the second one's wall-clock is e2e_wall_s) ----
     data_type = 3 if alphabet == "CODON" else 0               # 0: guessed from the residues, as the reference does
-    t0 = time.time()
-    msa = host.Msa(names, seqs, newick, use_anchors=anchors, first_device=device, n_devices=1, data_type=data_type)
-    msa.align()
-    e2e_wall_cold = time.time() - t0
-    del msa
-    t0 = time.time()
-    msa = host.Msa(names, seqs, newick, use_anchors=anchors, first_device=device, n_devices=1, data_type=data_type)
-    msa.align()
-    e2e_wall = time.time() - t0
-    tm = msa.timing()
+
+    def walk():
+        t0 = time.time()
+        m = host.Msa(names, seqs, newick, use_anchors=anchors, first_device=device, n_devices=1, data_type=data_type)
+        m.align()
+        return m, time.time() - t0
+
+    if args.full:
+        msa, e2e_wall_cold = walk()
+        del msa
+    msa, e2e_wall = walk()
     n_nodes = msa.n_internal
     infos = [msa.node_info(k) for k in range(n_nodes)]
     levels = sorted({i.level for i in infos})
@@ -289,7 +362,6 @@ def bench_one_gpu(args, device):
     batches = [resident(ks) for ks in by_level]
     cells_level = [int(L.pagan_batch_cells(hb)) for hb in batches]
     cells = sum(cells_level)
-    steps_level = [max(infos[k].left_sites + infos[k].right_sites - 3 for k in ks) for ks in by_level]   # diagonals
 
     def run(hb):
         rc = L.pagan_batch_run(hb)
@@ -319,14 +391,51 @@ def bench_one_gpu(args, device):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
 
+    # what the last timed pass computed: every node's alignment, fetched from the resident batches (None: the fetch failed)
+    fetched = {}
+    if args.full or args.dump_outputs:
+        for ks, hb in zip(by_level, batches):
+            res = (abi.CResult * len(ks))()
+            rc = L.pagan_batch_fetch(hb, res)
+            for a, k in enumerate(ks):
+                fetched[k] = abi.Result(res[a]) if rc == 0 else None
+                L.pagan_result_free(C.byref(res[a]))
+    if args.dump_outputs:
+        if any(r is None for r in fetched.values()):
+            raise SystemExit("bench.py: pagan_batch_fetch failed")
+        write_outputs(args.dump_outputs, alignment_outputs([fetched[k] for k in range(n_nodes)]))
+
+    out = {
+        "metric": ("DP cells/sec, 32x100 kb DNA progressive align (hot path in dependency order: fill + traceback per tree level)"
+                   if workload.startswith("cfg4") else
+                   "DP cells/sec, %s (hot path in dependency order; not the headline workload)" % workload),
+        "value": cells * args.steps / elapsed,
+        "unit": "cells/s",
+        "n_gpus": 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": None,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": workload, "leaves": leaves, "length": length, "branch": branch,
+                   "data_type": "codon (1892 states)" if alphabet == "CODON" else "protein" if len(alphabet) == 20 else "dna",
+                   "anchors": "prefix, offset 15" if anchors else "none", "node_alignments": n_nodes,
+                   "levels": [len(ks) for ks in by_level], "cells_per_step": int(cells),
+                   "order": "guide-tree levels one after the other (a parent needs its children)"},
+    }
+    if not args.full:
+        for hb in batches:
+            L.pagan_batch_destroy(hb)
+        print(json.dumps(out))
+        return
+
+    tm = msa.timing()
+    steps_level = [max(infos[k].left_sites + infos[k].right_sites - 3 for k in ks) for ks in by_level]   # diagonals
     # parity of the resident batches against what the tree walk produced
-    ok = True
-    for ks, hb in zip(by_level, batches):
-        res = (abi.CResult * len(ks))()
-        rc = L.pagan_batch_fetch(hb, res)
-        ok = ok and rc == 0 and all(abi.Result(res[a]).same_alignment(msa.node_result(k)) for a, k in enumerate(ks))
-        for a in range(len(ks)):
-            L.pagan_result_free(C.byref(res[a]))
+    ok = all(fetched[k] is not None and fetched[k].same_alignment(msa.node_result(k)) for k in range(n_nodes))
     # how much of the back-pointer work the banded fill's follower workgroups did in the last timed pass (chunks of 16
     # diagonals written while the fill ran / all chunks of the banded alignments; the rest was pg_backptr's)
     followed = [0, 0]
@@ -406,26 +515,7 @@ def bench_one_gpu(args, device):
             per_kernel[-1]["row_strip_cells"] = int(strip_cells)
     dom = max(per_kernel, key=lambda e: e["ms_per_step"])
     achieved = dom["achieved"]
-    out = {
-        "metric": ("DP cells/sec, 32x100 kb DNA progressive align (hot path in dependency order: fill + traceback per tree level)"
-                   if workload.startswith("cfg4") else
-                   "DP cells/sec, %s (hot path in dependency order; not the headline workload)" % workload),
-        "value": cells * args.steps / elapsed,
-        "unit": "cells/s",
-        "n_gpus": 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": None,
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": workload, "leaves": leaves, "length": length, "branch": branch,
-                   "data_type": "codon (1892 states)" if alphabet == "CODON" else "protein" if len(alphabet) == 20 else "dna",
-                   "anchors": "prefix, offset 15" if anchors else "none", "node_alignments": n_nodes,
-                   "levels": [len(ks) for ks in by_level], "cells_per_step": int(cells),
-                   "order": "guide-tree levels one after the other (a parent needs its children)"},
+    out.update({
         "value_resident_batch": side_by_side,
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS,
@@ -453,7 +543,7 @@ def bench_one_gpu(args, device):
         "e2e_cells_per_s": cells / e2e_wall,
         "e2e_breakdown_s": tm,
         "parity_self_check": bool(ok),
-    }
+    })
     out["roofline"].update(pmc_traffic(workload, cells, dom["kernel"], dom["launches_per_step"], args.strict_traffic))
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(msa, n_nodes, args.cpu_seconds)
@@ -468,7 +558,8 @@ def bench_work_queue(args, rank, local_rank, world):
     """N > 1: one guide tree farmed over N GPUs as a work queue (pagan2-msa_amd/dist.py).  A step is one whole
     progressive alignment; `value` = cells of the tree / wall-clock of the walk (max over ranks).  Without --workload the
     line is about BASELINE.json's headline, cfg4 -- the workload `--gpus 1` times, so that a 1 -> N curve compares one
-    workload with itself -- and carries cfg5 (the workload whose units fill more than one GPU) in `also`."""
+    workload with itself -- and, with --full, carries cfg5 (the workload whose units fill more than one GPU) in `also`."""
+    import numpy as np
     import torch
     import torch.distributed as dist
     import pagan2_msa_amd as pg
@@ -508,9 +599,9 @@ def bench_work_queue(args, rank, local_rank, world):
                 msa.align()
             return time.perf_counter() - t0, msa
 
-        # rank 0 alone first: the one-GPU time of the same workload (and the reference alignment for the check below)
+        # --full: rank 0 alone first, the one-GPU time of the same workload (and the reference alignment for the check below)
         solo_s, solo = None, None
-        if rank == 0:
+        if rank == 0 and args.full:
             walk(False)
             solo_s, solo = walk(False)
         for _ in range(warmup):
@@ -534,22 +625,10 @@ def bench_work_queue(args, rank, local_rank, world):
             fills = [float(t[2 * r].item()) for r in range(world)]
             aligned = [int(t[2 * r + 1].item()) for r in range(world)]
         if rank != 0:
-            return None, True
+            return None, True, None
         n_nodes = msa.n_internal
         cells = sum(int(msa.node_info(k).cells) for k in range(n_nodes))
-        same = msa.alignment() == solo.alignment() and all(
-            msa.node_info(k).score == solo.node_info(k).score and msa.node_info(k).cells == solo.node_info(k).cells
-            for k in range(n_nodes))
         wall = elapsed_max / steps
-        # Aggregate HBM roofline of the walk: the fill's algorithmic bytes (24 B of scores + 12 B of back-pointers per cell,
-        # DESIGN.md s.2.1) over the WALL-CLOCK of the walk against N x the chip's peak -- host work and idle devices
-        # included, which is what an end-to-end farm is worth; the fill kernels' own device time per rank beside it.
-        ach = BYTES_PER_CELL * cells / wall / 1e9
-        roof = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS * args.gpus, "unit": "GB/s", "frac": ach / (HBM_PEAK_GBS * args.gpus),
-                "traffic": None, "basis": "36 B x cells of the tree / wall-clock of the walk, against %d x %.0f GB/s" % (args.gpus, HBM_PEAK_GBS),
-                "fill_device_s_by_rank": fills, "nodes_aligned_by_rank": aligned,
-                "fill_frac_of_one_gpu_peak_by_rank": [BYTES_PER_CELL * cells * (a / max(n_nodes, 1)) / f / 1e9 / HBM_PEAK_GBS if f > 0 else None
-                                                       for f, a in zip(fills, aligned)]}
         out = {
             "metric": "DP cells/sec, %s, one guide tree farmed over %d GPUs as a work queue (end-to-end walk)" % (workload, args.gpus),
             "value": cells * steps / elapsed_max,
@@ -573,6 +652,22 @@ def bench_work_queue(args, rank, local_rank, world):
                                        % ("RCCL" if args.dist_backend == "nccl" else "gloo", aligned,
                                           "; REHEARSAL: ranks share a device" if args.share_device else "")),
                        "step": "one whole progressive alignment: model + anchors + DP + parent graphs, host work included"},
+        }
+        if not args.full:
+            return out, True, msa
+        same = msa.alignment() == solo.alignment() and all(
+            msa.node_info(k).score == solo.node_info(k).score and msa.node_info(k).cells == solo.node_info(k).cells
+            for k in range(n_nodes))
+        # Aggregate HBM roofline of the walk: the fill's algorithmic bytes (24 B of scores + 12 B of back-pointers per cell,
+        # DESIGN.md s.2.1) over the WALL-CLOCK of the walk against N x the chip's peak -- host work and idle devices
+        # included, which is what an end-to-end farm is worth; the fill kernels' own device time per rank beside it.
+        ach = BYTES_PER_CELL * cells / wall / 1e9
+        roof = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS * args.gpus, "unit": "GB/s", "frac": ach / (HBM_PEAK_GBS * args.gpus),
+                "traffic": None, "basis": "36 B x cells of the tree / wall-clock of the walk, against %d x %.0f GB/s" % (args.gpus, HBM_PEAK_GBS),
+                "fill_device_s_by_rank": fills, "nodes_aligned_by_rank": aligned,
+                "fill_frac_of_one_gpu_peak_by_rank": [BYTES_PER_CELL * cells * (a / max(n_nodes, 1)) / f / 1e9 / HBM_PEAK_GBS if f > 0 else None
+                                                       for f, a in zip(fills, aligned)]}
+        out.update({
             "value_one_gpu_same_workload": cells / solo_s,
             "one_gpu_wall_s": solo_s,
             "speedup_vs_one_gpu": solo_s / wall,
@@ -580,14 +675,20 @@ def bench_work_queue(args, rank, local_rank, world):
             "parity_self_check": bool(same),
             "roofline": roof,
             "cpu_baseline": cpu_baseline(solo, n_nodes, args.cpu_seconds) if with_cpu and not args.no_cpu_baseline else None,
-        }
-        return out, same
+        })
+        return out, same, msa
 
-    if args.workload:
-        out, same = one_workload(args.workload, args.steps, args.warmup, True)
-    else:
-        out, same = one_workload("cfg4_32x100kb_dna_anchored", args.steps, args.warmup, True)
-        also, same5 = one_workload("cfg5_512x10kb_dna_anchored", max(1, min(args.steps, 2)), min(args.warmup, 1), False)
+    out, same, msa = one_workload(args.workload or "cfg4_32x100kb_dna_anchored", args.steps, args.warmup, True)
+    if rank == 0 and args.dump_outputs:
+        # the last timed walk: the rows of the alignment (character codes) and every node's score and cells
+        rows = msa.alignment()
+        write_outputs(args.dump_outputs, {
+            "alignment_rows": np.frombuffer("".join(rows).encode(), np.uint8).reshape(len(rows), -1),
+            "node_score": np.array([msa.node_info(k).score for k in range(msa.n_internal)], np.float64),
+            "node_cells": np.array([msa.node_info(k).cells for k in range(msa.n_internal)], np.float64)})
+    del msa
+    if args.full and not args.workload:
+        also, same5, _ = one_workload("cfg5_512x10kb_dna_anchored", max(1, min(args.steps, 2)), min(args.warmup, 1), False)
         same = same and same5
         if rank == 0:
             out["also"] = {k: also[k] for k in ("metric", "value", "unit", "steps", "ms_per_step", "config", "value_one_gpu_same_workload",

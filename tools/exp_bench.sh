@@ -4,7 +4,7 @@ TAG=$1; shift
 O=gpurun_out/r05
 mkdir -p $O
 for L in "$@"; do
-  PAGAN_DP_LIB=$PWD/pagan2-msa_amd/$L PAGAN_DP_SCORE_CHECK=${SCORE_CHECK:-0} PAGAN_DP_RERUN=0 python bench.py --no-cpu-baseline ${BENCH_ARGS} > $O/exp_${TAG}_$L.json 2> $O/exp_${TAG}_$L.err
+  PAGAN_DP_LIB=$PWD/pagan2-msa_amd/$L PAGAN_DP_SCORE_CHECK=${SCORE_CHECK:-0} PAGAN_DP_RERUN=0 python bench.py --full --no-cpu-baseline ${BENCH_ARGS} > $O/exp_${TAG}_$L.json 2> $O/exp_${TAG}_$L.err
   python - $O/exp_${TAG}_$L.json $L <<'PY'
 import json, sys
 try:

@@ -22,7 +22,7 @@ def per_pass(path):
 w, wk = per_pass(src + "/fb_band_pmc_write.txt")
 f, fk = per_pass(src + "/fb_band_pmc_fetch.txt")
 json.dump({
-    "command": "rocprofv3 --kernel-trace --pmc WRITE_SIZE (and, in a separate pass, FETCH_SIZE) -- python3 bench.py --workload fb_cfg4_leafpairs_banded --steps 2 --warmup 1 --no-cpu-baseline (tools/profile_fb_band.sh); per-dispatch sums by tools/rocpd_summary.py pmc, this file by tools/make_pmc_fb_profile.py",
+    "command": "rocprofv3 --kernel-trace --pmc WRITE_SIZE (and, in a separate pass, FETCH_SIZE) -- python3 bench.py --full --workload fb_cfg4_leafpairs_banded --steps 2 --warmup 1 --no-cpu-baseline (tools/profile_fb_band.sh); per-dispatch sums by tools/rocpd_summary.py pmc, this file by tools/make_pmc_fb_profile.py",
     "workload": "fb_cfg4_leafpairs_banded", "kernel": "pg_fb_forward_ring + pg_fb_backward_ring", "cells_per_step": cells,
     "algorithmic_bytes_per_cell": 48.0, "hbm_bytes_per_step": w + f,
     "write_bytes_per_cell": w / cells, "fetch_bytes_per_cell": f / cells,

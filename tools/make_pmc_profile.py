@@ -91,7 +91,7 @@ def main():
     main_k["write_bytes_per_cell"] = main_k["write_bytes_per_step"] / kcd
     main_k["fetch_bytes_per_cell"] = main_k["fetch_bytes_per_step_raw"] / kcd
     out = {
-        "command": "rocprofv3 --kernel-trace --pmc WRITE_SIZE (and, in a separate pass, FETCH_SIZE) -- python3 bench.py --workload %s --steps 2 "
+        "command": "rocprofv3 --kernel-trace --pmc WRITE_SIZE (and, in a separate pass, FETCH_SIZE) -- python3 bench.py --full --workload %s --steps 2 "
                    "--warmup 1 --no-cpu-baseline (tools/profile_bench.sh / profile_cfg2.sh); per-dispatch sums by tools/rocpd_summary.py pmc, "
                    "this file by tools/make_pmc_profile.py" % workload,
         "kernel": dom, "workload": workload, "cells_per_step": cells, "launches_per_step": main_k["launches_per_step"],

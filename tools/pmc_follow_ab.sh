@@ -11,7 +11,7 @@ cd $R
 for mode in 1 0; do
   export PAGAN_DP_FOLLOW=$mode
   for c in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --kernel-trace --pmc $c -d $O/p -o p -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_follow${mode}_$c.json 2> $O/err_follow${mode}_$c.txt
+    rocprofv3 --kernel-trace --pmc $c -d $O/p -o p -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_follow${mode}_$c.json 2> $O/err_follow${mode}_$c.txt
     python tools/rocpd_summary.py pmc $(find $O/p -name "*_results.db" | head -1) $c > $O/pmc_follow${mode}_$c.txt
     rm -rf $O/p
     echo "follow=$mode $c"; grep "pg_fill_pipe\|pg_backptr" $O/pmc_follow${mode}_$c.txt | cut -c1-260

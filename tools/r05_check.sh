@@ -12,7 +12,7 @@ rc=$?
 tail -2 $O/sweep_$TAG.log
 [ $rc -ne 0 ] && exit $rc
 grep -q "mismatches: 0" $O/sweep_$TAG.log || exit 9
-python bench.py > $O/bench_$TAG.json 2> $O/bench_$TAG.err
+python bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.err
 rc=$?
 python - $O/bench_$TAG.json <<'PY'
 import json, sys
