@@ -283,6 +283,17 @@ int  pagan_fb_kernel_ms(const pagan_fb *fb, double ms[2]);
  * a wave each (wide matrices, and -- round 5 -- tunnels of 4,096 cell diagonals or more), 0 = the LDS-ring sweeps (two
  * plain sequences, widest diagonal <= 1,024 cells: one workgroup, lane = row mod B); diagnostic, for the tests                          */
 int  pagan_fb_groups(const pagan_fb *fb);
+/* the schedule the pair's sweeps took: 0 = the one-workgroup kernels, 1 = 64 x 64 blocks, 2 = the LDS-ring sweeps (two plain
+ * sequences), 3 = the deep-ring sweeps (a graph pair inside a tunnel: pg_fb_forward_deep / pg_fb_backward_deep, a ring of the last
+ * D diagonals whose shape follows the tunnel segment by segment, edges that reach further back read from the stored matrix) */
+int  pagan_fb_schedule(const pagan_fb *fb);
+/* Host only, no device needed: the schedule code pagan_fb_run would choose for this pair under the current environment
+ * (PAGAN_FB_DEEP, PAGAN_FB_DEEP_MIN_ND, PAGAN_FB_RING, PAGAN_FB_RING_MIN_ND, PAGAN_FB_BAND_MIN_ND, PAGAN_FB_GROUPS) -- the
+ * same function decides in pagan_fb_run -- or a negative PAGAN_E_*.  info (optional): [0] cell diagonals, [1] widest diagonal,
+ * [2] segments of the deep-ring plan, [3] smallest D of any segment, [4] longest reach of a left edge, [5] of a right edge,
+ * [6] cells with a far predecessor (further back than the segment's ring holds; forward sweep), [7] diagonals marked far;
+ * [2], [3], [6], [7] are 0 unless the code is 3.                                                                          */
+int  pagan_fb_debug_route(const pagan_graph *left, const pagan_graph *right, const pagan_band *band, int32_t info[8]);
 /* which: 0 log forward, 1 log backward, 2 posterior (compute_posterior_score, VA:1029-1034);
  * dst [Lx][Ly][3] row-major, states X, Y, M; outside the tunnel -inf / 0.                                  */
 int  pagan_fb_dump(pagan_fb *fb, int32_t which, double *dst);

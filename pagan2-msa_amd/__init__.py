@@ -116,6 +116,7 @@ class FullProbability:
         _check(self._L.pagan_fb_kernel_ms(self._h, kms), "pagan_fb_kernel_ms")
         self.forward_ms, self.backward_ms = kms[0], kms[1]
         self.groups = self._L.pagan_fb_groups(self._h)       # 1: one-workgroup sweeps; > 1: 64 x 64 blocks, a wave each; 0: LDS-ring sweeps
+        self.schedule = self._L.pagan_fb_schedule(self._h)   # 0 one-workgroup kernels, 1 blocks, 2 LDS ring (plain sequences), 3 deep ring (graph pairs in a tunnel)
         self.shape = (left.n_sites - 1, right.n_sites - 1, 3)
 
     def _dump(self, which):
@@ -237,6 +238,19 @@ def debug_strips(left, right, band=None, max_sites=0):
     _check(min(n, 0), "pagan_dp_debug_strips")
     desc = desc.reshape(-1, 4)
     return [tuple(int(v) for v in strips[6 * k: 6 * k + 6]) + (desc[off[k]: off[k + 1]].copy(),) for k in range(n)]
+
+
+FB_ROUTE_INFO = ("diagonals", "widest", "segments", "min_D", "reach_left", "reach_right", "far_cells", "far_diagonals")
+
+
+def fb_route(left, right, band=None):
+    """pagan_fb_debug_route (host only): (schedule code FullProbability would take under the current environment, info dict)."""
+    import numpy as np
+    info = np.zeros(8, np.int32)
+    rc = lib().pagan_fb_debug_route(C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None,
+                                    info.ctypes.data_as(C.POINTER(C.c_int32)))
+    _check(min(rc, 0), "pagan_fb_debug_route")
+    return rc, dict(zip(FB_ROUTE_INFO, (int(v) for v in info)))
 
 
 def full_probability_batch(pairs, device=-1):

@@ -57,6 +57,10 @@ struct PgFbJob {
     int groups, groups_b;                    // workgroups of this pair's forward / backward sweep (blockIdx.x beyond: nothing to do)
     int *sync;                               // [64] ints: forward barrier at [0..7], backward at [8..15], diagnostics behind
     int init_dmin;                           // the first cell diagonal that holds a cell of init_at (nd: none)
+    // the deep-ring sweeps (graph pairs inside a tunnel, dp_fb_deep.inc): the segments of the pair's diagonals
+    int nseg; const int *seg_start;          // [nseg + 1] first diagonal of a segment, then nd
+    const int *seg_B;                        // [nseg] rows B of the segment's workgroup layout | 1 << 16: the segment holds a far cell
+    const int *dfar;                         // [nd] bit 0: the diagonal holds a cell with a far predecessor (forward), bit 1: a far successor (backward)
 };
 
 namespace {
@@ -260,7 +264,7 @@ __global__ __launch_bounds__(1024) void pg_fb_backward(const PgFbJob *jobs) {
 // diagonal, which two compares against the diagonal's interval tell --, the rows' and the columns' records (state, log weight of
 // the one edge) and the diagonals' intervals sit in LDS windows refilled every FB_RG_REFILL diagonals, and the step ends in
 // s_waitcnt lgkmcnt(0) + s_barrier: the scores go to memory unwaited-for.  Graph pairs (any site with another edge
-// list) and diagonals wider than 512 cells keep the block schedule.
+// list) inside a tunnel take the deep-ring sweeps of dp_fb_deep.inc; diagonals wider than 1,024 cells keep the block schedule.
 #define FB_RG_COLS 1024          // columns / rows in the LDS windows (>= B + 2 * FB_RG_REFILL) up to B = 512; 2,048 for B = 1,024
 #define FB_RG_REFILL 256
 #define FB_RG_MAXB 1024         // rows of the widest diagonal a ring sweep takes
@@ -483,6 +487,8 @@ __global__ __launch_bounds__(FB_RG_THREADS) void pg_fb_backward_ring(const PgFbJ
     if (threadIdx.x == 0) J.totals[1] = rd(J.B, cell_at(J, 0, 0), 2);
 }
 #undef FB_RING_THREADS
+
+#include "dp_fb_deep.inc"
 
 // ---- wide alignments: 64 x 64 blocks on a block-anti-diagonal schedule ----
 // Block (a, b) needs blocks (a', b') <= (a, b) only (bwd edges point to earlier sites), so the blocks of one block
@@ -1024,6 +1030,7 @@ struct pagan_fb {
     float kernel_ms[2] = {0, 0};                        // pg_fb_forward, pg_fb_backward (HIP events)
     int groups = 1;                                     // workgroups a diagonal's cells were spread over
     bool ring = false;                                  // the LDS-ring sweeps ran
+    bool deep = false;                                  // the deep-ring sweeps (graph pairs) ran
     std::vector<double> hF;                             // downloaded lazily
     long long at(int i, int j) const {
         if (i < 0 || j < 0 || i >= Lx || j >= Ly) return -1;
@@ -1037,6 +1044,185 @@ extern "C" {
 } // extern "C"
 
 namespace {
+// initialise_array_corner_bwd (VA:740-854): assignments onto the cells the end corner reads
+static void fb_corner_init(const pagan_graph *left, const pagan_graph *right, int Lx, int Ly, const DiagIndex &dx, double l_ng,
+                           std::vector<long long> &init_at, std::vector<double> &init_val, int &init_dmin) {
+    auto at = [&](int i, int j) -> long long {
+        if (i < 0 || j < 0 || i >= Lx || j >= Ly) return -1;
+        const int d = i + j;
+        return (i >= dx.imin[d] && i <= dx.imax[d]) ? dx.doff[d] + (i - dx.imin[d]) : -1;
+    };
+    init_dmin = Lx + Ly - 1;
+    auto put_init = [&](int i, int j, int s, double v) {
+        const long long a = at(i, j);
+        if (a < 0) return;
+        init_dmin = std::min(init_dmin, i + j);
+        for (size_t k = 0; k < init_at.size(); ++k) if (init_at[k] == 3 * a + s) { init_val[k] = v; return; }   // later assignment wins
+        init_at.push_back(3 * a + s); init_val.push_back(v);
+    };
+    put_init(Lx - 1, Ly - 1, PAGAN_M_MAT, l_ng);
+    const int l0 = left->bwd_off[Lx], l1 = left->bwd_off[Lx + 1], r0 = right->bwd_off[Ly], r1 = right->bwd_off[Ly + 1];
+    if (l1 > l0 && r1 > r0)
+        for (int k1 = l0; k1 < l1; ++k1)
+            for (int k2 = r0; k2 < r1; ++k2)
+                put_init(left->bwd_src[k1], right->bwd_src[k2], PAGAN_M_MAT, l_ng + (double)left->bwd_logw[k1] + (double)right->bwd_logw[k2]);
+    for (int k1 = l0; k1 < l1; ++k1) put_init(left->bwd_src[k1], Ly - 1, PAGAN_X_MAT, 0.0);
+    for (int k2 = r0; k2 < r1; ++k2) put_init(Lx - 1, right->bwd_src[k2], PAGAN_Y_MAT, 0.0);
+}
+
+// Which schedule a pair's sweeps take, decided in ONE place (fb_stage and pagan_fb_debug_route both call this), and for the deep-ring
+// sweeps their plan: the segments and the diagonals that hold a far cell.
+struct FbRoute {
+    int groups = 1;                          // workgroups of a tiled sweep before the caller's caps (1: not tiled)
+    bool ring = false, deep = false;
+    int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // see pagan_fb_debug_route
+    std::vector<int> seg_start, seg_B, dfar;
+    int deep_block = 64;                     // threads of a deep-ring workgroup
+    int schedule() const { return deep ? 3 : (ring && groups == 1 ? 2 : (groups > 1 ? 1 : 0)); }
+};
+
+// v[k] := max of v over [k - before, k + after]
+static void fb_window_max(std::vector<int> &v, int before, int after) {
+    const int n = (int)v.size();
+    std::vector<int> out(n), dq(n);
+    int head = 0, tail = 0, nxt = 0;
+    for (int k = 0; k < n; ++k) {
+        for (; nxt < n && nxt <= k + after; ++nxt) { while (tail > head && v[dq[tail - 1]] <= v[nxt]) --tail; dq[tail++] = nxt; }
+        while (dq[head] < k - before) ++head;
+        out[k] = v[dq[head]];
+    }
+    v.swap(out);
+}
+
+// The deep-ring plan.  A diagonal needs B >= its own width and that of the FB_DP_HALO diagonals either side of it (the ring of a
+// segment is rebuilt from them at its boundary, in either direction).  Segments: greedy, a segment's B only grows while it is
+// shorter than FB_DP_MINSEG diagonals, ends where a wider diagonal comes, and where the next FB_DP_MINSEG diagonals all fit a smaller B.
+static void fb_deep_plan(int Lx, int Ly, const DiagIndex &dx, const std::vector<int> &rL, const std::vector<int> &rR,
+                         const std::vector<int> &sL, const std::vector<int> &sR, FbRoute *R) {
+    const int nd = Lx + Ly - 1;
+    std::vector<int> need(nd);
+    for (int d = 0; d < nd; ++d) { const int w = dx.imax[d] - dx.imin[d] + 1; need[d] = w > 512 ? 1024 : (w > 256 ? 512 : (w > 128 ? 256 : (w > 64 ? 128 : 64))); }
+    fb_window_max(need, FB_DP_HALO, FB_DP_HALO);
+    std::vector<int> ahead(need);
+    fb_window_max(ahead, 0, FB_DP_MINSEG - 1);
+    R->seg_start.clear(); R->seg_B.clear();
+    int maxB = 64, minD = FB_DP_CELLS / 64;
+    for (int s = 0; s < nd;) {
+        int B = need[s], e = s + 1;
+        for (; e < nd; ++e) {
+            const int nb = need[e];
+            if (nb == B) continue;
+            if (e - s < FB_DP_MINSEG) { B = std::max(B, nb); continue; }
+            if (nb > B || ahead[e] < B) break;
+        }
+        R->seg_start.push_back(s); R->seg_B.push_back(B);
+        maxB = std::max(maxB, B); minD = std::min(minD, FB_DP_CELLS / B);
+        s = e;
+    }
+    R->seg_start.push_back(nd);
+    // far cells: a predecessor (forward: reaches rL / rR of the bwd lists) or successor (backward: sL / sR of the fwd lists) D or more diagonals away
+    R->dfar.assign(nd, 0);
+    long long far_cells = 0; int far_diags = 0;
+    for (size_t g = 0; g + 1 < R->seg_start.size(); ++g) {
+        const int D = FB_DP_CELLS / R->seg_B[g];
+        int any = 0;
+        for (int d = R->seg_start[g]; d < R->seg_start[g + 1]; ++d) {
+            int f = 0;
+            for (int i = dx.imin[d]; i <= dx.imax[d]; ++i) {
+                const int j = d - i;
+                const int a = i > 0 ? rL[i] : 0, b = j > 0 ? rR[j] : 0;
+                if (a >= D || b >= D || (a > 0 && b > 0 && a + b >= D)) { ++far_cells; f |= 1; }
+                if (sL[i] >= D || sR[j] >= D || (sL[i] > 0 && sR[j] > 0 && sL[i] + sR[j] >= D)) f |= 2;
+            }
+            R->dfar[d] = f; any |= f;
+            if (f & 1) ++far_diags;
+        }
+        if (any) R->seg_B[g] |= 1 << 16;
+    }
+    R->deep_block = std::min(FB_RG_THREADS, 3 * maxB);
+    R->info[2] = (int)R->seg_B.size(); R->info[3] = minD;
+    R->info[6] = (int)std::min<long long>(far_cells, 0x7fffffff); R->info[7] = far_diags;
+}
+
+static void fb_route(const pagan_graph *left, const pagan_graph *right, int Lx, int Ly, const DiagIndex &dx, bool has_band, int n_init,
+                     const FwdLists &fl, const FwdLists &fr, FbRoute *R) {
+    const int nd = Lx + Ly - 1, mw = dx.max_width;
+    // wide diagonals: 64 x 64 blocks over as many workgroups as a block anti-diagonal has blocks; PAGAN_FB_GROUPS=1 keeps the
+    // one-workgroup sweeps
+    int groups = mw > 256 ? std::min({FB_MAX_GROUPS, (Lx + FB_T - 1) / FB_T, (Ly + FB_T - 1) / FB_T}) : 1;
+    // A long tunnel (round 5; the leaf pairs of 32 x 100 kb: 2e5 diagonals of ~25 cells) on the block schedule as well: its one
+    // workgroup paid a __syncthreads() and a round trip to L2 per cell diagonal (2.7 us: 0.55 s a sweep); as blocks it is the few
+    // blocks the band has on a block anti-diagonal (fb_live_rows), a wave each, operands in registers / LDS, one counter barrier per
+    // 64 diagonals.  Workgroups: the blocks a diagonal of `mw` cells can lie in while it moves through 127 diagonals.
+    // PAGAN_FB_BAND_MIN_ND: the shortest pair (in cell diagonals) that takes this path (tests: 0; "off": none).
+    // ... and a long tunnel between plain sequences (every site one edge, from the site before it: leaves) on the LDS-ring sweeps
+    // (pg_fb_forward_ring): PAGAN_FB_RING=0 switches them off, PAGAN_FB_RING_MIN_ND is their shortest pair (default 256 diagonals)
+    // ... and a graph pair (any other edge lists) inside a tunnel on the deep-ring sweeps (pg_fb_forward_deep, dp_fb_deep.inc):
+    // PAGAN_FB_DEEP=0 switches them off, PAGAN_FB_DEEP_MIN_ND is their shortest pair (default 4,096 diagonals)
+    auto plain = [](const pagan_graph *g) {
+        for (int sidx = 1; sidx < g->n_sites; ++sidx)
+            if (g->bwd_off[sidx + 1] - g->bwd_off[sidx] != 1 || g->bwd_src[g->bwd_off[sidx]] != sidx - 1) return false;
+        return g->bwd_off[1] == 0;
+    };
+    bool gapless = true;                                          // (no cell diagonal without a cell)
+    for (int d = 0; d < nd && gapless; ++d) gapless = dx.imax[d] >= dx.imin[d];
+    const bool both_plain = plain(left) && plain(right);
+    const bool shape_ok = mw <= FB_RG_MAXB && Lx >= 2 && Ly >= 2 && n_init <= FB_RG_INIT && gapless;
+    bool ring = false, deep = false;
+    {
+        int min_nd = 256;            // (a step of the ring sweeps is 1 us against the one-workgroup kernels' 2.7: worth it from a few hundred diagonals on)
+        if (const char *e = std::getenv("PAGAN_FB_RING_MIN_ND")) min_nd = std::atoi(e);
+        const char *re = std::getenv("PAGAN_FB_RING");
+        ring = !(re && std::strcmp(re, "0") == 0) && nd >= min_nd && shape_ok && both_plain;
+        if (ring && !std::getenv("PAGAN_FB_GROUPS")) groups = 1;
+    }
+    // the longest reach of a site's lists: bwd (the forward sweep's predecessors), fwd without the edges into the end site (the backward sweep's successors)
+    std::vector<int> rL, rR, sL, sR;
+    if (!both_plain) { rL.assign(Lx + 1, 0); rR.assign(Ly + 1, 0); sL.assign(Lx + 1, 0); sR.assign(Ly + 1, 0); }
+    // (two plain sequences: every reach is 1, and nothing below reads the arrays -- such a pair is never a deep-ring pair)
+    auto reaches = [&](const pagan_graph *g, const FwdLists &f, int n, std::vector<int> &r, std::vector<int> &s) {
+        int longest = 0;
+        if (both_plain) return n > 1 ? 1 : 0;
+        for (int v = 1; v < n; ++v) {
+            for (int k = g->bwd_off[v]; k < g->bwd_off[v + 1]; ++k) r[v] = std::max(r[v], v - g->bwd_src[k]);
+            longest = std::max(longest, r[v]);
+        }
+        for (int v = 0; v < n; ++v)
+            for (int k = f.off[v]; k < f.off[v + 1]; ++k) if (f.dst[k] < n) s[v] = std::max(s[v], f.dst[k] - v);
+        return longest;
+    };
+    R->info[0] = nd; R->info[1] = mw;
+    R->info[4] = reaches(left, fl, Lx, rL, sL); R->info[5] = reaches(right, fr, Ly, rR, sR);
+    {
+        int min_nd = 4096;
+        if (const char *e = std::getenv("PAGAN_FB_DEEP_MIN_ND")) min_nd = std::atoi(e);
+        const char *de = std::getenv("PAGAN_FB_DEEP");
+        // the list windows hold FB_DP_E entries of any FB_DP_W consecutive sites
+        auto lists_fit = [](const int *off, int n_sites) {
+            for (int v = 0; v < n_sites; ++v) if (off[std::min(n_sites, v + FB_DP_W)] - off[v] > FB_DP_E) return false;
+            return true;
+        };
+        deep = !(de && std::strcmp(de, "0") == 0) && !std::getenv("PAGAN_FB_GROUPS") && has_band && nd >= min_nd && shape_ok && !both_plain &&
+               lists_fit(left->bwd_off, left->n_sites) && lists_fit(right->bwd_off, right->n_sites) &&
+               lists_fit(fl.off.data(), left->n_sites) && lists_fit(fr.off.data(), right->n_sites);
+        if (deep) { groups = 1; ring = false; fb_deep_plan(Lx, Ly, dx, rL, rR, sL, sR, R); }
+    }
+    {
+        int min_nd = 4096;
+        if (const char *e = std::getenv("PAGAN_FB_BAND_MIN_ND")) min_nd = std::strcmp(e, "off") == 0 ? 0x7fffffff : std::atoi(e);
+        if (ring || deep) {}
+        else if (groups == 1 && nd >= min_nd && Lx >= 2 && Ly >= 2)
+            groups = std::max(2, std::min({FB_MAX_GROUPS, (mw + FB_T - 1) / FB_T + 2, (Lx + FB_T - 1) / FB_T, (Ly + FB_T - 1) / FB_T}));
+        // (and a pair that is "wide" by a box of its tunnel -- one of the 16 leaf pairs has a diagonal of 295 cells -- does not need
+        //  the 64 workgroups of a full matrix at every barrier: a diagonal of mw cells lies in mw / 64 + 2 blocks at most)
+        else if (groups > 1) groups = std::max(2, std::min(groups, (mw + FB_T - 1) / FB_T + 2));
+    }
+    if (const char *e = std::getenv("PAGAN_FB_GROUPS")) { groups = std::max(1, std::min(FB_MAX_GROUPS, std::atoi(e))); ring = false; }
+    R->groups = groups; R->ring = ring; R->deep = deep;
+}
+} // namespace
+
+namespace {
 // One pair up to the upload of its inputs: validation, band index, lists, arena, the job record with its workgroup count
 // (`groups_cap`: what the caller's launch leaves this pair) -- what pagan_fb_run and pagan_fb_run_batch share.
 struct FbStaged {
@@ -1046,6 +1232,7 @@ struct FbStaged {
     char *d_tot = nullptr, *d_sync = nullptr;
     int groups = 1, groups_b = 1, block = 64;
     bool ring = false;                       // the sweeps are pg_fb_forward_ring / pg_fb_backward_ring (block = their B)
+    bool deep = false;                       // ... pg_fb_forward_deep / pg_fb_backward_deep (block = their threads)
     double t_host[4] = {0, 0, 0, 0};         // band index + lists, arena, staging, upload (seconds)
     size_t arena_bytes = 0;
 };
@@ -1078,28 +1265,13 @@ static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pag
     const FwdLists fl = forward_lists(left), fr = forward_lists(right);
     std::vector<double> ltab((size_t)S * S);
     for (size_t k = 0; k < ltab.size(); ++k) ltab[k] = std::log((double)model->score[k]);
-    // initialise_array_corner_bwd (VA:740-854): assignments onto the cells the end corner reads
     std::vector<long long> init_at;
     std::vector<double> init_val;
     const double l_ng = std::log((double)model->non_gap);
     int init_dmin = nd;
-    auto put_init = [&](int i, int j, int s, double v) {
-        const long long a = fb->at(i, j);
-        if (a < 0) return;
-        init_dmin = std::min(init_dmin, i + j);
-        for (size_t k = 0; k < init_at.size(); ++k) if (init_at[k] == 3 * a + s) { init_val[k] = v; return; }   // later assignment wins
-        init_at.push_back(3 * a + s); init_val.push_back(v);
-    };
-    put_init(Lx - 1, Ly - 1, PAGAN_M_MAT, l_ng);
-    {
-        const int l0 = left->bwd_off[Lx], l1 = left->bwd_off[Lx + 1], r0 = right->bwd_off[Ly], r1 = right->bwd_off[Ly + 1];
-        if (l1 > l0 && r1 > r0)
-            for (int k1 = l0; k1 < l1; ++k1)
-                for (int k2 = r0; k2 < r1; ++k2)
-                    put_init(left->bwd_src[k1], right->bwd_src[k2], PAGAN_M_MAT, l_ng + (double)left->bwd_logw[k1] + (double)right->bwd_logw[k2]);
-        for (int k1 = l0; k1 < l1; ++k1) put_init(left->bwd_src[k1], Ly - 1, PAGAN_X_MAT, 0.0);
-        for (int k2 = r0; k2 < r1; ++k2) put_init(Lx - 1, right->bwd_src[k2], PAGAN_Y_MAT, 0.0);
-    }
+    fb_corner_init(left, right, Lx, Ly, fb->dx, l_ng, init_at, init_val, init_dmin);
+    FbRoute route;
+    fb_route(left, right, Lx, Ly, fb->dx, band != nullptr, (int)init_at.size(), fl, fr, &route);
     // one arena: inputs, then F and B
     size_t cur = 0;
     auto take = [&](size_t bytes) { const size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
@@ -1112,6 +1284,7 @@ static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pag
     const size_t o_tab = take(8 * ltab.size());
     const size_t o_imin = take(4 * (size_t)nd), o_imax = take(4 * (size_t)nd), o_doff = take(8 * (size_t)nd);
     const size_t o_iat = take(8 * init_at.size()), o_ival = take(8 * init_val.size());
+    const size_t o_segs = take(4 * route.seg_start.size()), o_segB = take(4 * route.seg_B.size()), o_dfar = take(4 * route.dfar.size());
     const size_t o_tot = take(16);
     const size_t o_sync = take(256);                      // two barrier counters + give-up words of the wide sweeps (zero)
     const size_t in_bytes = cur;
@@ -1130,44 +1303,12 @@ static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pag
     put(o_tab, ltab.data(), 8 * ltab.size());
     put(o_imin, fb->dx.imin.data(), 4 * (size_t)nd); put(o_imax, fb->dx.imax.data(), 4 * (size_t)nd); put(o_doff, fb->dx.doff.data(), 8 * (size_t)nd);
     put(o_iat, init_at.data(), 8 * init_at.size()); put(o_ival, init_val.data(), 8 * init_val.size());
+    put(o_segs, route.seg_start.data(), 4 * route.seg_start.size()); put(o_segB, route.seg_B.data(), 4 * route.seg_B.size()); put(o_dfar, route.dfar.data(), 4 * route.dfar.size());
     char *b = fb->arena;
-    // wide diagonals: 64 x 64 blocks over as many workgroups as a block anti-diagonal has blocks; PAGAN_FB_GROUPS=1 keeps the
-    // one-workgroup sweeps
+    // the schedule: fb_route above
     const int mw = fb->dx.max_width;
-    int groups = mw > 256 ? std::min({FB_MAX_GROUPS, (Lx + FB_T - 1) / FB_T, (Ly + FB_T - 1) / FB_T}) : 1;
-    // A long tunnel (round 5; the leaf pairs of 32 x 100 kb: 2e5 diagonals of ~25 cells) on the block schedule as well: its one
-    // workgroup paid a __syncthreads() and a round trip to L2 per cell diagonal (2.7 us: 0.55 s a sweep); as blocks it is the few
-    // blocks the band has on a block anti-diagonal (fb_live_rows), a wave each, operands in registers / LDS, one counter barrier per
-    // 64 diagonals.  Workgroups: the blocks a diagonal of `mw` cells can lie in while it moves through 127 diagonals.
-    // PAGAN_FB_BAND_MIN_ND: the shortest pair (in cell diagonals) that takes this path (tests: 0; "off": none).
-    // ... and a long tunnel between plain sequences (every site one edge, from the site before it: leaves) on the LDS-ring sweeps
-    // (pg_fb_forward_ring): PAGAN_FB_RING=0 switches them off, PAGAN_FB_RING_MIN_ND is their shortest pair (default 256 diagonals)
-    bool ring = false;
-    {
-        int min_nd = 256;            // (a step of the ring sweeps is 1 us against the one-workgroup kernels' 2.7: worth it from a few hundred diagonals on)
-        if (const char *e = std::getenv("PAGAN_FB_RING_MIN_ND")) min_nd = std::atoi(e);
-        const char *re = std::getenv("PAGAN_FB_RING");
-        auto plain = [](const pagan_graph *g) {
-            for (int sidx = 1; sidx < g->n_sites; ++sidx)
-                if (g->bwd_off[sidx + 1] - g->bwd_off[sidx] != 1 || g->bwd_src[g->bwd_off[sidx]] != sidx - 1) return false;
-            return g->bwd_off[1] == 0;
-        };
-        bool gapless = true;                                          // (no cell diagonal without a cell)
-        for (int d = 0; d < nd && gapless; ++d) gapless = fb->dx.imax[d] >= fb->dx.imin[d];
-        ring = !(re && std::strcmp(re, "0") == 0) && nd >= min_nd && mw <= FB_RG_MAXB && Lx >= 2 && Ly >= 2 && (int)init_at.size() <= FB_RG_INIT && gapless && plain(left) && plain(right);
-        if (ring && !std::getenv("PAGAN_FB_GROUPS")) groups = 1;
-    }
-    {
-        int min_nd = 4096;
-        if (const char *e = std::getenv("PAGAN_FB_BAND_MIN_ND")) min_nd = std::strcmp(e, "off") == 0 ? 0x7fffffff : std::atoi(e);
-        if (ring) {}
-        else if (groups == 1 && nd >= min_nd && Lx >= 2 && Ly >= 2)
-            groups = std::max(2, std::min({FB_MAX_GROUPS, (mw + FB_T - 1) / FB_T + 2, (Lx + FB_T - 1) / FB_T, (Ly + FB_T - 1) / FB_T}));
-        // (and a pair that is "wide" by a box of its tunnel -- one of the 16 leaf pairs has a diagonal of 295 cells -- does not need
-        //  the 64 workgroups of a full matrix at every barrier: a diagonal of mw cells lies in mw / 64 + 2 blocks at most)
-        else if (groups > 1) groups = std::max(2, std::min(groups, (mw + FB_T - 1) / FB_T + 2));
-    }
-    if (const char *e = std::getenv("PAGAN_FB_GROUPS")) { groups = std::max(1, std::min(FB_MAX_GROUPS, std::atoi(e))); ring = false; }
+    int groups = route.groups;
+    const bool ring = route.ring;
     const int groups_b = groups > 1 ? std::max(2, std::min(groups, groups_cap_b)) : 1;
     if (groups > 1) groups = std::max(2, std::min(groups, groups_cap));
     fb->groups = groups;
@@ -1186,6 +1327,7 @@ static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pag
     J.totals = (double *)(b + o_tot);
     J.groups = groups; J.groups_b = groups_b; J.sync = (int *)(b + o_sync);
     J.init_dmin = init_dmin;
+    J.nseg = (int)route.seg_B.size(); J.seg_start = (const int *)(b + o_segs); J.seg_B = (const int *)(b + o_segB); J.dfar = (const int *)(b + o_dfar);
     std::memcpy(stage.data() + o_job, &J, sizeof(J));
     fb->dF = J.F; fb->dB = J.B;
     const double th2 = now_();
@@ -1196,7 +1338,9 @@ static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pag
     st->block = mw >= 768 ? 1024 : mw >= 384 ? 512 : mw >= 192 ? 256 : (mw >= 96 ? 128 : 64);
     st->ring = ring && groups == 1;
     if (st->ring) st->block = mw > 512 ? 1024 : (mw > 256 ? 512 : (mw > 128 ? 256 : (mw > 64 ? 128 : 64)));     // a thread per row of the widest diagonal
-    fb->ring = st->ring;
+    st->deep = route.deep;
+    if (st->deep) st->block = route.deep_block;
+    fb->ring = st->ring; fb->deep = st->deep;
     st->groups = groups; st->groups_b = groups_b;
     st->d_job = (const PgFbJob *)(b + o_job); st->d_tot = b + o_tot; st->d_sync = b + o_sync; st->job = J;
     st->t_host[0] = th1 - th0; st->t_host[1] = th2 - th1; st->t_host[2] = 0.0; st->t_host[3] = th3 - th2;
@@ -1268,6 +1412,12 @@ static void fb_launch_ring(bool fwd, bool all_lds, unsigned grid, int B, hipStre
     if (fwd) { if (all_lds) fb_launch_ring_<true, true>(ns, grid, B, st, jobs); else fb_launch_ring_<true, false>(ns, grid, B, st, jobs); }
     else { if (all_lds) fb_launch_ring_<false, true>(ns, grid, B, st, jobs); else fb_launch_ring_<false, false>(ns, grid, B, st, jobs); }
 }
+// one launch of deep-ring sweeps: `grid` graph pairs, workgroups of `threads` threads
+static void fb_launch_deep(bool fwd, bool all_lds, unsigned grid, int threads, hipStream_t st, const PgFbJob *jobs) {
+    const dim3 g(grid), t((unsigned)threads);
+    if (fwd) { if (all_lds) hipLaunchKernelGGL((pg_fb_forward_deep<true>), g, t, 0, st, jobs); else hipLaunchKernelGGL((pg_fb_forward_deep<false>), g, t, 0, st, jobs); }
+    else { if (all_lds) hipLaunchKernelGGL((pg_fb_backward_deep<true>), g, t, 0, st, jobs); else hipLaunchKernelGGL((pg_fb_backward_deep<false>), g, t, 0, st, jobs); }
+}
 struct FbSlotLease { FbSlots *s; int n; ~FbSlotLease() { if (n > 0) s->give(n); } };
 
 } // namespace
@@ -1296,11 +1446,13 @@ int pagan_fb_run(const pagan_graph *left, const pagan_graph *right, const pagan_
     FbSlotLease lease{&slots, groups > 1 ? 2 * groups : 0};
     if (groups > 1) slots.take(2 * groups, fb_slot_cap(fb->device));
     if (groups > 1) { if (all_lds) hipLaunchKernelGGL((pg_fb_forward_tiled<true>), dim3(groups, 1), dim3(64), 0, s1, st.d_job); else hipLaunchKernelGGL((pg_fb_forward_tiled<false>), dim3(groups, 1), dim3(64), 0, s1, st.d_job); }
+    else if (st.deep) fb_launch_deep(true, all_lds, 1, block, s1, st.d_job);
     else if (st.ring) fb_launch_ring(true, all_lds, 1, block, s1, st.d_job);
     else hipLaunchKernelGGL(pg_fb_forward, dim3(1), dim3(block), 0, s1, st.d_job);
     FB_TRY(hipEventRecord(e1, s1));
     FB_TRY(hipEventRecord(e2, s2));
     if (groups > 1) { if (all_lds) hipLaunchKernelGGL((pg_fb_backward_tiled<true>), dim3(groups, 1), dim3(64), 0, s2, st.d_job); else hipLaunchKernelGGL((pg_fb_backward_tiled<false>), dim3(groups, 1), dim3(64), 0, s2, st.d_job); }
+    else if (st.deep) fb_launch_deep(false, all_lds, 1, block, s2, st.d_job);
     else if (st.ring) fb_launch_ring(false, all_lds, 1, block, s2, st.d_job);
     else hipLaunchKernelGGL(pg_fb_backward, dim3(1), dim3(block), 0, s2, st.d_job);
     FB_TRY(hipEventRecord(e3, s2));
@@ -1364,7 +1516,7 @@ int pagan_fb_run_batch(int32_t n, const pagan_graph *const *left, const pagan_gr
         for (int q = 0; q < chunk; ++q) if (rcs[done + q] != PAGAN_OK) rc = rcs[done + q];
         if (rc != PAGAN_OK) break;
         std::vector<PgFbJob> tiled;
-        std::vector<int> tiled_k, small_k, ring_k;
+        std::vector<int> tiled_k, small_k, ring_k, deep_k;
         int gmax = 0, gmax_b = 0, slots_needed = 0;
         bool tiled_all_lds = true;                                // every tiled pair's score table fits LDS
         for (int q = 0; q < chunk; ++q) {
@@ -1373,7 +1525,8 @@ int pagan_fb_run_batch(int32_t n, const pagan_graph *const *left, const pagan_gr
                 tiled.push_back(st[k].job); tiled_k.push_back(k);
                 tiled_all_lds = tiled_all_lds && st[k].job.S * st[k].job.S <= 256;
                 gmax = std::max(gmax, st[k].groups); gmax_b = std::max(gmax_b, st[k].groups_b); slots_needed += st[k].groups + st[k].groups_b;
-            } else if (st[k].ring) ring_k.push_back(k);
+            } else if (st[k].deep) deep_k.push_back(k);
+            else if (st[k].ring) ring_k.push_back(k);
             else small_k.push_back(k);
         }
         // the LDS-ring sweeps of the chunk: one launch per direction and workgroup size (a workgroup a pair)
@@ -1381,8 +1534,16 @@ int pagan_fb_run_batch(int32_t n, const pagan_graph *const *left, const pagan_gr
         std::stable_sort(ring_k.begin(), ring_k.end(), [&](int a, int b_) { return ring_key(a) < ring_key(b_); });
         std::vector<PgFbJob> ring_jobs;
         for (int k : ring_k) ring_jobs.push_back(st[k].job);
+        // ... and its deep-ring sweeps the same way (graph pairs inside tunnels), behind the tiled sweeps: a deep-ring workgroup
+        // declares 153 KB of LDS, so no tiled workgroup shares its compute unit, and the tiled sweeps' slot budget counts on three a
+        // compute unit being resident at once -- the deep launches go out once the tiled streams are synchronised
+        std::stable_sort(deep_k.begin(), deep_k.end(), [&](int a, int b_) { return ring_key(a) < ring_key(b_); });
+        std::vector<PgFbJob> deep_jobs;
+        for (int k : deep_k) deep_jobs.push_back(st[k].job);
         if (rc != PAGAN_OK) break;
-        PgFbJob *d_jobs = nullptr, *d_ring = nullptr;
+        PgFbJob *d_jobs = nullptr, *d_ring = nullptr, *d_deep = nullptr;
+        std::vector<hipStream_t> deep_s;
+        hipEvent_t h0 = nullptr, h1 = nullptr, h2 = nullptr, h3 = nullptr;
         hipStream_t s1 = nullptr, s2 = nullptr, r1 = nullptr, r2 = nullptr;
         hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr, g0 = nullptr, g1 = nullptr, g2 = nullptr, g3 = nullptr;
         std::vector<hipStream_t> small_s(2 * small_k.size(), nullptr), ring_s;
@@ -1390,6 +1551,9 @@ int pagan_fb_run_batch(int32_t n, const pagan_graph *const *left, const pagan_gr
         auto release = [&]() {
             if (d_jobs) (void)hipFree(d_jobs);
             if (d_ring) (void)hipFree(d_ring);
+            if (d_deep) (void)hipFree(d_deep);
+            for (hipStream_t x : deep_s) if (x) (void)hipStreamDestroy(x);
+            for (hipEvent_t e : {h0, h1, h2, h3}) if (e) (void)hipEventDestroy(e);
             for (hipStream_t x : {s1, s2, r1, r2}) if (x) (void)hipStreamDestroy(x);
             for (hipEvent_t e : {e0, e1, e2, e3, g0, g1, g2, g3}) if (e) (void)hipEventDestroy(e);
             for (hipStream_t x : small_s) if (x) (void)hipStreamDestroy(x);
@@ -1461,6 +1625,30 @@ int pagan_fb_run_batch(int32_t n, const pagan_graph *const *left, const pagan_gr
             }
             FB_TRY(hipGetLastError());
             FB_TRY(hipStreamSynchronize(s1)); FB_TRY(hipStreamSynchronize(s2));
+            float df_ms = 0, db_ms = 0;
+            if (!deep_jobs.empty()) {
+                FB_TRY(hipMalloc((void **)&d_deep, deep_jobs.size() * sizeof(PgFbJob)));
+                FB_TRY(hipMemcpy(d_deep, deep_jobs.data(), deep_jobs.size() * sizeof(PgFbJob), hipMemcpyHostToDevice));
+                FB_TRY(hipEventCreate(&h0)); FB_TRY(hipEventCreate(&h1)); FB_TRY(hipEventCreate(&h2)); FB_TRY(hipEventCreate(&h3));
+                // one launch per direction and (workgroup size, table in LDS or not), each on a stream of its own; the times are the first group's
+                for (size_t a = 0; a < deep_k.size();) {
+                    size_t z = a;
+                    while (z < deep_k.size() && ring_key(deep_k[z]) == ring_key(deep_k[a])) ++z;
+                    hipStream_t f = nullptr, bk = nullptr;
+                    FB_TRY(hipStreamCreate(&f)); deep_s.push_back(f);
+                    FB_TRY(hipStreamCreate(&bk)); deep_s.push_back(bk);
+                    const bool lds = (ring_key(deep_k[a]) & 1) != 0;
+                    if (a == 0) { FB_TRY(hipEventRecord(h0, f)); FB_TRY(hipEventRecord(h2, bk)); }
+                    fb_launch_deep(true, lds, (unsigned)(z - a), st[deep_k[a]].block, f, (const PgFbJob *)(d_deep + a));
+                    fb_launch_deep(false, lds, (unsigned)(z - a), st[deep_k[a]].block, bk, (const PgFbJob *)(d_deep + a));
+                    if (a == 0) { FB_TRY(hipEventRecord(h1, f)); FB_TRY(hipEventRecord(h3, bk)); }
+                    a = z;
+                }
+                FB_TRY(hipGetLastError());
+                for (hipStream_t x : deep_s) FB_TRY(hipStreamSynchronize(x));
+                (void)hipEventElapsedTime(&df_ms, h0, h1); (void)hipEventElapsedTime(&db_ms, h2, h3);
+            }
+            for (size_t q = 0; q < deep_k.size(); ++q) { const int r_ = fb_finish(&st[deep_k[q]], q == 0 ? df_ms : 0.0f, q == 0 ? db_ms : 0.0f); if (r_ != PAGAN_OK) return r_; }
             if (r1) { FB_TRY(hipStreamSynchronize(r1)); FB_TRY(hipStreamSynchronize(r2)); }
             for (hipStream_t x : small_s) FB_TRY(hipStreamSynchronize(x));
             float fwd_ms = 0, bwd_ms = 0, rf_ms = 0, rb_ms = 0;
@@ -1487,7 +1675,32 @@ int pagan_fb_kernel_ms(const pagan_fb *fb, double ms[2]) {
     return PAGAN_OK;
 }
 
-int pagan_fb_groups(const pagan_fb *fb) { return fb ? (fb->ring ? 0 : fb->groups) : PAGAN_E_ARG; }
+int pagan_fb_groups(const pagan_fb *fb) { return fb ? (fb->ring || fb->deep ? 0 : fb->groups) : PAGAN_E_ARG; }
+
+int pagan_fb_schedule(const pagan_fb *fb) { return fb ? (fb->deep ? 3 : (fb->ring ? 2 : (fb->groups > 1 ? 1 : 0))) : PAGAN_E_ARG; }
+
+// Host only: what fb_stage would decide for this pair under the current environment (it calls the same fb_route).
+int pagan_fb_debug_route(const pagan_graph *left, const pagan_graph *right, const pagan_band *band, int32_t info[8]) {
+    if (!left || !right) return PAGAN_E_ARG;
+    int rc = check_graph(left);
+    if (rc == PAGAN_OK) rc = check_graph(right);
+    if (rc != PAGAN_OK) return rc;
+    const int Lx = left->n_sites - 1, Ly = right->n_sites - 1;
+    RowBand rb;
+    rc = rb.build(Lx, Ly, band);
+    if (rc != PAGAN_OK) return rc;
+    DiagIndex dx;
+    dx.build(Lx, Ly, rb);
+    std::vector<long long> init_at;
+    std::vector<double> init_val;
+    int init_dmin = 0;
+    fb_corner_init(left, right, Lx, Ly, dx, 0.0, init_at, init_val, init_dmin);
+    const FwdLists fl = forward_lists(left), fr = forward_lists(right);
+    FbRoute route;
+    fb_route(left, right, Lx, Ly, dx, band != nullptr, (int)init_at.size(), fl, fr, &route);
+    if (info) for (int k = 0; k < 8; ++k) info[k] = route.info[k];
+    return route.schedule();
+}
 
 int pagan_fb_totals(const pagan_fb *fb, double *log_fwd, double *log_bwd, int64_t *cells) {
     if (!fb) return PAGAN_E_ARG;
