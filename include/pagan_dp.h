@@ -297,7 +297,7 @@ int  pagan_fb_debug_route(const pagan_graph *left, const pagan_graph *right, con
 /* which: 0 log forward, 1 log backward, 2 posterior (compute_posterior_score, VA:1029-1034);
  * dst [Lx][Ly][3] row-major, states X, Y, M; outside the tunnel -inf / 0.                                  */
 int  pagan_fb_dump(pagan_fb *fb, int32_t which, double *dst);
-/* posterior of n cells given as (state, i, j) triples                                                     */
+/* posterior of n cells given as (state, i, j) triples (one upload, one gather kernel, one download)         */
 int  pagan_fb_posterior_cells(pagan_fb *fb, int32_t n, const int32_t *cells, double *post);
 /* sample_new_path (VA:1193-1322): u[k] in [0,1) replaces rand()/(RAND_MAX+1), one per step, the end corner
  * first (at most Lx+Ly+1 are consumed).  `out` has the shape of a Viterbi result (free with
@@ -305,6 +305,39 @@ int  pagan_fb_posterior_cells(pagan_fb *fb, int32_t n, const int32_t *cells, dou
 int  pagan_fb_sample_path(pagan_fb *fb, const double *u, int32_t n_u, pagan_result *out,
                           int32_t *visited, int32_t *n_visited);
 void pagan_fb_destroy(pagan_fb *fb);
+
+/* ---- reading a finished pagan_fb on the device (dp_fb_post.inc) ------------------------------------------
+ * Host only, no device needed: the DP cell each column of a path sits on, as (state, i, j) triples.  With ci = cj = 0 at the
+ * start: matched -> (M, left, right) and ci = left, cj = right; xgapped -> (X, left, cj) and ci = left; ygapped ->
+ * (Y, ci, right) and cj = right; xskipped / yskipped -> (-1, -1, -1), ci and cj unchanged.  Another path state: PAGAN_E_ARG.   */
+int  pagan_path_cells(const pagan_col *cols, int32_t n_cols, int32_t *cells /* [3 * n_cols] */);
+/* support[k] = posterior of column k's OWN cell (one upload of the cells, one gather kernel, one download); skip columns
+ * get -1, a cell outside the tunnel 0; a column whose sites lie outside the matrices: PAGAN_E_ARG.  The reference's
+ * Site::posterior_support is this array shifted by one column.                                              */
+int  pagan_fb_path_support(pagan_fb *fb, const pagan_col *cols, int32_t n_cols, double *support /* [n_cols] */);
+/* The posterior matrix reduced on the device.  Rows i = 0 .. Lx-1: pX[i] = sum_j post(X,i,j), pM_left[i] = sum_j post(M,i,j),
+ * best_j[i] / best_p_left[i] = the column with the largest post(M,i,j) and that value (ties: the lowest j; every post(M,i,.)
+ * 0: -1 and 0).  Columns j = 0 .. Ly-1 the mirror: pY, pM_right, best_i, best_p_right.  Any output may be NULL; a side all of
+ * whose outputs are NULL is not computed.  The sums are taken in a fixed order: two runs give the same bits.                 */
+int  pagan_fb_site_marginals(pagan_fb *fb, double *pX, double *pM_left, int32_t *best_j, double *best_p_left,
+                             double *pY, double *pM_right, int32_t *best_i, double *best_p_right);
+/* The same for n handles on one device (those of one pagan_fb_run_batch), one launch per pass: every argument an array of
+ * n pointers, or NULL, with any entry NULL.                                                                                */
+int  pagan_fb_site_marginals_batch(int32_t n, pagan_fb *const *fbs, double *const *pX, double *const *pM_left,
+                                   int32_t *const *best_j, double *const *best_p_left, double *const *pY,
+                                   double *const *pM_right, int32_t *const *best_i, double *const *best_p_right);
+/* device time of the handle's last gather (path support / posterior cells), row pass and column pass, milliseconds; a batch's
+ * passes are booked at the first handle that took part, 0 at the others                                                    */
+int  pagan_fb_post_ms(const pagan_fb *fb, double ms[3]);
+/* Host only: the device bytes pagan_fb_run takes for a pair (F and B at 24 B a cell each, the diagonals' index, the lists);
+ * an estimate from above as far as the lists go (four edges a site).  A caller cuts a level's pairs into batches by it.      */
+int64_t pagan_fb_predict_bytes(int32_t left_sites, int32_t right_sites, const pagan_band *band);
+/* Host only: n uniform numbers in [0, 1) with 53 bits, a pure function of (seed, node, s):
+ *     mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31
+ *     u[s] = (mix(mix(mix(seed) ^ node) ^ s) >> 11) / 2^53          (64-bit unsigned arithmetic; node sign-extended)
+ * (splitmix64's step as a counter-based generator.)  A path sampled with these does not depend on which thread, device or
+ * rank handled the node, nor on what was sampled before it.                                                                 */
+int  pagan_sample_uniforms(uint64_t seed, int32_t node, int32_t n, double *u);
 
 const char *pagan_dp_version(void);
 

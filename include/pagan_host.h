@@ -63,6 +63,17 @@ typedef struct pagan_msa_opts {
     int32_t  mostcommon;         /* --mostcommon: a matched column's parent state from the most-common table
                                     (basic_alignment.cpp:146-147) and Node::fix_ambiguous_states
                                     (node.cpp:1610-1690) after every node                            */
+    int32_t  full_probability;   /* --full-probability (viterbi_alignment.cpp:329-371): 1 = behind every node's Viterbi
+                                    alignment, on the band the node finally used, the forward/backward pass runs on the GPU
+                                    (pagan_fb_run_batch, the model's probability-space view at the node's distance) and the
+                                    node keeps log_fwd, log_bwd and the posterior support of its path's columns; 2 = its
+                                    site marginals too.  The alignment itself does not change.                         */
+    int32_t  sample_path;        /* --sample-path (viterbi_alignment.cpp:395-417): 1 = no Viterbi alignment; every node's
+                                    path is sampled from its forward matrix (pagan_fb_sample_path, on the host: the
+                                    forward matrix is downloaded, 24 B a cell) with pagan_sample_uniforms(sample_seed,
+                                    public node id, Lx + Ly + 1); node score = log full probability; a tunnel whose full
+                                    probability is 0 is retried without the tunnel                                      */
+    uint64_t sample_seed;
 } pagan_msa_opts;
 
 void pagan_msa_default_opts(pagan_msa_opts *o);
@@ -123,7 +134,8 @@ int     pagan_msa_data_type(const pagan_msa *m);                           /* 1 
 int     pagan_msa_node_device(const pagan_msa *m, int32_t k);              /* device internal node k ran on; -1: another rank */
 /* TEST SEAM, never set by the product: replaces pagan_dp_align_batch as the thing the work queue hands its
  * batches to, so that the queue (dealing, feeder threads, retries, result exchange) can be exercised on a
- * machine without a GPU.  fn has pagan_dp_align_batch's contract (results released with free()); the device a
+ * machine without a GPU (with full_probability or sample_path set the walk then fails with PAGAN_E_NODEVICE: the seam has
+ * no forward/backward pass, and the pass is never skipped silently).  fn has pagan_dp_align_batch's contract (results released with free()); the device a
  * batch was dealt to arrives in opts->device.  NULL restores the HIP path.                                    */
 typedef int (*pagan_batch_fn)(int32_t n, const pagan_job *jobs, const pagan_opts *opts, pagan_result *out, void *user);
 int     pagan_msa_set_batch_backend(pagan_msa *m, pagan_batch_fn fn, void *user);
@@ -133,6 +145,22 @@ int  pagan_msa_node_info(const pagan_msa *m, int32_t k, pagan_node_info *out);
  * produced: usable as a pagan_job for pagan_batch_create / the oracle.                   */
 int  pagan_msa_node_job(const pagan_msa *m, int32_t k, pagan_job *out);
 int  pagan_msa_node_result(const pagan_msa *m, int32_t k, pagan_result *out);
+/* What the forward/backward pass left at internal node k (full_probability / sample_path).  All of these return PAGAN_E_ARG
+ * for a node this process did not align (rank mode: support is not part of the exchange format) or when no pass ran.
+ * node_fb: out[0] log_fwd, [1] log_bwd, [2] device ms of the two sweeps, [3] device ms of support + marginals (a batch's
+ *   launches are booked at its first node, 0 at the others).
+ * node_support: [n_cols] posterior of each column's own cell along the node's path, -1 at skip columns (pagan_fb_path_support).
+ * node_marginals: the eight arrays of pagan_fb_site_marginals (any may be NULL); valid with full_probability == 2.
+ * node_model_prob: borrowed view of the probability-space model the pass used (valid until pagan_msa_destroy).
+ * support_row: node `node`'s (n_leaves .. 2 n_leaves - 2) column support laid onto the final alignment's columns, -1 where
+ *   the node has no matched / xgapped / ygapped column; buf holds alignment_length floats (codons: one per column of three
+ *   characters).  Leaves: PAGAN_E_ARG.                                                                                    */
+int  pagan_msa_node_fb(const pagan_msa *m, int32_t k, double out[4]);
+int  pagan_msa_node_support(const pagan_msa *m, int32_t k, double *support);
+int  pagan_msa_node_marginals(const pagan_msa *m, int32_t k, double *pX, double *pM_left, int32_t *best_j, double *best_p_left,
+                              double *pY, double *pM_right, int32_t *best_i, double *best_p_right);
+int  pagan_msa_node_model_prob(const pagan_msa *m, int32_t k, pagan_model_prob *out);
+int  pagan_msa_support_row(const pagan_msa *m, int32_t node, float *buf);
 int  pagan_msa_timing_get(const pagan_msa *m, pagan_msa_timing *out);
 int  pagan_msa_alignment_length(const pagan_msa *m);
 /* Row of node `node` of the final alignment, '-' for gaps; buf >= length+1.  Leaves 0..n-1 in input order;

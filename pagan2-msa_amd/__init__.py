@@ -140,6 +140,25 @@ class FullProbability:
                                                 out.ctypes.data_as(C.POINTER(C.c_double))), "pagan_fb_posterior_cells")
         return out
 
+    def path_support(self, cols):
+        """pagan_fb_path_support: the posterior of every column's own cell along a path (Result.cols), -1 at skip columns."""
+        c = self._np.ascontiguousarray(cols, self._np.int32).reshape(-1, 3)
+        out = self._np.zeros(c.shape[0], self._np.float64)
+        _check(self._L.pagan_fb_path_support(self._h, c.ctypes.data_as(C.POINTER(abi.CCol)), c.shape[0],
+                                             out.ctypes.data_as(C.POINTER(C.c_double))), "pagan_fb_path_support")
+        return out
+
+    def site_marginals(self, rows=True, columns=True):
+        """pagan_fb_site_marginals: dict of pX, pM_left, best_j, best_p_left ([Lx], rows=True) and pY, pM_right, best_i,
+        best_p_right ([Ly], columns=True), reduced on the device."""
+        return site_marginals_batch([self], rows, columns)[0]
+
+    def post_ms(self):
+        """Device ms of the handle's last gather, row pass, column pass."""
+        ms = (C.c_double * 3)()
+        _check(self._L.pagan_fb_post_ms(self._h, ms), "pagan_fb_post_ms")
+        return ms[0], ms[1], ms[2]
+
     def sample_path(self, u):
         """(Result, visited cells end -> start as rows (i, j, state))."""
         uu = self._np.ascontiguousarray(u, self._np.float64)
@@ -267,6 +286,57 @@ def full_probability_batch(pairs, device=-1):
     opts = abi.COpts(0, device)
     _check(L.pagan_fb_run_batch(n, lefts, rights, models, bands, C.byref(opts), outs), "pagan_fb_run_batch")
     return [FullProbability(p[0], p[1], p[2], p[3], device=device, _handle=C.c_void_p(outs[k])) for k, p in enumerate(pairs)]
+
+
+_MARGINALS = (("pX", 0, "f"), ("pM_left", 0, "f"), ("best_j", 0, "i"), ("best_p_left", 0, "f"),
+              ("pY", 1, "f"), ("pM_right", 1, "f"), ("best_i", 1, "i"), ("best_p_right", 1, "f"))
+
+
+def site_marginals_batch(fbs, rows=True, columns=True):
+    """pagan_fb_site_marginals_batch over FullProbability handles of one device (one launch per pass): a list of dicts as
+    FullProbability.site_marginals returns."""
+    import numpy as np
+    L = lib()
+    n = len(fbs)
+    f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    out = [{} for _ in range(n)]
+    args = []
+    for name, side, kind in _MARGINALS:
+        if not (columns if side else rows):
+            args.append(None)
+            continue
+        ptrs = ((f64p if kind == "f" else i32p) * n)()
+        for k, fb in enumerate(fbs):
+            a = np.zeros(fb.shape[side], np.float64 if kind == "f" else np.int32)
+            out[k][name] = a
+            ptrs[k] = a.ctypes.data_as(f64p if kind == "f" else i32p)
+        args.append(ptrs)
+    handles = (C.c_void_p * n)(*[fb._h for fb in fbs])
+    _check(L.pagan_fb_site_marginals_batch(n, handles, *args), "pagan_fb_site_marginals_batch")
+    return out
+
+
+def path_cells(cols):
+    """pagan_path_cells (host only): [n, 3] int32 rows (state, i, j) of the DP cell each column sits on, (-1, -1, -1) at skip columns."""
+    import numpy as np
+    c = np.ascontiguousarray(cols, np.int32).reshape(-1, 3)
+    out = np.zeros((c.shape[0], 3), np.int32)
+    _check(lib().pagan_path_cells(c.ctypes.data_as(C.POINTER(abi.CCol)), c.shape[0], out.ctypes.data_as(C.POINTER(C.c_int32))),
+           "pagan_path_cells")
+    return out
+
+
+def sample_uniforms(seed, node, n):
+    """pagan_sample_uniforms (host only): n numbers in [0, 1), a pure function of (seed, node, index)."""
+    import numpy as np
+    u = np.zeros(n, np.float64)
+    _check(lib().pagan_sample_uniforms(int(seed) & 0xFFFFFFFFFFFFFFFF, int(node), int(n), u.ctypes.data_as(C.POINTER(C.c_double))),
+           "pagan_sample_uniforms")
+    return u
+
+
+def fb_predict_bytes(left_sites, right_sites, band=None):
+    return lib().pagan_fb_predict_bytes(left_sites, right_sites, C.byref(band.c) if band is not None else None)
 
 
 def debug_far(left, right, band=None):

@@ -246,6 +246,21 @@ def declare(lib):
     lib.pagan_fb_posterior_cells.restype = C.c_int
     lib.pagan_fb_sample_path.argtypes = [C.c_void_p, f64p, C.c_int32, rp, _i32p, _i32p]
     lib.pagan_fb_sample_path.restype = C.c_int
+    colp, f64pp, i32pp = C.POINTER(CCol), C.POINTER(f64p), C.POINTER(_i32p)
+    lib.pagan_path_cells.argtypes = [colp, C.c_int32, _i32p]
+    lib.pagan_path_cells.restype = C.c_int
+    lib.pagan_fb_path_support.argtypes = [C.c_void_p, colp, C.c_int32, f64p]
+    lib.pagan_fb_path_support.restype = C.c_int
+    lib.pagan_fb_site_marginals.argtypes = [C.c_void_p, f64p, f64p, _i32p, f64p, f64p, f64p, _i32p, f64p]
+    lib.pagan_fb_site_marginals.restype = C.c_int
+    lib.pagan_fb_site_marginals_batch.argtypes = [C.c_int32, C.POINTER(C.c_void_p), f64pp, f64pp, i32pp, f64pp, f64pp, f64pp, i32pp, f64pp]
+    lib.pagan_fb_site_marginals_batch.restype = C.c_int
+    lib.pagan_fb_post_ms.argtypes = [C.c_void_p, f64p]
+    lib.pagan_fb_post_ms.restype = C.c_int
+    lib.pagan_fb_predict_bytes.argtypes = [C.c_int32, C.c_int32, bp]
+    lib.pagan_fb_predict_bytes.restype = C.c_int64
+    lib.pagan_sample_uniforms.argtypes = [C.c_uint64, C.c_int32, C.c_int32, f64p]
+    lib.pagan_sample_uniforms.restype = C.c_int
     lib.pagan_fb_destroy.argtypes = [C.c_void_p]
     lib.pagan_fb_destroy.restype = None
     lib.pagan_dp_version.argtypes = []
@@ -258,4 +273,5 @@ EXPORTED = ["pagan_dp_align", "pagan_dp_align_batch", "pagan_result_free", "paga
             "pagan_batch_run", "pagan_batch_sync", "pagan_batch_fetch", "pagan_batch_last_ms",
             "pagan_batch_cells", "pagan_batch_last_ms_detail", "pagan_batch_destroy", "pagan_batch_debug_trace", "pagan_dp_debug_plan", "pagan_dp_debug_far", "pagan_dp_debug_strips", "pagan_dp_debug_tiles", "pagan_dp_debug_compact", "pagan_dp_debug_tiles_staircase", "pagan_dp_release_cache", "pagan_dp_cached_device_bytes", "pagan_dp_debug_route", "pagan_batch_debug_scores", "pagan_batch_debug_backptrs", "pagan_batch_debug_poison", "pagan_batch_debug_followed", "pagan_batch_debug_poke_bp", "pagan_batch_debug_reruns",
             "pagan_fb_run", "pagan_fb_run_batch", "pagan_fb_totals", "pagan_fb_kernel_ms", "pagan_fb_groups", "pagan_fb_schedule", "pagan_fb_debug_route", "pagan_fb_dump", "pagan_fb_posterior_cells", "pagan_fb_sample_path",
+            "pagan_path_cells", "pagan_fb_path_support", "pagan_fb_site_marginals", "pagan_fb_site_marginals_batch", "pagan_fb_post_ms", "pagan_fb_predict_bytes", "pagan_sample_uniforms",
             "pagan_fb_destroy", "pagan_dp_version"]

@@ -489,6 +489,7 @@ __global__ __launch_bounds__(FB_RG_THREADS) void pg_fb_backward_ring(const PgFbJ
 #undef FB_RING_THREADS
 
 #include "dp_fb_deep.inc"
+#include "dp_fb_post.inc"
 
 // ---- wide alignments: 64 x 64 blocks on a block-anti-diagonal schedule ----
 // Block (a, b) needs blocks (a', b') <= (a, b) only (bwd edges point to earlier sites), so the blocks of one block
@@ -1032,6 +1033,9 @@ struct pagan_fb {
     bool ring = false;                                  // the LDS-ring sweeps ran
     bool deep = false;                                  // the deep-ring sweeps (graph pairs) ran
     std::vector<double> hF;                             // downloaded lazily
+    PgFbJob job{};                                      // the pair's job record (device pointers into the arena) ...
+    const PgFbJob *d_job = nullptr;                     // ... and where it sits on the device
+    float post_ms[3] = {0, 0, 0};                       // last pg_fb_gather, row pass, column pass (HIP events)
     long long at(int i, int j) const {
         if (i < 0 || j < 0 || i >= Lx || j >= Ly) return -1;
         const int d = i + j;
@@ -1330,6 +1334,7 @@ static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pag
     J.nseg = (int)route.seg_B.size(); J.seg_start = (const int *)(b + o_segs); J.seg_B = (const int *)(b + o_segB); J.dfar = (const int *)(b + o_dfar);
     std::memcpy(stage.data() + o_job, &J, sizeof(J));
     fb->dF = J.F; fb->dB = J.B;
+    fb->job = J; fb->d_job = (const PgFbJob *)(b + o_job);
     const double th2 = now_();
     FB_TRY(hipMemcpy(fb->arena, stage.data(), in_bytes, hipMemcpyHostToDevice));
     const double th3 = now_();
@@ -1419,6 +1424,12 @@ static void fb_launch_deep(bool fwd, bool all_lds, unsigned grid, int threads, h
     else { if (all_lds) hipLaunchKernelGGL((pg_fb_backward_deep<true>), g, t, 0, st, jobs); else hipLaunchKernelGGL((pg_fb_backward_deep<false>), g, t, 0, st, jobs); }
 }
 struct FbSlotLease { FbSlots *s; int n; ~FbSlotLease() { if (n > 0) s->give(n); } };
+// the calling thread on `device` for the length of a call, back on the device it came with afterwards
+struct FbDeviceScope {
+    int back; bool ok;
+    FbDeviceScope(int device, int caller) : back(caller), ok(hipSetDevice(device) == hipSuccess) {}
+    ~FbDeviceScope() { (void)hipSetDevice(back); }
+};
 
 } // namespace
 
@@ -1484,8 +1495,16 @@ int pagan_fb_run_batch(int32_t n, const pagan_graph *const *left, const pagan_gr
     if (n < 0 || (n > 0 && (!left || !right || !model || !out))) return PAGAN_E_ARG;
     for (int k = 0; k < n; ++k) out[k] = nullptr;
     if (n == 0) return PAGAN_OK;
-    int device = 0;
-    if (opts && opts->device >= 0) device = opts->device; else if (hipGetDevice(&device) != hipSuccess) return PAGAN_E_NODEVICE;
+    // the device, resolved once: the calling thread is put on it before any allocation, stream or launch (a caller may pass a
+    // device that is not its current one), the staging threads are handed it, and the caller's device is restored on the way out
+    int caller_device = 0;
+    if (hipGetDevice(&caller_device) != hipSuccess) return PAGAN_E_NODEVICE;
+    const int device = opts && opts->device >= 0 ? opts->device : caller_device;
+    FbDeviceScope on_device(device, caller_device);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    pagan_opts staged_opts;
+    staged_opts.flags = opts ? opts->flags : 0u;
+    staged_opts.device = device;
     const int cap = fb_slot_cap(device);
     std::vector<FbStaged> st(n);
     std::vector<int> rcs(n, PAGAN_OK);
@@ -1505,15 +1524,17 @@ int pagan_fb_run_batch(int32_t n, const pagan_graph *const *left, const pagan_gr
             const int nt = std::min(chunk, 16);
             std::atomic<int> next{0};
             for (int t = 0; t < nt; ++t) pool.emplace_back([&] {
-                if (opts && opts->device >= 0) (void)hipSetDevice(opts->device);
+                const bool on = hipSetDevice(device) == hipSuccess;
                 for (int q; (q = next.fetch_add(1)) < chunk;) {
                     const int k = done + q;
-                    rcs[k] = fb_stage(left[k], right[k], model[k], band ? band[k] : nullptr, opts, groups_cap, groups_cap_b, &st[k]);
+                    rcs[k] = on ? fb_stage(left[k], right[k], model[k], band ? band[k] : nullptr, &staged_opts, groups_cap, groups_cap_b, &st[k]) : PAGAN_E_NODEVICE;
                 }
             });
             for (auto &th : pool) th.join();
         }
         for (int q = 0; q < chunk; ++q) if (rcs[done + q] != PAGAN_OK) rc = rcs[done + q];
+        if (rc != PAGAN_OK) break;
+        for (int q = 0; q < chunk; ++q) if (st[done + q].fb->device != device) rc = PAGAN_E_INTERNAL;      // (every pair's arena is on the launches' device)
         if (rc != PAGAN_OK) break;
         std::vector<PgFbJob> tiled;
         std::vector<int> tiled_k, small_k, ring_k, deep_k;
@@ -1730,20 +1751,206 @@ int pagan_fb_dump(pagan_fb *fb, int32_t which, double *dst) {
     return PAGAN_OK;
 }
 
-// Posterior of n cells given as (state, i, j) triples.
+} // extern "C"
+
+namespace {
+// pg_fb_gather over one pair: the triples go up in one copy, the posteriors come back in one (state outside 0..2: -1)
+static int fb_gather(pagan_fb *fb, int32_t n, const int32_t *cells, double *post) {
+    if (n == 0) return PAGAN_OK;
+    int caller = 0;
+    FB_TRY(hipGetDevice(&caller));
+    FbDeviceScope on_device(fb->device, caller);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    const size_t o_cells = 256, o_out = o_cells + (12 * (size_t)n + 255) / 256 * 256, bytes = o_out + 8 * (size_t)n;
+    char *buf = nullptr;
+    FB_TRY(hipMalloc((void **)&buf, bytes));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto body = [&]() -> int {
+        std::vector<char> up(o_out, 0);
+        PgFbGather G;
+        G.cells = (const int *)(buf + o_cells); G.out = (double *)(buf + o_out); G.n = n;
+        std::memcpy(up.data(), &G, sizeof(G));
+        std::memcpy(up.data() + o_cells, cells, 12 * (size_t)n);
+        FB_TRY(hipMemcpy(buf, up.data(), o_out, hipMemcpyHostToDevice));
+        FB_TRY(hipEventCreate(&e0)); FB_TRY(hipEventCreate(&e1));
+        FB_TRY(hipEventRecord(e0, nullptr));
+        const unsigned blocks = (unsigned)std::min<long long>(((long long)n + 255) / 256, 4096);
+        hipLaunchKernelGGL(pg_fb_gather, dim3(blocks, 1), dim3(256), 0, nullptr, fb->d_job, (const PgFbGather *)buf);
+        FB_TRY(hipGetLastError());
+        FB_TRY(hipEventRecord(e1, nullptr));
+        FB_TRY(hipMemcpy(post, buf + o_out, 8 * (size_t)n, hipMemcpyDeviceToHost));
+        (void)hipEventElapsedTime(&fb->post_ms[0], e0, e1);
+        return PAGAN_OK;
+    };
+    const int rc = body();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(buf);
+    return rc;
+}
+
+// The two marginal passes over n handles of one device: one launch per pass, grid = (blocks of the longest pair, pairs that want
+// the pass).  o[0..3] rows (pX, pM, best_j, best_p), o[4..7] columns (pY, pM', best_i, best_p'): arrays of n pointers or null,
+// any entry null.  A pass none of whose outputs is wanted anywhere is not launched.  The launches' times go to the first handle.
+static int fb_marginals(int32_t n, pagan_fb *const *fbs, void *const *const o[8]) {
+    if (n < 0 || (n > 0 && !fbs)) return PAGAN_E_ARG;
+    if (n == 0) return PAGAN_OK;
+    for (int k = 0; k < n; ++k) if (!fbs[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
+    int caller = 0;
+    FB_TRY(hipGetDevice(&caller));
+    FbDeviceScope on_device(fbs[0]->device, caller);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    auto wanted = [&](int k, int side) { for (int q = 4 * side; q < 4 * side + 4; ++q) if (o[q] && o[q][k]) return true; return false; };
+    struct Side { std::vector<int> ks; std::vector<size_t> at; int blocks = 0; size_t o_jobs = 0, o_recs = 0; };
+    Side sd[2];
+    size_t cur = 0;
+    auto take = [&](size_t bytes) { const size_t at = cur; cur = (cur + bytes + 255) / 256 * 256; return at; };
+    for (int side = 0; side < 2; ++side) {
+        for (int k = 0; k < n; ++k) if (wanted(k, side)) sd[side].ks.push_back(k);
+        sd[side].o_jobs = take(sd[side].ks.size() * sizeof(PgFbJob));
+        sd[side].o_recs = take(sd[side].ks.size() * sizeof(PgFbMarg));
+    }
+    const size_t in_bytes = cur;
+    for (int side = 0; side < 2; ++side)
+        for (int k : sd[side].ks) {
+            const int len = side ? fbs[k]->Ly : fbs[k]->Lx;
+            sd[side].at.push_back(take(28 * (size_t)len));          // three doubles and an int a site
+            sd[side].blocks = std::max(sd[side].blocks, (len + FB_PM_ROWS - 1) / FB_PM_ROWS);
+        }
+    if (sd[0].ks.empty() && sd[1].ks.empty()) return PAGAN_OK;
+    char *buf = nullptr;
+    FB_TRY(hipMalloc((void **)&buf, cur));
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<char> host(cur, 0);
+    auto body = [&]() -> int {
+        for (int side = 0; side < 2; ++side)
+            for (size_t q = 0; q < sd[side].ks.size(); ++q) {
+                const pagan_fb *fb = fbs[sd[side].ks[q]];
+                const size_t len = side ? fb->Ly : fb->Lx;
+                char *base = buf + sd[side].at[q];
+                PgFbMarg M;
+                M.gap = (double *)base; M.match = (double *)(base + 8 * len); M.best_p = (double *)(base + 16 * len); M.best = (int *)(base + 24 * len);
+                std::memcpy(host.data() + sd[side].o_jobs + q * sizeof(PgFbJob), &fb->job, sizeof(PgFbJob));
+                std::memcpy(host.data() + sd[side].o_recs + q * sizeof(PgFbMarg), &M, sizeof(M));
+            }
+        FB_TRY(hipMemcpy(buf, host.data(), in_bytes, hipMemcpyHostToDevice));
+        for (int side = 0; side < 2; ++side) {
+            if (sd[side].ks.empty()) continue;
+            FB_TRY(hipEventCreate(&ev[2 * side])); FB_TRY(hipEventCreate(&ev[2 * side + 1]));
+            FB_TRY(hipEventRecord(ev[2 * side], nullptr));
+            const dim3 grid((unsigned)sd[side].blocks, (unsigned)sd[side].ks.size());
+            const PgFbJob *jobs = (const PgFbJob *)(buf + sd[side].o_jobs);
+            const PgFbMarg *recs = (const PgFbMarg *)(buf + sd[side].o_recs);
+            if (side) hipLaunchKernelGGL((pg_fb_marginals<true>), grid, dim3(FB_PM_ROWS), 0, nullptr, jobs, recs);
+            else hipLaunchKernelGGL((pg_fb_marginals<false>), grid, dim3(FB_PM_ROWS), 0, nullptr, jobs, recs);
+            FB_TRY(hipGetLastError());
+            FB_TRY(hipEventRecord(ev[2 * side + 1], nullptr));
+        }
+        FB_TRY(hipMemcpy(host.data() + in_bytes, buf + in_bytes, cur - in_bytes, hipMemcpyDeviceToHost));
+        for (int k = 0; k < n; ++k) fbs[k]->post_ms[1] = fbs[k]->post_ms[2] = 0.0f;
+        for (int side = 0; side < 2; ++side) {
+            if (sd[side].ks.empty()) continue;
+            (void)hipEventElapsedTime(&fbs[sd[side].ks[0]]->post_ms[1 + side], ev[2 * side], ev[2 * side + 1]);
+            for (size_t q = 0; q < sd[side].ks.size(); ++q) {
+                const int k = sd[side].ks[q];
+                const size_t len = side ? fbs[k]->Ly : fbs[k]->Lx;
+                const char *base = host.data() + sd[side].at[q];
+                void *const *const *oo = o + 4 * side;
+                if (oo[0] && oo[0][k]) std::memcpy(oo[0][k], base, 8 * len);
+                if (oo[1] && oo[1][k]) std::memcpy(oo[1][k], base + 8 * len, 8 * len);
+                if (oo[2] && oo[2][k]) std::memcpy(oo[2][k], base + 24 * len, 4 * len);
+                if (oo[3] && oo[3][k]) std::memcpy(oo[3][k], base + 16 * len, 8 * len);
+            }
+        }
+        return PAGAN_OK;
+    };
+    const int rc = body();
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    (void)hipFree(buf);
+    return rc;
+}
+
+static uint64_t fb_splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+} // namespace
+
+extern "C" {
+
+// Posterior of n cells given as (state, i, j) triples: one upload, pg_fb_gather, one download.
 int pagan_fb_posterior_cells(pagan_fb *fb, int32_t n, const int32_t *cells, double *post) {
     if (!fb || n < 0 || (n > 0 && (!cells || !post))) return PAGAN_E_ARG;
-    FB_TRY(hipSetDevice(fb->device));
-    for (int k = 0; k < n; ++k) {
-        const int s = cells[3 * k];
-        const long long at = fb->at(cells[3 * k + 1], cells[3 * k + 2]);
-        if (s < 0 || s > 2) return PAGAN_E_ARG;
-        if (at < 0) { post[k] = 0.0; continue; }
-        double f = 0, b = 0;
-        FB_TRY(hipMemcpy(&f, fb->dF + 3 * at + s, 8, hipMemcpyDeviceToHost));
-        FB_TRY(hipMemcpy(&b, fb->dB + 3 * at + s, 8, hipMemcpyDeviceToHost));
-        post[k] = std::exp(f + b - fb->totals[0]);
+    for (int k = 0; k < n; ++k) if (cells[3 * k] < 0 || cells[3 * k] > 2) return PAGAN_E_ARG;
+    return fb_gather(fb, n, cells, post);
+}
+
+// Host only: the DP cell every column of a path sits on (include/pagan_dp.h).
+int pagan_path_cells(const pagan_col *cols, int32_t n_cols, int32_t *cells) {
+    if (n_cols < 0 || (n_cols > 0 && (!cols || !cells))) return PAGAN_E_ARG;
+    int ci = 0, cj = 0;
+    for (int k = 0; k < n_cols; ++k) {
+        int s = -1, i = -1, j = -1;
+        switch (cols[k].path_state) {
+        case PAGAN_MATCHED: ci = cols[k].left; cj = cols[k].right; s = PAGAN_M_MAT; i = ci; j = cj; break;
+        case PAGAN_XGAPPED: ci = cols[k].left; s = PAGAN_X_MAT; i = ci; j = cj; break;
+        case PAGAN_YGAPPED: cj = cols[k].right; s = PAGAN_Y_MAT; i = ci; j = cj; break;
+        case PAGAN_XSKIPPED: case PAGAN_YSKIPPED: break;
+        default: return PAGAN_E_ARG;
+        }
+        cells[3 * k] = s; cells[3 * k + 1] = i; cells[3 * k + 2] = j;
     }
+    return PAGAN_OK;
+}
+
+int pagan_fb_path_support(pagan_fb *fb, const pagan_col *cols, int32_t n_cols, double *support) {
+    if (!fb || n_cols < 0 || (n_cols > 0 && (!cols || !support))) return PAGAN_E_ARG;
+    std::vector<int32_t> cells(3 * (size_t)n_cols);
+    const int rc = pagan_path_cells(cols, n_cols, cells.data());
+    if (rc != PAGAN_OK) return rc;
+    for (int k = 0; k < n_cols; ++k)
+        if (cells[3 * k] >= 0 && (cells[3 * k + 1] < 0 || cells[3 * k + 1] >= fb->Lx || cells[3 * k + 2] < 0 || cells[3 * k + 2] >= fb->Ly)) return PAGAN_E_ARG;
+    return fb_gather(fb, n_cols, cells.data(), support);
+}
+
+int pagan_fb_site_marginals_batch(int32_t n, pagan_fb *const *fbs, double *const *pX, double *const *pM_left, int32_t *const *best_j,
+                                  double *const *best_p_left, double *const *pY, double *const *pM_right, int32_t *const *best_i,
+                                  double *const *best_p_right) {
+    void *const *const o[8] = {(void *const *)pX, (void *const *)pM_left, (void *const *)best_j, (void *const *)best_p_left,
+                               (void *const *)pY, (void *const *)pM_right, (void *const *)best_i, (void *const *)best_p_right};
+    return fb_marginals(n, fbs, o);
+}
+
+int pagan_fb_site_marginals(pagan_fb *fb, double *pX, double *pM_left, int32_t *best_j, double *best_p_left, double *pY,
+                            double *pM_right, int32_t *best_i, double *best_p_right) {
+    if (!fb) return PAGAN_E_ARG;
+    return pagan_fb_site_marginals_batch(1, &fb, &pX, &pM_left, &best_j, &best_p_left, &pY, &pM_right, &best_i, &best_p_right);
+}
+
+int pagan_fb_post_ms(const pagan_fb *fb, double ms[3]) {
+    if (!fb || !ms) return PAGAN_E_ARG;
+    for (int k = 0; k < 3; ++k) ms[k] = fb->post_ms[k];
+    return PAGAN_OK;
+}
+
+// What fb_stage's arena takes: F and B (24 B a cell each), the per-diagonal index and plan (20 B a diagonal), the graphs' lists
+// in both directions (sized for four edges a site: 96 B), the score table (up to 211 x 211 doubles) and the record's small
+// pieces; then the pool's allowance of a sixteenth (FbArenaPool::take).  Only the lists are an estimate.
+int64_t pagan_fb_predict_bytes(int32_t left_sites, int32_t right_sites, const pagan_band *band) {
+    const int64_t cells = pagan_dp_count_cells(left_sites, right_sites, band);
+    if (cells < 0) return cells;
+    const int64_t nd = (int64_t)left_sites + right_sites - 3;
+    const int64_t need = 48 * cells + 20 * nd + 96 * ((int64_t)left_sites + right_sites) + (512 << 10) + 8192;
+    return need + need / 16;
+}
+
+// u[s] = (mix(mix(mix(seed) ^ node) ^ s) >> 11) * 2^-53, mix = splitmix64's output function of x + 0x9E3779B97F4A7C15
+int pagan_sample_uniforms(uint64_t seed, int32_t node, int32_t n, double *u) {
+    if (n < 0 || (n > 0 && !u)) return PAGAN_E_ARG;
+    const uint64_t key = fb_splitmix64(fb_splitmix64(seed) ^ (uint64_t)(int64_t)node);
+    for (int s = 0; s < n; ++s) u[s] = (double)(fb_splitmix64(key ^ (uint64_t)s) >> 11) * (1.0 / 9007199254740992.0);
     return PAGAN_OK;
 }
 

@@ -126,6 +126,13 @@ struct NodeWork {                // everything one internal node's alignment con
     bool has_job = false;        // gl/gr/pm/pb are valid: this process prepared and aligned the node
     int  device = -1;            // device the alignment ran on (-1: another rank)
     bool parent_pending = false; // imported: the result is stored, the parent graph is built when somebody needs it (ensure_graph)
+    // the forward/backward pass of the node (full_probability / sample_path), on the band the node finally used
+    bool has_fb = false;
+    double log_fwd = 0, log_bwd = 0, fb_sweep_ms = 0, fb_post_ms = 0;
+    std::vector<double> support;         // [res.n_cols] posterior of every column's own cell, -1 at skip columns
+    bool has_marg = false;               // full_probability == 2: the site marginals (pagan_fb_site_marginals' eight arrays)
+    std::vector<double> mg_d[6];         // pX, pM_left, best_p_left [Lx]; pY, pM_right, best_p_right [Ly]
+    std::vector<int32_t> mg_i[2];        // best_j [Lx], best_i [Ly]
 };
 
 } // namespace
@@ -207,6 +214,99 @@ int align_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, double *f
 }
 
 int host_threads_of(const pagan_msa *m);
+
+// The compute_full_score pass of the nodes `ks` on device `dev` (viterbi_alignment.cpp:329-371), behind their Viterbi batch:
+// pagan_fb_run_batch in sub-batches that fit the memory budget by pagan_fb_predict_bytes, the model's probability-space view
+// at the node's distance, the band the node finally used.  Per node: the totals, the support of its path's columns (one
+// gather), with full_probability == 2 the site marginals (one launch per pass and sub-batch).  The handles are destroyed before
+// this returns: before the parents are built.
+// sample_path: there was no Viterbi batch; the node's result is a path sampled from its forward matrix on the host
+// (pagan_fb_sample_path downloads the matrix: 24 B a cell) with the numbers pagan_sample_uniforms gives for (sample_seed, public
+// node id) -- no state shared between nodes, so neither batching nor the device that took a node changes its path.  A banded
+// node whose full probability is 0 is handed back in `retry` (run again without the band, as an unreachable Viterbi corner is).
+int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads, std::vector<int> *retry) {
+    int64_t budget = 0;
+    int rc = device_budget(m, dev, &budget);
+    if (rc != PAGAN_OK) return rc;
+    pagan_opts po;
+    po.flags = 0; po.device = dev;
+    const bool sample = m->opts.sample_path != 0, marg = m->opts.full_probability == 2;
+    size_t at = 0;
+    while (at < ks.size()) {
+        std::vector<int> which;
+        int64_t used = 0;
+        while (at < ks.size()) {
+            NodeWork &w = m->work[ks[at]];
+            const int64_t need = pagan_fb_predict_bytes(w.gl.n_sites, w.gr.n_sites, w.banded ? &w.pb : nullptr);
+            if (need < 0) return (int)need;
+            if (need > budget) return PAGAN_E_MEMCAP;
+            if (!which.empty() && used + need > budget) break;
+            used += need;
+            which.push_back(ks[at]); ++at;
+        }
+        const int n = (int)which.size();
+        std::vector<pagan_model_prob> mp(n);
+        std::vector<const pagan_graph *> gl(n), gr(n);
+        std::vector<const pagan_model_prob *> mpp(n);
+        std::vector<const pagan_band *> bd(n);
+        for (int q = 0; q < n; ++q) {
+            NodeWork &w = m->work[which[q]];
+            mp[q] = w.model->prob_view();
+            gl[q] = &w.gl; gr[q] = &w.gr; mpp[q] = &mp[q]; bd[q] = w.banded ? &w.pb : nullptr;
+        }
+        std::vector<pagan_fb *> fbs(n, nullptr);
+        rc = pagan_fb_run_batch(n, gl.data(), gr.data(), mpp.data(), bd.data(), &po, fbs.data());
+        if (rc != PAGAN_OK) return rc;
+        std::vector<int> rcs(n, PAGAN_OK);
+        std::vector<char> again(n, 0);
+        parallel_for(n, threads, [&](int q) {
+            NodeWork &w = m->work[which[q]];
+            double ms[2] = {0, 0};
+            int r = pagan_fb_totals(fbs[q], &w.log_fwd, &w.log_bwd, nullptr);
+            if (r == PAGAN_OK) r = pagan_fb_kernel_ms(fbs[q], ms);
+            w.fb_sweep_ms = ms[0] + ms[1]; w.fb_post_ms = 0;
+            w.has_marg = false; w.support.clear();
+            if (r == PAGAN_OK && sample) {
+                if (w.has_res) { pagan_result_free(&w.res); w.has_res = false; }
+                if (!(w.log_fwd > -HUGE_VAL) && w.banded) { again[q] = 1; rcs[q] = PAGAN_OK; return; }
+                const int n_u = w.gl.n_sites + w.gr.n_sites - 1;                     // Lx + Ly + 1
+                std::vector<double> u((size_t)n_u);
+                r = pagan_sample_uniforms(m->opts.sample_seed, w.node, n_u, u.data());
+                if (r == PAGAN_OK) r = pagan_fb_sample_path(fbs[q], u.data(), n_u, &w.res, nullptr, nullptr);
+                w.has_res = r == PAGAN_OK;
+            }
+            if (r == PAGAN_OK && w.res.status == PAGAN_DP_REACHED) {
+                w.support.assign((size_t)w.res.n_cols, 0.0);
+                r = pagan_fb_path_support(fbs[q], w.res.cols, w.res.n_cols, w.support.data());
+            }
+            rcs[q] = r;
+        });
+        for (int q = 0; q < n && rc == PAGAN_OK; ++q) rc = rcs[q];
+        if (rc == PAGAN_OK && marg) {
+            std::vector<double *> pd[6];
+            std::vector<int32_t *> pi[2];
+            for (int q = 0; q < n; ++q) {
+                NodeWork &w = m->work[which[q]];
+                const size_t Lx = (size_t)w.gl.n_sites - 1, Ly = (size_t)w.gr.n_sites - 1;
+                for (int a = 0; a < 6; ++a) { w.mg_d[a].assign(a < 3 ? Lx : Ly, 0.0); pd[a].push_back(again[q] ? nullptr : w.mg_d[a].data()); }
+                for (int a = 0; a < 2; ++a) { w.mg_i[a].assign(a < 1 ? Lx : Ly, 0); pi[a].push_back(again[q] ? nullptr : w.mg_i[a].data()); }
+                w.has_marg = !again[q];
+            }
+            rc = pagan_fb_site_marginals_batch(n, fbs.data(), pd[0].data(), pd[1].data(), pi[0].data(), pd[2].data(),
+                                               pd[3].data(), pd[4].data(), pi[1].data(), pd[5].data());
+        }
+        for (int q = 0; q < n; ++q) {
+            NodeWork &w = m->work[which[q]];
+            double ms[3] = {0, 0, 0};
+            if (rc == PAGAN_OK && pagan_fb_post_ms(fbs[q], ms) == PAGAN_OK) w.fb_post_ms = ms[0] + ms[1] + ms[2];
+            w.has_fb = rc == PAGAN_OK && !again[q];
+            if (again[q]) retry->push_back(which[q]);
+            pagan_fb_destroy(fbs[q]);
+        }
+        if (rc != PAGAN_OK) return rc;
+    }
+    return PAGAN_OK;
+}
 
 void build_rows(pagan_msa *m) {
     const int n = m->n_leaves;
@@ -716,14 +816,30 @@ int run_unit(pagan_msa *m, const std::vector<int> &ids, int dev, int round, int 
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
     for (size_t r = 0; r < ids.size(); ++r) ks[r] = ids[order[r]] - n;
     double fill_ms = 0, trace_ms = 0;
-    int rc = align_on_device(m, ks, dev, &fill_ms, &trace_ms);
-    if (rc != PAGAN_OK) return rc;
-    std::vector<int> retry;
-    for (int k : ks) if (m->work[k].banded && m->work[k].res.status == PAGAN_DP_UNREACHABLE) retry.push_back(k);
-    if (!retry.empty()) {
-        for (int k : retry) { m->work[k].banded = false; pagan_result_free(&m->work[k].res); m->work[k].has_res = false; }
-        rc = align_on_device(m, retry, dev, &fill_ms, &trace_ms);
+    int rc = PAGAN_OK;
+    const bool sample = m->opts.sample_path != 0;
+    if (!sample) {
+        rc = align_on_device(m, ks, dev, &fill_ms, &trace_ms);
         if (rc != PAGAN_OK) return rc;
+        std::vector<int> retry;
+        for (int k : ks) if (m->work[k].banded && m->work[k].res.status == PAGAN_DP_UNREACHABLE) retry.push_back(k);
+        if (!retry.empty()) {
+            for (int k : retry) { m->work[k].banded = false; pagan_result_free(&m->work[k].res); m->work[k].has_res = false; }
+            rc = align_on_device(m, retry, dev, &fill_ms, &trace_ms);
+            if (rc != PAGAN_OK) return rc;
+        }
+    }
+    if (sample || m->opts.full_probability) {
+        // behind the retry: on the band the node finally used (--sample-path: in the Viterbi batch's place, VA:395-417)
+        std::vector<int> retry, none;
+        rc = fb_on_device(m, ks, dev, threads, &retry);
+        if (rc != PAGAN_OK) return rc;
+        if (!retry.empty()) {
+            for (int k : retry) m->work[k].banded = false;
+            rc = fb_on_device(m, retry, dev, threads, &none);
+            if (rc != PAGAN_OK) return rc;
+        }
+        for (int k : ks) if (!m->work[k].has_res) return PAGAN_E_INTERNAL;
     }
     const double t_dp = now_s() - t0;
     t0 = now_s();
@@ -774,6 +890,7 @@ int64_t pagan_msa_node_cost(const pagan_msa *m, int32_t id) {
 // device that finishes early picks up what is ready without waiting for the others.
 int pagan_msa_align_nodes(pagan_msa *m, int32_t n_ids, const int32_t *ids) {
     if (!m || m->aligned || n_ids < 0 || (n_ids > 0 && !ids)) return PAGAN_E_ARG;
+    if (m->backend && (m->opts.full_probability || m->opts.sample_path)) return PAGAN_E_NODEVICE;   // (the seam has no forward/backward pass: never skipped silently)
     for (int k = 0; k < n_ids; ++k)
         if (ids[k] < m->n_leaves || ids[k] >= 2 * m->n_leaves - 1 || !node_ready(m, ids[k])) return PAGAN_E_ARG;
     if (n_ids == 0) return PAGAN_OK;
@@ -842,6 +959,7 @@ int pagan_msa_parents_built(const pagan_msa *m) { return m ? m->parents_built.lo
 
 int pagan_msa_align(pagan_msa *m) {
     if (!m || m->aligned) return PAGAN_E_ARG;
+    if (m->backend && (m->opts.full_probability || m->opts.sample_path)) return PAGAN_E_NODEVICE;
     int ndev = m->opts.n_devices;
     int first_dev = m->opts.first_device;
     if (ndev <= 0) { ndev = 1; if (!m->backend && hipGetDevice(&first_dev) != hipSuccess) return PAGAN_E_NODEVICE; }
@@ -1002,6 +1120,7 @@ int pagan_msa_import_result(pagan_msa *m, const void *buf, int64_t bytes) {
     }
     if (!good) { pagan_result_free(&r); std::memset(&r, 0, sizeof(r)); return PAGAN_E_ARG; }
     w.has_res = true; w.has_job = false; w.device = -1; w.node = id; w.level = m->rounds;
+    w.has_fb = false; w.has_marg = false;                          // (support is not part of the exchange format)
     w.imp_l = sites_of(m, m->id_of_tree[t.left]); w.imp_r = sites_of(m, m->id_of_tree[t.right]);   // (no job was prepared here: node_info reports the children's sizes from these)
     if (r.status != PAGAN_DP_REACHED) return PAGAN_E_INTERNAL;       // (the owner retries an unreachable corner itself: it never posts one)
     w.parent_pending = true;
@@ -1038,6 +1157,69 @@ int pagan_msa_node_job(const pagan_msa *m, int32_t k, pagan_job *o) {
 int pagan_msa_node_result(const pagan_msa *m, int32_t k, pagan_result *o) {
     if (!m || !o || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_res) return PAGAN_E_ARG;
     *o = m->work[k].res;
+    return PAGAN_OK;
+}
+
+// ---- what the forward/backward pass left at a node (full_probability / sample_path); PAGAN_E_ARG for a node this process
+// did not align
+int pagan_msa_node_fb(const pagan_msa *m, int32_t k, double out[4]) {
+    if (!m || !out || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_fb) return PAGAN_E_ARG;
+    const NodeWork &w = m->work[k];
+    out[0] = w.log_fwd; out[1] = w.log_bwd; out[2] = w.fb_sweep_ms; out[3] = w.fb_post_ms;
+    return PAGAN_OK;
+}
+
+int pagan_msa_node_support(const pagan_msa *m, int32_t k, double *support) {
+    if (!m || !support || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_fb) return PAGAN_E_ARG;
+    const NodeWork &w = m->work[k];
+    if (!w.support.empty()) std::memcpy(support, w.support.data(), 8 * w.support.size());
+    return PAGAN_OK;
+}
+
+int pagan_msa_node_marginals(const pagan_msa *m, int32_t k, double *pX, double *pM_left, int32_t *best_j, double *best_p_left,
+                             double *pY, double *pM_right, int32_t *best_i, double *best_p_right) {
+    if (!m || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_fb || !m->work[k].has_marg) return PAGAN_E_ARG;
+    const NodeWork &w = m->work[k];
+    double *const d[6] = {pX, pM_left, best_p_left, pY, pM_right, best_p_right};
+    int32_t *const i[2] = {best_j, best_i};
+    for (int a = 0; a < 6; ++a) if (d[a] && !w.mg_d[a].empty()) std::memcpy(d[a], w.mg_d[a].data(), 8 * w.mg_d[a].size());
+    for (int a = 0; a < 2; ++a) if (i[a] && !w.mg_i[a].empty()) std::memcpy(i[a], w.mg_i[a].data(), 4 * w.mg_i[a].size());
+    return PAGAN_OK;
+}
+
+int pagan_msa_node_model_prob(const pagan_msa *m, int32_t k, pagan_model_prob *out) {
+    if (!m || !out || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_job || !m->work[k].model) return PAGAN_E_ARG;
+    *out = m->work[k].model->prob_view();
+    return PAGAN_OK;
+}
+
+// A node's column support on the columns of the final alignment: the node's sites are followed up the tree, parent by parent,
+// to the root's sites, which are the alignment's columns (as build_rows follows them down).
+int pagan_msa_support_row(const pagan_msa *m, int32_t node, float *buf) {
+    if (!m || !m->aligned || !buf) return PAGAN_E_ARG;
+    if (node < m->n_leaves || node >= 2 * m->n_leaves - 1 || !m->work[node - m->n_leaves].has_fb) return PAGAN_E_ARG;
+    if (const int rc = ensure_rows(const_cast<pagan_msa *>(m))) return rc;
+    const NodeWork &w = m->work[node - m->n_leaves];
+    const int width = (int)m->rows[0].size() / (m->mf.type == kCodon ? 3 : 1);
+    for (int c = 0; c < width; ++c) buf[c] = -1.0f;
+    const int ns = m->graph[node]->g.n_sites();
+    if (ns != w.res.n_cols + 2 || (int)w.support.size() != w.res.n_cols) return PAGAN_E_INTERNAL;
+    std::vector<int32_t> at(ns);                                   // site of `node` -> site of the ancestor reached so far
+    for (int s = 0; s < ns; ++s) at[s] = s;
+    for (int t = m->tree_of_id[node]; m->tree[t].parent >= 0; t = m->tree[t].parent) {
+        const int pt = m->tree[t].parent;
+        const SeqGraph &pg = m->graph[m->id_of_tree[pt]]->g;
+        const std::vector<int32_t> &child = m->tree[pt].left == t ? pg.child_l : pg.child_r;
+        std::vector<int32_t> up((size_t)m->graph[m->id_of_tree[t]]->g.n_sites(), -1);
+        for (int s = 1; s < pg.n_sites() - 1; ++s) if (child[s] >= 0) up[child[s]] = s;
+        for (int s = 1; s < ns - 1; ++s) if (at[s] >= 0) at[s] = up[at[s]];
+    }
+    for (int k = 0; k < w.res.n_cols; ++k) {
+        const int ps = w.res.cols[k].path_state;
+        if (ps != PAGAN_MATCHED && ps != PAGAN_XGAPPED && ps != PAGAN_YGAPPED) continue;
+        const int c = at[k + 1] - 1;                               // (the root's site s is column s - 1)
+        if (c >= 0 && c < width) buf[c] = (float)w.support[k];
+    }
     return PAGAN_OK;
 }
 

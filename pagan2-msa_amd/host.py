@@ -22,7 +22,8 @@ class CMsaOpts(C.Structure):
                 ("host_threads", C.c_int32), ("truncate_branches", C.c_float), ("device_mem_budget", C.c_int64),
                 ("data_type", C.c_int32), ("pileup_rates", C.c_int32), ("anchor_mode", C.c_int32),
                 ("overlap_total", C.c_int32), ("overlap_partly", C.c_int32), ("force_gap", C.c_int32),
-                ("force_gap_threshold", C.c_int32), ("force_gap_wide", C.c_int32), ("mostcommon", C.c_int32)]
+                ("force_gap_threshold", C.c_int32), ("force_gap_wide", C.c_int32), ("mostcommon", C.c_int32),
+                ("full_probability", C.c_int32), ("sample_path", C.c_int32), ("sample_seed", C.c_uint64)]
 
 
 class CNodeInfo(C.Structure):
@@ -194,6 +195,16 @@ def _lib():
         L.pagan_pileup_set_batch_backend.restype = C.c_int
         L.pagan_pileup_destroy.argtypes = [vp]
         L.pagan_pileup_destroy.restype = None
+        L.pagan_msa_node_fb.argtypes = [vp, C.c_int32, f64p]
+        L.pagan_msa_node_fb.restype = C.c_int
+        L.pagan_msa_node_support.argtypes = [vp, C.c_int32, f64p]
+        L.pagan_msa_node_support.restype = C.c_int
+        L.pagan_msa_node_marginals.argtypes = [vp, C.c_int32, f64p, f64p, _i32p, f64p, f64p, f64p, _i32p, f64p]
+        L.pagan_msa_node_marginals.restype = C.c_int
+        L.pagan_msa_node_model_prob.argtypes = [vp, C.c_int32, C.POINTER(abi.CModelProb)]
+        L.pagan_msa_node_model_prob.restype = C.c_int
+        L.pagan_msa_support_row.argtypes = [vp, C.c_int32, _f32p]
+        L.pagan_msa_support_row.restype = C.c_int
         _declared = True
     return L
 
@@ -213,7 +224,8 @@ HOST_EXPORTED = ["pagan_assign_units", "pagan_msa_default_opts", "pagan_msa_crea
                  "pagan_pileup_default_opts", "pagan_pileup_create", "pagan_pileup_align", "pagan_pileup_n_steps",
                  "pagan_pileup_step_info", "pagan_pileup_step_job", "pagan_pileup_step_result",
                  "pagan_pileup_alignment_length", "pagan_pileup_alignment_row", "pagan_pileup_set_batch_backend",
-                 "pagan_pileup_destroy"]
+                 "pagan_pileup_destroy",
+                 "pagan_msa_node_fb", "pagan_msa_node_support", "pagan_msa_node_marginals", "pagan_msa_node_model_prob", "pagan_msa_support_row"]
 
 
 def _ip(a):
@@ -463,6 +475,12 @@ def model_prob(data_type, dist, base_freq=None):
     return abi.ModelProb(score.reshape(S, S).T, *params)
 
 
+def sample_uniforms(seed, node, n):
+    """pagan_sample_uniforms: the numbers the walk samples node `node`'s path with under sample_seed=seed."""
+    from . import sample_uniforms as f
+    return f(seed, node, n)
+
+
 def alphabets(data_type):
     """(leaf alphabet, ancestral alphabet) of a data type: 1 DNA, 2 protein."""
     a, b = C.create_string_buffer(256), C.create_string_buffer(256)
@@ -704,6 +722,53 @@ class Msa:
         if rc != 0:
             raise RuntimeError("pagan_msa_node_result failed: %d" % rc)
         return abi.Result(r)
+
+    # ---- what the forward/backward pass left at a node (full_probability= / sample_path=) ----
+    def _fb_check(self, rc, what):
+        if rc != 0:
+            from . import PaganError
+            raise PaganError(rc, what)
+
+    def node_fb(self, k):
+        """(log_fwd, log_bwd, device ms of the sweeps, device ms of support + marginals) of internal node k."""
+        out = (C.c_double * 4)()
+        self._fb_check(self._L.pagan_msa_node_fb(self._h, k, out), "pagan_msa_node_fb")
+        return tuple(out)
+
+    def node_support(self, k):
+        """Posterior of every column's own cell along node k's path; -1 at skip columns."""
+        out = np.zeros(self.node_result(k).cols.shape[0], np.float64)
+        self._fb_check(self._L.pagan_msa_node_support(self._h, k, out.ctypes.data_as(C.POINTER(C.c_double))), "pagan_msa_node_support")
+        return out
+
+    def node_marginals(self, k):
+        """Node k's site marginals (full_probability=2): the dict FullProbability.site_marginals returns."""
+        info = self.node_info(k)
+        Lx, Ly = info.left_sites - 1, info.right_sites - 1
+        f64p = C.POINTER(C.c_double)
+        out = {"pX": np.zeros(Lx), "pM_left": np.zeros(Lx), "best_j": np.zeros(Lx, np.int32), "best_p_left": np.zeros(Lx),
+               "pY": np.zeros(Ly), "pM_right": np.zeros(Ly), "best_i": np.zeros(Ly, np.int32), "best_p_right": np.zeros(Ly)}
+        args = [out[k_].ctypes.data_as(_i32p if k_.startswith("best_") and not k_.startswith("best_p") else f64p)
+                for k_ in ("pX", "pM_left", "best_j", "best_p_left", "pY", "pM_right", "best_i", "best_p_right")]
+        self._fb_check(self._L.pagan_msa_node_marginals(self._h, k, *args), "pagan_msa_node_marginals")
+        return out
+
+    def node_model_prob(self, k):
+        """abi.ModelProb copy of the probability-space model node k's forward/backward pass takes."""
+        v = abi.CModelProb()
+        self._fb_check(self._L.pagan_msa_node_model_prob(self._h, k, C.byref(v)), "pagan_msa_node_model_prob")
+        S = v.n_states
+        score = np.ctypeslib.as_array(v.score, shape=(S * S,)).copy()
+        return abi.ModelProb(score.reshape(S, S).T, v.gap_open, v.gap_ext, v.non_gap)
+
+    def support_row(self, node):
+        """Node `node`'s column support on the final alignment's columns (float32, -1 where the node has no column)."""
+        n = self._L.pagan_msa_alignment_length(self._h)
+        if n < 0:
+            self._fb_check(n, "pagan_msa_alignment_length")
+        buf = np.zeros(n, np.float32)
+        self._fb_check(self._L.pagan_msa_support_row(self._h, node, _fp(buf)), "pagan_msa_support_row")
+        return buf
 
     def node_graph(self, node):
         return HGraph(self._L.pagan_msa_node_graph(self._h, node), owned=False, keep=self)

@@ -1,0 +1,122 @@
+"""GPU: the forward/backward pass inside the tree walk (host_tree.cpp: full_probability, sample_path, sample_seed) -- the
+walk's per-node totals, column support and site marginals against the same calls made pair by pair on the node's job, the
+alignment untouched by full_probability, and sampled walks that depend on (seed, node) only."""
+import numpy as np
+import pytest
+
+import pagan2_msa_amd as pgm
+from pagan2_msa_amd import abi, host, synth
+
+pytestmark = pytest.mark.gpu
+
+
+def _trees():
+    a = synth.evolve_balanced(8, 400, branch=0.04, sub=0.04, indel_start=0.01, mean_len=4, seed=46)
+    b = synth.evolve_balanced(4, 3000, branch=0.01, sub=0.01, indel_start=0.008, mean_len=4, seed=61)
+    return [(a, {"use_anchors": 0}), (b, {"use_anchors": 1})]
+
+
+@pytest.fixture(scope="module")
+def walks(pg):
+    """[(off, with full_probability=2)] per tree, aligned once."""
+    out = []
+    for (names, seqs, nwk), opts in _trees():
+        off = host.Msa(names, seqs, nwk, **opts).align()
+        fp2 = host.Msa(names, seqs, nwk, full_probability=2, **opts).align()
+        out.append((off, fp2, (names, seqs, nwk), opts))
+    return out
+
+
+def _same_walk(a, b):
+    assert a.alignment_all() == b.alignment_all()
+    for k in range(a.n_internal):
+        ra, rb = a.node_result(k), b.node_result(k)
+        assert ra.same_alignment(rb), k
+        assert np.float64(a.node_info(k).score).tobytes() == np.float64(b.node_info(k).score).tobytes()
+
+
+def test_full_probability_leaves_the_alignment_alone_and_reports_every_node(pg, walks):
+    for off, fp2, (names, seqs, nwk), opts in walks:
+        fp1 = host.Msa(names, seqs, nwk, full_probability=1, **opts).align()
+        _same_walk(off, fp1)
+        _same_walk(off, fp2)
+        n = len(names)
+        banded = 0
+        for k in range(fp1.n_internal):
+            left, right, _model, band = fp1.node_job(k)
+            banded += band is not None
+            res = fp1.node_result(k)
+            fb = pgm.FullProbability(left, right, fp1.node_model_prob(k), band)
+            lf, lb, sweep_ms, post_ms = fp1.node_fb(k)
+            assert (lf, lb) == (fb.log_fwd, fb.log_bwd), k
+            assert abs(lf - lb) <= 1e-7 * abs(lf)
+            assert sweep_ms >= 0 and post_ms >= 0
+            sup = fp1.node_support(k)
+            assert sup.tobytes() == fb.path_support(res.cols).tobytes(), k
+            assert np.all(sup[res.cols[:, 2] >= 5] == -1.0) and np.all(sup[res.cols[:, 2] <= 4] > 0)
+            fb.close()
+            row = fp1.support_row(n + k)
+            assert row.shape == (len(fp1.alignment()[0]),) and row.dtype == np.float32
+            assert np.array_equal(row[row >= 0], sup[sup >= 0].astype(np.float32)), k
+            with pytest.raises(pgm.PaganError) as e:                   # marginals were not asked for
+                fp1.node_marginals(k)
+            assert e.value.code == abi.PAGAN_E_ARG
+        assert banded == (fp1.n_internal if opts["use_anchors"] else 0)
+        # the root's columns are the alignment's: its support covers every column that is not a skip column
+        root = fp1.n_internal - 1
+        rrow, rsup = fp1.support_row(n + root), fp1.node_support(root)
+        assert np.array_equal(rrow, rsup.astype(np.float32))
+        with pytest.raises(pgm.PaganError) as e:
+            fp1.support_row(0)
+        assert e.value.code == abi.PAGAN_E_ARG
+        with pytest.raises(pgm.PaganError) as e:
+            off.node_fb(0)
+        assert e.value.code == abi.PAGAN_E_ARG
+
+
+def test_full_probability_2_keeps_the_site_marginals(pg, walks):
+    for _off, fp2, _tree, _opts in walks:
+        for k in range(fp2.n_internal):
+            left, right, _model, band = fp2.node_job(k)
+            fb = pgm.FullProbability(left, right, fp2.node_model_prob(k), band)
+            want, got = fb.site_marginals(), fp2.node_marginals(k)
+            assert set(want) == set(got)
+            for name in want:
+                assert want[name].tobytes() == got[name].tobytes(), (k, name)
+            assert fp2.node_support(k).tobytes() == fb.path_support(fp2.node_result(k).cols).tobytes()
+            fb.close()
+
+
+def _cols(msa):
+    return [msa.node_result(k).cols.copy() for k in range(msa.n_internal)]
+
+
+def test_sampled_walks_depend_on_seed_and_node_only(pg, walks):
+    for _off, _fp2, (names, seqs, nwk), opts in walks:
+        n = len(names)
+        a = host.Msa(names, seqs, nwk, sample_path=1, sample_seed=1, **opts).align()
+        b = host.Msa(names, seqs, nwk, sample_path=1, sample_seed=1, **opts).align()
+        c = host.Msa(names, seqs, nwk, sample_path=1, sample_seed=2, **opts).align()
+        assert a.alignment_all() == b.alignment_all()
+        assert any(not np.array_equal(x, y) for x, y in zip(_cols(a), _cols(c)))
+        # node by node instead of level by level: the same rows
+        d = host.Msa(names, seqs, nwk, sample_path=1, sample_seed=1, **opts)
+        while d.remaining > 0:
+            d.align_nodes(d.ready()[-1:])
+        d.finish()
+        assert d.alignment_all() == a.alignment_all()
+        for k in range(a.n_internal):
+            left, right, _model, band = a.node_job(k)
+            res = a.node_result(k)
+            fb = pgm.FullProbability(left, right, a.node_model_prob(k), band)
+            u = host.sample_uniforms(1, n + k, left.n_sites + right.n_sites - 1)
+            want, _visited = fb.sample_path(u)
+            assert np.array_equal(want.cols, res.cols), k
+            assert np.array_equal(want.left_used, res.left_used) and np.array_equal(want.right_used, res.right_used)
+            lf, lb, _, _ = a.node_fb(k)
+            assert a.node_info(k).score == lf == fb.log_fwd and res.status == 0
+            assert a.node_support(k).tobytes() == fb.path_support(res.cols).tobytes()
+            fb.close()
+            # every site of both children is used once, in order
+            assert [x for x in res.cols[:, 0] if x >= 0] == list(range(1, left.n_sites - 1))
+            assert [x for x in res.cols[:, 1] if x >= 0] == list(range(1, right.n_sites - 1))
