@@ -338,6 +338,45 @@ int64_t pagan_fb_predict_bytes(int32_t left_sites, int32_t right_sites, const pa
  * (splitmix64's step as a counter-based generator.)  A path sampled with these does not depend on which thread, device or
  * rank handled the node, nor on what was sampled before it.                                                                 */
 int  pagan_sample_uniforms(uint64_t seed, int32_t node, int32_t n, double *u);
+/* Host only: the stream of path `path` (>= 0) of a node's ensemble -- the same key, the path in the counter's upper half:
+ *     u[s] = (mix(mix(mix(seed) ^ node) ^ (s + ((uint64_t)path << 32))) >> 11) / 2^53
+ * Path 0 is pagan_sample_uniforms bit for bit.                                                                               */
+int  pagan_sample_uniforms_path(uint64_t seed, int32_t node, int32_t path, int32_t n, double *u);
+
+/* ---- K sampled paths per pair, drawn on the device (dp_fb_sample.inc) ----------------------------------------
+ * The reference draws additional paths one at a time (--sample-additional-paths, viterbi_alignment.cpp:420-451).  Here one
+ * launch draws n_paths paths for each pair of a batch over the forward matrices where pagan_fb_run left them: path p of a pair
+ * is what pagan_fb_sample_path gives for pagan_sample_uniforms_path(seed, node, p, Lx + Ly + 1), cell for cell (the device's exp
+ * differs from the host's in the last bits: a pick can differ only where total * u lies within a few ulp of a running sum).
+ * Only the paths' traces (12 B a step) and summaries ever leave the device, never the matrix.  All pairs of a batch are on one
+ * device, the handles' own; the calling thread is put on it and restored on exit.  A handle stays valid after
+ * pagan_fb_destroy of its pair; the pair's graphs must outlive it (pagan_fb_samples_result reads them).
+ * Errors: n_paths < 1, a NULL handle, unknown flags, handles of different devices: PAGAN_E_ARG.                               */
+typedef struct pagan_fb_samples pagan_fb_samples;
+#define PAGAN_SAMPLE_NO_TRACES 1u   /* keep the summaries only (ensembles on large pairs); visited / result: PAGAN_E_ARG    */
+int  pagan_fb_sample_paths_batch(int32_t n, pagan_fb *const *fbs, uint64_t seed, const int32_t *nodes,
+                                 int32_t n_paths, uint32_t flags, pagan_fb_samples **out); /* out[n] */
+int  pagan_fb_sample_paths(pagan_fb *fb, uint64_t seed, int32_t node, int32_t n_paths, uint32_t flags,
+                           pagan_fb_samples **out);
+/* Per path ([n_paths] each, any NULL): status 0 sampled, 1 full probability zero, 2 internal (no candidate, or more than
+ * Lx + Ly steps); the steps of its trace; how many of them left an M, X, Y cell; log_q = the log posterior probability of the
+ * path (the sum over its picks, the end corner's included, of log(exp(lw_k - hi) / total)).                                  */
+int  pagan_fb_samples_summary(const pagan_fb_samples *s, int32_t *status, int32_t *n_steps,
+                              int32_t *n_m, int32_t *n_x, int32_t *n_y, double *log_q);
+/* one path's cells end -> start as (i, j, state), 3 * (Lx + Ly) ints at most: pagan_fb_sample_path's `visited`             */
+int  pagan_fb_samples_visited(pagan_fb_samples *s, int32_t path, int32_t *visited, int32_t *n_visited);
+/* all paths' cells in ONE copy of the trace buffer: visited [n_paths][Lx + Ly][3] (0 behind a path's last step),
+ * n_visited [n_paths] (may be NULL)                                                                                        */
+int  pagan_fb_samples_visited_all(pagan_fb_samples *s, int32_t *visited, int32_t *n_visited);
+/* replay of one trace: pagan_fb_sample_path's result (score = log full probability; a path of status 1 replays as the
+ * unreachable result, one of status 2 is PAGAN_E_INTERNAL); free with pagan_result_free                                    */
+int  pagan_fb_samples_result(pagan_fb_samples *s, int32_t path, pagan_result *out);
+/* device time of pg_fb_sample, milliseconds: booked at the batch's first pair, 0 at the others (as pagan_fb_post_ms is)    */
+int  pagan_fb_samples_ms(const pagan_fb_samples *s, double *ms);
+/* Host only: the device bytes one pair's samples take -- 12 B a path step with traces, 64 B a path of summary; nothing that
+ * grows with the product of the lengths.                                                                                   */
+int64_t pagan_fb_sample_predict_bytes(int32_t left_sites, int32_t right_sites, int32_t n_paths, uint32_t flags);
+void pagan_fb_samples_destroy(pagan_fb_samples *s);
 
 const char *pagan_dp_version(void);
 

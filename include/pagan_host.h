@@ -139,6 +139,13 @@ int     pagan_msa_node_device(const pagan_msa *m, int32_t k);              /* de
  * batch was dealt to arrives in opts->device.  NULL restores the HIP path.                                    */
 typedef int (*pagan_batch_fn)(int32_t n, const pagan_job *jobs, const pagan_opts *opts, pagan_result *out, void *user);
 int     pagan_msa_set_batch_backend(pagan_msa *m, pagan_batch_fn fn, void *user);
+/* Where a walk with sample_path set draws its paths (a setter: pagan_msa_opts does not grow).  0, the default: on the host,
+ * pagan_fb_sample_path behind a download of the node's forward matrix (24 B a cell).  1: on the device -- a sub-batch's nodes
+ * go through one pagan_fb_sample_paths_batch(n, fbs, sample_seed, public node ids, 1, 0), a node's result is the replay of
+ * its path 0, and 12 B a path step come to the host.  The same paths either way (pagan_dp.h); support, the retry without the
+ * tunnel and the totals do not change; the sampler's device time is added to pagan_msa_node_fb's out[3] at the sub-batch's
+ * first node.  Call before aligning.                                                                                        */
+int     pagan_msa_set_sampler(pagan_msa *m, int32_t on_device);
 int  pagan_msa_n_internal(const pagan_msa *m);
 int  pagan_msa_node_info(const pagan_msa *m, int32_t k, pagan_node_info *out);
 /* Borrowed views (valid until pagan_msa_destroy) of what node k's alignment consumed and

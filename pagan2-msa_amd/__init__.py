@@ -94,6 +94,7 @@ class FullProbability:
         fb.log_fwd, fb.log_bwd          log max_end.fwd_score, log match[0][0].bwd_score
         fb.posterior()                  [Lx, Ly, 3] (X, Y, M), compute_posterior_score
         fb.sample_path(u)               Result with the shape of a Viterbi result
+        fb.sample_paths(seed, node, K)  K paths drawn on the device (SampledPaths)
     """
 
     def __init__(self, left, right, model_prob, band=None, device=-1, _handle=None):
@@ -173,6 +174,11 @@ class FullProbability:
         finally:
             self._L.pagan_result_free(C.byref(res))
 
+    def sample_paths(self, seed, node, n_paths, traces=True):
+        """pagan_fb_sample_paths: n_paths paths drawn on the device (pg_fb_sample); path p is what sample_path gives for
+        sample_uniforms_path(seed, node, p, Lx + Ly + 1).  Returns a SampledPaths."""
+        return sample_paths_batch([self], seed, [node], n_paths, traces)[0]
+
     def close(self):
         if self._h:
             self._L.pagan_fb_destroy(self._h)
@@ -183,6 +189,90 @@ class FullProbability:
             self.close()
         except Exception:
             pass
+
+
+class SampledPaths:
+    """pagan_fb_samples: the paths one pg_fb_sample launch drew for a pair -- summaries on the host, traces on the device until
+    a path is asked for.  Keeps its FullProbability (and with it the graphs result() reads) alive."""
+
+    def __init__(self, fb, handle, n_paths, traces):
+        import numpy as np
+        self._np = np
+        self._L = lib()
+        self._fb = fb
+        self._h = handle
+        self.n_paths = int(n_paths)
+        self.traces = bool(traces)
+        self.max_steps = fb.shape[0] + fb.shape[1]
+        ms = C.c_double()
+        _check(self._L.pagan_fb_samples_ms(self._h, C.byref(ms)), "pagan_fb_samples_ms")
+        self.ms = ms.value               # device ms of pg_fb_sample, booked at the batch's first pair
+
+    def summary(self):
+        """dict of status, n_steps, n_m, n_x, n_y (int32 [n_paths]) and log_q (float64 [n_paths])."""
+        np = self._np
+        i32p = C.POINTER(C.c_int32)
+        out = {k: np.zeros(self.n_paths, np.int32) for k in ("status", "n_steps", "n_m", "n_x", "n_y")}
+        out["log_q"] = np.zeros(self.n_paths, np.float64)
+        _check(self._L.pagan_fb_samples_summary(self._h, *[out[k].ctypes.data_as(i32p) for k in ("status", "n_steps", "n_m", "n_x", "n_y")],
+                                                out["log_q"].ctypes.data_as(C.POINTER(C.c_double))), "pagan_fb_samples_summary")
+        return out
+
+    def visited(self, p):
+        """Path p's cells end -> start as rows (i, j, state): FullProbability.sample_path's second value."""
+        vis = self._np.zeros((self.max_steps + 1, 3), self._np.int32)
+        n = C.c_int32()
+        _check(self._L.pagan_fb_samples_visited(self._h, int(p), vis.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)),
+               "pagan_fb_samples_visited")
+        return vis[:n.value].copy()
+
+    def visited_all(self):
+        """Every path's cells in one copy of the trace buffer: ([n_paths, Lx + Ly, 3] int32, [n_paths] step counts)."""
+        vis = self._np.zeros((self.n_paths, self.max_steps, 3), self._np.int32)
+        n = self._np.zeros(self.n_paths, self._np.int32)
+        _check(self._L.pagan_fb_samples_visited_all(self._h, vis.ctypes.data_as(C.POINTER(C.c_int32)), n.ctypes.data_as(C.POINTER(C.c_int32))),
+               "pagan_fb_samples_visited_all")
+        return vis, n
+
+    def result(self, p):
+        """The replay of path p's trace: a Result of FullProbability.sample_path's shape."""
+        res = abi.CResult()
+        rc = self._L.pagan_fb_samples_result(self._h, int(p), C.byref(res))
+        try:
+            _check(rc, "pagan_fb_samples_result")
+            return Result(res)
+        finally:
+            self._L.pagan_result_free(C.byref(res))
+
+    def close(self):
+        if self._h:
+            self._L.pagan_fb_samples_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sample_paths_batch(fbs, seed, nodes, n_paths, traces=True):
+    """pagan_fb_sample_paths_batch: n_paths paths for each FullProbability of one device in one launch (node k's key is
+    (seed, nodes[k])) -> [SampledPaths, ...]."""
+    import numpy as np
+    L = lib()
+    n = len(fbs)
+    ids = np.ascontiguousarray(nodes, np.int32)
+    assert ids.shape == (n,)
+    handles = (C.c_void_p * n)(*[fb._h for fb in fbs])
+    outs = (C.c_void_p * n)()
+    _check(L.pagan_fb_sample_paths_batch(n, handles, int(seed) & 0xFFFFFFFFFFFFFFFF, ids.ctypes.data_as(C.POINTER(C.c_int32)), int(n_paths),
+                                         0 if traces else abi.SAMPLE_NO_TRACES, outs), "pagan_fb_sample_paths_batch")
+    return [SampledPaths(fb, C.c_void_p(outs[k]), n_paths, traces) for k, fb in enumerate(fbs)]
+
+
+def fb_sample_predict_bytes(left_sites, right_sites, n_paths, traces=True):
+    return lib().pagan_fb_sample_predict_bytes(left_sites, right_sites, n_paths, 0 if traces else abi.SAMPLE_NO_TRACES)
 
 
 def debug_tiles(left, right, band=None):
@@ -332,6 +422,15 @@ def sample_uniforms(seed, node, n):
     u = np.zeros(n, np.float64)
     _check(lib().pagan_sample_uniforms(int(seed) & 0xFFFFFFFFFFFFFFFF, int(node), int(n), u.ctypes.data_as(C.POINTER(C.c_double))),
            "pagan_sample_uniforms")
+    return u
+
+
+def sample_uniforms_path(seed, node, path, n):
+    """pagan_sample_uniforms_path (host only): the stream of path `path` of node `node`'s ensemble; path 0 is sample_uniforms."""
+    import numpy as np
+    u = np.zeros(n, np.float64)
+    _check(lib().pagan_sample_uniforms_path(int(seed) & 0xFFFFFFFFFFFFFFFF, int(node), int(path), int(n), u.ctypes.data_as(C.POINTER(C.c_double))),
+           "pagan_sample_uniforms_path")
     return u
 
 

@@ -14,6 +14,7 @@ PAGAN_E_NODEVICE, PAGAN_E_NOMEM, PAGAN_E_INTERNAL = -5, -6, -7
 PAGAN_DP_REACHED, PAGAN_DP_UNREACHABLE = 0, 1
 OPT_NO_TERMINAL_EDGES = 1
 OPT_NO_REDUCED_TERMINAL_PEN = 2
+SAMPLE_NO_TRACES = 1
 X_MAT, Y_MAT, M_MAT = 0, 1, 2
 MATCHED, XGAPPED, YGAPPED, XSKIPPED, YSKIPPED = 2, 3, 4, 5, 6
 
@@ -261,6 +262,26 @@ def declare(lib):
     lib.pagan_fb_predict_bytes.restype = C.c_int64
     lib.pagan_sample_uniforms.argtypes = [C.c_uint64, C.c_int32, C.c_int32, f64p]
     lib.pagan_sample_uniforms.restype = C.c_int
+    lib.pagan_sample_uniforms_path.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, f64p]
+    lib.pagan_sample_uniforms_path.restype = C.c_int
+    lib.pagan_fb_sample_paths_batch.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, _i32p, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.pagan_fb_sample_paths_batch.restype = C.c_int
+    lib.pagan_fb_sample_paths.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.pagan_fb_sample_paths.restype = C.c_int
+    lib.pagan_fb_samples_summary.argtypes = [C.c_void_p, _i32p, _i32p, _i32p, _i32p, _i32p, f64p]
+    lib.pagan_fb_samples_summary.restype = C.c_int
+    lib.pagan_fb_samples_visited.argtypes = [C.c_void_p, C.c_int32, _i32p, _i32p]
+    lib.pagan_fb_samples_visited.restype = C.c_int
+    lib.pagan_fb_samples_visited_all.argtypes = [C.c_void_p, _i32p, _i32p]
+    lib.pagan_fb_samples_visited_all.restype = C.c_int
+    lib.pagan_fb_samples_result.argtypes = [C.c_void_p, C.c_int32, rp]
+    lib.pagan_fb_samples_result.restype = C.c_int
+    lib.pagan_fb_samples_ms.argtypes = [C.c_void_p, f64p]
+    lib.pagan_fb_samples_ms.restype = C.c_int
+    lib.pagan_fb_sample_predict_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
+    lib.pagan_fb_sample_predict_bytes.restype = C.c_int64
+    lib.pagan_fb_samples_destroy.argtypes = [C.c_void_p]
+    lib.pagan_fb_samples_destroy.restype = None
     lib.pagan_fb_destroy.argtypes = [C.c_void_p]
     lib.pagan_fb_destroy.restype = None
     lib.pagan_dp_version.argtypes = []
@@ -274,4 +295,6 @@ EXPORTED = ["pagan_dp_align", "pagan_dp_align_batch", "pagan_result_free", "paga
             "pagan_batch_cells", "pagan_batch_last_ms_detail", "pagan_batch_destroy", "pagan_batch_debug_trace", "pagan_dp_debug_plan", "pagan_dp_debug_far", "pagan_dp_debug_strips", "pagan_dp_debug_tiles", "pagan_dp_debug_compact", "pagan_dp_debug_tiles_staircase", "pagan_dp_release_cache", "pagan_dp_cached_device_bytes", "pagan_dp_debug_route", "pagan_batch_debug_scores", "pagan_batch_debug_backptrs", "pagan_batch_debug_poison", "pagan_batch_debug_followed", "pagan_batch_debug_poke_bp", "pagan_batch_debug_reruns",
             "pagan_fb_run", "pagan_fb_run_batch", "pagan_fb_totals", "pagan_fb_kernel_ms", "pagan_fb_groups", "pagan_fb_schedule", "pagan_fb_debug_route", "pagan_fb_dump", "pagan_fb_posterior_cells", "pagan_fb_sample_path",
             "pagan_path_cells", "pagan_fb_path_support", "pagan_fb_site_marginals", "pagan_fb_site_marginals_batch", "pagan_fb_post_ms", "pagan_fb_predict_bytes", "pagan_sample_uniforms",
+            "pagan_sample_uniforms_path", "pagan_fb_sample_paths_batch", "pagan_fb_sample_paths", "pagan_fb_samples_summary", "pagan_fb_samples_visited",
+            "pagan_fb_samples_visited_all", "pagan_fb_samples_result", "pagan_fb_samples_ms", "pagan_fb_sample_predict_bytes", "pagan_fb_samples_destroy",
             "pagan_fb_destroy", "pagan_dp_version"]

@@ -490,6 +490,7 @@ __global__ __launch_bounds__(FB_RG_THREADS) void pg_fb_backward_ring(const PgFbJ
 
 #include "dp_fb_deep.inc"
 #include "dp_fb_post.inc"
+#include "dp_fb_sample.inc"
 
 // ---- wide alignments: 64 x 64 blocks on a block-anti-diagonal schedule ----
 // Block (a, b) needs blocks (a', b') <= (a, b) only (bwd edges point to earlier sites), so the blocks of one block
@@ -1954,6 +1955,16 @@ int pagan_sample_uniforms(uint64_t seed, int32_t node, int32_t n, double *u) {
     return PAGAN_OK;
 }
 
+// The stream of path `path` of a node: the counter of pagan_sample_uniforms with the path in its upper half,
+// u[s] = (mix(key ^ (s + (path << 32))) >> 11) * 2^-53 -- path 0 is pagan_sample_uniforms bit for bit.  pg_fb_sample computes the
+// same numbers from (key, path, s) where it uses them (dp_fb_sample.inc, fs_uniform).
+int pagan_sample_uniforms_path(uint64_t seed, int32_t node, int32_t path, int32_t n, double *u) {
+    if (path < 0 || n < 0 || (n > 0 && !u)) return PAGAN_E_ARG;
+    const uint64_t key = fb_splitmix64(fb_splitmix64(seed) ^ (uint64_t)(int64_t)node);
+    for (int s = 0; s < n; ++s) u[s] = (double)(fb_splitmix64(key ^ ((uint64_t)s + ((uint64_t)path << 32))) >> 11) * (1.0 / 9007199254740992.0);
+    return PAGAN_OK;
+}
+
 // sample_new_path (VA:1193-1322): a path drawn from the posterior by walking back from the end corner; at every step
 // the predecessors are listed in the forward pass's candidate order with weight fwd(pred) * transition (add_sample_*,
 // VA:2309-2446) and the first one whose running sum reaches u * total is taken (VA:1757-1769).  u[k] in [0, 1) stands
@@ -2047,6 +2058,248 @@ int pagan_fb_sample_path(pagan_fb *fb, const double *u, int32_t n_u, pagan_resul
     trace.resize(trace.size() + 3, 0);
     return pagan_internal_replay(L, R, fb->dx.cells, endcell, fb->totals[0], trace.data(), out);
 }
+
+} // extern "C"
+
+// ---- K sampled paths per pair on the device (pg_fb_sample, dp_fb_sample.inc) ----
+// One allocation serves a whole batch call -- the job records, the launch records, every pair's summaries, traces and pack
+// buffer -- and lives as long as any of the batch's handles does.
+namespace {
+struct FbDevBuf {
+    int device = 0;
+    char *p = nullptr;
+    ~FbDevBuf() {
+        if (!p) return;
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        (void)hipSetDevice(device); (void)hipFree(p);
+        if (cur >= 0) (void)hipSetDevice(cur);
+    }
+};
+} // namespace
+
+struct pagan_fb_samples {
+    int device = 0;
+    int Lx = 0, Ly = 0, n_paths = 0, max_steps = 0;
+    uint32_t flags = 0;
+    const pagan_graph *L = nullptr, *R = nullptr;       // borrowed from the pagan_fb: must outlive the handle for result()
+    long long cells = 0;
+    double log_fwd = 0;
+    std::shared_ptr<FbDevBuf> buf;
+    const int *d_trace = nullptr;                       // [group][step][lane of the group][3]; null: PAGAN_SAMPLE_NO_TRACES
+    int *d_pack = nullptr;                              // [max_steps][3]: one path out of a group of several (n_paths > 1)
+    std::mutex pack_mu;
+    std::vector<int32_t> summary;                       // [n_paths][FS_SUMMARY_INTS], downloaded by the batch call
+    float ms = 0;                                       // pg_fb_sample (HIP events), at the batch's first pair
+};
+
+namespace {
+// bytes of one pair's part of the allocation: summaries, traces, pack buffer (each rounded up to 256)
+struct FsSizes { size_t summary, trace, pack; };
+static FsSizes fs_sizes(int Lx, int Ly, int n_paths, uint32_t flags) {
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t steps = (size_t)Lx + Ly;
+    const bool traces = !(flags & PAGAN_SAMPLE_NO_TRACES);
+    return {up(4 * (size_t)FS_SUMMARY_INTS * n_paths), traces ? up(12 * (size_t)n_paths * steps) : 0, traces && n_paths > 1 ? up(12 * steps) : 0};
+}
+
+// path `path`'s records, contiguous, three zero ints behind them (pagan_internal_replay's format); *n_steps of a path that was
+// not sampled (status 1 or 2): 0
+static int fs_fetch(pagan_fb_samples *s, int path, std::vector<int> *trace, int *n_steps) {
+    const int32_t *sm = s->summary.data() + (size_t)FS_SUMMARY_INTS * path;
+    const int n = sm[0] == 0 ? sm[6] : 0;
+    if (n < 0 || n > s->max_steps) return PAGAN_E_INTERNAL;
+    trace->assign(3 * ((size_t)n + 1), 0);
+    *n_steps = n;
+    if (n == 0) return PAGAN_OK;
+    int caller = 0;
+    FB_TRY(hipGetDevice(&caller));
+    FbDeviceScope on_device(s->device, caller);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    const int g = path / 64, lane = path % 64, width = std::min(64, s->n_paths - 64 * g);
+    const int *group = s->d_trace + 3 * (64ll * g * s->max_steps);
+    if (width == 1) {                                   // (one path a group: its records are one run already)
+        FB_TRY(hipMemcpy(trace->data(), group, 12 * (size_t)n, hipMemcpyDeviceToHost));
+        return PAGAN_OK;
+    }
+    std::lock_guard<std::mutex> lock(s->pack_mu);
+    hipLaunchKernelGGL(pg_fb_trace_pack, dim3((unsigned)std::min((n + 255) / 256, 1024)), dim3(256), 0, nullptr, group, width, lane, n, s->d_pack);
+    FB_TRY(hipGetLastError());
+    FB_TRY(hipMemcpy(trace->data(), s->d_pack, 12 * (size_t)n, hipMemcpyDeviceToHost));
+    return PAGAN_OK;
+}
+} // namespace
+
+extern "C" {
+
+// n_paths paths for each of n pairs of one device in one launch: grid = (groups of 64 paths, pairs).  The summaries come back
+// with the call; the traces stay on the device until somebody asks for a path (pagan_fb_samples_visited / _result).
+int pagan_fb_sample_paths_batch(int32_t n, pagan_fb *const *fbs, uint64_t seed, const int32_t *nodes, int32_t n_paths, uint32_t flags,
+                                pagan_fb_samples **out) {
+    if (n < 0 || n_paths < 1 || (flags & ~PAGAN_SAMPLE_NO_TRACES) || (n > 0 && (!fbs || !nodes || !out))) return PAGAN_E_ARG;
+    for (int k = 0; k < n; ++k) out[k] = nullptr;
+    for (int k = 0; k < n; ++k) if (!fbs[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
+    if (n == 0) return PAGAN_OK;
+    int caller = 0;
+    FB_TRY(hipGetDevice(&caller));
+    const int device = fbs[0]->device;
+    FbDeviceScope on_device(device, caller);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    size_t cur = 0;
+    auto take = [&](size_t bytes) { const size_t at = cur; cur = (cur + bytes + 255) / 256 * 256; return at; };
+    const size_t o_jobs = take((size_t)n * sizeof(PgFbJob)), o_recs = take((size_t)n * sizeof(PgFbSample));
+    const size_t in_bytes = cur;
+    std::vector<size_t> o_sum(n), o_trace(n), o_pack(n);
+    for (int k = 0; k < n; ++k) o_sum[k] = take(fs_sizes(fbs[k]->Lx, fbs[k]->Ly, n_paths, flags).summary);
+    const size_t sum_end = cur;
+    for (int k = 0; k < n; ++k) {
+        const FsSizes z = fs_sizes(fbs[k]->Lx, fbs[k]->Ly, n_paths, flags);
+        o_trace[k] = take(z.trace); o_pack[k] = take(z.pack);
+    }
+    std::shared_ptr<FbDevBuf> buf = std::make_shared<FbDevBuf>();
+    buf->device = device;
+    FB_TRY(hipMalloc((void **)&buf->p, cur));
+    const bool traces = !(flags & PAGAN_SAMPLE_NO_TRACES);
+    const int groups = (n_paths + 63) / 64;
+    std::vector<char> host(sum_end, 0);
+    for (int k = 0; k < n; ++k) {
+        PgFbSample R;
+        R.key = fb_splitmix64(fb_splitmix64(seed) ^ (uint64_t)(int64_t)nodes[k]);
+        R.n_paths = n_paths; R.groups = groups; R.max_steps = fbs[k]->Lx + fbs[k]->Ly; R.pad = 0;
+        R.trace = traces ? (int *)(buf->p + o_trace[k]) : nullptr;
+        R.summary = (int *)(buf->p + o_sum[k]);
+        std::memcpy(host.data() + o_jobs + (size_t)k * sizeof(PgFbJob), &fbs[k]->job, sizeof(PgFbJob));
+        std::memcpy(host.data() + o_recs + (size_t)k * sizeof(PgFbSample), &R, sizeof(R));
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0;
+    auto body = [&]() -> int {
+        FB_TRY(hipMemcpy(buf->p, host.data(), in_bytes, hipMemcpyHostToDevice));
+        FB_TRY(hipEventCreate(&e0)); FB_TRY(hipEventCreate(&e1));
+        FB_TRY(hipEventRecord(e0, nullptr));
+        for (int at = 0; at < n; at += 65535) {                    // (a grid's y extent)
+            const dim3 grid((unsigned)groups, (unsigned)std::min(65535, n - at));
+            hipLaunchKernelGGL(pg_fb_sample, grid, dim3(64), 0, nullptr, (const PgFbJob *)(buf->p + o_jobs) + at, (const PgFbSample *)(buf->p + o_recs) + at);
+        }
+        FB_TRY(hipGetLastError());
+        FB_TRY(hipEventRecord(e1, nullptr));
+        FB_TRY(hipMemcpy(host.data() + in_bytes, buf->p + in_bytes, sum_end - in_bytes, hipMemcpyDeviceToHost));
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        return PAGAN_OK;
+    };
+    const int rc = body();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (rc != PAGAN_OK) return rc;
+    for (int k = 0; k < n; ++k) {
+        pagan_fb_samples *s = new pagan_fb_samples();
+        s->device = device; s->Lx = fbs[k]->Lx; s->Ly = fbs[k]->Ly; s->n_paths = n_paths; s->max_steps = s->Lx + s->Ly; s->flags = flags;
+        s->L = fbs[k]->L; s->R = fbs[k]->R; s->cells = fbs[k]->dx.cells; s->log_fwd = fbs[k]->totals[0];
+        s->buf = buf;
+        s->d_trace = traces ? (const int *)(buf->p + o_trace[k]) : nullptr;
+        s->d_pack = traces && n_paths > 1 ? (int *)(buf->p + o_pack[k]) : nullptr;
+        const int32_t *sm = (const int32_t *)(host.data() + o_sum[k]);
+        s->summary.assign(sm, sm + (size_t)FS_SUMMARY_INTS * n_paths);
+        s->ms = k == 0 ? ms : 0.0f;
+        out[k] = s;
+    }
+    return PAGAN_OK;
+}
+
+int pagan_fb_sample_paths(pagan_fb *fb, uint64_t seed, int32_t node, int32_t n_paths, uint32_t flags, pagan_fb_samples **out) {
+    if (!fb || !out) return PAGAN_E_ARG;
+    return pagan_fb_sample_paths_batch(1, &fb, seed, &node, n_paths, flags, out);
+}
+
+int pagan_fb_samples_summary(const pagan_fb_samples *s, int32_t *status, int32_t *n_steps, int32_t *n_m, int32_t *n_x, int32_t *n_y,
+                             double *log_q) {
+    if (!s) return PAGAN_E_ARG;
+    for (int p = 0; p < s->n_paths; ++p) {
+        const int32_t *sm = s->summary.data() + (size_t)FS_SUMMARY_INTS * p;
+        if (status) status[p] = sm[0];
+        if (n_steps) n_steps[p] = sm[6];
+        if (n_m) n_m[p] = sm[7];
+        if (n_x) n_x[p] = sm[8];
+        if (n_y) n_y[p] = sm[9];
+        if (log_q) std::memcpy(&log_q[p], sm + 10, 8);
+    }
+    return PAGAN_OK;
+}
+
+// the path's cells end -> start as (i, j, state), 3 * (Lx + Ly) ints at most: pagan_fb_sample_path's `visited`
+int pagan_fb_samples_visited(pagan_fb_samples *s, int32_t path, int32_t *visited, int32_t *n_visited) {
+    if (!s || !s->d_trace || path < 0 || path >= s->n_paths || !visited) return PAGAN_E_ARG;
+    std::vector<int> trace;
+    int n = 0;
+    const int rc = fs_fetch(s, path, &trace, &n);
+    if (rc != PAGAN_OK) return rc;
+    for (int t = 0; t < n; ++t) { visited[3 * t] = trace[3 * t]; visited[3 * t + 1] = trace[3 * t + 1]; visited[3 * t + 2] = trace[3 * t + 2] & 3; }
+    if (n_visited) *n_visited = n;
+    return PAGAN_OK;
+}
+
+// every path's cells in ONE copy of the trace buffer: visited [n_paths][Lx + Ly][3] (rows behind a path's last step: 0),
+// n_visited [n_paths]
+int pagan_fb_samples_visited_all(pagan_fb_samples *s, int32_t *visited, int32_t *n_visited) {
+    if (!s || !s->d_trace || !visited) return PAGAN_E_ARG;
+    int caller = 0;
+    FB_TRY(hipGetDevice(&caller));
+    FbDeviceScope on_device(s->device, caller);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    const size_t ms = (size_t)s->max_steps;
+    std::vector<int32_t> raw(3 * (size_t)s->n_paths * ms);
+    if (!raw.empty()) FB_TRY(hipMemcpy(raw.data(), s->d_trace, 4 * raw.size(), hipMemcpyDeviceToHost));
+    for (int p = 0; p < s->n_paths; ++p) {
+        const int32_t *sm = s->summary.data() + (size_t)FS_SUMMARY_INTS * p;
+        const int n = sm[0] == 0 ? sm[6] : 0;
+        if (n < 0 || n > s->max_steps) return PAGAN_E_INTERNAL;
+        const int g = p / 64, lane = p % 64, width = std::min(64, s->n_paths - 64 * g);
+        const int32_t *group = raw.data() + 3 * (64 * (size_t)g * ms);
+        int32_t *o = visited + 3 * (size_t)p * ms;
+        for (int t = 0; t < n; ++t) {
+            const int32_t *r = group + 3 * ((size_t)t * width + lane);
+            o[3 * t] = r[0]; o[3 * t + 1] = r[1]; o[3 * t + 2] = r[2] & 3;
+        }
+        std::memset(o + 3 * (size_t)n, 0, 12 * (ms - (size_t)n));
+        if (n_visited) n_visited[p] = n;
+    }
+    return PAGAN_OK;
+}
+
+// the replay of one trace: pagan_fb_sample_path's result (score = log full probability; status 1: the unreachable result)
+int pagan_fb_samples_result(pagan_fb_samples *s, int32_t path, pagan_result *out) {
+    if (!s || !s->d_trace || path < 0 || path >= s->n_paths || !out) return PAGAN_E_ARG;
+    const int32_t *sm = s->summary.data() + (size_t)FS_SUMMARY_INTS * path;
+    int endcell[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (sm[0] == 1) {
+        endcell[0] = 1; endcell[4] = endcell[5] = -1;
+        return pagan_internal_replay(s->L, s->R, s->cells, endcell, s->log_fwd, nullptr, out);
+    }
+    if (sm[0] != 0) return PAGAN_E_INTERNAL;
+    std::vector<int> trace;
+    int n = 0;
+    const int rc = fs_fetch(s, path, &trace, &n);
+    if (rc != PAGAN_OK) return rc;
+    for (int k = 1; k <= 5; ++k) endcell[k] = sm[k];
+    endcell[6] = n;
+    return pagan_internal_replay(s->L, s->R, s->cells, endcell, s->log_fwd, trace.data(), out);
+}
+
+int pagan_fb_samples_ms(const pagan_fb_samples *s, double *ms) {
+    if (!s || !ms) return PAGAN_E_ARG;
+    *ms = s->ms;
+    return PAGAN_OK;
+}
+
+// What pagan_fb_sample_paths_batch allocates for one pair: 12 B a path step (and one path's pack buffer when a group holds
+// several), 64 B a path of summary, the records.  The matrix is the pagan_fb's: nothing here grows with Lx * Ly.
+int64_t pagan_fb_sample_predict_bytes(int32_t left_sites, int32_t right_sites, int32_t n_paths, uint32_t flags) {
+    if (left_sites < 2 || right_sites < 2 || n_paths < 1 || (flags & ~PAGAN_SAMPLE_NO_TRACES)) return PAGAN_E_ARG;
+    const FsSizes z = fs_sizes(left_sites - 1, right_sites - 1, n_paths, flags);
+    return (int64_t)(z.summary + z.trace + z.pack + sizeof(PgFbJob) + sizeof(PgFbSample) + 1024);
+}
+
+void pagan_fb_samples_destroy(pagan_fb_samples *s) { delete s; }
 
 void pagan_fb_destroy(pagan_fb *fb) {
     if (!fb) return;

@@ -160,6 +160,7 @@ struct pagan_msa {
                                          // most-common table where it is defined (basic_alignment.cpp:146-149)
     pagan_batch_fn backend = nullptr;    // test seam (pagan_msa_set_batch_backend); null = pagan_dp_align_batch
     void *backend_user = nullptr;
+    int sample_on_device = 0;            // pagan_msa_set_sampler: sample_path's paths come from pg_fb_sample (1) or the host's walk (0)
     std::atomic<int> parents_built{0};   // parent graphs this process has built (pagan_msa_parents_built)
     std::atomic<int> lazy_err{0};        // first error of a deferred parent build (an imported result that does not fit the child graphs)
     bool rows_built = false;             // m->rows are valid (pagan_msa_finish builds them at once, pagan_msa_finish_lazy on first use)
@@ -224,6 +225,9 @@ int host_threads_of(const pagan_msa *m);
 // (pagan_fb_sample_path downloads the matrix: 24 B a cell) with the numbers pagan_sample_uniforms gives for (sample_seed, public
 // node id) -- no state shared between nodes, so neither batching nor the device that took a node changes its path.  A banded
 // node whose full probability is 0 is handed back in `retry` (run again without the band, as an unreachable Viterbi corner is).
+// With the sampler on the device (pagan_msa_set_sampler) the sub-batch's paths are drawn by one pagan_fb_sample_paths_batch
+// instead -- the same numbers, the same paths -- and a node's result is the replay of its path 0: 12 B a path step come to the
+// host, not the matrix.
 int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads, std::vector<int> *retry) {
     int64_t budget = 0;
     int rc = device_budget(m, dev, &budget);
@@ -237,8 +241,9 @@ int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads,
         int64_t used = 0;
         while (at < ks.size()) {
             NodeWork &w = m->work[ks[at]];
-            const int64_t need = pagan_fb_predict_bytes(w.gl.n_sites, w.gr.n_sites, w.banded ? &w.pb : nullptr);
+            int64_t need = pagan_fb_predict_bytes(w.gl.n_sites, w.gr.n_sites, w.banded ? &w.pb : nullptr);
             if (need < 0) return (int)need;
+            if (sample && m->sample_on_device) need += pagan_fb_sample_predict_bytes(w.gl.n_sites, w.gr.n_sites, 1, 0);    // (the path's trace)
             if (need > budget) return PAGAN_E_MEMCAP;
             if (!which.empty() && used + need > budget) break;
             used += need;
@@ -259,6 +264,18 @@ int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads,
         if (rc != PAGAN_OK) return rc;
         std::vector<int> rcs(n, PAGAN_OK);
         std::vector<char> again(n, 0);
+        std::vector<pagan_fb_samples *> smp(n, nullptr);
+        double smp_ms = 0;
+        if (sample && m->sample_on_device) {
+            std::vector<int32_t> ids(n);
+            for (int q = 0; q < n; ++q) ids[q] = m->work[which[q]].node;
+            rc = pagan_fb_sample_paths_batch(n, fbs.data(), m->opts.sample_seed, ids.data(), 1, 0, smp.data());
+            if (rc == PAGAN_OK) rc = pagan_fb_samples_ms(smp[0], &smp_ms);
+            if (rc != PAGAN_OK) {
+                for (int q = 0; q < n; ++q) { pagan_fb_samples_destroy(smp[q]); pagan_fb_destroy(fbs[q]); }
+                return rc;
+            }
+        }
         parallel_for(n, threads, [&](int q) {
             NodeWork &w = m->work[which[q]];
             double ms[2] = {0, 0};
@@ -269,10 +286,14 @@ int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads,
             if (r == PAGAN_OK && sample) {
                 if (w.has_res) { pagan_result_free(&w.res); w.has_res = false; }
                 if (!(w.log_fwd > -HUGE_VAL) && w.banded) { again[q] = 1; rcs[q] = PAGAN_OK; return; }
-                const int n_u = w.gl.n_sites + w.gr.n_sites - 1;                     // Lx + Ly + 1
-                std::vector<double> u((size_t)n_u);
-                r = pagan_sample_uniforms(m->opts.sample_seed, w.node, n_u, u.data());
-                if (r == PAGAN_OK) r = pagan_fb_sample_path(fbs[q], u.data(), n_u, &w.res, nullptr, nullptr);
+                if (smp[q]) {
+                    r = pagan_fb_samples_result(smp[q], 0, &w.res);
+                } else {
+                    const int n_u = w.gl.n_sites + w.gr.n_sites - 1;                 // Lx + Ly + 1
+                    std::vector<double> u((size_t)n_u);
+                    r = pagan_sample_uniforms(m->opts.sample_seed, w.node, n_u, u.data());
+                    if (r == PAGAN_OK) r = pagan_fb_sample_path(fbs[q], u.data(), n_u, &w.res, nullptr, nullptr);
+                }
                 w.has_res = r == PAGAN_OK;
             }
             if (r == PAGAN_OK && w.res.status == PAGAN_DP_REACHED) {
@@ -298,7 +319,8 @@ int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads,
         for (int q = 0; q < n; ++q) {
             NodeWork &w = m->work[which[q]];
             double ms[3] = {0, 0, 0};
-            if (rc == PAGAN_OK && pagan_fb_post_ms(fbs[q], ms) == PAGAN_OK) w.fb_post_ms = ms[0] + ms[1] + ms[2];
+            if (rc == PAGAN_OK && pagan_fb_post_ms(fbs[q], ms) == PAGAN_OK) w.fb_post_ms = ms[0] + ms[1] + ms[2] + (q == 0 ? smp_ms : 0.0);
+            pagan_fb_samples_destroy(smp[q]);
             w.has_fb = rc == PAGAN_OK && !again[q];
             if (again[q]) retry->push_back(which[q]);
             pagan_fb_destroy(fbs[q]);
@@ -1509,6 +1531,12 @@ int pagan_eigen_qrev(const double *Q, const double *pi, int32_t n, double *root,
 int pagan_msa_set_batch_backend(pagan_msa *m, pagan_batch_fn fn, void *user) {
     if (!m) return PAGAN_E_ARG;
     m->backend = fn; m->backend_user = user;
+    return PAGAN_OK;
+}
+
+int pagan_msa_set_sampler(pagan_msa *m, int32_t on_device) {
+    if (!m || (on_device != 0 && on_device != 1)) return PAGAN_E_ARG;
+    m->sample_on_device = on_device;
     return PAGAN_OK;
 }
 

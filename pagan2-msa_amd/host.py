@@ -173,6 +173,8 @@ def _lib():
         L.pagan_msa_node_device.restype = C.c_int
         L.pagan_msa_set_batch_backend.argtypes = [vp, BATCH_FN, C.c_void_p]
         L.pagan_msa_set_batch_backend.restype = C.c_int
+        L.pagan_msa_set_sampler.argtypes = [vp, C.c_int32]
+        L.pagan_msa_set_sampler.restype = C.c_int
         L.pagan_pileup_default_opts.argtypes = [C.POINTER(CPileupOpts)]
         L.pagan_pileup_default_opts.restype = None
         L.pagan_pileup_create.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(CPileupOpts), C.POINTER(vp)]
@@ -225,7 +227,8 @@ HOST_EXPORTED = ["pagan_assign_units", "pagan_msa_default_opts", "pagan_msa_crea
                  "pagan_pileup_step_info", "pagan_pileup_step_job", "pagan_pileup_step_result",
                  "pagan_pileup_alignment_length", "pagan_pileup_alignment_row", "pagan_pileup_set_batch_backend",
                  "pagan_pileup_destroy",
-                 "pagan_msa_node_fb", "pagan_msa_node_support", "pagan_msa_node_marginals", "pagan_msa_node_model_prob", "pagan_msa_support_row"]
+                 "pagan_msa_node_fb", "pagan_msa_node_support", "pagan_msa_node_marginals", "pagan_msa_node_model_prob", "pagan_msa_support_row",
+                 "pagan_msa_set_sampler"]
 
 
 def _ip(a):
@@ -481,6 +484,12 @@ def sample_uniforms(seed, node, n):
     return f(seed, node, n)
 
 
+def sample_uniforms_path(seed, node, path, n):
+    """pagan_sample_uniforms_path: the numbers path `path` of node `node`'s ensemble is sampled with (path 0: sample_uniforms)."""
+    from . import sample_uniforms_path as f
+    return f(seed, node, path, n)
+
+
 def alphabets(data_type):
     """(leaf alphabet, ancestral alphabet) of a data type: 1 DNA, 2 protein."""
     a, b = C.create_string_buffer(256), C.create_string_buffer(256)
@@ -597,7 +606,9 @@ class Pileup:
 class Msa:
     """Progressive alignment of sequences on a rooted binary guide tree (Node mirror)."""
 
-    def __init__(self, names, seqs, newick, **opts):
+    def __init__(self, names, seqs, newick, sample_on_device=0, **opts):
+        """opts: fields of pagan_msa_opts.  sample_on_device=1 (pagan_msa_set_sampler): with sample_path set, the nodes' paths
+        are drawn by pg_fb_sample on the device instead of on the host behind a download of the forward matrix."""
         L = _lib()
         o = CMsaOpts()
         L.pagan_msa_default_opts(C.byref(o))
@@ -614,6 +625,11 @@ class Msa:
             from . import PaganError
             raise PaganError(rc, "pagan_msa_create")
         self._L = L
+        if sample_on_device:
+            rc = L.pagan_msa_set_sampler(self._h, int(sample_on_device))
+            if rc != 0:
+                from . import PaganError
+                raise PaganError(rc, "pagan_msa_set_sampler")
 
     def align(self):
         rc = self._L.pagan_msa_align(self._h)
