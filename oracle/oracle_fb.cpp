@@ -26,6 +26,10 @@
 // (:1476-1547), so those terms are counted more than once in fwd_end.
 // Deviation: cells outside the tunnel are not computed and read as probability 0 (the reference
 // accumulates into the shared out-of-tunnel cell, src/utils/tunnel_matrix.h:85-98).
+// Convention: a pair whose forward total is 0 (no path reaches the end: predecessor-less sites, a tunnel that
+// misses the end corner) has posterior 0 in every cell, where the division of :1029-1034 would give NaN.  The
+// product documents and does this (fb_pexp, dp_fb_post.inc) and tests/pycheck_fb.py defines it so; this file
+// is test infrastructure catching up with that convention, not a change of what the product computes.
 #include "../include/pagan_dp.h"
 
 #include <algorithm>
@@ -230,13 +234,14 @@ int run(const pagan_graph *l, const pagan_graph *r, const ProbModel &pm, const p
     *log_fwd = ps.fwd_end.log();
     *log_bwd = ps.B(2, 0, 0).log();
     // (outside the band: probability 0 -- posterior 0, log forward -inf -- as the stored zeros gave before)
+    const bool none = ps.fwd_end.log() == -HUGE_VAL;   // total probability 0: posterior 0, not exp(-inf + b + inf)
     if (post || log_f)
         for (int i = 0; i < ps.Lx; i++)
             for (int j = 0; j < ps.Ly; j++)
                 for (int st = 0; st < 3; st++) {
                     const size_t k = ((size_t)i * ps.Ly + j) * 3 + st;
                     const bool in = ps.in(i, j);
-                    if (post) post[k] = in ? std::exp(ps.F(st, i, j).log() + ps.B(st, i, j).log() - ps.fwd_end.log()) : 0.0;   // VA:1029-1034
+                    if (post) post[k] = in && !none ? std::exp(ps.F(st, i, j).log() + ps.B(st, i, j).log() - ps.fwd_end.log()) : 0.0;   // VA:1029-1034
                     if (log_f) log_f[k] = in ? ps.F(st, i, j).log() : -HUGE_VAL;
                 }
     return 0;

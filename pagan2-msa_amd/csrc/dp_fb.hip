@@ -1746,8 +1746,15 @@ int pagan_fb_dump(pagan_fb *fb, int32_t which, double *dst) {
         for (int j = 0; j < fb->Ly; ++j) {
             const long long at = fb->at(i, j);
             double *o = dst + ((size_t)i * fb->Ly + j) * 3;
-            for (int s = 0; s < 3; ++s)
-                o[s] = at < 0 ? outside : which == 2 ? std::exp(a[3 * at + s] + bb[3 * at + s] - fb->totals[0]) : a[3 * at + s];
+            for (int s = 0; s < 3; ++s) {
+                if (at < 0) { o[s] = outside; continue; }
+                if (which != 2) { o[s] = a[3 * at + s]; continue; }
+                // fb_post's zero rule (dp_fb_post.inc): a pair whose full probability is 0 has posterior 0 in every cell -- the
+                // argument is then -inf minus -inf, a NaN, which compares false.  Its clamp of the argument to <= 0 is NOT taken over:
+                // as before, a value here may exceed 1 by an ulp where pg_fb_gather returns exactly 1
+                const double x = a[3 * at + s] + bb[3 * at + s] - fb->totals[0];
+                o[s] = x > -HUGE_VAL ? std::exp(x) : 0.0;
+            }
         }
     return PAGAN_OK;
 }

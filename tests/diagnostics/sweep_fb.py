@@ -1,7 +1,9 @@
 """Diagnostic: a randomized sweep of the forward/backward sweeps' three schedules for tunnels (LDS-ring sweeps, block schedule,
 one-workgroup kernels) against the oracle: leaf pairs and graph pairs of random lengths behind random tunnels with boxes (rows whose
 band jumps wider and narrower than a workgroup / a block).  Totals to 1e-9 for every case, both matrices cell by cell for the
-shorter ones.  Usage: sweep_fb.py [cases] (PG_SWEEP_SEED: another seed)."""
+shorter ones.  Usage: sweep_fb.py [cases] (PG_SWEEP_SEED: another seed).
+--random-graphs: instead, the comparison of tests/test_fb_fuzz_gpu.py (synth.random_graph pairs of 150-300 sites on every schedule, full
+matrix and behind four ranges of tunnels) over fresh seeds; it stops at the first mismatch."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -11,8 +13,15 @@ from pagan2_msa_amd import abi, host, synth
 import oracle
 
 oracle.build()
-n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+n_cases = int(args[0]) if args else 40
 seed0 = int(os.environ.get("PG_SWEEP_SEED", "5000"))
+if "--random-graphs" in sys.argv:
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import test_fb_fuzz_gpu as fuzz
+    failed = fuzz.sweep(oracle, n_cases, seed0)
+    print("sweep_fb --random-graphs: seed %d, %d cases asked for: %s" % (seed0, n_cases, "MISMATCH" if failed else "all equal"))
+    sys.exit(1 if failed else 0)
 TOL = 1e-9
 bad = 0
 used = {"ring": 0, "blocks": 0, "one": 0}

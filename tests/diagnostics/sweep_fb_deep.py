@@ -4,7 +4,8 @@ half-widths from a few columns to ~200, and boxes that make the ring change shap
 matrix and every posterior, the totals to 1e-9.  A pair that does not route to schedule 3 is reported and counts as a failure
 unless it is not eligible by its shape (a diagonal wider than 1,024 cells).
 Usage: sweep_fb_deep.py [trees] (PG_SWEEP_SEED: another seed; --route-only: no GPU, the walk runs on the oracle's DP and only the
-routing and the plans are printed)."""
+routing and the plans are printed; --random-graphs: instead, the deep-ring runs of tests/test_fb_fuzz_gpu.py -- synth.random_graph pairs
+of 150-300 sites behind four ranges of tunnels -- over fresh seeds, stopping at the first mismatch)."""
 import ctypes as C
 import os
 import sys
@@ -20,6 +21,12 @@ route_only = "--route-only" in sys.argv
 n_trees = int(args[0]) if args else 6
 seed0 = int(os.environ.get("PG_SWEEP_SEED", "7000"))
 os.environ["PAGAN_FB_DEEP_MIN_ND"] = "0"
+if "--random-graphs" in sys.argv:
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import test_fb_fuzz_gpu as fuzz
+    failed = fuzz.sweep(oracle, n_trees, seed0, [r for r in fuzz.RUNS if r[2] == 3])
+    print("sweep_fb_deep --random-graphs: seed %d, %d cases asked for: %s" % (seed0, n_trees, "MISMATCH" if failed else "all equal"))
+    sys.exit(1 if failed else 0)
 TOL = 1e-9
 bad = 0
 seen = {"pairs": 0, "far_pairs": 0, "segments>1": 0, "min_D": set()}

@@ -1,0 +1,351 @@
+"""GPU: every forward/backward schedule (fb_route: 0 one-workgroup kernels, 1 64 x 64 blocks, 2 plain LDS ring, 3 deep ring) against
+the exact reading of the reference (tests/pycheck_fb.py: path sums in 50-digit decimals), on adversarial graphs from
+synth.random_graph -- degree up to 4 in shuffled list order, edges that span up to 21 sites, edge weights != 1, predecessor-less
+sites -- at the smallest shapes that still cross a block boundary (more than 64 sites a side), and on the degenerate shapes.
+
+Every case asserts the schedule it ran on.  Tolerances are the project's: 1e-9 on logs, 1e-7 relative + 1e-12 absolute on
+posteriors, 1e-12 per in-band cell on the marginals' sums.  log_fwd and log_bwd are NOT compared with one another here: with two or
+more edges at both end sites the reference's forward end corner counts some Y-closes once per left edge (pycheck_fb.py), so the
+forward total is the larger one, and pair P4 is built to show it.
+
+The exact references are computed once (fixture `refs`, a few seconds of CPU)."""
+import numpy as np
+import pytest
+
+import pagan2_msa_amd as pgm
+from pagan2_msa_amd import abi, host, synth
+
+import pycheck_fb
+import fb_testlib
+from fb_testlib import random_tunnel
+
+pytestmark = pytest.mark.gpu
+LOG_TOL = 1e-9
+FB_RG_INIT = 32                               # dp_fb.hip: the end-corner assignments a ring sweep holds
+FS_KEEP = 4                                   # dp_fb_sample.inc: predecessor cells whose candidates stay in registers
+ENVS = {
+    "default": {},
+    "groups": {"PAGAN_FB_GROUPS": "4"},
+    "band": {"PAGAN_FB_BAND_MIN_ND": "0"},
+    "deep": {"PAGAN_FB_DEEP_MIN_ND": "0"},
+    "deep+band": {"PAGAN_FB_DEEP_MIN_ND": "0", "PAGAN_FB_BAND_MIN_ND": "0"},
+    "ring": {"PAGAN_FB_RING_MIN_ND": "0"},
+}
+BF = [0.3, 0.2, 0.2, 0.3]
+
+
+def set_env(monkeypatch, name):
+    fb_testlib.set_env(monkeypatch, ENVS[name])
+
+
+def in_band(p):
+    return fb_testlib.in_band(p.Lx, p.Ly, p.band)
+
+
+def with_end_edges(g, sources, seed):
+    """g with its end site's bwd list replaced by edges from `sources` (in that order), some of weight != 1
+    (the rebuild of test_fb_deep_cpu.py::test_one_edge_beyond_any_ring_does_not_disqualify_the_pair)"""
+    rng = np.random.default_rng(seed)
+    n = g.n_sites
+    k0 = int(g.bwd_off[n - 1])
+    src = np.concatenate([g.bwd_src[:k0], np.array(sources, np.int32)])
+    w = np.where(rng.random(len(sources)) < 0.5, 1.0, rng.choice([0.9, 0.81, 0.25, 0.729], len(sources))).astype(np.float32)
+    lw = np.concatenate([g.bwd_logw[:k0], np.log(w)])
+    first = int(g.bwd_eid[:k0].max()) + 1
+    eid = np.concatenate([g.bwd_eid[:k0], np.arange(first, first + len(sources), dtype=np.int32)])
+    off = g.bwd_off.copy()
+    off[n] = k0 + len(sources)
+    return abi.Graph(g.state, off, src, lw, eid, n_edges=first + len(sources))
+
+
+def n_corner_inits(left, right, band):
+    """the distinct in-band cells initialise_array_corner_bwd assigns, as fb_corner_init (dp_fb.hip) counts them"""
+    Lx, Ly = left.n_sites - 1, right.n_sites - 1
+    inside = lambda i, j: 0 <= i < Lx and 0 <= j < Ly and (band is None or max(band.upper[i], 0) <= j <= min(band.lower[i], Ly - 1))
+    le = [int(p) for p in left.bwd_src[left.bwd_off[Lx]:left.bwd_off[Lx + 1]]]
+    re = [int(q) for q in right.bwd_src[right.bwd_off[Ly]:right.bwd_off[Ly + 1]]]
+    cells = {(Lx - 1, Ly - 1, 2)}
+    if le and re:
+        cells |= {(p, q, 2) for p in le for q in re}
+    cells |= {(p, Ly - 1, 0) for p in le} | {(Lx - 1, q, 1) for q in re}
+    return sum(1 for i, j, _s in cells if inside(i, j))
+
+
+class Pair:
+    def __init__(self, name, left, right, mp, band, model=None):
+        self.name, self.left, self.right, self.mp, self.band, self.model = name, left, right, mp, band, model
+        self.Lx, self.Ly = left.n_sites - 1, right.n_sites - 1
+
+    def args(self):
+        return (self.left, self.right, self.mp, self.band)
+
+
+def build_pairs():
+    """{name: Pair} -- host only.  Names: P1 .. P6 as the module docstring's; a trailing `t` is the same pair behind a tunnel."""
+    mp = host.model_prob(1, 0.1, base_freq=BF)
+    model = synth.random_model(4, 3)
+    out = {}
+
+    def graphs(seed, p_dead, nl=70, nr=66):
+        return (synth.random_graph(nl, 4, seed, p_extra=0.4, max_deg=4, max_span=20, p_dead=p_dead),
+                synth.random_graph(nr, 4, 500 + seed, p_extra=0.4, max_deg=4, max_span=20, p_dead=p_dead))
+
+    def add(name, left, right, halves, seed, model_=model, mp_=mp):
+        band = random_tunnel(np.random.default_rng(seed), left.n_sites - 1, right.n_sites - 1, *halves) if halves else None
+        out[name] = Pair(name, left, right, mp_, band, model_)
+
+    l1, r1 = graphs(P1_SEED, 0.0)
+    add("P1", l1, r1, None, 0)
+    add("P1t", l1, r1, (8, 30), 1)
+    l2, r2 = graphs(P2_SEED, 0.03)
+    add("P2", l2, r2, None, 0)
+    add("P2t", l2, r2, (8, 30), 2)
+    l3, r3 = graphs(P3_SEED, 0.08)
+    add("P3t", l3, r3, (8, 30), 3)
+    # P4: the end sites rebuilt -- 2 x 10 end edges: 20 + 2 + 10 = 32 assignments (the corner's own M cell is one of the 20), and
+    # 4 x 6: 24 + 4 + 6 = 34
+    l4, r4 = graphs(P4_SEED, 0.0)
+    nl, nr = l4.n_sites - 1, r4.n_sites - 1
+    rng = np.random.default_rng(4)
+    mp4 = host.model_prob(1, 0.5, base_freq=BF)              # (a longer branch: gaps, and with them the Y-closes, carry a few per cent)
+    add("P4at", with_end_edges(l4, [nl - 3, nl - 1], 1), with_end_edges(r4, list(nr - 1 - rng.permutation(10)), 2), (14, 30), 4, model, mp4)
+    add("P4bt", with_end_edges(l4, [nl - 2, nl - 6, nl - 1, nl - 4], 3), with_end_edges(r4, list(nr - 1 - rng.permutation(6)), 4), (14, 30), 4, model, mp4)
+    # P5: plain sequences behind a tunnel
+    _, seqs, _ = synth.evolve_balanced(2, 80, branch=0.1, sub=0.1, indel_start=0.03, mean_len=3, seed=9)
+    gl, gr = (host.HGraph.leaf(s).flatten() for s in seqs)
+    add("P5t", gl, gr, (8, 30), 5, host.dna_model(BF, 0.1)[0])
+    # P6: a one-residue sequence against ~30 sites, and 3 x 3
+    one = host.HGraph.leaf("G").flatten()
+    add("P6a", one, synth.random_graph(29, 4, 61, p_extra=0.4, max_span=8), None, 0)
+    add("P6b", synth.random_graph(2, 4, 62, p_extra=0.9, max_span=2), synth.random_graph(2, 4, 63, p_extra=0.9, max_span=2), None, 0)
+    return out
+
+
+P1_SEED, P2_SEED, P3_SEED, P4_SEED = 11, 30, 19, 14        # P2: finite total, two fifths of the cells unreachable; P3: total 0 (chosen on the CPU)
+
+# (pair, environment, schedule)
+CASES = [
+    ("P1", "default", 0), ("P1", "groups", 1), ("P1t", "band", 1), ("P1t", "deep", 3), ("P1t", "default", 0),
+    ("P2", "default", 0), ("P2", "groups", 1), ("P2t", "band", 1), ("P2t", "deep", 3), ("P2t", "default", 0),
+    ("P3t", "default", 0), ("P3t", "band", 1), ("P3t", "deep", 3),
+    ("P4at", "default", 0), ("P4at", "band", 1), ("P4at", "deep", 3), ("P4at", "deep+band", 3),
+    ("P4bt", "default", 0), ("P4bt", "band", 1), ("P4bt", "deep+band", 1),
+    ("P5t", "ring", 2),
+    ("P6a", "default", 0), ("P6a", "groups", 1), ("P6b", "default", 0), ("P6b", "groups", 1),
+]
+
+
+@pytest.fixture(scope="module")
+def pairs(pg):
+    return build_pairs()
+
+
+@pytest.fixture(scope="module")
+def refs(pairs):
+    """{name: pycheck_fb.run(...)}: the exact values of every pair, computed once and not modified"""
+    return {name: pycheck_fb.run(*p.args()) for name, p in pairs.items()}
+
+
+def check_totals_and_matrices(fb, ref, what):
+    for got, want in ((fb.log_fwd, ref["log_fwd"]), (fb.log_bwd, ref["log_bwd"])):
+        if np.isinf(want):
+            assert got == want, (what, got, want)
+        else:
+            assert abs(got - want) <= LOG_TOL * max(1.0, abs(want)), (what, got, want)
+    logf = fb.log_forward()
+    fin = np.isfinite(ref["log_f"])
+    assert not np.isnan(logf).any() and np.array_equal(np.isfinite(logf), fin) and np.all(np.isneginf(logf[~fin])), what
+    assert np.allclose(logf[fin], ref["log_f"][fin], rtol=LOG_TOL, atol=LOG_TOL), (what, np.abs(logf[fin] - ref["log_f"][fin]).max())
+    post = fb.posterior()
+    assert not np.isnan(post).any(), what
+    assert np.allclose(post, ref["posterior"], rtol=1e-7, atol=1e-12), (what, np.abs(post - ref["posterior"]).max())
+    return logf, post
+
+
+def check_marginals(fb, p, ref, what):
+    mg = fb.site_marginals()
+    post = ref["posterior"]
+    inb = in_band(p)
+    close = lambda got, want, n: np.all(np.abs(got - want) <= 1e-7 * np.abs(want) + 1e-12 * n)
+    for side, (gap, match, best, best_p, state) in enumerate((("pX", "pM_left", "best_j", "best_p_left", 0), ("pY", "pM_right", "best_i", "best_p_right", 1))):
+        axis = 1 - side
+        n = inb.sum(axis)
+        for key, want in ((gap, post[:, :, state].sum(axis)), (match, post[:, :, 2].sum(axis)), (best_p, post[:, :, 2].max(axis))):
+            assert not np.isnan(mg[key]).any() and close(mg[key], want, n), (what, key, np.abs(mg[key] - want).max())
+        b, top = mg[best], post[:, :, 2].max(axis)
+        assert np.all((b >= -1) & (b < post.shape[axis])), (what, best)
+        has = b >= 0
+        idx = np.arange(post.shape[side])
+        at = post[idx[has], b[has], 2] if side == 0 else post[b[has], idx[has], 2]
+        assert close(at, top[has], n[has]) and np.all(top[~has] <= 1e-12 * n[~has]), (what, best)
+    return mg
+
+
+@pytest.mark.parametrize("name, env, schedule", CASES, ids=["%s-%s-%d" % c for c in CASES])
+def test_schedule_against_the_exact_reference(pg, pairs, refs, monkeypatch, name, env, schedule):
+    """Totals, every log forward cell (equal -inf sets), every posterior, the site marginals against the exact posterior summed in
+    numpy, and the Viterbi path's support."""
+    set_env(monkeypatch, env)
+    p, ref = pairs[name], refs[name]
+    what = (name, env)
+    code, info = pgm.fb_route(p.left, p.right, p.band)
+    assert code == schedule, (what, code, info)
+    fb = pgm.FullProbability(*p.args())
+    assert fb.schedule == schedule, (what, fb.schedule, info)
+    print("%s under %s: schedule %d %s | log_fwd %.12g (exact %.12g) log_bwd %.12g (exact %.12g)"
+          % (name, env, fb.schedule, info, fb.log_fwd, ref["log_fwd"], fb.log_bwd, ref["log_bwd"]))
+    check_totals_and_matrices(fb, ref, what)
+    mg = check_marginals(fb, p, ref, what)
+    if name.startswith("P3"):
+        assert fb.log_fwd == -np.inf and fb.log_bwd == -np.inf
+        assert not fb.posterior().any() and all(not v.any() for v in mg.values() if v.dtype == np.float64)
+        sp = fb.sample_paths(5, 3, 66)
+        sm = sp.summary()
+        assert np.all(sm["status"] == 1) and not sm["n_steps"].any()
+        sp.close()
+    res = pgm.align(p.left, p.right, p.model, p.band)
+    if name.startswith(("P1", "P4", "P5", "P6")):
+        assert res.status == 0, what
+    if res.status == 0:
+        cells = pgm.path_cells(res.cols)
+        real = cells[:, 0] >= 0
+        want = ref["posterior"][cells[real, 1], cells[real, 2], cells[real, 0]]
+        sup = fb.path_support(res.cols)
+        assert np.all(sup[~real] == -1.0) and np.allclose(sup[real], want, rtol=1e-7, atol=1e-12), what
+        assert fb.posterior_cells(cells[real]).tobytes() == sup[real].tobytes(), what
+    fb.close()
+
+
+def test_the_inputs_are_what_the_cases_need(pg, pairs, refs, monkeypatch):
+    """Conditions on the inputs, not results: block boundaries are crossed; P2 has many unreachable cells and a finite total; P3's
+    total is 0; P4's totals differ and its end-corner assignments sit at, and just past, what a ring sweep holds -- and fb_route
+    gives the second variant to the blocks where it gives the first to the deep ring."""
+    for name in ("P1", "P2", "P3t", "P4at", "P4bt"):
+        assert pairs[name].Lx > 64 and pairs[name].Ly > 64
+    assert np.isfinite(refs["P1"]["log_fwd"]) and np.isfinite(refs["P1t"]["log_fwd"])
+    for name in ("P2", "P2t"):
+        inb = in_band(pairs[name])
+        dead = np.isneginf(refs[name]["log_f"]).all(axis=2) & inb
+        assert np.isfinite(refs[name]["log_fwd"]) and dead.sum() > 0.02 * inb.sum(), (name, dead.sum())
+    assert refs["P3t"]["log_fwd"] == refs["P3t"]["log_bwd"] == -np.inf and np.isfinite(refs["P3t"]["log_f"]).sum() > 100
+    for name in ("P4at", "P4bt"):
+        assert refs[name]["log_fwd"] - refs[name]["log_bwd"] > 1e-6, name
+    assert n_corner_inits(*[getattr(pairs["P4at"], k) for k in ("left", "right", "band")]) == FB_RG_INIT
+    assert n_corner_inits(*[getattr(pairs["P4bt"], k) for k in ("left", "right", "band")]) == FB_RG_INIT + 2
+    set_env(monkeypatch, "deep+band")
+    assert pgm.fb_route(*[getattr(pairs["P4at"], k) for k in ("left", "right", "band")])[0] == 3
+    assert pgm.fb_route(*[getattr(pairs["P4bt"], k) for k in ("left", "right", "band")])[0] == 1
+    assert pairs["P6a"].Lx == 2 and (pairs["P6b"].Lx, pairs["P6b"].Ly) == (3, 3)
+
+
+def _bits(fb):
+    return (np.float64(fb.log_fwd).tobytes(), np.float64(fb.log_bwd).tobytes(), fb.log_forward().tobytes(), fb.posterior().tobytes(), fb.schedule)
+
+
+@pytest.mark.parametrize("env", ["default", "band", "deep+band", "groups", "ring"])
+def test_batch_over_all_pairs_is_the_one_pair_call_bit_for_bit(pg, pairs, refs, monkeypatch, env):
+    set_env(monkeypatch, env)
+    names = sorted(pairs)
+    fbs = pgm.full_probability_batch([pairs[n].args() for n in names])
+    schedules = set()
+    for n, fb in zip(names, fbs):
+        one = pgm.FullProbability(*pairs[n].args())
+        assert _bits(fb) == _bits(one), (env, n)
+        check_totals_and_matrices(fb, refs[n], (env, n, "batch"))
+        schedules.add(fb.schedule)
+        one.close()
+        fb.close()
+    assert schedules == {"default": {0}, "band": {1}, "deep+band": {1, 3}, "groups": {1}, "ring": {0, 2}}[env], schedules
+
+
+# ---- the sampler ----
+
+SAMPLED = ("P1", "P2", "P4at")
+SEED, NODE, N_REF = 5, 7, 200
+
+
+def wide_steps(p, visited):
+    """the steps of a trace that had more than FS_KEEP predecessor cells, from the graphs.  The count is the sampler's own n_cells:
+    fs_preds (dp_fb_sample.inc) lists one cell per edge (X, Y) or edge pair (M) whether or not the cell lies inside the band (a cell
+    outside reads as -inf but is listed and counted), so the degrees alone decide which of the two code paths a step takes."""
+    dl, dr = np.diff(p.left.bwd_off), np.diff(p.right.bwd_off)
+    i, j, s = visited[:, 0], visited[:, 1], visited[:, 2]
+    cells = np.where(s == 0, dl[i], np.where(s == 1, dr[j], dl[i] * dr[j]))
+    return int((cells > FS_KEEP).sum())
+
+
+def test_sampler_traces_and_log_q_on_adversarial_graphs(pg, pairs, refs, monkeypatch):
+    """200 paths a pair on the device: cell for cell the host sampler's, and summary()["log_q"] equal to the exact reading's
+    path_log_prob (edge weights and multi-edge sites included) to 1e-9.  At least two pairs must have steps with more than
+    FS_KEEP predecessor cells -- the sampler's second code path."""
+    set_env(monkeypatch, "default")
+    wide = {}
+    for name in SAMPLED:
+        p, ex = pairs[name], refs[name]["exact"]
+        fb = pgm.FullProbability(*p.args())
+        assert fb.schedule == 0
+        sp = fb.sample_paths(SEED, NODE, N_REF)
+        sm = sp.summary()
+        assert np.all(sm["status"] == 0), (name, sm["status"])
+        wide[name] = 0
+        worst = 0.0
+        for q in range(N_REF):
+            u = host.sample_uniforms_path(SEED, NODE, q, p.Lx + p.Ly + 1)
+            want_res, want_vis = fb.sample_path(u)
+            got = sp.visited(q)
+            assert np.array_equal(got, want_vis), (name, q)
+            res = sp.result(q)
+            assert res.status == 0 and res.same_alignment(want_res), (name, q)
+            wide[name] += wide_steps(p, got)
+            end = (int(got[0, 2]), int(got[0, 0]), int(got[0, 1]))          # the end pick is the first visited cell
+            assert tuple(res.end[:3]) == end, (name, q, res.end)
+            want = ex.path_log_prob(got, end)
+            worst = max(worst, abs(sm["log_q"][q] - want))
+            assert abs(sm["log_q"][q] - want) <= LOG_TOL * max(1.0, abs(want)), (name, q, sm["log_q"][q], want)
+        print("%s: %d steps with more than %d predecessor cells in %d paths; log_q against the exact reading: %.3g" % (name, wide[name], FS_KEEP, N_REF, worst))
+        sp.close()
+        fb.close()
+    assert sum(1 for v in wide.values() if v > 0) >= 2, wide
+
+
+P4_K, P4_SEED_DRAW, P4_NODE = 4096, 22, 9
+
+
+def visit_counts(p, traces):
+    count = np.zeros((p.Lx, p.Ly, 3))
+    for v in traces:
+        np.add.at(count, (v[:, 0], v[:, 1], v[:, 2]), 1)
+    return count
+
+
+def test_the_sampler_visits_cells_as_the_forward_matrix_says_not_as_the_posterior(pg, pairs, refs, monkeypatch):
+    """P4 (2 x 10 end edges), 4,096 paths: the visit frequency of every cell against the exact visit_prob (prefix times the suffix
+    with the forward end corner's multiplicities, over the forward total) within 5 sqrt(p (1 - p) / K) + 4 / K.  The posterior
+    (compute_posterior_score: forward times backward over the forward total) is NOT what a sampler built on the forward matrix
+    draws from when the end corner counts a Y-close more than once, and the two differ here by more than the bound.
+    The seed is fixed, chosen on the CPU among 14: the oracle's sampler on these uniform numbers stays inside the bound at every
+    cell and deviates by 3.94 standard deviations at the worst of the 5,761 cells with K p (1 - p) > 1 (no seed stayed below 3:
+    that many cells, most of them with a skewed binomial count, always hold a deviate near 4; the seeds gave 3.94 to 7.11)."""
+    set_env(monkeypatch, "default")
+    p, ref = pairs["P4at"], refs["P4at"]
+    K = P4_K
+    fb = pgm.FullProbability(*p.args())
+    sp = fb.sample_paths(P4_SEED_DRAW, P4_NODE, K)
+    assert np.all(sp.summary()["status"] == 0)
+    vis, n = sp.visited_all()
+    sp.close()
+    fb.close()
+    f = visit_counts(p, [vis[q, :n[q]] for q in range(K)]) / K
+    want = np.clip(ref["visit_prob"], 0.0, 1.0)
+    sd = np.sqrt(want * (1 - want) / K)
+    bound = 5 * sd + 4.0 / K
+    dev = np.abs(f - want)
+    dev[0, 0, :] = 0                                          # (a trace never holds the start corner)
+    z = (dev / np.maximum(sd, 1e-300))[want * (1 - want) * K > 1]
+    print("P4 K %d: largest normalised deviation from visit_prob %.2f" % (K, z.max()))
+    worst = np.unravel_index(np.argmax(dev - bound), dev.shape)
+    assert np.all(dev <= bound), (worst, f[worst], want[worst])
+    # the distinction is real: at the end corner's Y-close cells the posterior is outside the bound around visit_prob
+    gap = np.abs(ref["visit_prob"] - ref["posterior"])
+    assert (gap > bound)[p.Lx - 1, :, 1].any(), gap[p.Lx - 1, :, 1].max()
+    assert (np.abs(f - ref["posterior"]) > bound)[p.Lx - 1, :, 1].any()       # ... and so are the frequencies drawn here
