@@ -179,6 +179,12 @@ int64_t pagan_batch_cells(const pagan_batch *b);
 void pagan_batch_destroy(pagan_batch *b);
 /* diagnostic builds only: raw bytes of job k's device trace buffer                    */
 int  pagan_batch_debug_trace(pagan_batch *b, int32_t k, void *dst, int64_t bytes);
+/* diagnostic: how job k's last traceback was cut at the boundary diagonal pairs (dp_device.h) -- info[4] = boundaries K
+ * the job was planned with (0: one lane walks the whole path), segments, cells of the path, device status; segs[5 * s] =
+ * start i, start j, start matrix, cells, offset in the trace buffer of segment s, for the first min(segments, cap)
+ * segments.  The cells of the path no segment covers were walked one by one.  A download after the batch's stream has
+ * synchronised; in the numbering of the compacted graphs where pagan_dp_debug_compact says the job runs on those.  */
+int  pagan_batch_debug_segments(pagan_batch *b, int32_t k, int32_t info[4], int32_t *segs, int64_t cap);
 /* diagnostic, host only (no device needed): the plan the banded fill kernel would get for a job --
  * cls[Lx+Ly-1] = class of every anti-diagonal (0 simple, 1 multi-edge, 2 multi-edge with far edges,
  * 3 general, 4 wide) and the four compute waves' awake intervals (layout: dp_device.h, sched)      */

@@ -555,6 +555,18 @@ class Batch:
         _check(self._L.pagan_batch_debug_trace(self._h, k, out.ctypes.data_as(C.c_void_p), out.nbytes), "pagan_batch_debug_trace")
         return out
 
+    def debug_segments(self, k):
+        """Diagnostic: (n_bound, [n_segments, 5] int32 rows (i, j, state, cells, offset), cells of the path, device status)
+        of job k's last traceback."""
+        import numpy as np
+        info = np.zeros(4, np.int32)
+        i32p = C.POINTER(C.c_int32)
+        _check(self._L.pagan_batch_debug_segments(self._h, k, info.ctypes.data_as(i32p), None, 0), "pagan_batch_debug_segments")
+        segs = np.zeros((int(info[1]), 5), np.int32)
+        _check(self._L.pagan_batch_debug_segments(self._h, k, info.ctypes.data_as(i32p), segs.ctypes.data_as(i32p), segs.shape[0]),
+               "pagan_batch_debug_segments")
+        return int(info[0]), segs, int(info[2]), int(info[3])
+
     def cells_of(self, k):
         left, right, _, band = self.jobs[k]
         return self._L.pagan_dp_count_cells(left.n_sites, right.n_sites, C.byref(band.c) if band is not None else None)

@@ -2468,6 +2468,26 @@ int pagan_batch_debug_trace(pagan_batch *b, int32_t k, void *dst, int64_t bytes)
     return PAGAN_OK;
 }
 
+// Diagnostic: how job k's last traceback was cut (pg_trace_compose's output; tests/trace_plan.py predicts it).  A download only.
+int pagan_batch_debug_segments(pagan_batch *b, int32_t k, int32_t info[4], int32_t *segs, int64_t cap) {
+    if (!b || k < 0 || k >= b->n || !info || cap < 0 || (cap > 0 && !segs) || !b->ran) return PAGAN_E_ARG;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    int ec[8];
+    HIP_TRY(hipMemcpy(ec, b->dj[k].endcell, sizeof ec, hipMemcpyDeviceToHost));
+    const int seg_cap = 2 * b->jobs[k].n_bound + 8;                    // (what pg_trace_compose stops at)
+    int nseg = ec[0] == 0 ? ec[7] : 0;
+    if (nseg < 0 || nseg > seg_cap) return PAGAN_E_INTERNAL;
+    info[0] = b->jobs[k].n_bound; info[1] = nseg; info[2] = ec[0] == 0 ? ec[6] : 0; info[3] = ec[0];
+    const int n = (int)std::min<int64_t>(nseg, cap);
+    if (n > 0) {
+        std::vector<int> raw(6 * (size_t)n);
+        HIP_TRY(hipMemcpy(raw.data(), b->dj[k].segs, sizeof(int) * raw.size(), hipMemcpyDeviceToHost));
+        for (int s = 0; s < n; ++s)
+            for (int c = 0; c < 5; ++c) segs[5 * s + c] = raw[6 * (size_t)s + c];
+    }
+    return PAGAN_OK;
+}
+
 void pagan_batch_destroy(pagan_batch *b) {
     if (!b) return;
     if (b->stream) {

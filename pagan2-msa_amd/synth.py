@@ -176,6 +176,54 @@ def random_graph(n_real, n_states, seed, p_extra=0.3, max_deg=4, max_span=6, p_d
                  np.array(eid, np.int32), n_edges=next_eid)
 
 
+def planted_graph(core_states, blocks, seed, bypass_logw=0.0, n_states=4):
+    """A chain over `core_states` with planted long edges: for every (pos, length) of `blocks`, `length` junk sites with
+    random states follow core site `pos` (1-based; 0: the start site), and the first site after the block gets a second
+    bwd edge from core site `pos` itself, of log weight `bypass_logw` -- so that a path which has no use for the junk
+    skips the block through one edge of span length + 1.  Which of the site's two edges comes first in its list is drawn
+    from `seed`.  A block behind the last core site puts the bypass on the stop site.  Positions must differ.
+    The site of core site c is c + (junk of the blocks with pos < c)."""
+    rng = np.random.default_rng(seed)
+    core = np.asarray(core_states, np.int32)
+    n_core = int(core.shape[0])
+    at = {}
+    for pos, length in blocks:
+        assert 0 <= pos <= n_core and length >= 1 and pos not in at
+        at[int(pos)] = int(length)
+    state, off, src, lw, eid = [-1], [0, 0], [], [], []
+
+    def site(st, srcs):
+        state.append(st)
+        for p, w in srcs:
+            src.append(p); lw.append(w); eid.append(len(eid) + 1)
+        off.append(len(src))
+
+    bypass = None                               # the site a bypass of the next site starts at
+    for c in range(n_core + 1):                 # c == 0: the start site (already there), then core site c
+        if c > 0:
+            here = len(state)
+            srcs = [(here - 1, 0.0)]
+            if bypass is not None:
+                srcs.append((bypass, float(bypass_logw)))
+                if rng.random() < 0.5:
+                    srcs.reverse()
+                bypass = None
+            site(int(core[c - 1]), srcs)
+        if c in at:
+            bypass = len(state) - 1
+            for _ in range(at[c]):
+                site(int(rng.integers(0, n_states)), [(len(state) - 1, 0.0)])
+    here = len(state)
+    srcs = [(here - 1, 0.0)]
+    if bypass is not None:
+        srcs.append((bypass, float(bypass_logw)))
+        if rng.random() < 0.5:
+            srcs.reverse()
+    site(-1, srcs)
+    return Graph(np.array(state, np.int32), np.array(off, np.int32), np.array(src, np.int32), np.array(lw, np.float32),
+                 np.array(eid, np.int32), n_edges=len(eid) + 1)
+
+
 def random_model(n_states, seed, dist=0.1):
     """A log-odds-like table with many exact ties (values on a coarse float grid) plus the
     indel parameters of Model_factory::alignment_model (model_factory.cpp:1898-1925)."""
