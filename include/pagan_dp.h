@@ -268,15 +268,18 @@ typedef struct pagan_model_prob {   /* Evol_model's probability-space accessors 
 
 typedef struct pagan_fb pagan_fb;   /* forward and backward matrices of one alignment, resident in HBM     */
 
-/* Runs both passes.  left/right must stay valid until pagan_fb_destroy (sample_path reads them).          */
+/* Runs both passes: pagan_fb_run_batch with n = 1.  left/right must stay valid until pagan_fb_destroy (sample_path reads them).
+ * The calling thread is back on the device it came with when the call returns, whatever opts->device names.              */
 int  pagan_fb_run(const pagan_graph *left, const pagan_graph *right, const pagan_model_prob *model,
                   const pagan_band *band, const pagan_opts *opts, pagan_fb **out);
 /* The same pass for n alignments at once (the reference runs compute_full_score node by node, viterbi_alignment.cpp:329-371; a
  * caller that holds several independent node pairs -- a level of the guide tree -- hands them over together): the forward sweeps
  * of all wide pairs in ONE launch and the backward sweeps in another, so that how many run side by side is what the device holds,
  * not what the runtime's hardware queues allow.  band may be null (no pair has a band) or hold null entries.  out[k] as from
- * pagan_fb_run (pagan_fb_kernel_ms: the launches' times at the batch's first wide pair, 0 at the others); on an error nothing
- * is handed back.                                                                                                        */
+ * pagan_fb_run; on an error nothing is handed back.  pagan_fb_kernel_ms: the pairs on the block schedule are timed as one, the
+ * LDS-ring pairs as one and the deep-ring pairs as one (each the span over all of the kind's launches); the two times go to the
+ * kind's first pair and 0 to its others, so that a sum over the batch is the launches'; a one-workgroup pair reports its
+ * own times when it is the call's only pair and 0 otherwise.                                                             */
 int  pagan_fb_run_batch(int32_t n, const pagan_graph *const *left, const pagan_graph *const *right,
                         const pagan_model_prob *const *model, const pagan_band *const *band, const pagan_opts *opts,
                         pagan_fb **out);

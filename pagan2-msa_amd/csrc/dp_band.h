@@ -58,7 +58,15 @@ struct DiagIndex {
     std::vector<long long> doff;
     long long cells = 0;
     int max_width = 0;
-    void build(int Lx, int Ly, const RowBand &rb) {
+    int Lx = 0, Ly = 0;
+    // the index of cell (i, j) in the diagonal-major layout, -1 outside the matrix or the band (the device's cell_at)
+    long long at(int i, int j) const {
+        if (i < 0 || j < 0 || i >= Lx || j >= Ly) return -1;
+        const int d = i + j;
+        return (i >= imin[d] && i <= imax[d]) ? doff[d] + (i - imin[d]) : -1;
+    }
+    void build(int Lx_, int Ly_, const RowBand &rb) {
+        Lx = Lx_; Ly = Ly_;
         const int nd = Lx + Ly - 1;
         imin.resize(nd); imax.resize(nd); doff.resize(nd);
         int a = -1, b = 0;       // a = max{i: lo[i]+i <= d}, b = min{i: hi[i]+i >= d}

@@ -74,6 +74,13 @@ namespace {
         }                                                                                                    \
     } while (0)
 
+// the environment's switches: is `name` set to 0; `name` as an integer, or `dflt` where it is not set
+static bool fb_env_off(const char *name) { const char *e = std::getenv(name); return e && std::strcmp(e, "0") == 0; }
+static int fb_env_int(const char *name, int dflt) { const char *e = std::getenv(name); return e ? std::atoi(e) : dflt; }
+
+// ... and for a call that answers with a PAGAN_* code of its own
+#define FB_DO(call) do { const int rc_ = (call); if (rc_ != PAGAN_OK) return rc_; } while (0)
+
 __device__ __forceinline__ double ninf() { return -__builtin_huge_val(); }
 
 // The sums' transcendental functions.  A log-sum-exp only ever asks for exp(x) with x <= 0 and for log(z) with
@@ -153,6 +160,26 @@ __device__ __forceinline__ long long cell_at(const PgFbJob &J, int p, int q) {
 
 __device__ __forceinline__ double rd(const double *A, long long at, int s) { return at >= 0 ? A[3 * at + s] : ninf(); }
 
+// The end corner, VA:1440-1552, behind a forward sweep: what the end site's edge lists reach, in the reference's order (the Y-close term
+// of a non-first right edge once per left edge).  cell(p, q, s): the log forward score of state s of cell (p, q), -inf outside the band.
+template <class Cell>
+__device__ __forceinline__ double fb_end_corner(const PgFbJob &J, Cell cell) {
+    double acc = ninf();
+    const int l0 = J.offL[J.Lx], l1 = J.offL[J.Lx + 1], r0 = J.offR[J.Ly], r1 = J.offR[J.Ly + 1];
+    auto mt = [&](int k1, int k2) { return cell(J.srcL[k1], J.srcR[k2], 2) + J.l_ng + (double)J.lwL[k1] + (double)J.lwR[k2]; };
+    auto xc = [&](int k1) { return cell(J.srcL[k1], J.Ly - 1, 0); };
+    auto yc = [&](int k2) { return cell(J.Lx - 1, J.srcR[k2], 1); };
+    if (l1 > l0 && r1 > r0) {
+        acc = lse(acc, mt(l0, r0)); acc = lse(acc, xc(l0)); acc = lse(acc, yc(r0));
+        for (int k2 = r0 + 1; k2 < r1; ++k2) { acc = lse(acc, mt(l0, k2)); acc = lse(acc, yc(k2)); }
+        for (int k1 = l0 + 1; k1 < l1; ++k1) {
+            acc = lse(acc, mt(k1, r0)); acc = lse(acc, xc(k1));
+            for (int k2 = r0 + 1; k2 < r1; ++k2) { acc = lse(acc, mt(k1, k2)); acc = lse(acc, yc(k2)); }
+        }
+    }
+    return acc;
+}
+
 __global__ __launch_bounds__(1024) void pg_fb_forward(const PgFbJob *jobs) {
     const PgFbJob J = jobs[blockIdx.x];
     for (int d = 0; d < J.nd; ++d) {
@@ -194,23 +221,8 @@ __global__ __launch_bounds__(1024) void pg_fb_forward(const PgFbJob *jobs) {
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        // end corner, VA:1440-1552
-        double acc = ninf();
-        const int l0 = J.offL[J.Lx], l1 = J.offL[J.Lx + 1], r0 = J.offR[J.Ly], r1 = J.offR[J.Ly + 1];
-        auto mt = [&](int k1, int k2) { return rd(J.F, cell_at(J, J.srcL[k1], J.srcR[k2]), 2) + J.l_ng + (double)J.lwL[k1] + (double)J.lwR[k2]; };
-        auto xc = [&](int k1) { return rd(J.F, cell_at(J, J.srcL[k1], J.Ly - 1), 0); };
-        auto yc = [&](int k2) { return rd(J.F, cell_at(J, J.Lx - 1, J.srcR[k2]), 1); };
-        if (l1 > l0 && r1 > r0) {
-            acc = lse(acc, mt(l0, r0)); acc = lse(acc, xc(l0)); acc = lse(acc, yc(r0));
-            for (int k2 = r0 + 1; k2 < r1; ++k2) { acc = lse(acc, mt(l0, k2)); acc = lse(acc, yc(k2)); }
-            for (int k1 = l0 + 1; k1 < l1; ++k1) {
-                acc = lse(acc, mt(k1, r0)); acc = lse(acc, xc(k1));
-                for (int k2 = r0 + 1; k2 < r1; ++k2) { acc = lse(acc, mt(k1, k2)); acc = lse(acc, yc(k2)); }
-            }
-        }
-        J.totals[0] = acc;
-    }
+    if (threadIdx.x == 0)
+        J.totals[0] = fb_end_corner(J, [&](int p, int q, int s_) { return rd(J.F, cell_at(J, p, q), s_); });
 }
 
 __global__ __launch_bounds__(1024) void pg_fb_backward(const PgFbJob *jobs) {
@@ -379,23 +391,8 @@ __global__ __launch_bounds__(FB_RG_THREADS) void pg_fb_forward_ring(const PgFbJo
         fb_lds_barrier();
     }
     __syncthreads();                                                               // (the end corner reads the scores from memory)
-    if (threadIdx.x == 0) {
-        // end corner, VA:1440-1552
-        double acc = ninf();
-        const int l0 = J.offL[J.Lx], l1 = J.offL[J.Lx + 1], r0 = J.offR[J.Ly], r1 = J.offR[J.Ly + 1];
-        auto mt = [&](int k1, int k2) { return rd(J.F, cell_at(J, J.srcL[k1], J.srcR[k2]), 2) + J.l_ng + (double)J.lwL[k1] + (double)J.lwR[k2]; };
-        auto xc = [&](int k1) { return rd(J.F, cell_at(J, J.srcL[k1], J.Ly - 1), 0); };
-        auto yc = [&](int k2) { return rd(J.F, cell_at(J, J.Lx - 1, J.srcR[k2]), 1); };
-        if (l1 > l0 && r1 > r0) {
-            acc = lse(acc, mt(l0, r0)); acc = lse(acc, xc(l0)); acc = lse(acc, yc(r0));
-            for (int k2 = r0 + 1; k2 < r1; ++k2) { acc = lse(acc, mt(l0, k2)); acc = lse(acc, yc(k2)); }
-            for (int k1 = l0 + 1; k1 < l1; ++k1) {
-                acc = lse(acc, mt(k1, r0)); acc = lse(acc, xc(k1));
-                for (int k2 = r0 + 1; k2 < r1; ++k2) { acc = lse(acc, mt(k1, k2)); acc = lse(acc, yc(k2)); }
-            }
-        }
-        J.totals[0] = acc;
-    }
+    if (threadIdx.x == 0)
+        J.totals[0] = fb_end_corner(J, [&](int p, int q, int s_) { return rd(J.F, cell_at(J, p, q), s_); });
 }
 
 // Mirrored: diagonals nd-1 .. 0; a cell reads (i+1, j), (i, j+1) of the diagonal after it and (i+1, j+1) of the one after that;
@@ -765,23 +762,8 @@ __global__ __launch_bounds__(64) void pg_fb_forward_tiled(const PgFbJob *jobs) {
         if (r == 0) atomicAdd((unsigned long long *)(sync + 22), __builtin_readcyclecounter() - sb0);
 #endif
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        // end corner, VA:1440-1552
-        double acc = NI;
-        const int l0 = J.offL[J.Lx], l1 = J.offL[J.Lx + 1], r0 = J.offR[J.Ly], r1 = J.offR[J.Ly + 1];
-        auto mt = [&](int k1, int k2) { return rd(J.F, cell_at(J, J.srcL[k1], J.srcR[k2]), 2) + J.l_ng + (double)J.lwL[k1] + (double)J.lwR[k2]; };
-        auto xc = [&](int k1) { return rd(J.F, cell_at(J, J.srcL[k1], J.Ly - 1), 0); };
-        auto yc = [&](int k2) { return rd(J.F, cell_at(J, J.Lx - 1, J.srcR[k2]), 1); };
-        if (l1 > l0 && r1 > r0) {
-            acc = lse(acc, mt(l0, r0)); acc = lse(acc, xc(l0)); acc = lse(acc, yc(r0));
-            for (int k2 = r0 + 1; k2 < r1; ++k2) { acc = lse(acc, mt(l0, k2)); acc = lse(acc, yc(k2)); }
-            for (int k1 = l0 + 1; k1 < l1; ++k1) {
-                acc = lse(acc, mt(k1, r0)); acc = lse(acc, xc(k1));
-                for (int k2 = r0 + 1; k2 < r1; ++k2) { acc = lse(acc, mt(k1, k2)); acc = lse(acc, yc(k2)); }
-            }
-        }
-        J.totals[0] = acc;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        J.totals[0] = fb_end_corner(J, [&](int p, int q, int s_) { return rd(J.F, cell_at(J, p, q), s_); });
 }
 
 template <bool ALL_LDS>
@@ -1037,29 +1019,16 @@ struct pagan_fb {
     PgFbJob job{};                                      // the pair's job record (device pointers into the arena) ...
     const PgFbJob *d_job = nullptr;                     // ... and where it sits on the device
     float post_ms[3] = {0, 0, 0};                       // last pg_fb_gather, row pass, column pass (HIP events)
-    long long at(int i, int j) const {
-        if (i < 0 || j < 0 || i >= Lx || j >= Ly) return -1;
-        const int d = i + j;
-        return (i >= dx.imin[d] && i <= dx.imax[d]) ? dx.doff[d] + (i - dx.imin[d]) : -1;
-    }
+    long long at(int i, int j) const { return dx.at(i, j); }
 };
-
-extern "C" {
-
-} // extern "C"
 
 namespace {
 // initialise_array_corner_bwd (VA:740-854): assignments onto the cells the end corner reads
 static void fb_corner_init(const pagan_graph *left, const pagan_graph *right, int Lx, int Ly, const DiagIndex &dx, double l_ng,
                            std::vector<long long> &init_at, std::vector<double> &init_val, int &init_dmin) {
-    auto at = [&](int i, int j) -> long long {
-        if (i < 0 || j < 0 || i >= Lx || j >= Ly) return -1;
-        const int d = i + j;
-        return (i >= dx.imin[d] && i <= dx.imax[d]) ? dx.doff[d] + (i - dx.imin[d]) : -1;
-    };
     init_dmin = Lx + Ly - 1;
     auto put_init = [&](int i, int j, int s, double v) {
-        const long long a = at(i, j);
+        const long long a = dx.at(i, j);
         if (a < 0) return;
         init_dmin = std::min(init_dmin, i + j);
         for (size_t k = 0; k < init_at.size(); ++k) if (init_at[k] == 3 * a + s) { init_val[k] = v; return; }   // later assignment wins
@@ -1175,10 +1144,8 @@ static void fb_route(const pagan_graph *left, const pagan_graph *right, int Lx, 
     const bool shape_ok = mw <= FB_RG_MAXB && Lx >= 2 && Ly >= 2 && n_init <= FB_RG_INIT && gapless;
     bool ring = false, deep = false;
     {
-        int min_nd = 256;            // (a step of the ring sweeps is 1 us against the one-workgroup kernels' 2.7: worth it from a few hundred diagonals on)
-        if (const char *e = std::getenv("PAGAN_FB_RING_MIN_ND")) min_nd = std::atoi(e);
-        const char *re = std::getenv("PAGAN_FB_RING");
-        ring = !(re && std::strcmp(re, "0") == 0) && nd >= min_nd && shape_ok && both_plain;
+        const int min_nd = fb_env_int("PAGAN_FB_RING_MIN_ND", 256);   // (a step of the ring sweeps is 1 us against the one-workgroup kernels' 2.7: worth it from a few hundred diagonals on)
+        ring = !fb_env_off("PAGAN_FB_RING") && nd >= min_nd && shape_ok && both_plain;
         if (ring && !std::getenv("PAGAN_FB_GROUPS")) groups = 1;
     }
     // the longest reach of a site's lists: bwd (the forward sweep's predecessors), fwd without the edges into the end site (the backward sweep's successors)
@@ -1199,22 +1166,20 @@ static void fb_route(const pagan_graph *left, const pagan_graph *right, int Lx, 
     R->info[0] = nd; R->info[1] = mw;
     R->info[4] = reaches(left, fl, Lx, rL, sL); R->info[5] = reaches(right, fr, Ly, rR, sR);
     {
-        int min_nd = 4096;
-        if (const char *e = std::getenv("PAGAN_FB_DEEP_MIN_ND")) min_nd = std::atoi(e);
-        const char *de = std::getenv("PAGAN_FB_DEEP");
+        const int min_nd = fb_env_int("PAGAN_FB_DEEP_MIN_ND", 4096);
         // the list windows hold FB_DP_E entries of any FB_DP_W consecutive sites
         auto lists_fit = [](const int *off, int n_sites) {
             for (int v = 0; v < n_sites; ++v) if (off[std::min(n_sites, v + FB_DP_W)] - off[v] > FB_DP_E) return false;
             return true;
         };
-        deep = !(de && std::strcmp(de, "0") == 0) && !std::getenv("PAGAN_FB_GROUPS") && has_band && nd >= min_nd && shape_ok && !both_plain &&
+        deep = !fb_env_off("PAGAN_FB_DEEP") && !std::getenv("PAGAN_FB_GROUPS") && has_band && nd >= min_nd && shape_ok && !both_plain &&
                lists_fit(left->bwd_off, left->n_sites) && lists_fit(right->bwd_off, right->n_sites) &&
                lists_fit(fl.off.data(), left->n_sites) && lists_fit(fr.off.data(), right->n_sites);
         if (deep) { groups = 1; ring = false; fb_deep_plan(Lx, Ly, dx, rL, rR, sL, sR, R); }
     }
     {
-        int min_nd = 4096;
-        if (const char *e = std::getenv("PAGAN_FB_BAND_MIN_ND")) min_nd = std::strcmp(e, "off") == 0 ? 0x7fffffff : std::atoi(e);
+        const char *e = std::getenv("PAGAN_FB_BAND_MIN_ND");
+        const int min_nd = e && std::strcmp(e, "off") == 0 ? 0x7fffffff : fb_env_int("PAGAN_FB_BAND_MIN_ND", 4096);
         if (ring || deep) {}
         else if (groups == 1 && nd >= min_nd && Lx >= 2 && Ly >= 2)
             groups = std::max(2, std::min({FB_MAX_GROUPS, (mw + FB_T - 1) / FB_T + 2, (Lx + FB_T - 1) / FB_T, (Ly + FB_T - 1) / FB_T}));
@@ -1222,25 +1187,87 @@ static void fb_route(const pagan_graph *left, const pagan_graph *right, int Lx, 
         //  the 64 workgroups of a full matrix at every barrier: a diagonal of mw cells lies in mw / 64 + 2 blocks at most)
         else if (groups > 1) groups = std::max(2, std::min(groups, (mw + FB_T - 1) / FB_T + 2));
     }
-    if (const char *e = std::getenv("PAGAN_FB_GROUPS")) { groups = std::max(1, std::min(FB_MAX_GROUPS, std::atoi(e))); ring = false; }
+    if (std::getenv("PAGAN_FB_GROUPS")) { groups = std::max(1, std::min(FB_MAX_GROUPS, fb_env_int("PAGAN_FB_GROUPS", 1))); ring = false; }
     R->groups = groups; R->ring = ring; R->deep = deep;
 }
 } // namespace
 
 namespace {
+// The calling thread on `device` (negative: the one it is on) for the length of a call, back on the device it came with afterwards.
+struct FbDeviceScope {
+    int back = -1, device; bool ok;
+    explicit FbDeviceScope(int want) : device(want) {
+        ok = hipGetDevice(&back) == hipSuccess;
+        if (ok && device < 0) device = back;
+        ok = ok && hipSetDevice(device) == hipSuccess;
+    }
+    ~FbDeviceScope() { if (back >= 0) (void)hipSetDevice(back); }
+};
+
+// Owners of what a call makes on the device: a stream, an event, an allocation.  Move-only; each frees in its destructor, on the
+// device it was made on, so a return from the middle of a function (FB_TRY) leaks nothing.  A stream is SYNCHRONISED before it is
+// destroyed: on a failure path its kernels may still be writing a pair's arena, and the arena must not reach fb_arena_pool (whose
+// next take would hand it out) before they are done -- so whatever destroys a pagan_fb does so after the streams' owners are gone.
+// On a success path the code has synchronised already and the destructor's wait is a no-op.
+template <class T>
+struct FbOwned {
+    T h = nullptr; int device = 0;
+    FbOwned() = default;
+    FbOwned(FbOwned &&o) noexcept : h(o.h), device(o.device) { o.h = nullptr; }
+    FbOwned(const FbOwned &) = delete;
+    FbOwned &operator=(const FbOwned &) = delete;
+    ~FbOwned() {
+        if (!h) return;
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        if (cur != device) (void)hipSetDevice(device);
+        drop(h);
+        if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
+    }
+    operator T() const { return h; }
+    static void drop(hipStream_t s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+    static void drop(hipEvent_t e) { (void)hipEventDestroy(e); }
+    static void drop(char *p) { (void)hipFree(p); }
+};
+struct FbStream : FbOwned<hipStream_t> {
+    int create() { FB_TRY(hipGetDevice(&device)); FB_TRY(hipStreamCreate(&h)); return PAGAN_OK; }
+};
+struct FbEvent : FbOwned<hipEvent_t> {
+    int create(bool timing = true) { FB_TRY(hipGetDevice(&device)); FB_TRY(hipEventCreateWithFlags(&h, timing ? hipEventDefault : hipEventDisableTiming)); return PAGAN_OK; }
+};
+struct FbDevBuf : FbOwned<char *> {
+    int alloc(size_t bytes) { FB_TRY(hipGetDevice(&device)); FB_TRY(hipMalloc((void **)&h, bytes)); return PAGAN_OK; }
+};
+
+// The arena's arrays, each named once: add() reserves the array's range (rounded up to 256 bytes) and remembers where its bytes
+// come from and which pointer of the job record is to point at it; bind() fills the staging buffer and sets the pointers once
+// the arena's base is known.
+struct FbLayout {
+    struct Item { size_t off, bytes; const void *src; void *field; };
+    std::vector<Item> items;
+    size_t cur = 0;
+    template <class P>
+    void add(const void *src, size_t bytes, P **field) {
+        items.push_back({cur, bytes, src, (void *)field});
+        cur = (cur + bytes + 255) / 256 * 256;
+    }
+    void bind(char *base, char *stage) const {
+        for (const Item &it : items) { char *p = base + it.off; std::memcpy(it.field, &p, sizeof(p)); }
+        for (const Item &it : items) if (it.src && it.bytes) std::memcpy(stage + it.off, it.src, it.bytes);
+    }
+};
+
 // One pair up to the upload of its inputs: validation, band index, lists, arena, the job record with its workgroup count
-// (`groups_cap`: what the caller's launch leaves this pair) -- what pagan_fb_run and pagan_fb_run_batch share.
+// (`groups_cap`, `groups_cap_b`: what the caller's launch leaves this pair's forward / backward sweep).  What the handle does not
+// hold itself stays here.
 struct FbStaged {
-    pagan_fb *fb = nullptr;
-    const PgFbJob *d_job = nullptr;          // the pair's job record on the device
-    PgFbJob job;                             // ... and what it holds
-    char *d_tot = nullptr, *d_sync = nullptr;
-    int groups = 1, groups_b = 1, block = 64;
-    bool ring = false;                       // the sweeps are pg_fb_forward_ring / pg_fb_backward_ring (block = their B)
-    bool deep = false;                       // ... pg_fb_forward_deep / pg_fb_backward_deep (block = their threads)
-    double t_host[4] = {0, 0, 0, 0};         // band index + lists, arena, staging, upload (seconds)
+    std::unique_ptr<pagan_fb, void (*)(pagan_fb *)> fb{nullptr, pagan_fb_destroy};
+    int groups_b = 1;                        // workgroups of the backward tiled sweep (the forward sweep's: fb->groups)
+    int block = 64;                          // threads of a workgroup; ring sweeps: their rows B
+    double t_host[3] = {0, 0, 0};            // band index + lists, arena, upload (seconds)
     size_t arena_bytes = 0;
 };
+static double fb_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pagan_model_prob *model, const pagan_band *band,
                     const pagan_opts *opts, int groups_cap, int groups_cap_b, FbStaged *st) {
     if (!left || !right || !model || !st || !model->score || model->n_states < 1) return PAGAN_E_ARG;
@@ -1248,15 +1275,14 @@ static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pag
     if (rc == PAGAN_OK) rc = check_graph(right);
     if (rc != PAGAN_OK) return rc;
     const int Lx = left->n_sites - 1, Ly = right->n_sites - 1, S = model->n_states;
-    auto now_ = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double th0 = now_();
+    const double th0 = fb_now();
     for (int s = 1; s < Lx; ++s) if (left->state[s] < 0 || left->state[s] >= S) return PAGAN_E_MODEL;
     for (int s = 1; s < Ly; ++s) if (right->state[s] < 0 || right->state[s] >= S) return PAGAN_E_MODEL;
     if (!(model->gap_open > 0) || !(model->gap_ext > 0) || !(model->non_gap > 0)) return PAGAN_E_MODEL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return PAGAN_E_NODEVICE;
-    pagan_fb *fb = new pagan_fb();
-    std::unique_ptr<pagan_fb, void (*)(pagan_fb *)> guard(fb, [](pagan_fb *p) { pagan_fb_destroy(p); });
+    st->fb.reset(new pagan_fb());            // (st owns the handle: an error from here on destroys it with st)
+    pagan_fb *fb = st->fb.get();
     if (opts && opts->device >= 0) { FB_TRY(hipSetDevice(opts->device)); fb->device = opts->device; }
     else FB_TRY(hipGetDevice(&fb->device));
     fb->Lx = Lx; fb->Ly = Ly; fb->S = S; fb->L = left; fb->R = right;
@@ -1277,98 +1303,68 @@ static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pag
     fb_corner_init(left, right, Lx, Ly, fb->dx, l_ng, init_at, init_val, init_dmin);
     FbRoute route;
     fb_route(left, right, Lx, Ly, fb->dx, band != nullptr, (int)init_at.size(), fl, fr, &route);
-    // one arena: inputs, then F and B
-    size_t cur = 0;
-    auto take = [&](size_t bytes) { const size_t o = cur; cur = (cur + bytes + 255) / 256 * 256; return o; };
-    const int nbL = left->bwd_off[left->n_sites], nbR = right->bwd_off[right->n_sites];
-    const size_t o_job = take(sizeof(PgFbJob));
-    const size_t o_stL = take(4 * (size_t)left->n_sites), o_offL = take(4 * ((size_t)left->n_sites + 1)), o_srcL = take(4 * (size_t)nbL), o_lwL = take(4 * (size_t)nbL);
-    const size_t o_stR = take(4 * (size_t)right->n_sites), o_offR = take(4 * ((size_t)right->n_sites + 1)), o_srcR = take(4 * (size_t)nbR), o_lwR = take(4 * (size_t)nbR);
-    const size_t o_foL = take(4 * fl.off.size()), o_fdL = take(4 * fl.dst.size()), o_fwL = take(4 * fl.lw.size());
-    const size_t o_foR = take(4 * fr.off.size()), o_fdR = take(4 * fr.dst.size()), o_fwR = take(4 * fr.lw.size());
-    const size_t o_tab = take(8 * ltab.size());
-    const size_t o_imin = take(4 * (size_t)nd), o_imax = take(4 * (size_t)nd), o_doff = take(8 * (size_t)nd);
-    const size_t o_iat = take(8 * init_at.size()), o_ival = take(8 * init_val.size());
-    const size_t o_segs = take(4 * route.seg_start.size()), o_segB = take(4 * route.seg_B.size()), o_dfar = take(4 * route.dfar.size());
-    const size_t o_tot = take(16);
-    const size_t o_sync = take(256);                      // two barrier counters + give-up words of the wide sweeps (zero)
-    const size_t in_bytes = cur;
-    const size_t o_F = take(24 * (size_t)cells), o_B = take(24 * (size_t)cells);
-    const double th1 = now_();
-    fb->arena = fb_arena_pool.take(fb->device, cur, &fb->arena_cap);
-    if (!fb->arena) return PAGAN_E_NOMEM;
-    std::vector<char> stage(in_bytes, 0);
-    auto put = [&](size_t off, const void *src, size_t bytes) { if (bytes) std::memcpy(stage.data() + off, src, bytes); };
-    put(o_stL, left->state, 4 * (size_t)left->n_sites); put(o_offL, left->bwd_off, 4 * ((size_t)left->n_sites + 1));
-    put(o_srcL, left->bwd_src, 4 * (size_t)nbL); put(o_lwL, left->bwd_logw, 4 * (size_t)nbL);
-    put(o_stR, right->state, 4 * (size_t)right->n_sites); put(o_offR, right->bwd_off, 4 * ((size_t)right->n_sites + 1));
-    put(o_srcR, right->bwd_src, 4 * (size_t)nbR); put(o_lwR, right->bwd_logw, 4 * (size_t)nbR);
-    put(o_foL, fl.off.data(), 4 * fl.off.size()); put(o_fdL, fl.dst.data(), 4 * fl.dst.size()); put(o_fwL, fl.lw.data(), 4 * fl.lw.size());
-    put(o_foR, fr.off.data(), 4 * fr.off.size()); put(o_fdR, fr.dst.data(), 4 * fr.dst.size()); put(o_fwR, fr.lw.data(), 4 * fr.lw.size());
-    put(o_tab, ltab.data(), 8 * ltab.size());
-    put(o_imin, fb->dx.imin.data(), 4 * (size_t)nd); put(o_imax, fb->dx.imax.data(), 4 * (size_t)nd); put(o_doff, fb->dx.doff.data(), 8 * (size_t)nd);
-    put(o_iat, init_at.data(), 8 * init_at.size()); put(o_ival, init_val.data(), 8 * init_val.size());
-    put(o_segs, route.seg_start.data(), 4 * route.seg_start.size()); put(o_segB, route.seg_B.data(), 4 * route.seg_B.size()); put(o_dfar, route.dfar.data(), 4 * route.dfar.size());
-    char *b = fb->arena;
-    // the schedule: fb_route above
+    // the schedule: fb_route above, the tiled sweeps' workgroups within the caller's caps
     const int mw = fb->dx.max_width;
-    int groups = route.groups;
-    const bool ring = route.ring;
-    const int groups_b = groups > 1 ? std::max(2, std::min(groups, groups_cap_b)) : 1;
-    if (groups > 1) groups = std::max(2, std::min(groups, groups_cap));
-    fb->groups = groups;
-    PgFbJob J;
+    fb->groups = route.groups > 1 ? std::max(2, std::min(route.groups, groups_cap)) : route.groups;
+    st->groups_b = route.groups > 1 ? std::max(2, std::min(route.groups, groups_cap_b)) : 1;
+    PgFbJob &J = fb->job;
     J.Lx = Lx; J.Ly = Ly; J.nd = nd; J.S = S;
     J.l_ext = std::log((double)model->gap_ext); J.l_open = std::log((double)model->gap_open); J.l_ng = l_ng;
-    J.stL = (const int *)(b + o_stL); J.offL = (const int *)(b + o_offL); J.srcL = (const int *)(b + o_srcL); J.lwL = (const float *)(b + o_lwL);
-    J.stR = (const int *)(b + o_stR); J.offR = (const int *)(b + o_offR); J.srcR = (const int *)(b + o_srcR); J.lwR = (const float *)(b + o_lwR);
-    J.foffL = (const int *)(b + o_foL); J.fdstL = (const int *)(b + o_fdL); J.flwL = (const float *)(b + o_fwL);
-    J.foffR = (const int *)(b + o_foR); J.fdstR = (const int *)(b + o_fdR); J.flwR = (const float *)(b + o_fwR);
-    J.ltab = (const double *)(b + o_tab);
-    J.imin = (const int *)(b + o_imin); J.imax = (const int *)(b + o_imax); J.doff = (const long long *)(b + o_doff);
     J.cells = cells;
-    J.F = (double *)(b + o_F); J.B = (double *)(b + o_B);
-    J.n_init = (int)init_at.size(); J.init_at = (const long long *)(b + o_iat); J.init_val = (const double *)(b + o_ival);
-    J.totals = (double *)(b + o_tot);
-    J.groups = groups; J.groups_b = groups_b; J.sync = (int *)(b + o_sync);
-    J.init_dmin = init_dmin;
-    J.nseg = (int)route.seg_B.size(); J.seg_start = (const int *)(b + o_segs); J.seg_B = (const int *)(b + o_segB); J.dfar = (const int *)(b + o_dfar);
-    std::memcpy(stage.data() + o_job, &J, sizeof(J));
+    J.n_init = (int)init_at.size(); J.init_dmin = init_dmin;
+    J.groups = fb->groups; J.groups_b = st->groups_b;
+    J.nseg = (int)route.seg_B.size();
+    // one arena: the job record and the inputs, then F and B (pagan_fb_predict_bytes and the pool's fit rule know this layout)
+    FbLayout lay;
+    auto vec = [&](const auto &v, auto **field) { lay.add(v.data(), sizeof(v[0]) * v.size(), field); };
+    const size_t nL = (size_t)left->n_sites, nR = (size_t)right->n_sites, nbL = (size_t)left->bwd_off[nL], nbR = (size_t)right->bwd_off[nR];
+    lay.add(&J, sizeof(PgFbJob), &fb->d_job);
+    lay.add(left->state, 4 * nL, &J.stL); lay.add(left->bwd_off, 4 * (nL + 1), &J.offL); lay.add(left->bwd_src, 4 * nbL, &J.srcL); lay.add(left->bwd_logw, 4 * nbL, &J.lwL);
+    lay.add(right->state, 4 * nR, &J.stR); lay.add(right->bwd_off, 4 * (nR + 1), &J.offR); lay.add(right->bwd_src, 4 * nbR, &J.srcR); lay.add(right->bwd_logw, 4 * nbR, &J.lwR);
+    vec(fl.off, &J.foffL); vec(fl.dst, &J.fdstL); vec(fl.lw, &J.flwL);
+    vec(fr.off, &J.foffR); vec(fr.dst, &J.fdstR); vec(fr.lw, &J.flwR);
+    vec(ltab, &J.ltab);
+    vec(fb->dx.imin, &J.imin); vec(fb->dx.imax, &J.imax); vec(fb->dx.doff, &J.doff);
+    vec(init_at, &J.init_at); vec(init_val, &J.init_val);
+    vec(route.seg_start, &J.seg_start); vec(route.seg_B, &J.seg_B); vec(route.dfar, &J.dfar);
+    lay.add(nullptr, 16, &J.totals);
+    lay.add(nullptr, 256, &J.sync);                       // two barrier counters + give-up words of the wide sweeps (zero)
+    const size_t in_bytes = lay.cur;
+    lay.add(nullptr, 24 * (size_t)cells, &J.F); lay.add(nullptr, 24 * (size_t)cells, &J.B);
+    const double th1 = fb_now();
+    fb->arena = fb_arena_pool.take(fb->device, lay.cur, &fb->arena_cap);
+    if (!fb->arena) return PAGAN_E_NOMEM;
+    std::vector<char> stage(in_bytes, 0);
+    lay.bind(fb->arena, stage.data());
     fb->dF = J.F; fb->dB = J.B;
-    fb->job = J; fb->d_job = (const PgFbJob *)(b + o_job);
-    const double th2 = now_();
+    const double th2 = fb_now();
     FB_TRY(hipMemcpy(fb->arena, stage.data(), in_bytes, hipMemcpyHostToDevice));
-    const double th3 = now_();
     // a thread per cell of the widest diagonal, up to the 1024 of a workgroup (a cell is ~20 exp / log1p calls: a thread with
     // eight cells of a 2,000-cell diagonal was the whole sweep's pace)
     st->block = mw >= 768 ? 1024 : mw >= 384 ? 512 : mw >= 192 ? 256 : (mw >= 96 ? 128 : 64);
-    st->ring = ring && groups == 1;
-    if (st->ring) st->block = mw > 512 ? 1024 : (mw > 256 ? 512 : (mw > 128 ? 256 : (mw > 64 ? 128 : 64)));     // a thread per row of the widest diagonal
-    st->deep = route.deep;
-    if (st->deep) st->block = route.deep_block;
-    fb->ring = st->ring; fb->deep = st->deep;
-    st->groups = groups; st->groups_b = groups_b;
-    st->d_job = (const PgFbJob *)(b + o_job); st->d_tot = b + o_tot; st->d_sync = b + o_sync; st->job = J;
-    st->t_host[0] = th1 - th0; st->t_host[1] = th2 - th1; st->t_host[2] = 0.0; st->t_host[3] = th3 - th2;
-    st->arena_bytes = cur;
-    st->fb = guard.release();
+    fb->ring = route.ring && fb->groups == 1;
+    if (fb->ring) st->block = mw > 512 ? 1024 : (mw > 256 ? 512 : (mw > 128 ? 256 : (mw > 64 ? 128 : 64)));     // a thread per row of the widest diagonal
+    fb->deep = route.deep;
+    if (fb->deep) st->block = route.deep_block;
+    st->t_host[0] = th1 - th0; st->t_host[1] = th2 - th1; st->t_host[2] = fb_now() - th2;
+    st->arena_bytes = lay.cur;
     return PAGAN_OK;
 }
 
-// ... and behind the kernels: the totals, the barriers' give-up words
+// ... and behind the kernels: the kernel times, the totals, the barriers' give-up words
 static int fb_finish(FbStaged *st, float fwd_ms, float bwd_ms) {
-    pagan_fb *fb = st->fb;
+    pagan_fb *fb = st->fb.get();
     fb->kernel_ms[0] = fwd_ms; fb->kernel_ms[1] = bwd_ms;
-    FB_TRY(hipMemcpy(fb->totals, st->d_tot, 16, hipMemcpyDeviceToHost));
+    FB_TRY(hipMemcpy(fb->totals, fb->job.totals, 16, hipMemcpyDeviceToHost));
     int sy[64];
-    FB_TRY(hipMemcpy(sy, st->d_sync, sizeof(sy), hipMemcpyDeviceToHost));
+    FB_TRY(hipMemcpy(sy, fb->job.sync, sizeof(sy), hipMemcpyDeviceToHost));
     if (sy[1] != 0 || sy[9] != 0) return PAGAN_E_INTERNAL;          // a barrier of a wide sweep ran into its limit
 #ifdef PG_FB_STATS
     {
         const unsigned long long *q = (const unsigned long long *)(sy + 16);
         std::fprintf(stderr, "pagan_fb: forward: %llu blocks, prologue %.0f cycles per block, steps %.0f per block, barrier %.0f per workgroup and block diagonal (%d groups)\n",
                      q[0], q[0] ? (double)q[1] / q[0] : 0.0, q[0] ? (double)q[2] / q[0] : 0.0,
-                     st->groups ? (double)q[3] / st->groups / ((fb->Lx + 63) / 64 + (fb->Ly + 63) / 64 - 1) : 0.0, st->groups);
+                     (double)q[3] / fb->groups / ((fb->Lx + 63) / 64 + (fb->Ly + 63) / 64 - 1), fb->groups);
     }
 #endif
     return PAGAN_OK;
@@ -1385,310 +1381,227 @@ struct FbSlots {
     void give(int n) { { std::lock_guard<std::mutex> l(m); used -= n; } cv.notify_all(); }
 };
 static FbSlots fb_slots_of[64];
+struct FbSlotLease { FbSlots *s; int n; ~FbSlotLease() { if (n > 0) s->give(n); } };
 static int fb_slot_cap(int device) {
-    int n_cu = 0, per_cu_x16 = 46;                              // 2.9 workgroups per compute unit of the 3 that fit (PAGAN_FB_SLOTS_X16: A/B; 2.5 until round 5)
-    if (const char *e = std::getenv("PAGAN_FB_SLOTS_X16")) per_cu_x16 = std::max(8, std::min(48, std::atoi(e)));
+    int n_cu = 0;
+    const int per_cu_x16 = std::max(8, std::min(48, fb_env_int("PAGAN_FB_SLOTS_X16", 46)));   // 2.9 workgroups per compute unit of the 3 that fit (A/B; 2.5 until round 5)
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0) return per_cu_x16 * n_cu / 16;
     return 512;
 }
-// threads a row of a ring sweep's workgroup of B rows: three up to B = 256, two with 512 (PAGAN_FB_RING_SPLIT=0: one), see FB_RING_THREADS
-static int fb_ring_split(int B) {
-    const char *e = std::getenv("PAGAN_FB_RING_SPLIT");
-    if (e && std::strcmp(e, "0") == 0) return 1;
-    return B <= 256 ? 3 : (B <= 512 ? 2 : 1);          // (1,024 threads is what a workgroup holds)
+
+// The four schedules' kernels behind one launch.  `block`: the threads of a one-workgroup, tiled or deep-ring workgroup, the rows
+// B of a ring sweep's -- its workgroup has three threads a row up to B = 256, two with 512 (PAGAN_FB_RING_SPLIT=0: one), see
+// FB_RING_THREADS; 1,024 threads is what a workgroup holds.  all_lds: every pair's score table fits LDS (the kernels without the
+// table's load from memory; the one-workgroup kernels have one form).
+enum FbKind { FB_K_SMALL = 0, FB_K_TILED = 1, FB_K_RING = 2, FB_K_DEEP = 3 };      // (pagan_fb_schedule's codes)
+typedef void (*FbKernel)(const PgFbJob *);
+template <bool ALL_LDS>
+static FbKernel fb_kernel(FbKind kind, bool fwd, int block, int nsplit) {
+    if (kind == FB_K_TILED) return fwd ? pg_fb_forward_tiled<ALL_LDS> : pg_fb_backward_tiled<ALL_LDS>;
+    if (kind == FB_K_DEEP) return fwd ? pg_fb_forward_deep<ALL_LDS> : pg_fb_backward_deep<ALL_LDS>;
+    if (kind == FB_K_SMALL) return fwd ? pg_fb_forward : pg_fb_backward;
+    if (block > 512) return fwd ? pg_fb_forward_ring<ALL_LDS, 1, 1024> : pg_fb_backward_ring<ALL_LDS, 1, 1024>;
+    if (nsplit == 3) return fwd ? pg_fb_forward_ring<ALL_LDS, 3, 512> : pg_fb_backward_ring<ALL_LDS, 3, 512>;
+    if (nsplit == 2) return fwd ? pg_fb_forward_ring<ALL_LDS, 2, 512> : pg_fb_backward_ring<ALL_LDS, 2, 512>;
+    return fwd ? pg_fb_forward_ring<ALL_LDS, 1, 512> : pg_fb_backward_ring<ALL_LDS, 1, 512>;
 }
-template <bool FWD, bool ALL_LDS>
-static void fb_launch_ring_(int nsplit, unsigned grid, int B, hipStream_t st, const PgFbJob *jobs) {
-    const dim3 g(grid), t((unsigned)(nsplit * B));
-    if (FWD) {
-        if (B > 512) hipLaunchKernelGGL((pg_fb_forward_ring<ALL_LDS, 1, 1024>), g, t, 0, st, jobs);
-        else if (nsplit == 3) hipLaunchKernelGGL((pg_fb_forward_ring<ALL_LDS, 3, 512>), g, t, 0, st, jobs);
-        else if (nsplit == 2) hipLaunchKernelGGL((pg_fb_forward_ring<ALL_LDS, 2, 512>), g, t, 0, st, jobs);
-        else hipLaunchKernelGGL((pg_fb_forward_ring<ALL_LDS, 1, 512>), g, t, 0, st, jobs);
-    } else {
-        if (B > 512) hipLaunchKernelGGL((pg_fb_backward_ring<ALL_LDS, 1, 1024>), g, t, 0, st, jobs);
-        else if (nsplit == 3) hipLaunchKernelGGL((pg_fb_backward_ring<ALL_LDS, 3, 512>), g, t, 0, st, jobs);
-        else if (nsplit == 2) hipLaunchKernelGGL((pg_fb_backward_ring<ALL_LDS, 2, 512>), g, t, 0, st, jobs);
-        else hipLaunchKernelGGL((pg_fb_backward_ring<ALL_LDS, 1, 512>), g, t, 0, st, jobs);
-    }
+static void fb_launch(FbKind kind, bool fwd, bool all_lds, dim3 grid, int block, hipStream_t stream, const PgFbJob *jobs) {
+    const int nsplit = kind != FB_K_RING || fb_env_off("PAGAN_FB_RING_SPLIT") ? 1 : (block <= 256 ? 3 : (block <= 512 ? 2 : 1));
+    const FbKernel k = all_lds ? fb_kernel<true>(kind, fwd, block, nsplit) : fb_kernel<false>(kind, fwd, block, nsplit);
+    hipLaunchKernelGGL(k, grid, dim3((unsigned)(nsplit * block)), 0, stream, jobs);
 }
-// one launch of ring sweeps: `grid` pairs of B rows each, forward or backward, score tables all in LDS or not
-static void fb_launch_ring(bool fwd, bool all_lds, unsigned grid, int B, hipStream_t st, const PgFbJob *jobs) {
-    const int ns = fb_ring_split(B);
-    if (fwd) { if (all_lds) fb_launch_ring_<true, true>(ns, grid, B, st, jobs); else fb_launch_ring_<true, false>(ns, grid, B, st, jobs); }
-    else { if (all_lds) fb_launch_ring_<false, true>(ns, grid, B, st, jobs); else fb_launch_ring_<false, false>(ns, grid, B, st, jobs); }
-}
-// one launch of deep-ring sweeps: `grid` graph pairs, workgroups of `threads` threads
-static void fb_launch_deep(bool fwd, bool all_lds, unsigned grid, int threads, hipStream_t st, const PgFbJob *jobs) {
-    const dim3 g(grid), t((unsigned)threads);
-    if (fwd) { if (all_lds) hipLaunchKernelGGL((pg_fb_forward_deep<true>), g, t, 0, st, jobs); else hipLaunchKernelGGL((pg_fb_forward_deep<false>), g, t, 0, st, jobs); }
-    else { if (all_lds) hipLaunchKernelGGL((pg_fb_backward_deep<true>), g, t, 0, st, jobs); else hipLaunchKernelGGL((pg_fb_backward_deep<false>), g, t, 0, st, jobs); }
-}
-struct FbSlotLease { FbSlots *s; int n; ~FbSlotLease() { if (n > 0) s->give(n); } };
-// the calling thread on `device` for the length of a call, back on the device it came with afterwards
-struct FbDeviceScope {
-    int back; bool ok;
-    FbDeviceScope(int device, int caller) : back(caller), ok(hipSetDevice(device) == hipSuccess) {}
-    ~FbDeviceScope() { (void)hipSetDevice(back); }
+
+// A chunk's launches are described before any goes out.  A GROUP is one launch per direction: the pairs that share a kind, a
+// workgroup size and `all_lds`.  A SPAN is what is timed as one: the groups [a, z) of one kind, side by side -- the first on
+// the span's two streams (forward, backward), each other on streams of its own that those two wait for, so that the events
+// around the two span them all.  The tiled pairs are one group; the ring pairs one span, the deep-ring pairs another, of a group
+// per (workgroup size, table in LDS or not) -- a handful at most; a one-workgroup pair is a group and a span of its own.
+// (Only the tiled group is charged to the slot budget: see ADVICE.md's fourth finding; this list is where the others would be.)
+struct FbGroup {
+    FbKind kind; bool all_lds; int block;
+    unsigned gx, gx_b, gy;                   // the grid: x of the forward / of the backward launch, y
+    std::vector<int> ks;                     // its pairs, in the order of its job records
+    const PgFbJob *jobs;                     // ... which are here on the device
 };
+struct FbSpan {
+    size_t a, z; bool timed;
+    hipStream_t lane[2]; hipEvent_t ev[4];   // forward, backward; forward's start and end, backward's
+};
+// what a chunk's launches run on (the streams last: they are synchronised and destroyed before anything else goes)
+struct FbChunkRes {
+    std::vector<FbEvent> events;
+    std::vector<FbStream> streams;
+    int stream(hipStream_t *s) { streams.emplace_back(); const int rc = streams.back().create(); *s = streams.back(); return rc; }
+    int event(bool timing, hipEvent_t *e) { events.emplace_back(); const int rc = events.back().create(timing); *e = events.back(); return rc; }
+};
+static int fb_launch_span(FbChunkRes &res, const std::vector<FbGroup> &groups, FbSpan &S, bool bwd_first) {
+    for (int dir = 0; dir < 2; ++dir) FB_DO(res.stream(&S.lane[dir]));
+    for (int q = 0; q < 4 && S.timed; ++q) FB_DO(res.event(true, &S.ev[q]));
+    for (size_t g = S.a; g < S.z; ++g) {
+        const FbGroup &G = groups[g];
+        for (int q = 0; q < 2; ++q) {
+            const int dir = bwd_first ? 1 - q : q;
+            hipStream_t s = S.lane[dir];
+            if (g > S.a) FB_DO(res.stream(&s));
+            else if (S.timed) FB_TRY(hipEventRecord(S.ev[2 * dir], s));
+            fb_launch(G.kind, dir == 0, G.all_lds, dim3(dir ? G.gx_b : G.gx, G.gy), G.block, s, G.jobs);
+            if (g > S.a) {
+                hipEvent_t done = nullptr;
+                FB_DO(res.event(false, &done));
+                FB_TRY(hipEventRecord(done, s)); FB_TRY(hipStreamWaitEvent(S.lane[dir], done, 0));
+            }
+        }
+    }
+    if (S.timed) { FB_TRY(hipEventRecord(S.ev[1], S.lane[0])); FB_TRY(hipEventRecord(S.ev[3], S.lane[1])); }
+    return PAGAN_OK;
+}
+
+// A chunk of pairs whose tiled sweeps fit the slot budget: staged, launched, synchronised, their totals fetched.  st[q].fb is the
+// caller's to hand back or to destroy -- after this function has returned, that is after every stream of the chunk has been
+// synchronised by its owner, whichever way the function was left.  `only_pair`: the chunk is the call's one pair.
+static int fb_run_chunk(int chunk, const pagan_graph *const *left, const pagan_graph *const *right, const pagan_model_prob *const *model,
+                        const pagan_band *const *band, const pagan_opts *opts, bool only_pair, int cap, FbStaged *st) {
+    const int device = opts->device;
+    // the backward sweep is the slower of the two when a block anti-diagonal takes several turns: it gets the larger share
+    // of the slots (PAGAN_FB_SPLIT: the forward sweeps' per cent, A/B).  A single pair's caps come out at or above FB_MAX_GROUPS
+    // at the default budget; with PAGAN_FB_SLOTS_X16 near its minimum they can cut a single pair's sweeps too.
+    const int split = std::max(20, std::min(80, fb_env_int("PAGAN_FB_SPLIT", 40)));
+    const int per_pair = std::max(4, cap / chunk);            // slots of one pair, both sweeps
+    const int groups_cap = std::max(2, (per_pair * split + 50) / 100), groups_cap_b = std::max(2, per_pair - groups_cap);
+    std::vector<int> rcs(chunk, PAGAN_OK);
+    auto stage = [&](int q) { rcs[q] = fb_stage(left[q], right[q], model[q], band ? band[q] : nullptr, opts, groups_cap, groups_cap_b, &st[q]); };
+    if (chunk == 1) stage(0);        // on the calling thread: a caller with a thread per pair makes no second thread per call
+    else {
+        std::vector<std::thread> pool;
+        std::atomic<int> next{0};
+        for (int t = 0; t < std::min(chunk, 16); ++t) pool.emplace_back([&] {
+            const bool on = hipSetDevice(device) == hipSuccess;
+            for (int q; (q = next.fetch_add(1)) < chunk;) { if (on) stage(q); else rcs[q] = PAGAN_E_NODEVICE; }
+        });
+        for (auto &th : pool) th.join();
+    }
+    int rc = PAGAN_OK;
+    for (int q = 0; q < chunk; ++q) if (rcs[q] != PAGAN_OK) rc = rcs[q];
+    if (rc != PAGAN_OK) return rc;
+    for (int q = 0; q < chunk; ++q) if (st[q].fb->device != device) return PAGAN_E_INTERNAL;      // (every pair's arena is on the launches' device)
+    const double th3 = fb_now();
+    // the launch groups, in the order they go out: tiled, ring, one-workgroup, and the deep-ring groups last (below)
+    auto lds = [&](int q) { return st[q].fb->S * st[q].fb->S <= 256; };
+    auto key = [&](int q) { return 2 * st[q].block + (lds(q) ? 1 : 0); };              // workgroup size, table in LDS
+    std::vector<int> of[4];
+    for (int q = 0; q < chunk; ++q) of[st[q].fb->groups > 1 ? FB_K_TILED : (st[q].fb->deep ? FB_K_DEEP : (st[q].fb->ring ? FB_K_RING : FB_K_SMALL))].push_back(q);
+    std::vector<FbGroup> groups;
+    std::vector<FbSpan> spans;
+    std::vector<PgFbJob> jobs;           // the records of the groups of several pairs, group by group
+    int slots_needed = 0;
+    for (FbKind kind : {FB_K_TILED, FB_K_RING, FB_K_SMALL, FB_K_DEEP}) {
+        std::vector<int> &ks = of[kind];
+        if (kind == FB_K_RING || kind == FB_K_DEEP) std::stable_sort(ks.begin(), ks.end(), [&](int a, int b) { return key(a) < key(b); });
+        for (size_t a = 0, z; a < ks.size(); a = z) {
+            z = kind == FB_K_TILED ? ks.size() : a + 1;
+            while (kind != FB_K_SMALL && z < ks.size() && key(ks[z]) == key(ks[a])) ++z;
+            FbGroup G{kind, true, kind == FB_K_TILED ? 64 : st[ks[a]].block, (unsigned)(z - a), (unsigned)(z - a), 1, {ks.begin() + a, ks.begin() + z}, st[ks[a]].fb->d_job};
+            if (kind == FB_K_TILED) { G.gx = G.gx_b = 0; G.gy = (unsigned)(z - a); }
+            for (int q : G.ks) {
+                G.all_lds = G.all_lds && lds(q);
+                if (kind != FB_K_TILED) continue;
+                G.gx = std::max(G.gx, (unsigned)st[q].fb->groups); G.gx_b = std::max(G.gx_b, (unsigned)st[q].groups_b);   // (a launch is as wide as its widest pair)
+                slots_needed += st[q].fb->groups + st[q].groups_b;
+            }
+            // (a group of one pair launches on the record in the pair's own arena; the others' records: one array, one copy, below)
+            if (G.ks.size() > 1) { G.jobs = nullptr; for (int q : G.ks) jobs.push_back(st[q].fb->job); }
+            if (a == 0 || kind == FB_K_SMALL) spans.push_back({groups.size(), groups.size(), kind != FB_K_SMALL || only_pair, {nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}});
+            spans.back().z = groups.size() + 1;
+            groups.push_back(std::move(G));
+        }
+    }
+    // Owners, in the order they must outlive each other: the records, the slot lease, the events, the streams.
+    FbDevBuf d_jobs;
+    FbSlotLease lease{&fb_slots_of[device & 63], 0};
+    FbChunkRes res;
+    if (!jobs.empty()) {
+        FB_DO(d_jobs.alloc(jobs.size() * sizeof(PgFbJob)));
+        FB_TRY(hipMemcpy(d_jobs, jobs.data(), jobs.size() * sizeof(PgFbJob), hipMemcpyHostToDevice));
+        const PgFbJob *at = (const PgFbJob *)d_jobs.h;
+        for (FbGroup &G : groups) if (!G.jobs) { G.jobs = at; at += G.ks.size(); }
+    }
+    // the lease is taken before the tiled launches and given back at the end of the chunk
+    if (slots_needed > 0) { lease.s->take(slots_needed, cap); lease.n = slots_needed; }
+    const bool bwd_first = std::getenv("PAGAN_FB_BWD_FIRST") != nullptr;      // (A/B: which tiled sweep's workgroups are dealt out first)
+    for (FbSpan &S : spans) {
+        const FbKind kind = groups[S.a].kind;
+        if (kind == FB_K_DEEP) {
+            // behind the tiled sweeps: a deep-ring workgroup declares 153 KB of LDS, so no tiled workgroup shares its compute unit, and
+            // the tiled sweeps' slot budget counts on three a compute unit being resident at once -- the deep launches go out once the
+            // tiled streams are synchronised
+            FB_TRY(hipGetLastError());
+            if (groups[0].kind == FB_K_TILED) { FB_TRY(hipStreamSynchronize(spans[0].lane[0])); FB_TRY(hipStreamSynchronize(spans[0].lane[1])); }
+        }
+        FB_DO(fb_launch_span(res, groups, S, bwd_first && kind == FB_K_TILED));
+    }
+    FB_TRY(hipGetLastError());
+    const double th4 = fb_now();
+    for (const FbStream &s : res.streams) FB_TRY(hipStreamSynchronize(s));
+    const double th5 = fb_now();
+    // A span's two times go to its first pair, 0 to its others: a sum over the batch is the launches'.  (A one-workgroup pair is
+    // timed when it is the call's only pair.)
+    for (const FbSpan &S : spans) {
+        float ms[2] = {0, 0};
+        if (S.timed) { (void)hipEventElapsedTime(&ms[0], S.ev[0], S.ev[1]); (void)hipEventElapsedTime(&ms[1], S.ev[2], S.ev[3]); }
+        for (size_t g = S.a; g < S.z; ++g)
+            for (int q : groups[g].ks) {
+                const bool first = q == groups[S.a].ks[0];
+                FB_DO(fb_finish(&st[q], first ? ms[0] : 0.0f, first ? ms[1] : 0.0f));
+            }
+    }
+    if (std::getenv("PAGAN_DP_VERBOSE")) {
+        double t[3] = {0, 0, 0}, mb = 0;
+        for (int q = 0; q < chunk; ++q) { for (int k = 0; k < 3; ++k) t[k] += st[q].t_host[k]; mb += st[q].arena_bytes / 1048576.0; }
+        std::fprintf(stderr, "pagan_fb: host: %d pair(s): band index + lists %.1f ms, arena (%.0f MB) %.1f ms, upload %.1f ms, streams + launch (+ slot wait) %.1f ms, kernels %.1f ms, rest %.1f ms\n",
+                     chunk, 1e3 * t[0], mb, 1e3 * t[1], 1e3 * t[2], 1e3 * (th4 - th3), 1e3 * (th5 - th4), 1e3 * (fb_now() - th5));
+    }
+    return PAGAN_OK;
+}
 
 } // namespace
 
 extern "C" {
 
-int pagan_fb_run(const pagan_graph *left, const pagan_graph *right, const pagan_model_prob *model, const pagan_band *band,
-                 const pagan_opts *opts, pagan_fb **out) {
-    if (!out) return PAGAN_E_ARG;
-    auto now_ = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    FbStaged st;
-    int rc = fb_stage(left, right, model, band, opts, FB_MAX_GROUPS, FB_MAX_GROUPS, &st);
-    if (rc != PAGAN_OK) return rc;
-    pagan_fb *fb = st.fb;
-    std::unique_ptr<pagan_fb, void (*)(pagan_fb *)> guard(fb, [](pagan_fb *p) { pagan_fb_destroy(p); });
-    const double th3 = now_();
-    const int groups = st.groups, block = st.block;
-    const bool all_lds = st.job.S * st.job.S <= 256;         // (the kernels without the score table's load from memory)
-    // the two sweeps are independent of each other: side by side on two streams
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-    hipStream_t s1 = nullptr, s2 = nullptr;
-    FB_TRY(hipStreamCreate(&s1)); FB_TRY(hipStreamCreate(&s2));
-    FB_TRY(hipEventCreate(&e0)); FB_TRY(hipEventCreate(&e1)); FB_TRY(hipEventCreate(&e2)); FB_TRY(hipEventCreate(&e3));
-    FB_TRY(hipEventRecord(e0, s1));
-    FbSlots &slots = fb_slots_of[fb->device & 63];
-    FbSlotLease lease{&slots, groups > 1 ? 2 * groups : 0};
-    if (groups > 1) slots.take(2 * groups, fb_slot_cap(fb->device));
-    if (groups > 1) { if (all_lds) hipLaunchKernelGGL((pg_fb_forward_tiled<true>), dim3(groups, 1), dim3(64), 0, s1, st.d_job); else hipLaunchKernelGGL((pg_fb_forward_tiled<false>), dim3(groups, 1), dim3(64), 0, s1, st.d_job); }
-    else if (st.deep) fb_launch_deep(true, all_lds, 1, block, s1, st.d_job);
-    else if (st.ring) fb_launch_ring(true, all_lds, 1, block, s1, st.d_job);
-    else hipLaunchKernelGGL(pg_fb_forward, dim3(1), dim3(block), 0, s1, st.d_job);
-    FB_TRY(hipEventRecord(e1, s1));
-    FB_TRY(hipEventRecord(e2, s2));
-    if (groups > 1) { if (all_lds) hipLaunchKernelGGL((pg_fb_backward_tiled<true>), dim3(groups, 1), dim3(64), 0, s2, st.d_job); else hipLaunchKernelGGL((pg_fb_backward_tiled<false>), dim3(groups, 1), dim3(64), 0, s2, st.d_job); }
-    else if (st.deep) fb_launch_deep(false, all_lds, 1, block, s2, st.d_job);
-    else if (st.ring) fb_launch_ring(false, all_lds, 1, block, s2, st.d_job);
-    else hipLaunchKernelGGL(pg_fb_backward, dim3(1), dim3(block), 0, s2, st.d_job);
-    FB_TRY(hipEventRecord(e3, s2));
-    FB_TRY(hipGetLastError());
-    const double th4 = now_();
-    FB_TRY(hipStreamSynchronize(s1)); FB_TRY(hipStreamSynchronize(s2));
-    const double th5 = now_();
-    float fwd_ms = 0, bwd_ms = 0;
-    (void)hipEventElapsedTime(&fwd_ms, e0, e1);
-    (void)hipEventElapsedTime(&bwd_ms, e2, e3);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2); (void)hipEventDestroy(e3);
-    (void)hipStreamDestroy(s1); (void)hipStreamDestroy(s2);
-    rc = fb_finish(&st, fwd_ms, bwd_ms);
-    if (rc != PAGAN_OK) return rc;
-    if (std::getenv("PAGAN_DP_VERBOSE"))
-        std::fprintf(stderr, "pagan_fb: host: band index + lists %.1f ms, arena (%.0f MB) %.1f ms, upload %.1f ms, streams + launch (+ slot wait) %.1f ms, kernels %.1f ms, rest %.1f ms\n",
-                     1e3 * st.t_host[0], st.arena_bytes / 1048576.0, 1e3 * st.t_host[1], 1e3 * st.t_host[3], 1e3 * (th4 - th3), 1e3 * (th5 - th4), 1e3 * (now_() - th5));
-    *out = guard.release();
-    return PAGAN_OK;
-}
-
 // Several pairs at once (round 5): the sweeps of ALL the pairs' wide matrices in ONE launch per direction, grid = (most workgroups
 // of any pair, pairs) -- concurrency is no longer what the HIP runtime's hardware queues allow (eight kernels at a time: four
 // pairs), but what the chip holds.  Every tiled pair gets an equal share of the device's workgroup slots (its sweeps may then
 // take a block anti-diagonal in two or three turns); pairs whose diagonals are narrow keep their one-workgroup kernels, a
-// stream each.  out[k] as from pagan_fb_run; on an error nothing is handed back.
+// stream per direction each.  On an error nothing is handed back and every staged handle is destroyed.
 int pagan_fb_run_batch(int32_t n, const pagan_graph *const *left, const pagan_graph *const *right, const pagan_model_prob *const *model,
                        const pagan_band *const *band, const pagan_opts *opts, pagan_fb **out) {
     if (n < 0 || (n > 0 && (!left || !right || !model || !out))) return PAGAN_E_ARG;
     for (int k = 0; k < n; ++k) out[k] = nullptr;
+    for (int k = 0; k < n; ++k) if (!left[k] || !right[k] || !model[k]) return PAGAN_E_ARG;
     if (n == 0) return PAGAN_OK;
     // the device, resolved once: the calling thread is put on it before any allocation, stream or launch (a caller may pass a
     // device that is not its current one), the staging threads are handed it, and the caller's device is restored on the way out
-    int caller_device = 0;
-    if (hipGetDevice(&caller_device) != hipSuccess) return PAGAN_E_NODEVICE;
-    const int device = opts && opts->device >= 0 ? opts->device : caller_device;
-    FbDeviceScope on_device(device, caller_device);
+    FbDeviceScope on_device(opts ? opts->device : -1);
     if (!on_device.ok) return PAGAN_E_NODEVICE;
     pagan_opts staged_opts;
     staged_opts.flags = opts ? opts->flags : 0u;
-    staged_opts.device = device;
-    const int cap = fb_slot_cap(device);
-    std::vector<FbStaged> st(n);
-    std::vector<int> rcs(n, PAGAN_OK);
-    int done = 0, rc = PAGAN_OK;
-    auto cleanup = [&]() { for (int k = 0; k < n; ++k) if (st[k].fb) { pagan_fb_destroy(st[k].fb); st[k].fb = nullptr; } };
-    while (done < n && rc == PAGAN_OK) {
-        // a chunk of pairs whose tiled sweeps fit the slot budget with at least eight workgroups a sweep
-        const int chunk = std::min(n - done, std::max(1, cap / 16));
-        // the backward sweep is the slower of the two when a block anti-diagonal takes several turns: it gets the larger share
-        // of the slots (PAGAN_FB_SPLIT: the forward sweeps' per cent, A/B)
-        int split = 40;
-        if (const char *e = std::getenv("PAGAN_FB_SPLIT")) split = std::max(20, std::min(80, std::atoi(e)));
-        const int per_pair = std::max(4, cap / chunk);            // slots of one pair, both sweeps
-        const int groups_cap = std::max(2, (per_pair * split + 50) / 100), groups_cap_b = std::max(2, per_pair - groups_cap);
-        {
-            std::vector<std::thread> pool;
-            const int nt = std::min(chunk, 16);
-            std::atomic<int> next{0};
-            for (int t = 0; t < nt; ++t) pool.emplace_back([&] {
-                const bool on = hipSetDevice(device) == hipSuccess;
-                for (int q; (q = next.fetch_add(1)) < chunk;) {
-                    const int k = done + q;
-                    rcs[k] = on ? fb_stage(left[k], right[k], model[k], band ? band[k] : nullptr, &staged_opts, groups_cap, groups_cap_b, &st[k]) : PAGAN_E_NODEVICE;
-                }
-            });
-            for (auto &th : pool) th.join();
-        }
-        for (int q = 0; q < chunk; ++q) if (rcs[done + q] != PAGAN_OK) rc = rcs[done + q];
-        if (rc != PAGAN_OK) break;
-        for (int q = 0; q < chunk; ++q) if (st[done + q].fb->device != device) rc = PAGAN_E_INTERNAL;      // (every pair's arena is on the launches' device)
-        if (rc != PAGAN_OK) break;
-        std::vector<PgFbJob> tiled;
-        std::vector<int> tiled_k, small_k, ring_k, deep_k;
-        int gmax = 0, gmax_b = 0, slots_needed = 0;
-        bool tiled_all_lds = true;                                // every tiled pair's score table fits LDS
-        for (int q = 0; q < chunk; ++q) {
-            const int k = done + q;
-            if (st[k].groups > 1) {
-                tiled.push_back(st[k].job); tiled_k.push_back(k);
-                tiled_all_lds = tiled_all_lds && st[k].job.S * st[k].job.S <= 256;
-                gmax = std::max(gmax, st[k].groups); gmax_b = std::max(gmax_b, st[k].groups_b); slots_needed += st[k].groups + st[k].groups_b;
-            } else if (st[k].deep) deep_k.push_back(k);
-            else if (st[k].ring) ring_k.push_back(k);
-            else small_k.push_back(k);
-        }
-        // the LDS-ring sweeps of the chunk: one launch per direction and workgroup size (a workgroup a pair)
-        auto ring_key = [&](int k) { return 2 * st[k].block + (st[k].job.S * st[k].job.S <= 256 ? 1 : 0); };     // workgroup size, table in LDS
-        std::stable_sort(ring_k.begin(), ring_k.end(), [&](int a, int b_) { return ring_key(a) < ring_key(b_); });
-        std::vector<PgFbJob> ring_jobs;
-        for (int k : ring_k) ring_jobs.push_back(st[k].job);
-        // ... and its deep-ring sweeps the same way (graph pairs inside tunnels), behind the tiled sweeps: a deep-ring workgroup
-        // declares 153 KB of LDS, so no tiled workgroup shares its compute unit, and the tiled sweeps' slot budget counts on three a
-        // compute unit being resident at once -- the deep launches go out once the tiled streams are synchronised
-        std::stable_sort(deep_k.begin(), deep_k.end(), [&](int a, int b_) { return ring_key(a) < ring_key(b_); });
-        std::vector<PgFbJob> deep_jobs;
-        for (int k : deep_k) deep_jobs.push_back(st[k].job);
-        if (rc != PAGAN_OK) break;
-        PgFbJob *d_jobs = nullptr, *d_ring = nullptr, *d_deep = nullptr;
-        std::vector<hipStream_t> deep_s;
-        hipEvent_t h0 = nullptr, h1 = nullptr, h2 = nullptr, h3 = nullptr;
-        hipStream_t s1 = nullptr, s2 = nullptr, r1 = nullptr, r2 = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr, g0 = nullptr, g1 = nullptr, g2 = nullptr, g3 = nullptr;
-        std::vector<hipStream_t> small_s(2 * small_k.size(), nullptr), ring_s;
-        std::vector<hipEvent_t> ring_e;
-        auto release = [&]() {
-            if (d_jobs) (void)hipFree(d_jobs);
-            if (d_ring) (void)hipFree(d_ring);
-            if (d_deep) (void)hipFree(d_deep);
-            for (hipStream_t x : deep_s) if (x) (void)hipStreamDestroy(x);
-            for (hipEvent_t e : {h0, h1, h2, h3}) if (e) (void)hipEventDestroy(e);
-            for (hipStream_t x : {s1, s2, r1, r2}) if (x) (void)hipStreamDestroy(x);
-            for (hipEvent_t e : {e0, e1, e2, e3, g0, g1, g2, g3}) if (e) (void)hipEventDestroy(e);
-            for (hipStream_t x : small_s) if (x) (void)hipStreamDestroy(x);
-            for (hipStream_t x : ring_s) if (x) (void)hipStreamDestroy(x);
-            for (hipEvent_t e : ring_e) if (e) (void)hipEventDestroy(e);
-        };
-        auto body = [&]() -> int {
-            FB_TRY(hipStreamCreate(&s1)); FB_TRY(hipStreamCreate(&s2));
-            FB_TRY(hipEventCreate(&e0)); FB_TRY(hipEventCreate(&e1)); FB_TRY(hipEventCreate(&e2)); FB_TRY(hipEventCreate(&e3));
-            FbSlots &slots = fb_slots_of[device & 63];
-            FbSlotLease lease{&slots, slots_needed};
-            if (slots_needed > 0) slots.take(slots_needed, cap);
-            if (!tiled.empty()) {
-                FB_TRY(hipMalloc((void **)&d_jobs, tiled.size() * sizeof(PgFbJob)));
-                FB_TRY(hipMemcpy(d_jobs, tiled.data(), tiled.size() * sizeof(PgFbJob), hipMemcpyHostToDevice));
-                const bool bwd_first = std::getenv("PAGAN_FB_BWD_FIRST") != nullptr;      // (A/B: which sweep's workgroups are dealt out first)
-                if (bwd_first) {
-                    FB_TRY(hipEventRecord(e2, s2));
-                    { if (tiled_all_lds) hipLaunchKernelGGL((pg_fb_backward_tiled<true>), dim3(gmax_b, (unsigned)tiled.size()), dim3(64), 0, s2, (const PgFbJob *)d_jobs); else hipLaunchKernelGGL((pg_fb_backward_tiled<false>), dim3(gmax_b, (unsigned)tiled.size()), dim3(64), 0, s2, (const PgFbJob *)d_jobs); }
-                    FB_TRY(hipEventRecord(e3, s2));
-                }
-                FB_TRY(hipEventRecord(e0, s1));
-                { if (tiled_all_lds) hipLaunchKernelGGL((pg_fb_forward_tiled<true>), dim3(gmax, (unsigned)tiled.size()), dim3(64), 0, s1, (const PgFbJob *)d_jobs); else hipLaunchKernelGGL((pg_fb_forward_tiled<false>), dim3(gmax, (unsigned)tiled.size()), dim3(64), 0, s1, (const PgFbJob *)d_jobs); }
-                FB_TRY(hipEventRecord(e1, s1));
-                if (!bwd_first) {
-                    FB_TRY(hipEventRecord(e2, s2));
-                    { if (tiled_all_lds) hipLaunchKernelGGL((pg_fb_backward_tiled<true>), dim3(gmax_b, (unsigned)tiled.size()), dim3(64), 0, s2, (const PgFbJob *)d_jobs); else hipLaunchKernelGGL((pg_fb_backward_tiled<false>), dim3(gmax_b, (unsigned)tiled.size()), dim3(64), 0, s2, (const PgFbJob *)d_jobs); }
-                    FB_TRY(hipEventRecord(e3, s2));
-                }
-            }
-            if (!ring_jobs.empty()) {
-                FB_TRY(hipStreamCreate(&r1)); FB_TRY(hipStreamCreate(&r2));
-                FB_TRY(hipEventCreate(&g0)); FB_TRY(hipEventCreate(&g1)); FB_TRY(hipEventCreate(&g2)); FB_TRY(hipEventCreate(&g3));
-                FB_TRY(hipMalloc((void **)&d_ring, ring_jobs.size() * sizeof(PgFbJob)));
-                FB_TRY(hipMemcpy(d_ring, ring_jobs.data(), ring_jobs.size() * sizeof(PgFbJob), hipMemcpyHostToDevice));
-                FB_TRY(hipEventRecord(g0, r1)); FB_TRY(hipEventRecord(g2, r2));
-                // (the workgroup sizes side by side, not one after the other: the first group (size, table in LDS or not) on r1 / r2, the others -- a handful at most --
-                //  on streams of their own that r1 / r2 wait for)
-                for (size_t a = 0; a < ring_k.size();) {
-                    size_t z = a;
-                    while (z < ring_k.size() && ring_key(ring_k[z]) == ring_key(ring_k[a])) ++z;
-                    const int blk = st[ring_k[a]].block;
-                    const bool lds = (ring_key(ring_k[a]) & 1) != 0;
-                    hipStream_t f = r1, bk = r2;
-                    if (a > 0) {
-                        hipStream_t x1 = nullptr, x2 = nullptr;
-                        FB_TRY(hipStreamCreate(&x1)); ring_s.push_back(x1);
-                        FB_TRY(hipStreamCreate(&x2)); ring_s.push_back(x2);
-                        f = x1; bk = x2;
-                    }
-                    fb_launch_ring(true, lds, (unsigned)(z - a), blk, f, (const PgFbJob *)(d_ring + a));
-                    fb_launch_ring(false, lds, (unsigned)(z - a), blk, bk, (const PgFbJob *)(d_ring + a));
-                    if (a > 0) {
-                        hipEvent_t ev1 = nullptr, ev2 = nullptr;
-                        FB_TRY(hipEventCreateWithFlags(&ev1, hipEventDisableTiming)); ring_e.push_back(ev1);
-                        FB_TRY(hipEventCreateWithFlags(&ev2, hipEventDisableTiming)); ring_e.push_back(ev2);
-                        FB_TRY(hipEventRecord(ev1, f)); FB_TRY(hipStreamWaitEvent(r1, ev1, 0));
-                        FB_TRY(hipEventRecord(ev2, bk)); FB_TRY(hipStreamWaitEvent(r2, ev2, 0));
-                    }
-                    a = z;
-                }
-                FB_TRY(hipEventRecord(g1, r1)); FB_TRY(hipEventRecord(g3, r2));
-            }
-            for (size_t q = 0; q < small_k.size(); ++q) {
-                const FbStaged &x = st[small_k[q]];
-                FB_TRY(hipStreamCreate(&small_s[2 * q])); FB_TRY(hipStreamCreate(&small_s[2 * q + 1]));
-                hipLaunchKernelGGL(pg_fb_forward, dim3(1), dim3(x.block), 0, small_s[2 * q], x.d_job);
-                hipLaunchKernelGGL(pg_fb_backward, dim3(1), dim3(x.block), 0, small_s[2 * q + 1], x.d_job);
-            }
-            FB_TRY(hipGetLastError());
-            FB_TRY(hipStreamSynchronize(s1)); FB_TRY(hipStreamSynchronize(s2));
-            float df_ms = 0, db_ms = 0;
-            if (!deep_jobs.empty()) {
-                FB_TRY(hipMalloc((void **)&d_deep, deep_jobs.size() * sizeof(PgFbJob)));
-                FB_TRY(hipMemcpy(d_deep, deep_jobs.data(), deep_jobs.size() * sizeof(PgFbJob), hipMemcpyHostToDevice));
-                FB_TRY(hipEventCreate(&h0)); FB_TRY(hipEventCreate(&h1)); FB_TRY(hipEventCreate(&h2)); FB_TRY(hipEventCreate(&h3));
-                // one launch per direction and (workgroup size, table in LDS or not), each on a stream of its own; the times are the first group's
-                for (size_t a = 0; a < deep_k.size();) {
-                    size_t z = a;
-                    while (z < deep_k.size() && ring_key(deep_k[z]) == ring_key(deep_k[a])) ++z;
-                    hipStream_t f = nullptr, bk = nullptr;
-                    FB_TRY(hipStreamCreate(&f)); deep_s.push_back(f);
-                    FB_TRY(hipStreamCreate(&bk)); deep_s.push_back(bk);
-                    const bool lds = (ring_key(deep_k[a]) & 1) != 0;
-                    if (a == 0) { FB_TRY(hipEventRecord(h0, f)); FB_TRY(hipEventRecord(h2, bk)); }
-                    fb_launch_deep(true, lds, (unsigned)(z - a), st[deep_k[a]].block, f, (const PgFbJob *)(d_deep + a));
-                    fb_launch_deep(false, lds, (unsigned)(z - a), st[deep_k[a]].block, bk, (const PgFbJob *)(d_deep + a));
-                    if (a == 0) { FB_TRY(hipEventRecord(h1, f)); FB_TRY(hipEventRecord(h3, bk)); }
-                    a = z;
-                }
-                FB_TRY(hipGetLastError());
-                for (hipStream_t x : deep_s) FB_TRY(hipStreamSynchronize(x));
-                (void)hipEventElapsedTime(&df_ms, h0, h1); (void)hipEventElapsedTime(&db_ms, h2, h3);
-            }
-            for (size_t q = 0; q < deep_k.size(); ++q) { const int r_ = fb_finish(&st[deep_k[q]], q == 0 ? df_ms : 0.0f, q == 0 ? db_ms : 0.0f); if (r_ != PAGAN_OK) return r_; }
-            if (r1) { FB_TRY(hipStreamSynchronize(r1)); FB_TRY(hipStreamSynchronize(r2)); }
-            for (hipStream_t x : small_s) FB_TRY(hipStreamSynchronize(x));
-            float fwd_ms = 0, bwd_ms = 0, rf_ms = 0, rb_ms = 0;
-            if (!tiled.empty()) { (void)hipEventElapsedTime(&fwd_ms, e0, e1); (void)hipEventElapsedTime(&bwd_ms, e2, e3); }
-            if (!ring_jobs.empty()) { (void)hipEventElapsedTime(&rf_ms, g0, g1); (void)hipEventElapsedTime(&rb_ms, g2, g3); }
-            for (size_t q = 0; q < ring_k.size(); ++q) { const int r_ = fb_finish(&st[ring_k[q]], q == 0 ? rf_ms : 0.0f, q == 0 ? rb_ms : 0.0f); if (r_ != PAGAN_OK) return r_; }
-            // (the launch's kernel times go to its first pair; the others report 0: a sum over the batch is the launch's)
-            for (size_t q = 0; q < tiled_k.size(); ++q) { const int r_ = fb_finish(&st[tiled_k[q]], q == 0 ? fwd_ms : 0.0f, q == 0 ? bwd_ms : 0.0f); if (r_ != PAGAN_OK) return r_; }
-            for (int k : small_k) { const int r_ = fb_finish(&st[k], 0.0f, 0.0f); if (r_ != PAGAN_OK) return r_; }
-            return PAGAN_OK;
-        };
-        rc = body();
-        release();
-        done += chunk;
+    staged_opts.device = on_device.device;
+    const int cap = fb_slot_cap(staged_opts.device);
+    std::vector<FbStaged> st(n);         // owns the handles until they are handed back
+    // chunks of pairs whose tiled sweeps fit the slot budget with at least eight workgroups a sweep
+    for (int done = 0, chunk; done < n; done += chunk) {
+        chunk = std::min(n - done, std::max(1, cap / 16));
+        FB_DO(fb_run_chunk(chunk, left + done, right + done, model + done, band ? band + done : nullptr, &staged_opts, n == 1, cap, &st[done]));
     }
-    if (rc != PAGAN_OK) { cleanup(); return rc; }
-    for (int k = 0; k < n; ++k) out[k] = st[k].fb;
+    for (int k = 0; k < n; ++k) out[k] = st[k].fb.release();
     return PAGAN_OK;
+}
+
+// One pair: the batch of one.  Like every other entry point it leaves the calling thread on the device it came with (until the two
+// calls shared one path, this one left the thread on opts->device).
+int pagan_fb_run(const pagan_graph *left, const pagan_graph *right, const pagan_model_prob *model, const pagan_band *band,
+                 const pagan_opts *opts, pagan_fb **out) {
+    if (!out) return PAGAN_E_ARG;
+    return pagan_fb_run_batch(1, &left, &right, &model, band ? &band : nullptr, opts, out);
 }
 
 int pagan_fb_kernel_ms(const pagan_fb *fb, double ms[2]) {
@@ -1736,7 +1649,8 @@ int pagan_fb_totals(const pagan_fb *fb, double *log_fwd, double *log_bwd, int64_
 // dst [Lx][Ly][3] row-major, state order X, Y, M; outside the tunnel -inf (logs) / 0 (posterior).
 int pagan_fb_dump(pagan_fb *fb, int32_t which, double *dst) {
     if (!fb || !dst || which < 0 || which > 2) return PAGAN_E_ARG;
-    FB_TRY(hipSetDevice(fb->device));
+    FbDeviceScope on_device(fb->device);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
     const size_t n = 3 * (size_t)fb->dx.cells;
     std::vector<double> a(n), bb;
     FB_TRY(hipMemcpy(a.data(), which == 1 ? fb->dB : fb->dF, 8 * n, hipMemcpyDeviceToHost));
@@ -1765,36 +1679,27 @@ namespace {
 // pg_fb_gather over one pair: the triples go up in one copy, the posteriors come back in one (state outside 0..2: -1)
 static int fb_gather(pagan_fb *fb, int32_t n, const int32_t *cells, double *post) {
     if (n == 0) return PAGAN_OK;
-    int caller = 0;
-    FB_TRY(hipGetDevice(&caller));
-    FbDeviceScope on_device(fb->device, caller);
+    FbDeviceScope on_device(fb->device);
     if (!on_device.ok) return PAGAN_E_NODEVICE;
     const size_t o_cells = 256, o_out = o_cells + (12 * (size_t)n + 255) / 256 * 256, bytes = o_out + 8 * (size_t)n;
-    char *buf = nullptr;
-    FB_TRY(hipMalloc((void **)&buf, bytes));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto body = [&]() -> int {
-        std::vector<char> up(o_out, 0);
-        PgFbGather G;
-        G.cells = (const int *)(buf + o_cells); G.out = (double *)(buf + o_out); G.n = n;
-        std::memcpy(up.data(), &G, sizeof(G));
-        std::memcpy(up.data() + o_cells, cells, 12 * (size_t)n);
-        FB_TRY(hipMemcpy(buf, up.data(), o_out, hipMemcpyHostToDevice));
-        FB_TRY(hipEventCreate(&e0)); FB_TRY(hipEventCreate(&e1));
-        FB_TRY(hipEventRecord(e0, nullptr));
-        const unsigned blocks = (unsigned)std::min<long long>(((long long)n + 255) / 256, 4096);
-        hipLaunchKernelGGL(pg_fb_gather, dim3(blocks, 1), dim3(256), 0, nullptr, fb->d_job, (const PgFbGather *)buf);
-        FB_TRY(hipGetLastError());
-        FB_TRY(hipEventRecord(e1, nullptr));
-        FB_TRY(hipMemcpy(post, buf + o_out, 8 * (size_t)n, hipMemcpyDeviceToHost));
-        (void)hipEventElapsedTime(&fb->post_ms[0], e0, e1);
-        return PAGAN_OK;
-    };
-    const int rc = body();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(buf);
-    return rc;
+    FbDevBuf buf;
+    FbEvent e0, e1;
+    FB_DO(buf.alloc(bytes));
+    std::vector<char> up(o_out, 0);
+    PgFbGather G;
+    G.cells = (const int *)(buf.h + o_cells); G.out = (double *)(buf.h + o_out); G.n = n;
+    std::memcpy(up.data(), &G, sizeof(G));
+    std::memcpy(up.data() + o_cells, cells, 12 * (size_t)n);
+    FB_TRY(hipMemcpy(buf, up.data(), o_out, hipMemcpyHostToDevice));
+    FB_DO(e0.create()); FB_DO(e1.create());
+    FB_TRY(hipEventRecord(e0, nullptr));
+    const unsigned blocks = (unsigned)std::min<long long>(((long long)n + 255) / 256, 4096);
+    hipLaunchKernelGGL(pg_fb_gather, dim3(blocks, 1), dim3(256), 0, nullptr, fb->d_job, (const PgFbGather *)buf.h);
+    FB_TRY(hipGetLastError());
+    FB_TRY(hipEventRecord(e1, nullptr));
+    FB_TRY(hipMemcpy(post, buf.h + o_out, 8 * (size_t)n, hipMemcpyDeviceToHost));
+    (void)hipEventElapsedTime(&fb->post_ms[0], e0, e1);
+    return PAGAN_OK;
 }
 
 // The two marginal passes over n handles of one device: one launch per pass, grid = (blocks of the longest pair, pairs that want
@@ -1804,9 +1709,7 @@ static int fb_marginals(int32_t n, pagan_fb *const *fbs, void *const *const o[8]
     if (n < 0 || (n > 0 && !fbs)) return PAGAN_E_ARG;
     if (n == 0) return PAGAN_OK;
     for (int k = 0; k < n; ++k) if (!fbs[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
-    int caller = 0;
-    FB_TRY(hipGetDevice(&caller));
-    FbDeviceScope on_device(fbs[0]->device, caller);
+    FbDeviceScope on_device(fbs[0]->device);
     if (!on_device.ok) return PAGAN_E_NODEVICE;
     auto wanted = [&](int k, int side) { for (int q = 4 * side; q < 4 * side + 4; ++q) if (o[q] && o[q][k]) return true; return false; };
     struct Side { std::vector<int> ks; std::vector<size_t> at; int blocks = 0; size_t o_jobs = 0, o_recs = 0; };
@@ -1826,56 +1729,50 @@ static int fb_marginals(int32_t n, pagan_fb *const *fbs, void *const *const o[8]
             sd[side].blocks = std::max(sd[side].blocks, (len + FB_PM_ROWS - 1) / FB_PM_ROWS);
         }
     if (sd[0].ks.empty() && sd[1].ks.empty()) return PAGAN_OK;
-    char *buf = nullptr;
-    FB_TRY(hipMalloc((void **)&buf, cur));
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    FbDevBuf buf;
+    FbEvent ev[4];
+    FB_DO(buf.alloc(cur));
     std::vector<char> host(cur, 0);
-    auto body = [&]() -> int {
-        for (int side = 0; side < 2; ++side)
-            for (size_t q = 0; q < sd[side].ks.size(); ++q) {
-                const pagan_fb *fb = fbs[sd[side].ks[q]];
-                const size_t len = side ? fb->Ly : fb->Lx;
-                char *base = buf + sd[side].at[q];
-                PgFbMarg M;
-                M.gap = (double *)base; M.match = (double *)(base + 8 * len); M.best_p = (double *)(base + 16 * len); M.best = (int *)(base + 24 * len);
-                std::memcpy(host.data() + sd[side].o_jobs + q * sizeof(PgFbJob), &fb->job, sizeof(PgFbJob));
-                std::memcpy(host.data() + sd[side].o_recs + q * sizeof(PgFbMarg), &M, sizeof(M));
-            }
-        FB_TRY(hipMemcpy(buf, host.data(), in_bytes, hipMemcpyHostToDevice));
-        for (int side = 0; side < 2; ++side) {
-            if (sd[side].ks.empty()) continue;
-            FB_TRY(hipEventCreate(&ev[2 * side])); FB_TRY(hipEventCreate(&ev[2 * side + 1]));
-            FB_TRY(hipEventRecord(ev[2 * side], nullptr));
-            const dim3 grid((unsigned)sd[side].blocks, (unsigned)sd[side].ks.size());
-            const PgFbJob *jobs = (const PgFbJob *)(buf + sd[side].o_jobs);
-            const PgFbMarg *recs = (const PgFbMarg *)(buf + sd[side].o_recs);
-            if (side) hipLaunchKernelGGL((pg_fb_marginals<true>), grid, dim3(FB_PM_ROWS), 0, nullptr, jobs, recs);
-            else hipLaunchKernelGGL((pg_fb_marginals<false>), grid, dim3(FB_PM_ROWS), 0, nullptr, jobs, recs);
-            FB_TRY(hipGetLastError());
-            FB_TRY(hipEventRecord(ev[2 * side + 1], nullptr));
+    for (int side = 0; side < 2; ++side)
+        for (size_t q = 0; q < sd[side].ks.size(); ++q) {
+            const pagan_fb *fb = fbs[sd[side].ks[q]];
+            const size_t len = side ? fb->Ly : fb->Lx;
+            char *base = buf.h + sd[side].at[q];
+            PgFbMarg M;
+            M.gap = (double *)base; M.match = (double *)(base + 8 * len); M.best_p = (double *)(base + 16 * len); M.best = (int *)(base + 24 * len);
+            std::memcpy(host.data() + sd[side].o_jobs + q * sizeof(PgFbJob), &fb->job, sizeof(PgFbJob));
+            std::memcpy(host.data() + sd[side].o_recs + q * sizeof(PgFbMarg), &M, sizeof(M));
         }
-        FB_TRY(hipMemcpy(host.data() + in_bytes, buf + in_bytes, cur - in_bytes, hipMemcpyDeviceToHost));
-        for (int k = 0; k < n; ++k) fbs[k]->post_ms[1] = fbs[k]->post_ms[2] = 0.0f;
-        for (int side = 0; side < 2; ++side) {
-            if (sd[side].ks.empty()) continue;
-            (void)hipEventElapsedTime(&fbs[sd[side].ks[0]]->post_ms[1 + side], ev[2 * side], ev[2 * side + 1]);
-            for (size_t q = 0; q < sd[side].ks.size(); ++q) {
-                const int k = sd[side].ks[q];
-                const size_t len = side ? fbs[k]->Ly : fbs[k]->Lx;
-                const char *base = host.data() + sd[side].at[q];
-                void *const *const *oo = o + 4 * side;
-                if (oo[0] && oo[0][k]) std::memcpy(oo[0][k], base, 8 * len);
-                if (oo[1] && oo[1][k]) std::memcpy(oo[1][k], base + 8 * len, 8 * len);
-                if (oo[2] && oo[2][k]) std::memcpy(oo[2][k], base + 24 * len, 4 * len);
-                if (oo[3] && oo[3][k]) std::memcpy(oo[3][k], base + 16 * len, 8 * len);
-            }
+    FB_TRY(hipMemcpy(buf, host.data(), in_bytes, hipMemcpyHostToDevice));
+    for (int side = 0; side < 2; ++side) {
+        if (sd[side].ks.empty()) continue;
+        FB_DO(ev[2 * side].create()); FB_DO(ev[2 * side + 1].create());
+        FB_TRY(hipEventRecord(ev[2 * side], nullptr));
+        const dim3 grid((unsigned)sd[side].blocks, (unsigned)sd[side].ks.size());
+        const PgFbJob *jobs = (const PgFbJob *)(buf.h + sd[side].o_jobs);
+        const PgFbMarg *recs = (const PgFbMarg *)(buf.h + sd[side].o_recs);
+        if (side) hipLaunchKernelGGL((pg_fb_marginals<true>), grid, dim3(FB_PM_ROWS), 0, nullptr, jobs, recs);
+        else hipLaunchKernelGGL((pg_fb_marginals<false>), grid, dim3(FB_PM_ROWS), 0, nullptr, jobs, recs);
+        FB_TRY(hipGetLastError());
+        FB_TRY(hipEventRecord(ev[2 * side + 1], nullptr));
+    }
+    FB_TRY(hipMemcpy(host.data() + in_bytes, buf.h + in_bytes, cur - in_bytes, hipMemcpyDeviceToHost));
+    for (int k = 0; k < n; ++k) fbs[k]->post_ms[1] = fbs[k]->post_ms[2] = 0.0f;
+    for (int side = 0; side < 2; ++side) {
+        if (sd[side].ks.empty()) continue;
+        (void)hipEventElapsedTime(&fbs[sd[side].ks[0]]->post_ms[1 + side], ev[2 * side], ev[2 * side + 1]);
+        for (size_t q = 0; q < sd[side].ks.size(); ++q) {
+            const int k = sd[side].ks[q];
+            const size_t len = side ? fbs[k]->Ly : fbs[k]->Lx;
+            const char *base = host.data() + sd[side].at[q];
+            void *const *const *oo = o + 4 * side;
+            if (oo[0] && oo[0][k]) std::memcpy(oo[0][k], base, 8 * len);
+            if (oo[1] && oo[1][k]) std::memcpy(oo[1][k], base + 8 * len, 8 * len);
+            if (oo[2] && oo[2][k]) std::memcpy(oo[2][k], base + 24 * len, 4 * len);
+            if (oo[3] && oo[3][k]) std::memcpy(oo[3][k], base + 16 * len, 8 * len);
         }
-        return PAGAN_OK;
-    };
-    const int rc = body();
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(buf);
-    return rc;
+    }
+    return PAGAN_OK;
 }
 
 static uint64_t fb_splitmix64(uint64_t x) {
@@ -1980,7 +1877,8 @@ int pagan_sample_uniforms_path(uint64_t seed, int32_t node, int32_t path, int32_
 // 3 * (Lx + Ly) ints): the cells of the path end -> start as (i, j, state).
 int pagan_fb_sample_path(pagan_fb *fb, const double *u, int32_t n_u, pagan_result *out, int32_t *visited, int32_t *n_visited) {
     if (!fb || !u || !out) return PAGAN_E_ARG;
-    FB_TRY(hipSetDevice(fb->device));
+    FbDeviceScope on_device(fb->device);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
     if (fb->hF.empty()) {
         fb->hF.resize(3 * (size_t)fb->dx.cells);
         FB_TRY(hipMemcpy(fb->hF.data(), fb->dF, 8 * fb->hF.size(), hipMemcpyDeviceToHost));
@@ -2071,19 +1969,6 @@ int pagan_fb_sample_path(pagan_fb *fb, const double *u, int32_t n_u, pagan_resul
 // ---- K sampled paths per pair on the device (pg_fb_sample, dp_fb_sample.inc) ----
 // One allocation serves a whole batch call -- the job records, the launch records, every pair's summaries, traces and pack
 // buffer -- and lives as long as any of the batch's handles does.
-namespace {
-struct FbDevBuf {
-    int device = 0;
-    char *p = nullptr;
-    ~FbDevBuf() {
-        if (!p) return;
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        (void)hipSetDevice(device); (void)hipFree(p);
-        if (cur >= 0) (void)hipSetDevice(cur);
-    }
-};
-} // namespace
 
 struct pagan_fb_samples {
     int device = 0;
@@ -2119,9 +2004,7 @@ static int fs_fetch(pagan_fb_samples *s, int path, std::vector<int> *trace, int 
     trace->assign(3 * ((size_t)n + 1), 0);
     *n_steps = n;
     if (n == 0) return PAGAN_OK;
-    int caller = 0;
-    FB_TRY(hipGetDevice(&caller));
-    FbDeviceScope on_device(s->device, caller);
+    FbDeviceScope on_device(s->device);
     if (!on_device.ok) return PAGAN_E_NODEVICE;
     const int g = path / 64, lane = path % 64, width = std::min(64, s->n_paths - 64 * g);
     const int *group = s->d_trace + 3 * (64ll * g * s->max_steps);
@@ -2147,10 +2030,8 @@ int pagan_fb_sample_paths_batch(int32_t n, pagan_fb *const *fbs, uint64_t seed, 
     for (int k = 0; k < n; ++k) out[k] = nullptr;
     for (int k = 0; k < n; ++k) if (!fbs[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
     if (n == 0) return PAGAN_OK;
-    int caller = 0;
-    FB_TRY(hipGetDevice(&caller));
     const int device = fbs[0]->device;
-    FbDeviceScope on_device(device, caller);
+    FbDeviceScope on_device(device);
     if (!on_device.ok) return PAGAN_E_NODEVICE;
     size_t cur = 0;
     auto take = [&](size_t bytes) { const size_t at = cur; cur = (cur + bytes + 255) / 256 * 256; return at; };
@@ -2164,8 +2045,7 @@ int pagan_fb_sample_paths_batch(int32_t n, pagan_fb *const *fbs, uint64_t seed, 
         o_trace[k] = take(z.trace); o_pack[k] = take(z.pack);
     }
     std::shared_ptr<FbDevBuf> buf = std::make_shared<FbDevBuf>();
-    buf->device = device;
-    FB_TRY(hipMalloc((void **)&buf->p, cur));
+    FB_DO(buf->alloc(cur));
     const bool traces = !(flags & PAGAN_SAMPLE_NO_TRACES);
     const int groups = (n_paths + 63) / 64;
     std::vector<char> host(sum_end, 0);
@@ -2173,38 +2053,31 @@ int pagan_fb_sample_paths_batch(int32_t n, pagan_fb *const *fbs, uint64_t seed, 
         PgFbSample R;
         R.key = fb_splitmix64(fb_splitmix64(seed) ^ (uint64_t)(int64_t)nodes[k]);
         R.n_paths = n_paths; R.groups = groups; R.max_steps = fbs[k]->Lx + fbs[k]->Ly; R.pad = 0;
-        R.trace = traces ? (int *)(buf->p + o_trace[k]) : nullptr;
-        R.summary = (int *)(buf->p + o_sum[k]);
+        R.trace = traces ? (int *)(buf->h + o_trace[k]) : nullptr;
+        R.summary = (int *)(buf->h + o_sum[k]);
         std::memcpy(host.data() + o_jobs + (size_t)k * sizeof(PgFbJob), &fbs[k]->job, sizeof(PgFbJob));
         std::memcpy(host.data() + o_recs + (size_t)k * sizeof(PgFbSample), &R, sizeof(R));
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    FbEvent e0, e1;
     float ms = 0;
-    auto body = [&]() -> int {
-        FB_TRY(hipMemcpy(buf->p, host.data(), in_bytes, hipMemcpyHostToDevice));
-        FB_TRY(hipEventCreate(&e0)); FB_TRY(hipEventCreate(&e1));
-        FB_TRY(hipEventRecord(e0, nullptr));
-        for (int at = 0; at < n; at += 65535) {                    // (a grid's y extent)
-            const dim3 grid((unsigned)groups, (unsigned)std::min(65535, n - at));
-            hipLaunchKernelGGL(pg_fb_sample, grid, dim3(64), 0, nullptr, (const PgFbJob *)(buf->p + o_jobs) + at, (const PgFbSample *)(buf->p + o_recs) + at);
-        }
-        FB_TRY(hipGetLastError());
-        FB_TRY(hipEventRecord(e1, nullptr));
-        FB_TRY(hipMemcpy(host.data() + in_bytes, buf->p + in_bytes, sum_end - in_bytes, hipMemcpyDeviceToHost));
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        return PAGAN_OK;
-    };
-    const int rc = body();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (rc != PAGAN_OK) return rc;
+    FB_TRY(hipMemcpy(buf->h, host.data(), in_bytes, hipMemcpyHostToDevice));
+    FB_DO(e0.create()); FB_DO(e1.create());
+    FB_TRY(hipEventRecord(e0, nullptr));
+    for (int at = 0; at < n; at += 65535) {                    // (a grid's y extent)
+        const dim3 grid((unsigned)groups, (unsigned)std::min(65535, n - at));
+        hipLaunchKernelGGL(pg_fb_sample, grid, dim3(64), 0, nullptr, (const PgFbJob *)(buf->h + o_jobs) + at, (const PgFbSample *)(buf->h + o_recs) + at);
+    }
+    FB_TRY(hipGetLastError());
+    FB_TRY(hipEventRecord(e1, nullptr));
+    FB_TRY(hipMemcpy(host.data() + in_bytes, buf->h + in_bytes, sum_end - in_bytes, hipMemcpyDeviceToHost));
+    (void)hipEventElapsedTime(&ms, e0, e1);
     for (int k = 0; k < n; ++k) {
         pagan_fb_samples *s = new pagan_fb_samples();
         s->device = device; s->Lx = fbs[k]->Lx; s->Ly = fbs[k]->Ly; s->n_paths = n_paths; s->max_steps = s->Lx + s->Ly; s->flags = flags;
         s->L = fbs[k]->L; s->R = fbs[k]->R; s->cells = fbs[k]->dx.cells; s->log_fwd = fbs[k]->totals[0];
         s->buf = buf;
-        s->d_trace = traces ? (const int *)(buf->p + o_trace[k]) : nullptr;
-        s->d_pack = traces && n_paths > 1 ? (int *)(buf->p + o_pack[k]) : nullptr;
+        s->d_trace = traces ? (const int *)(buf->h + o_trace[k]) : nullptr;
+        s->d_pack = traces && n_paths > 1 ? (int *)(buf->h + o_pack[k]) : nullptr;
         const int32_t *sm = (const int32_t *)(host.data() + o_sum[k]);
         s->summary.assign(sm, sm + (size_t)FS_SUMMARY_INTS * n_paths);
         s->ms = k == 0 ? ms : 0.0f;
@@ -2249,9 +2122,7 @@ int pagan_fb_samples_visited(pagan_fb_samples *s, int32_t path, int32_t *visited
 // n_visited [n_paths]
 int pagan_fb_samples_visited_all(pagan_fb_samples *s, int32_t *visited, int32_t *n_visited) {
     if (!s || !s->d_trace || !visited) return PAGAN_E_ARG;
-    int caller = 0;
-    FB_TRY(hipGetDevice(&caller));
-    FbDeviceScope on_device(s->device, caller);
+    FbDeviceScope on_device(s->device);
     if (!on_device.ok) return PAGAN_E_NODEVICE;
     const size_t ms = (size_t)s->max_steps;
     std::vector<int32_t> raw(3 * (size_t)s->n_paths * ms);

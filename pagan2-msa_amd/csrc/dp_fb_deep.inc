@@ -227,23 +227,8 @@ __global__ __launch_bounds__(FB_RG_THREADS) void pg_fb_forward_deep(const PgFbJo
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                                               // (the end corner reads the scores from memory)
-    if (threadIdx.x == 0) {
-        // end corner, VA:1440-1552
-        double acc = ninf();
-        const int l0 = J.offL[J.Lx], l1 = J.offL[J.Lx + 1], r0 = J.offR[J.Ly], r1 = J.offR[J.Ly + 1];
-        auto mt = [&](int k1, int k2) { return fb_far_rd(J, J.F, J.srcL[k1], J.srcR[k2], 2) + J.l_ng + (double)J.lwL[k1] + (double)J.lwR[k2]; };
-        auto xc = [&](int k1) { return fb_far_rd(J, J.F, J.srcL[k1], J.Ly - 1, 0); };
-        auto yc = [&](int k2) { return fb_far_rd(J, J.F, J.Lx - 1, J.srcR[k2], 1); };
-        if (l1 > l0 && r1 > r0) {
-            acc = lse(acc, mt(l0, r0)); acc = lse(acc, xc(l0)); acc = lse(acc, yc(r0));
-            for (int k2 = r0 + 1; k2 < r1; ++k2) { acc = lse(acc, mt(l0, k2)); acc = lse(acc, yc(k2)); }
-            for (int k1 = l0 + 1; k1 < l1; ++k1) {
-                acc = lse(acc, mt(k1, r0)); acc = lse(acc, xc(k1));
-                for (int k2 = r0 + 1; k2 < r1; ++k2) { acc = lse(acc, mt(k1, k2)); acc = lse(acc, yc(k2)); }
-            }
-        }
-        J.totals[0] = acc;
-    }
+    if (threadIdx.x == 0)
+        J.totals[0] = fb_end_corner(J, [&](int p, int q, int s_) { return fb_far_rd(J, J.F, p, q, s_); });
 }
 
 // one cell of the backward sweep (the recurrence of pg_fb_backward: the sums are taken one by one, in its order); the windows

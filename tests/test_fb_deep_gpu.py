@@ -190,9 +190,10 @@ def test_long_pair_by_default_and_sampling(pg, oracle, monkeypatch):
     fb0.close()
 
 
-def test_a_batch_mixes_deep_ring_pairs_with_the_other_schedules(pg, oracle, monkeypatch):
-    """full_probability_batch on deep-ring pairs (18, of two workgroup sizes), plain-ring, tiled and small pairs: every handle's
-    totals bit-equal to the one-pair call's, schedules as routed."""
+def _mixed_cases(monkeypatch, reps, per_rep=None):
+    """(cases, n_deep, the schedules they route to): deep-ring pairs of the 8-leaf tree behind a random tunnel per `reps` entry (the
+    range of half-widths HALVES[rep % 3], `per_rep` pairs each: all), then a plain-ring pair, two tiled pairs and a small one --
+    all of at most 700 sites"""
     for v in ("PAGAN_FB_DEEP", "PAGAN_FB_BAND_MIN_ND", "PAGAN_FB_RING_MIN_ND", "PAGAN_FB_GROUPS"):
         monkeypatch.delenv(v, raising=False)
     monkeypatch.setenv("PAGAN_FB_DEEP_MIN_ND", "1000")
@@ -200,12 +201,11 @@ def test_a_batch_mixes_deep_ring_pairs_with_the_other_schedules(pg, oracle, monk
     names, seqs, nwk = synth.evolve_balanced(8, 700, branch=0.04, sub=0.04, indel_start=0.01, mean_len=4, seed=46)
     ups = upper_pairs(names, seqs, nwk, use_anchors=0)
     cases = []
-    for rep in range(6):
-        for left, right, mp in ups:
+    for rep in reps:
+        for left, right, mp in ups[:per_rep]:
             lo_half, hi_half = HALVES[rep % 3]
             cases.append((left, right, mp, _random_tunnel(rng, left.n_sites - 1, right.n_sites - 1, lo_half, hi_half)))     # deep ring
     n_deep = len(cases)
-    assert n_deep >= 16
     gl, gr = (host.HGraph.leaf(s).flatten() for s in seqs[:2])
     mpl = host.model_prob(1, 0.08, base_freq=[0.25] * 4)
     cases.append((gl, gr, mpl, _random_tunnel(rng, gl.n_sites - 1, gr.n_sites - 1, 20, 70)))       # plain ring
@@ -215,17 +215,58 @@ def test_a_batch_mixes_deep_ring_pairs_with_the_other_schedules(pg, oracle, monk
     sl, sr = (host.HGraph.leaf(s).flatten() for s in short)
     cases.append((sl, sr, mpl, None))                                                             # small: one-workgroup kernels
     want_sched = [3] * n_deep + [2, 1, 1, 0]
-    assert len({pgm.fb_route(c[0], c[1], c[3])[1]["widest"] > 64 for c in cases[:n_deep]}) == 2      # two workgroup sizes among the deep pairs
     assert [pgm.fb_route(c[0], c[1], c[3])[0] for c in cases] == want_sched
+    return cases, n_deep, want_sched
+
+
+def _second_size(cases, n_deep):
+    """the first deep pair whose workgroup size is not the first deep pair's (widest diagonal beyond 64 cells or not)"""
+    wide = [pgm.fb_route(c[0], c[1], c[3])[1]["widest"] > 64 for c in cases[:n_deep]]
+    assert len(set(wide)) == 2                                                                    # two workgroup sizes among the deep pairs
+    return wide.index(not wide[0])
+
+
+def test_a_batch_mixes_deep_ring_pairs_with_the_other_schedules(pg, oracle, monkeypatch):
+    """full_probability_batch on deep-ring pairs (18, of two workgroup sizes), plain-ring, tiled and small pairs: every handle's
+    totals bit-equal to the one-pair call's, schedules as routed.  The one-pair call is the batch of one, so the oracle anchors
+    the batch itself: one pair of each schedule, and a deep pair of the second workgroup size, to LOG_TOL."""
+    cases, n_deep, want_sched = _mixed_cases(monkeypatch, range(6))
+    assert n_deep >= 16
+    second = _second_size(cases, n_deep)
     single = []
     for c in cases:
         fb = pgm.FullProbability(*c)
         single.append((fb.log_fwd, fb.log_bwd, fb.schedule))
         fb.close()
     assert [s[2] for s in single] == want_sched
-    lf, lb, _, _ = oracle.fb(*cases[0][:3], band=cases[0][3], matrices=False)
-    assert abs(single[0][0] - lf) <= LOG_TOL * max(1, abs(lf)) and abs(single[0][1] - lb) <= LOG_TOL * max(1, abs(lb))
     fbs = pgm.full_probability_batch(cases)
+    for k in (0, second, n_deep, n_deep + 1, n_deep + 3):                  # deep, deep of the other size, ring, tiled, small
+        lf, lb, _, _ = oracle.fb(*cases[k][:3], band=cases[k][3], matrices=False)
+        print("pair %d (schedule %d): log_fwd %.12g (oracle %.12g) log_bwd %.12g (oracle %.12g)" % (k, fbs[k].schedule, fbs[k].log_fwd, lf, fbs[k].log_bwd, lb))
+        assert abs(fbs[k].log_fwd - lf) <= LOG_TOL * max(1, abs(lf)) and abs(fbs[k].log_bwd - lb) <= LOG_TOL * max(1, abs(lb)), (k, fbs[k].log_fwd, lf, fbs[k].log_bwd, lb)
     for fb, (f, b, sch) in zip(fbs, single):
         assert fb.log_fwd == f and fb.log_bwd == b and fb.schedule == sch
         fb.close()
+
+
+def test_kernel_times_go_to_one_pair_per_launch_group(pg, monkeypatch):
+    """pagan_fb_kernel_ms across a batch of every schedule (two deep pairs, of two workgroup sizes): the tiled launch, the ring
+    kind and the deep kind each report their two times at exactly one pair; every other pair, the small one included, reports
+    exactly 0.0 -- and the same small pair alone, as the call's only pair, is timed."""
+    cases, n_deep, want_sched = _mixed_cases(monkeypatch, (0, 2), per_rep=1)
+    assert n_deep == 2
+    _second_size(cases, n_deep)
+    fbs = pgm.full_probability_batch(cases)
+    ms = [(fb.forward_ms, fb.backward_ms) for fb in fbs]
+    print("kernel ms by pair:", list(zip(want_sched, ms)))
+    assert [fb.schedule for fb in fbs] == want_sched
+    for fb in fbs:
+        fb.close()
+    for sched in (1, 2, 3):
+        timed = [m for m, s in zip(ms, want_sched) if s == sched and m[0] > 0 and m[1] > 0]
+        assert len(timed) == 1, (sched, ms)
+        assert all(m == (0.0, 0.0) for m, s in zip(ms, want_sched) if s == sched and m not in timed), (sched, ms)
+    assert ms[-1] == (0.0, 0.0) and want_sched[-1] == 0, ms
+    alone = pgm.FullProbability(*cases[-1])
+    assert alone.schedule == 0 and alone.forward_ms > 0 and alone.backward_ms > 0, (alone.forward_ms, alone.backward_ms)
+    alone.close()
