@@ -387,6 +387,44 @@ int  pagan_fb_samples_ms(const pagan_fb_samples *s, double *ms);
 int64_t pagan_fb_sample_predict_bytes(int32_t left_sites, int32_t right_sites, int32_t n_paths, uint32_t flags);
 void pagan_fb_samples_destroy(pagan_fb_samples *s);
 
+/* ---- Posterior decoding: the maximum expected accuracy path of a finished pass (dp_fb_decode.inc) -------------
+ * The alignment the posterior matrix itself recommends (ProbCons, AMAP, FSA): the path start -> end whose cells carry the
+ * largest summed weight w(s, i, j) = c_s * posterior(s, i, j), c_M = 1, c_X = c_Y = gap_weight (a finite double >= 0; 0.5
+ * counts every residue once).  A max-plus fill over the predecessors the forward pass lists, in its order (a transition of
+ * probability 0 is no step; strict >: the first maximum stays), then a walk back from the end corner's maximum: DESIGN.md 6.4.
+ * F and B of any sweep schedule decode alike.  The path comes back in the shape of a sampled one (summary, visited cells,
+ * replayed result with score = log full probability).  All pairs of a batch are on one device, the handles' own; the calling
+ * thread is put on it and restored on exit.  A handle stays valid after pagan_fb_destroy of its pair; the pair's graphs must
+ * outlive it (pagan_fb_decoded_result reads them).  While a decode is in flight its score matrix takes 24 B a cell beside the
+ * pair's two.
+ * Errors: a NULL handle, handles of different devices, unknown flags, a gap_weight that is negative or not finite: PAGAN_E_ARG. */
+typedef struct pagan_fb_decoded pagan_fb_decoded;
+#define PAGAN_DECODE_KEEP_MATRIX 1u  /* keep the score matrix for pagan_fb_decoded_dump; otherwise its arena goes back to the
+                                        pool behind the trace                                                               */
+int  pagan_fb_decode_batch(int32_t n, pagan_fb *const *fbs, double gap_weight, uint32_t flags,
+                           pagan_fb_decoded **out); /* out[n] */
+int  pagan_fb_decode(pagan_fb *fb, double gap_weight, uint32_t flags, pagan_fb_decoded **out);
+/* Any NULL.  status 0 decoded, 1 full probability zero (objective 0, no steps), 2 internal (no candidate, or more than
+ * Lx + Ly steps); objective = the sum of w over the path's cells; the steps of the trace; how many of them left an M, X, Y
+ * cell; schedule 0 pg_fb_decode_fill, 1 pg_fb_ring_decode.                                                                 */
+int  pagan_fb_decoded_summary(const pagan_fb_decoded *d, int32_t *status, double *objective, int32_t *n_steps,
+                              int32_t counts[3], int32_t *schedule);
+/* the path's cells end -> start as (i, j, state), 3 * (Lx + Ly) ints at most: pagan_fb_sample_path's `visited`             */
+int  pagan_fb_decoded_visited(pagan_fb_decoded *d, int32_t *visited, int32_t *n_visited);
+/* replay of the trace (a path of status 1 replays as the unreachable result, one of status 2 is PAGAN_E_INTERNAL); free with
+ * pagan_result_free                                                                                                        */
+int  pagan_fb_decoded_result(pagan_fb_decoded *d, pagan_result *out);
+/* the score matrix, dst [Lx][Ly][3] (X, Y, M), -inf outside the band; without PAGAN_DECODE_KEEP_MATRIX: PAGAN_E_ARG       */
+int  pagan_fb_decoded_dump(pagan_fb_decoded *d, double *dst);
+/* device time of the fill and of the trace, milliseconds: a batch's launches booked at its first pair, 0 at the others    */
+int  pagan_fb_decoded_ms(const pagan_fb_decoded *d, double ms[2]);
+/* Host only: the fill a pair would take under the current environment: 1 pg_fb_ring_decode (two plain sequences, widest
+ * diagonal <= 1,024 cells, PAGAN_FB_DECODE_RING not 0), 0 pg_fb_decode_fill                                                */
+int  pagan_fb_debug_decode_route(const pagan_graph *left, const pagan_graph *right, const pagan_band *band);
+/* Host only: the device bytes one pair's decode takes beside the pair itself: 24 B a cell, 12 B a step, the summary        */
+int64_t pagan_fb_decode_predict_bytes(int32_t left_sites, int32_t right_sites, const pagan_band *band);
+void pagan_fb_decoded_destroy(pagan_fb_decoded *d);
+
 const char *pagan_dp_version(void);
 
 #ifdef __cplusplus

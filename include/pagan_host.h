@@ -146,6 +146,13 @@ int     pagan_msa_set_batch_backend(pagan_msa *m, pagan_batch_fn fn, void *user)
  * tunnel and the totals do not change; the sampler's device time is added to pagan_msa_node_fb's out[3] at the sub-batch's
  * first node.  Call before aligning.                                                                                        */
 int     pagan_msa_set_sampler(pagan_msa *m, int32_t on_device);
+/* Posterior decoding in the walk (a setter: pagan_msa_opts does not grow).  on = 1: there is no Viterbi batch, as under
+ * sample_path; a unit's nodes go through pagan_fb_run_batch in sub-batches cut by pagan_fb_predict_bytes +
+ * pagan_fb_decode_predict_bytes, each sub-batch through one pagan_fb_decode_batch(n, fbs, gap_weight, 0), and a node's result is
+ * the replay of its maximum expected accuracy path (pagan_dp.h): score = log full probability, support along the decoded path,
+ * a band whose full probability is 0 retried without the band.  Together with sample_path: PAGAN_E_ARG at align time; with the
+ * test seam: PAGAN_E_NODEVICE.  gap_weight: a finite double >= 0 (0.5: a residue counts once).  Call before aligning.           */
+int     pagan_msa_set_decoder(pagan_msa *m, int32_t on, double gap_weight);
 int  pagan_msa_n_internal(const pagan_msa *m);
 int  pagan_msa_node_info(const pagan_msa *m, int32_t k, pagan_node_info *out);
 /* Borrowed views (valid until pagan_msa_destroy) of what node k's alignment consumed and
@@ -163,6 +170,9 @@ int  pagan_msa_node_result(const pagan_msa *m, int32_t k, pagan_result *out);
  *   the node has no matched / xgapped / ygapped column; buf holds alignment_length floats (codons: one per column of three
  *   characters).  Leaves: PAGAN_E_ARG.                                                                                    */
 int  pagan_msa_node_fb(const pagan_msa *m, int32_t k, double out[4]);
+/* node_decode (pagan_msa_set_decoder): out[0] the decoded path's objective, [1] its steps, [2] device ms of the decode's fill +
+ *   trace (a sub-batch's launches are booked at its first node, 0 at the others); PAGAN_E_ARG for a node this process did not align */
+int  pagan_msa_node_decode(const pagan_msa *m, int32_t k, double out[3]);
 int  pagan_msa_node_support(const pagan_msa *m, int32_t k, double *support);
 int  pagan_msa_node_marginals(const pagan_msa *m, int32_t k, double *pX, double *pM_left, int32_t *best_j, double *best_p_left,
                               double *pY, double *pM_right, int32_t *best_i, double *best_p_right);

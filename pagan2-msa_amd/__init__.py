@@ -95,6 +95,7 @@ class FullProbability:
         fb.posterior()                  [Lx, Ly, 3] (X, Y, M), compute_posterior_score
         fb.sample_path(u)               Result with the shape of a Viterbi result
         fb.sample_paths(seed, node, K)  K paths drawn on the device (SampledPaths)
+        fb.decode(gap_weight)           the maximum expected accuracy path (DecodedPath)
     """
 
     def __init__(self, left, right, model_prob, band=None, device=-1, _handle=None):
@@ -179,6 +180,11 @@ class FullProbability:
         sample_uniforms_path(seed, node, p, Lx + Ly + 1).  Returns a SampledPaths."""
         return sample_paths_batch([self], seed, [node], n_paths, traces)[0]
 
+    def decode(self, gap_weight=0.5, keep_matrix=False):
+        """pagan_fb_decode: the maximum expected accuracy path of the pair's posteriors (cell weight: the posterior, times
+        gap_weight in a gap state), found on the device.  Returns a DecodedPath."""
+        return decode_batch([self], gap_weight, keep_matrix)[0]
+
     def close(self):
         if self._h:
             self._L.pagan_fb_destroy(self._h)
@@ -254,6 +260,92 @@ class SampledPaths:
             self.close()
         except Exception:
             pass
+
+
+class DecodedPath:
+    """pagan_fb_decoded: the maximum expected accuracy path of one pair -- the summary on the host, the trace (and, with
+    keep_matrix, the score matrix) on the device.  Keeps its FullProbability (and with it the graphs result() reads) alive."""
+
+    def __init__(self, fb, handle, keep_matrix):
+        import numpy as np
+        self._np = np
+        self._L = lib()
+        self._fb = fb
+        self._h = handle
+        self.keep_matrix = bool(keep_matrix)
+        self.shape = fb.shape
+        self.max_steps = fb.shape[0] + fb.shape[1]
+
+    def summary(self):
+        """dict of status, objective, n_steps, n_m, n_x, n_y and schedule (0 pg_fb_decode_fill, 1 pg_fb_ring_decode)."""
+        status, steps, schedule, obj = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+        counts = (C.c_int32 * 3)()
+        _check(self._L.pagan_fb_decoded_summary(self._h, C.byref(status), C.byref(obj), C.byref(steps), counts, C.byref(schedule)),
+               "pagan_fb_decoded_summary")
+        return {"status": status.value, "objective": obj.value, "n_steps": steps.value, "n_m": counts[0], "n_x": counts[1],
+                "n_y": counts[2], "schedule": schedule.value}
+
+    def visited(self):
+        """The path's cells end -> start as rows (i, j, state): FullProbability.sample_path's second value."""
+        vis = self._np.zeros((self.max_steps + 1, 3), self._np.int32)
+        n = C.c_int32()
+        _check(self._L.pagan_fb_decoded_visited(self._h, vis.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "pagan_fb_decoded_visited")
+        return vis[:n.value].copy()
+
+    def result(self):
+        """The replay of the trace: a Result of FullProbability.sample_path's shape (score = log full probability)."""
+        res = abi.CResult()
+        rc = self._L.pagan_fb_decoded_result(self._h, C.byref(res))
+        try:
+            _check(rc, "pagan_fb_decoded_result")
+            return Result(res)
+        finally:
+            self._L.pagan_result_free(C.byref(res))
+
+    def matrix(self):
+        """The score matrix [Lx, Ly, 3] (X, Y, M), -inf outside the band; needs keep_matrix."""
+        out = self._np.zeros(self.shape, self._np.float64)
+        _check(self._L.pagan_fb_decoded_dump(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), "pagan_fb_decoded_dump")
+        return out
+
+    def ms(self):
+        """Device ms of the fill and of the trace, booked at the batch's first pair."""
+        ms = (C.c_double * 2)()
+        _check(self._L.pagan_fb_decoded_ms(self._h, ms), "pagan_fb_decoded_ms")
+        return ms[0], ms[1]
+
+    def close(self):
+        if self._h:
+            self._L.pagan_fb_decoded_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def decode_batch(fbs, gap_weight=0.5, keep_matrix=False):
+    """pagan_fb_decode_batch: the maximum expected accuracy paths of FullProbability handles of one device (the fills side by
+    side, one launch of the walks back) -> [DecodedPath, ...]."""
+    L = lib()
+    n = len(fbs)
+    handles = (C.c_void_p * n)(*[fb._h for fb in fbs])
+    outs = (C.c_void_p * n)()
+    _check(L.pagan_fb_decode_batch(n, handles, float(gap_weight), abi.DECODE_KEEP_MATRIX if keep_matrix else 0, outs), "pagan_fb_decode_batch")
+    return [DecodedPath(fb, C.c_void_p(outs[k]), keep_matrix) for k, fb in enumerate(fbs)]
+
+
+def fb_decode_route(left, right, band=None):
+    """pagan_fb_debug_decode_route (host only): 1 when the pair's decode would fill on the LDS ring, 0 on pg_fb_decode_fill."""
+    rc = lib().pagan_fb_debug_decode_route(C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None)
+    _check(min(rc, 0), "pagan_fb_debug_decode_route")
+    return rc
+
+
+def fb_decode_predict_bytes(left_sites, right_sites, band=None):
+    return lib().pagan_fb_decode_predict_bytes(left_sites, right_sites, C.byref(band.c) if band is not None else None)
 
 
 def sample_paths_batch(fbs, seed, nodes, n_paths, traces=True):

@@ -15,6 +15,7 @@ PAGAN_DP_REACHED, PAGAN_DP_UNREACHABLE = 0, 1
 OPT_NO_TERMINAL_EDGES = 1
 OPT_NO_REDUCED_TERMINAL_PEN = 2
 SAMPLE_NO_TRACES = 1
+DECODE_KEEP_MATRIX = 1
 X_MAT, Y_MAT, M_MAT = 0, 1, 2
 MATCHED, XGAPPED, YGAPPED, XSKIPPED, YSKIPPED = 2, 3, 4, 5, 6
 
@@ -284,6 +285,26 @@ def declare(lib):
     lib.pagan_fb_sample_predict_bytes.restype = C.c_int64
     lib.pagan_fb_samples_destroy.argtypes = [C.c_void_p]
     lib.pagan_fb_samples_destroy.restype = None
+    lib.pagan_fb_decode_batch.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.c_double, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.pagan_fb_decode_batch.restype = C.c_int
+    lib.pagan_fb_decode.argtypes = [C.c_void_p, C.c_double, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.pagan_fb_decode.restype = C.c_int
+    lib.pagan_fb_decoded_summary.argtypes = [C.c_void_p, _i32p, f64p, _i32p, _i32p, _i32p]
+    lib.pagan_fb_decoded_summary.restype = C.c_int
+    lib.pagan_fb_decoded_visited.argtypes = [C.c_void_p, _i32p, _i32p]
+    lib.pagan_fb_decoded_visited.restype = C.c_int
+    lib.pagan_fb_decoded_result.argtypes = [C.c_void_p, rp]
+    lib.pagan_fb_decoded_result.restype = C.c_int
+    lib.pagan_fb_decoded_dump.argtypes = [C.c_void_p, f64p]
+    lib.pagan_fb_decoded_dump.restype = C.c_int
+    lib.pagan_fb_decoded_ms.argtypes = [C.c_void_p, f64p]
+    lib.pagan_fb_decoded_ms.restype = C.c_int
+    lib.pagan_fb_debug_decode_route.argtypes = [gp, gp, bp]
+    lib.pagan_fb_debug_decode_route.restype = C.c_int
+    lib.pagan_fb_decode_predict_bytes.argtypes = [C.c_int32, C.c_int32, bp]
+    lib.pagan_fb_decode_predict_bytes.restype = C.c_int64
+    lib.pagan_fb_decoded_destroy.argtypes = [C.c_void_p]
+    lib.pagan_fb_decoded_destroy.restype = None
     lib.pagan_fb_destroy.argtypes = [C.c_void_p]
     lib.pagan_fb_destroy.restype = None
     lib.pagan_dp_version.argtypes = []
@@ -299,4 +320,6 @@ EXPORTED = ["pagan_dp_align", "pagan_dp_align_batch", "pagan_result_free", "paga
             "pagan_path_cells", "pagan_fb_path_support", "pagan_fb_site_marginals", "pagan_fb_site_marginals_batch", "pagan_fb_post_ms", "pagan_fb_predict_bytes", "pagan_sample_uniforms",
             "pagan_sample_uniforms_path", "pagan_fb_sample_paths_batch", "pagan_fb_sample_paths", "pagan_fb_samples_summary", "pagan_fb_samples_visited",
             "pagan_fb_samples_visited_all", "pagan_fb_samples_result", "pagan_fb_samples_ms", "pagan_fb_sample_predict_bytes", "pagan_fb_samples_destroy",
+            "pagan_fb_decode_batch", "pagan_fb_decode", "pagan_fb_decoded_summary", "pagan_fb_decoded_visited", "pagan_fb_decoded_result",
+            "pagan_fb_decoded_dump", "pagan_fb_decoded_ms", "pagan_fb_debug_decode_route", "pagan_fb_decode_predict_bytes", "pagan_fb_decoded_destroy",
             "pagan_fb_destroy", "pagan_dp_version"]

@@ -488,6 +488,7 @@ __global__ __launch_bounds__(FB_RG_THREADS) void pg_fb_backward_ring(const PgFbJ
 #include "dp_fb_deep.inc"
 #include "dp_fb_post.inc"
 #include "dp_fb_sample.inc"
+#include "dp_fb_decode.inc"
 
 // ---- wide alignments: 64 x 64 blocks on a block-anti-diagonal schedule ----
 // Block (a, b) needs blocks (a', b') <= (a, b) only (bwd edges point to earlier sites), so the blocks of one block
@@ -1118,6 +1119,28 @@ static void fb_deep_plan(int Lx, int Ly, const DiagIndex &dx, const std::vector<
     R->info[6] = (int)std::min<long long>(far_cells, 0x7fffffff); R->info[7] = far_diags;
 }
 
+// a plain sequence: every site has exactly one edge, from the site before it
+static bool fb_plain(const pagan_graph *g) {
+    for (int sidx = 1; sidx < g->n_sites; ++sidx)
+        if (g->bwd_off[sidx + 1] - g->bwd_off[sidx] != 1 || g->bwd_src[g->bwd_off[sidx]] != sidx - 1) return false;
+    return g->bwd_off[1] == 0;
+}
+// no cell diagonal without a cell
+static bool fb_gapless(const DiagIndex &dx, int nd) {
+    for (int d = 0; d < nd; ++d) if (dx.imax[d] < dx.imin[d]) return false;
+    return true;
+}
+
+// Which kernel fills a pair's decode matrix, decided in ONE place (pagan_fb_decode_batch and pagan_fb_debug_decode_route both call
+// this): 1 = pg_fb_ring_decode -- two plain sequences whose widest diagonal fits a workgroup, the predicate of fb_route's schedule 2
+// without its shortest-pair rule (there is no tiled alternative to win on a short pair) --, 0 = pg_fb_decode_fill.
+// PAGAN_FB_DECODE_RING=0 switches the ring off.  Which sweep schedule wrote F and B does not matter: the layout is one.
+static int fb_decode_route(const pagan_graph *left, const pagan_graph *right, int Lx, int Ly, const DiagIndex &dx) {
+    if (fb_env_off("PAGAN_FB_DECODE_RING")) return 0;
+    if (!(dx.max_width <= FB_RG_MAXB && Lx >= 2 && Ly >= 2)) return 0;
+    return fb_plain(left) && fb_plain(right) && fb_gapless(dx, Lx + Ly - 1) ? 1 : 0;
+}
+
 static void fb_route(const pagan_graph *left, const pagan_graph *right, int Lx, int Ly, const DiagIndex &dx, bool has_band, int n_init,
                      const FwdLists &fl, const FwdLists &fr, FbRoute *R) {
     const int nd = Lx + Ly - 1, mw = dx.max_width;
@@ -1133,14 +1156,8 @@ static void fb_route(const pagan_graph *left, const pagan_graph *right, int Lx, 
     // (pg_fb_forward_ring): PAGAN_FB_RING=0 switches them off, PAGAN_FB_RING_MIN_ND is their shortest pair (default 256 diagonals)
     // ... and a graph pair (any other edge lists) inside a tunnel on the deep-ring sweeps (pg_fb_forward_deep, dp_fb_deep.inc):
     // PAGAN_FB_DEEP=0 switches them off, PAGAN_FB_DEEP_MIN_ND is their shortest pair (default 4,096 diagonals)
-    auto plain = [](const pagan_graph *g) {
-        for (int sidx = 1; sidx < g->n_sites; ++sidx)
-            if (g->bwd_off[sidx + 1] - g->bwd_off[sidx] != 1 || g->bwd_src[g->bwd_off[sidx]] != sidx - 1) return false;
-        return g->bwd_off[1] == 0;
-    };
-    bool gapless = true;                                          // (no cell diagonal without a cell)
-    for (int d = 0; d < nd && gapless; ++d) gapless = dx.imax[d] >= dx.imin[d];
-    const bool both_plain = plain(left) && plain(right);
+    const bool gapless = fb_gapless(dx, nd);
+    const bool both_plain = fb_plain(left) && fb_plain(right);
     const bool shape_ok = mw <= FB_RG_MAXB && Lx >= 2 && Ly >= 2 && n_init <= FB_RG_INIT && gapless;
     bool ring = false, deep = false;
     {
@@ -2184,5 +2201,242 @@ void pagan_fb_destroy(pagan_fb *fb) {
     if (fb->arena) fb_arena_pool.give(fb->device, fb->arena, fb->arena_cap);
     delete fb;
 }
+
+} // extern "C"
+
+// ---- posterior decoding: the maximum expected accuracy path of a finished pass (dp_fb_decode.inc) ----
+// A pair's score matrix A (24 B a cell) is an arena of its own from fb_arena_pool: it goes back to the pool behind the trace
+// unless the caller keeps it (PAGAN_DECODE_KEEP_MATRIX).  One further allocation serves a whole batch call -- the job records,
+// the launch records, every pair's summary and trace -- and lives as long as any of the batch's handles does.
+
+struct pagan_fb_decoded {
+    int device = 0;
+    int Lx = 0, Ly = 0, max_steps = 0;
+    uint32_t flags = 0;
+    const pagan_graph *L = nullptr, *R = nullptr;       // borrowed from the pagan_fb: must outlive the handle for result()
+    long long cells = 0;
+    double log_fwd = 0;
+    DiagIndex dx;                                       // kept matrix only: where a cell sits (pagan_fb_decoded_dump)
+    char *arena = nullptr;                              // A; null once it went back to the pool
+    size_t arena_cap = 0;
+    std::shared_ptr<FbDevBuf> buf;
+    const int *d_trace = nullptr;                       // [max_steps][3]
+    int32_t summary[FD_SUMMARY_INTS] = {0};
+    float ms[2] = {0, 0};                               // fill, trace (HIP events), at the batch's first pair
+    int schedule = 0;                                   // 0 pg_fb_decode_fill, 1 pg_fb_ring_decode
+    ~pagan_fb_decoded() { if (arena) fb_arena_pool.give(device, arena, arena_cap); }
+};
+
+namespace {
+// the trace's records, three zero ints behind them (pagan_internal_replay's format)
+static int fd_fetch(pagan_fb_decoded *d, std::vector<int> *trace, int *n_steps) {
+    const int n = d->summary[0] == 0 ? d->summary[6] : 0;
+    if (n < 0 || n > d->max_steps) return PAGAN_E_INTERNAL;
+    trace->assign(3 * ((size_t)n + 1), 0);
+    *n_steps = n;
+    if (n == 0) return PAGAN_OK;
+    FbDeviceScope on_device(d->device);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    FB_TRY(hipMemcpy(trace->data(), d->d_trace, 12 * (size_t)n, hipMemcpyDeviceToHost));
+    return PAGAN_OK;
+}
+static size_t fd_up(size_t b) { return (b + 255) / 256 * 256; }
+// waits for the default stream when a call leaves, by whichever return: a handle's matrix must not reach fb_arena_pool (whose next
+// take would hand it out) while a kernel may still be writing it
+struct FdStreamWait { ~FdStreamWait() { (void)hipStreamSynchronize(nullptr); } };
+} // namespace
+
+extern "C" {
+
+// The decode of n finished pairs of one device: the fills (one launch of pg_fb_decode_fill over the fill pairs, one of
+// pg_fb_ring_decode per workgroup size over the ring pairs), then one launch of pg_fb_decode_trace over all pairs.
+int pagan_fb_decode_batch(int32_t n, pagan_fb *const *fbs, double gap_weight, uint32_t flags, pagan_fb_decoded **out) {
+    if (n < 0 || (flags & ~PAGAN_DECODE_KEEP_MATRIX) || !(gap_weight >= 0.0) || !(gap_weight < HUGE_VAL) || (n > 0 && (!fbs || !out))) return PAGAN_E_ARG;
+    for (int k = 0; k < n; ++k) out[k] = nullptr;
+    for (int k = 0; k < n; ++k) if (!fbs[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
+    if (n == 0) return PAGAN_OK;
+    const int device = fbs[0]->device;
+    FbDeviceScope on_device(device);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    // launch order: the fill pairs, then the ring pairs by workgroup size and by whether their score table needs looking at
+    std::vector<int> block(n, 0), order(n), tabfin(n, 1);
+    for (int k = 0; k < n; ++k) {
+        const pagan_fb *fb = fbs[k];
+        const int mw = fb->dx.max_width;
+        if (fb_decode_route(fb->L, fb->R, fb->Lx, fb->Ly, fb->dx)) block[k] = mw > 512 ? 1024 : (mw > 256 ? 512 : (mw > 128 ? 256 : (mw > 64 ? 128 : 64)));
+        for (float v : fb->score) if (!(v > 0.0f) || !(v < HUGE_VALF)) tabfin[k] = 0;
+        order[k] = k;
+    }
+    auto launch_key = [&](int k) { return block[k] ? 2 * block[k] + (tabfin[k] ? 0 : 1) : 0; };
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return launch_key(a) < launch_key(b); });
+    std::vector<std::unique_ptr<pagan_fb_decoded>> hs(n);
+    FdStreamWait wait_on_exit;                                   // (declared behind the handles: runs before they are destroyed)
+    size_t cur = 0;
+    auto take = [&](size_t bytes) { const size_t at = cur; cur = fd_up(cur + bytes); return at; };
+    const size_t o_jobs = take((size_t)n * sizeof(PgFbJob)), o_recs = take((size_t)n * sizeof(PgFbDecode));
+    const size_t in_bytes = cur;
+    std::vector<size_t> o_sum(n), o_trace(n);
+    for (int k = 0; k < n; ++k) o_sum[k] = take(4 * FD_SUMMARY_INTS);
+    const size_t sum_end = cur;
+    for (int k = 0; k < n; ++k) o_trace[k] = take(12 * ((size_t)fbs[k]->Lx + fbs[k]->Ly));
+    std::shared_ptr<FbDevBuf> buf = std::make_shared<FbDevBuf>();
+    FB_DO(buf->alloc(cur));
+    std::vector<char> host(sum_end, 0);
+    int fill_block = 64, n_fill = 0;
+    for (int q = 0; q < n; ++q) {
+        const int k = order[q];
+        const pagan_fb *fb = fbs[k];
+        hs[k].reset(new pagan_fb_decoded());
+        pagan_fb_decoded *d = hs[k].get();
+        d->device = device; d->Lx = fb->Lx; d->Ly = fb->Ly; d->max_steps = fb->Lx + fb->Ly; d->flags = flags;
+        d->L = fb->L; d->R = fb->R; d->cells = fb->dx.cells; d->log_fwd = fb->totals[0];
+        d->schedule = block[k] ? 1 : 0;
+        d->arena = fb_arena_pool.take(device, 24 * (size_t)fb->dx.cells, &d->arena_cap);
+        if (!d->arena) return PAGAN_E_NOMEM;
+        if (flags & PAGAN_DECODE_KEEP_MATRIX) d->dx = fb->dx;
+        d->buf = buf;
+        d->d_trace = (const int *)(buf->h + o_trace[k]);
+        PgFbDecode R;
+        R.g = gap_weight; R.A = (double *)d->arena; R.trace = (int *)(buf->h + o_trace[k]); R.summary = (int *)(buf->h + o_sum[k]);
+        R.max_steps = d->max_steps;
+        R.tab_finite = tabfin[k];
+        std::memcpy(host.data() + o_jobs + (size_t)q * sizeof(PgFbJob), &fb->job, sizeof(PgFbJob));
+        std::memcpy(host.data() + o_recs + (size_t)q * sizeof(PgFbDecode), &R, sizeof(R));
+        if (!block[k]) {
+            const int mw = fb->dx.max_width;
+            fill_block = std::max(fill_block, mw >= 768 ? 1024 : mw >= 384 ? 512 : mw >= 192 ? 256 : (mw >= 96 ? 128 : 64));
+            ++n_fill;
+        }
+    }
+    const PgFbJob *jobs = (const PgFbJob *)(buf->h + o_jobs);
+    const PgFbDecode *recs = (const PgFbDecode *)(buf->h + o_recs);
+    FbEvent e0, e1, e2;
+    float ms[2] = {0, 0};
+    FB_TRY(hipMemcpy(buf->h, host.data(), in_bytes, hipMemcpyHostToDevice));
+    FB_DO(e0.create()); FB_DO(e1.create()); FB_DO(e2.create());
+    FB_TRY(hipEventRecord(e0, nullptr));
+    if (n_fill > 0) hipLaunchKernelGGL(pg_fb_decode_fill, dim3((unsigned)n_fill), dim3((unsigned)fill_block), 0, nullptr, jobs, recs);
+    for (int q = n_fill; q < n;) {
+        const int b = block[order[q]], key = launch_key(order[q]);
+        int e = q;
+        while (e < n && launch_key(order[e]) == key) ++e;
+        const dim3 grid((unsigned)(e - q)), blk((unsigned)b);
+        if (b > 512 && tabfin[order[q]]) hipLaunchKernelGGL((pg_fb_ring_decode<1024, false>), grid, blk, 0, nullptr, jobs + q, recs + q);
+        else if (b > 512) hipLaunchKernelGGL((pg_fb_ring_decode<1024, true>), grid, blk, 0, nullptr, jobs + q, recs + q);
+        else if (tabfin[order[q]]) hipLaunchKernelGGL((pg_fb_ring_decode<512, false>), grid, blk, 0, nullptr, jobs + q, recs + q);
+        else hipLaunchKernelGGL((pg_fb_ring_decode<512, true>), grid, blk, 0, nullptr, jobs + q, recs + q);
+        q = e;
+    }
+    FB_TRY(hipGetLastError());
+    FB_TRY(hipEventRecord(e1, nullptr));
+    hipLaunchKernelGGL(pg_fb_decode_trace, dim3((unsigned)n), dim3(64), 0, nullptr, jobs, recs);
+    FB_TRY(hipGetLastError());
+    FB_TRY(hipEventRecord(e2, nullptr));
+    FB_TRY(hipMemcpy(host.data() + in_bytes, buf->h + in_bytes, sum_end - in_bytes, hipMemcpyDeviceToHost));
+    (void)hipEventElapsedTime(&ms[0], e0, e1);
+    (void)hipEventElapsedTime(&ms[1], e1, e2);
+    for (int k = 0; k < n; ++k) {
+        pagan_fb_decoded *d = hs[k].get();
+        std::memcpy(d->summary, host.data() + o_sum[k], 4 * FD_SUMMARY_INTS);
+        if (k == 0) { d->ms[0] = ms[0]; d->ms[1] = ms[1]; }
+        if (!(flags & PAGAN_DECODE_KEEP_MATRIX)) { fb_arena_pool.give(device, d->arena, d->arena_cap); d->arena = nullptr; }
+    }
+    for (int k = 0; k < n; ++k) out[k] = hs[k].release();
+    return PAGAN_OK;
+}
+
+int pagan_fb_decode(pagan_fb *fb, double gap_weight, uint32_t flags, pagan_fb_decoded **out) {
+    if (!fb || !out) return PAGAN_E_ARG;
+    return pagan_fb_decode_batch(1, &fb, gap_weight, flags, out);
+}
+
+int pagan_fb_decoded_summary(const pagan_fb_decoded *d, int32_t *status, double *objective, int32_t *n_steps, int32_t counts[3],
+                             int32_t *schedule) {
+    if (!d) return PAGAN_E_ARG;
+    if (status) *status = d->summary[0];
+    if (objective) std::memcpy(objective, d->summary + 10, 8);
+    if (n_steps) *n_steps = d->summary[6];
+    if (counts) { counts[0] = d->summary[7]; counts[1] = d->summary[8]; counts[2] = d->summary[9]; }
+    if (schedule) *schedule = d->schedule;
+    return PAGAN_OK;
+}
+
+// the path's cells end -> start as (i, j, state), 3 * (Lx + Ly) ints at most: pagan_fb_sample_path's `visited`
+int pagan_fb_decoded_visited(pagan_fb_decoded *d, int32_t *visited, int32_t *n_visited) {
+    if (!d || !visited) return PAGAN_E_ARG;
+    std::vector<int> trace;
+    int n = 0;
+    const int rc = fd_fetch(d, &trace, &n);
+    if (rc != PAGAN_OK) return rc;
+    for (int t = 0; t < n; ++t) { visited[3 * t] = trace[3 * t]; visited[3 * t + 1] = trace[3 * t + 1]; visited[3 * t + 2] = trace[3 * t + 2] & 3; }
+    if (n_visited) *n_visited = n;
+    return PAGAN_OK;
+}
+
+// the replay of the trace: a result of a sampled path's shape (score = log full probability; status 1: the unreachable result)
+int pagan_fb_decoded_result(pagan_fb_decoded *d, pagan_result *out) {
+    if (!d || !out) return PAGAN_E_ARG;
+    int endcell[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (d->summary[0] == 1) {
+        endcell[0] = 1; endcell[4] = endcell[5] = -1;
+        return pagan_internal_replay(d->L, d->R, d->cells, endcell, d->log_fwd, nullptr, out);
+    }
+    if (d->summary[0] != 0) return PAGAN_E_INTERNAL;
+    std::vector<int> trace;
+    int n = 0;
+    const int rc = fd_fetch(d, &trace, &n);
+    if (rc != PAGAN_OK) return rc;
+    for (int k = 1; k <= 5; ++k) endcell[k] = d->summary[k];
+    endcell[6] = n;
+    return pagan_internal_replay(d->L, d->R, d->cells, endcell, d->log_fwd, trace.data(), out);
+}
+
+// dst [Lx][Ly][3] row-major, state order X, Y, M; -inf outside the band
+int pagan_fb_decoded_dump(pagan_fb_decoded *d, double *dst) {
+    if (!d || !dst || !d->arena || !(d->flags & PAGAN_DECODE_KEEP_MATRIX)) return PAGAN_E_ARG;
+    FbDeviceScope on_device(d->device);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    std::vector<double> a(3 * (size_t)d->cells);
+    FB_TRY(hipMemcpy(a.data(), d->arena, 8 * a.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < d->Lx; ++i)
+        for (int j = 0; j < d->Ly; ++j) {
+            const long long at = d->dx.at(i, j);
+            double *o = dst + ((size_t)i * d->Ly + j) * 3;
+            for (int s = 0; s < 3; ++s) o[s] = at < 0 ? -HUGE_VAL : a[3 * at + s];
+        }
+    return PAGAN_OK;
+}
+
+int pagan_fb_decoded_ms(const pagan_fb_decoded *d, double ms[2]) {
+    if (!d || !ms) return PAGAN_E_ARG;
+    ms[0] = d->ms[0]; ms[1] = d->ms[1];
+    return PAGAN_OK;
+}
+
+// Host only: what pagan_fb_decode_batch would decide for this pair under the current environment (it calls the same fb_decode_route).
+int pagan_fb_debug_decode_route(const pagan_graph *left, const pagan_graph *right, const pagan_band *band) {
+    if (!left || !right) return PAGAN_E_ARG;
+    int rc = check_graph(left);
+    if (rc == PAGAN_OK) rc = check_graph(right);
+    if (rc != PAGAN_OK) return rc;
+    const int Lx = left->n_sites - 1, Ly = right->n_sites - 1;
+    RowBand rb;
+    rc = rb.build(Lx, Ly, band);
+    if (rc != PAGAN_OK) return rc;
+    DiagIndex dx;
+    dx.build(Lx, Ly, rb);
+    return fb_decode_route(left, right, Lx, Ly, dx);
+}
+
+// What a decode takes beside the pair's own arena: A (24 B a cell, with the pool's allowance of a sixteenth), 12 B a path step,
+// the summary and the records.
+int64_t pagan_fb_decode_predict_bytes(int32_t left_sites, int32_t right_sites, const pagan_band *band) {
+    const int64_t cells = pagan_dp_count_cells(left_sites, right_sites, band);
+    if (cells < 0) return cells;
+    const int64_t a = 24 * cells;
+    return a + a / 16 + (int64_t)fd_up(12 * ((size_t)left_sites + right_sites - 2)) + (int64_t)(fd_up(4 * FD_SUMMARY_INTS) + sizeof(PgFbJob) + sizeof(PgFbDecode) + 1024);
+}
+
+void pagan_fb_decoded_destroy(pagan_fb_decoded *d) { delete d; }
 
 } // extern "C"

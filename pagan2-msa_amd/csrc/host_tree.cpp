@@ -133,6 +133,9 @@ struct NodeWork {                // everything one internal node's alignment con
     bool has_marg = false;               // full_probability == 2: the site marginals (pagan_fb_site_marginals' eight arrays)
     std::vector<double> mg_d[6];         // pX, pM_left, best_p_left [Lx]; pY, pM_right, best_p_right [Ly]
     std::vector<int32_t> mg_i[2];        // best_j [Lx], best_i [Ly]
+    // posterior decoding (pagan_msa_set_decoder): the node's result is the replay of its maximum expected accuracy path
+    bool has_dec = false;
+    double dec_objective = 0, dec_steps = 0, dec_ms = 0;   // dec_ms: the sub-batch's fill + trace, booked at its first node
 };
 
 } // namespace
@@ -161,6 +164,8 @@ struct pagan_msa {
     pagan_batch_fn backend = nullptr;    // test seam (pagan_msa_set_batch_backend); null = pagan_dp_align_batch
     void *backend_user = nullptr;
     int sample_on_device = 0;            // pagan_msa_set_sampler: sample_path's paths come from pg_fb_sample (1) or the host's walk (0)
+    int decode_on = 0;                   // pagan_msa_set_decoder: the nodes' results are their posteriors' maximum expected accuracy paths
+    double decode_gap = 0.5;             // ... with this gap weight
     std::atomic<int> parents_built{0};   // parent graphs this process has built (pagan_msa_parents_built)
     std::atomic<int> lazy_err{0};        // first error of a deferred parent build (an imported result that does not fit the child graphs)
     bool rows_built = false;             // m->rows are valid (pagan_msa_finish builds them at once, pagan_msa_finish_lazy on first use)
@@ -228,13 +233,17 @@ int host_threads_of(const pagan_msa *m);
 // With the sampler on the device (pagan_msa_set_sampler) the sub-batch's paths are drawn by one pagan_fb_sample_paths_batch
 // instead -- the same numbers, the same paths -- and a node's result is the replay of its path 0: 12 B a path step come to the
 // host, not the matrix.
+// Posterior decoding (pagan_msa_set_decoder): no Viterbi batch either; the sub-batches are cut by pagan_fb_predict_bytes +
+// pagan_fb_decode_predict_bytes, each goes through one pagan_fb_decode_batch behind its sweeps, and a node's result is the
+// replay of its decoded path (score = log full probability, support along that path, the same retry without the band).
 int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads, std::vector<int> *retry) {
     int64_t budget = 0;
     int rc = device_budget(m, dev, &budget);
     if (rc != PAGAN_OK) return rc;
     pagan_opts po;
     po.flags = 0; po.device = dev;
-    const bool sample = m->opts.sample_path != 0, marg = m->opts.full_probability == 2;
+    const bool decode = m->decode_on != 0;
+    const bool sample = m->opts.sample_path != 0 || decode, marg = m->opts.full_probability == 2;   // sample: the node's path comes from this pass
     size_t at = 0;
     while (at < ks.size()) {
         std::vector<int> which;
@@ -243,6 +252,11 @@ int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads,
             NodeWork &w = m->work[ks[at]];
             int64_t need = pagan_fb_predict_bytes(w.gl.n_sites, w.gr.n_sites, w.banded ? &w.pb : nullptr);
             if (need < 0) return (int)need;
+            if (decode) {
+                const int64_t more = pagan_fb_decode_predict_bytes(w.gl.n_sites, w.gr.n_sites, w.banded ? &w.pb : nullptr);
+                if (more < 0) return (int)more;
+                need += more;
+            } else
             if (sample && m->sample_on_device) need += pagan_fb_sample_predict_bytes(w.gl.n_sites, w.gr.n_sites, 1, 0);    // (the path's trace)
             if (need > budget) return PAGAN_E_MEMCAP;
             if (!which.empty() && used + need > budget) break;
@@ -265,7 +279,18 @@ int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads,
         std::vector<int> rcs(n, PAGAN_OK);
         std::vector<char> again(n, 0);
         std::vector<pagan_fb_samples *> smp(n, nullptr);
-        double smp_ms = 0;
+        double smp_ms = 0, dec_ms = 0;
+        std::vector<pagan_fb_decoded *> dec(n, nullptr);
+        if (decode) {
+            double dms[2] = {0, 0};
+            rc = pagan_fb_decode_batch(n, fbs.data(), m->decode_gap, 0, dec.data());
+            if (rc == PAGAN_OK) rc = pagan_fb_decoded_ms(dec[0], dms);
+            if (rc != PAGAN_OK) {
+                for (int q = 0; q < n; ++q) { pagan_fb_decoded_destroy(dec[q]); pagan_fb_destroy(fbs[q]); }
+                return rc;
+            }
+            dec_ms = dms[0] + dms[1];
+        } else
         if (sample && m->sample_on_device) {
             std::vector<int32_t> ids(n);
             for (int q = 0; q < n; ++q) ids[q] = m->work[which[q]].node;
@@ -282,11 +307,17 @@ int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads,
             int r = pagan_fb_totals(fbs[q], &w.log_fwd, &w.log_bwd, nullptr);
             if (r == PAGAN_OK) r = pagan_fb_kernel_ms(fbs[q], ms);
             w.fb_sweep_ms = ms[0] + ms[1]; w.fb_post_ms = 0;
-            w.has_marg = false; w.support.clear();
+            w.has_marg = false; w.support.clear(); w.has_dec = false;
             if (r == PAGAN_OK && sample) {
                 if (w.has_res) { pagan_result_free(&w.res); w.has_res = false; }
                 if (!(w.log_fwd > -HUGE_VAL) && w.banded) { again[q] = 1; rcs[q] = PAGAN_OK; return; }
-                if (smp[q]) {
+                if (dec[q]) {
+                    int32_t steps = 0;
+                    r = pagan_fb_decoded_summary(dec[q], nullptr, &w.dec_objective, &steps, nullptr, nullptr);
+                    if (r == PAGAN_OK) r = pagan_fb_decoded_result(dec[q], &w.res);
+                    w.dec_steps = steps; w.dec_ms = q == 0 ? dec_ms : 0.0;
+                    w.has_dec = r == PAGAN_OK;
+                } else if (smp[q]) {
                     r = pagan_fb_samples_result(smp[q], 0, &w.res);
                 } else {
                     const int n_u = w.gl.n_sites + w.gr.n_sites - 1;                 // Lx + Ly + 1
@@ -321,7 +352,9 @@ int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads,
             double ms[3] = {0, 0, 0};
             if (rc == PAGAN_OK && pagan_fb_post_ms(fbs[q], ms) == PAGAN_OK) w.fb_post_ms = ms[0] + ms[1] + ms[2] + (q == 0 ? smp_ms : 0.0);
             pagan_fb_samples_destroy(smp[q]);
+            pagan_fb_decoded_destroy(dec[q]);
             w.has_fb = rc == PAGAN_OK && !again[q];
+            w.has_dec = w.has_dec && w.has_fb;
             if (again[q]) retry->push_back(which[q]);
             pagan_fb_destroy(fbs[q]);
         }
@@ -839,7 +872,7 @@ int run_unit(pagan_msa *m, const std::vector<int> &ids, int dev, int round, int 
     for (size_t r = 0; r < ids.size(); ++r) ks[r] = ids[order[r]] - n;
     double fill_ms = 0, trace_ms = 0;
     int rc = PAGAN_OK;
-    const bool sample = m->opts.sample_path != 0;
+    const bool sample = m->opts.sample_path != 0 || m->decode_on != 0;       // (no Viterbi batch: the forward/backward pass gives the path)
     if (!sample) {
         rc = align_on_device(m, ks, dev, &fill_ms, &trace_ms);
         if (rc != PAGAN_OK) return rc;
@@ -912,7 +945,8 @@ int64_t pagan_msa_node_cost(const pagan_msa *m, int32_t id) {
 // device that finishes early picks up what is ready without waiting for the others.
 int pagan_msa_align_nodes(pagan_msa *m, int32_t n_ids, const int32_t *ids) {
     if (!m || m->aligned || n_ids < 0 || (n_ids > 0 && !ids)) return PAGAN_E_ARG;
-    if (m->backend && (m->opts.full_probability || m->opts.sample_path)) return PAGAN_E_NODEVICE;   // (the seam has no forward/backward pass: never skipped silently)
+    if (m->decode_on && m->opts.sample_path) return PAGAN_E_ARG;        // (a node has one path: the decoded one or a sampled one)
+    if (m->backend && (m->opts.full_probability || m->opts.sample_path || m->decode_on)) return PAGAN_E_NODEVICE;   // (the seam has no forward/backward pass: never skipped silently)
     for (int k = 0; k < n_ids; ++k)
         if (ids[k] < m->n_leaves || ids[k] >= 2 * m->n_leaves - 1 || !node_ready(m, ids[k])) return PAGAN_E_ARG;
     if (n_ids == 0) return PAGAN_OK;
@@ -981,7 +1015,8 @@ int pagan_msa_parents_built(const pagan_msa *m) { return m ? m->parents_built.lo
 
 int pagan_msa_align(pagan_msa *m) {
     if (!m || m->aligned) return PAGAN_E_ARG;
-    if (m->backend && (m->opts.full_probability || m->opts.sample_path)) return PAGAN_E_NODEVICE;
+    if (m->decode_on && m->opts.sample_path) return PAGAN_E_ARG;
+    if (m->backend && (m->opts.full_probability || m->opts.sample_path || m->decode_on)) return PAGAN_E_NODEVICE;
     int ndev = m->opts.n_devices;
     int first_dev = m->opts.first_device;
     if (ndev <= 0) { ndev = 1; if (!m->backend && hipGetDevice(&first_dev) != hipSuccess) return PAGAN_E_NODEVICE; }
@@ -1188,6 +1223,14 @@ int pagan_msa_node_fb(const pagan_msa *m, int32_t k, double out[4]) {
     if (!m || !out || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_fb) return PAGAN_E_ARG;
     const NodeWork &w = m->work[k];
     out[0] = w.log_fwd; out[1] = w.log_bwd; out[2] = w.fb_sweep_ms; out[3] = w.fb_post_ms;
+    return PAGAN_OK;
+}
+
+// ... and the posterior decoding (pagan_msa_set_decoder)
+int pagan_msa_node_decode(const pagan_msa *m, int32_t k, double out[3]) {
+    if (!m || !out || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_dec) return PAGAN_E_ARG;
+    const NodeWork &w = m->work[k];
+    out[0] = w.dec_objective; out[1] = w.dec_steps; out[2] = w.dec_ms;
     return PAGAN_OK;
 }
 
@@ -1537,6 +1580,12 @@ int pagan_msa_set_batch_backend(pagan_msa *m, pagan_batch_fn fn, void *user) {
 int pagan_msa_set_sampler(pagan_msa *m, int32_t on_device) {
     if (!m || (on_device != 0 && on_device != 1)) return PAGAN_E_ARG;
     m->sample_on_device = on_device;
+    return PAGAN_OK;
+}
+
+int pagan_msa_set_decoder(pagan_msa *m, int32_t on, double gap_weight) {
+    if (!m || (on != 0 && on != 1) || !(gap_weight >= 0.0) || !(gap_weight < HUGE_VAL)) return PAGAN_E_ARG;
+    m->decode_on = on; m->decode_gap = gap_weight;
     return PAGAN_OK;
 }
 

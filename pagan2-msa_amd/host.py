@@ -175,6 +175,10 @@ def _lib():
         L.pagan_msa_set_batch_backend.restype = C.c_int
         L.pagan_msa_set_sampler.argtypes = [vp, C.c_int32]
         L.pagan_msa_set_sampler.restype = C.c_int
+        L.pagan_msa_set_decoder.argtypes = [vp, C.c_int32, C.c_double]
+        L.pagan_msa_set_decoder.restype = C.c_int
+        L.pagan_msa_node_decode.argtypes = [vp, C.c_int32, f64p]
+        L.pagan_msa_node_decode.restype = C.c_int
         L.pagan_pileup_default_opts.argtypes = [C.POINTER(CPileupOpts)]
         L.pagan_pileup_default_opts.restype = None
         L.pagan_pileup_create.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(CPileupOpts), C.POINTER(vp)]
@@ -228,7 +232,7 @@ HOST_EXPORTED = ["pagan_assign_units", "pagan_msa_default_opts", "pagan_msa_crea
                  "pagan_pileup_alignment_length", "pagan_pileup_alignment_row", "pagan_pileup_set_batch_backend",
                  "pagan_pileup_destroy",
                  "pagan_msa_node_fb", "pagan_msa_node_support", "pagan_msa_node_marginals", "pagan_msa_node_model_prob", "pagan_msa_support_row",
-                 "pagan_msa_set_sampler"]
+                 "pagan_msa_set_sampler", "pagan_msa_set_decoder", "pagan_msa_node_decode"]
 
 
 def _ip(a):
@@ -606,9 +610,11 @@ class Pileup:
 class Msa:
     """Progressive alignment of sequences on a rooted binary guide tree (Node mirror)."""
 
-    def __init__(self, names, seqs, newick, sample_on_device=0, **opts):
+    def __init__(self, names, seqs, newick, sample_on_device=0, posterior_decode=0, decode_gap_weight=0.5, **opts):
         """opts: fields of pagan_msa_opts.  sample_on_device=1 (pagan_msa_set_sampler): with sample_path set, the nodes' paths
-        are drawn by pg_fb_sample on the device instead of on the host behind a download of the forward matrix."""
+        are drawn by pg_fb_sample on the device instead of on the host behind a download of the forward matrix.
+        posterior_decode=1 (pagan_msa_set_decoder): a node's result is the maximum expected accuracy path of its posteriors,
+        gaps weighted by decode_gap_weight."""
         L = _lib()
         o = CMsaOpts()
         L.pagan_msa_default_opts(C.byref(o))
@@ -630,6 +636,11 @@ class Msa:
             if rc != 0:
                 from . import PaganError
                 raise PaganError(rc, "pagan_msa_set_sampler")
+        if posterior_decode:
+            rc = L.pagan_msa_set_decoder(self._h, int(posterior_decode), float(decode_gap_weight))
+            if rc != 0:
+                from . import PaganError
+                raise PaganError(rc, "pagan_msa_set_decoder")
 
     def align(self):
         rc = self._L.pagan_msa_align(self._h)
@@ -749,6 +760,12 @@ class Msa:
         """(log_fwd, log_bwd, device ms of the sweeps, device ms of support + marginals) of internal node k."""
         out = (C.c_double * 4)()
         self._fb_check(self._L.pagan_msa_node_fb(self._h, k, out), "pagan_msa_node_fb")
+        return tuple(out)
+
+    def node_decode(self, k):
+        """(objective, steps, device ms of fill + trace) of internal node k's decoded path (posterior_decode=1)."""
+        out = (C.c_double * 3)()
+        self._fb_check(self._L.pagan_msa_node_decode(self._h, k, out), "pagan_msa_node_decode")
         return tuple(out)
 
     def node_support(self, k):
