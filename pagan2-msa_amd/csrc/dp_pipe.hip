@@ -2625,6 +2625,51 @@ __device__ __noinline__ void wide_run(WaveCtx &C_) {
 #define PW7 7
 #define PW7L (64 * PW7)
 static_assert(PW7 == PNW + PNA && PG_PIPE_WINDOW <= PW7L - 16, "seven-wave wide runs: one row per lane");
+// One site's edges as a batched cell sees them: exactly one from the previous site (log weight wA), beside it none, one
+// (`two`: k1 sites back, w1) or two others (`three`: the second k3 back, w3).  Returns whether the site has that shape.
+// wide_run7 runs under the small model tables only, where the loader NORMALISES the records (load_rec_chunk): PR_TWO says
+// "two or three edges, one of them from the previous site, and that one in slot 0", PR_THREE "three, and the edge window
+// holds (previous-site edge, other, other)" -- nothing to sort out here.  One shape the loader leaves as it found it and
+// the step still batches: three edges, one from the previous site, one of them past PAGE - 2 (a far operand like any
+// other here, but out of the hand-scheduled loop's reach, hence not PR_THREE); it keeps the order-agnostic decode.
+template <bool LEFT>
+__device__ __forceinline__ bool site7(const pg_i4 &rec, int site, bool &two, bool &three, int &k1, int &k3, double &wA, double &w1, double &w3) {
+    const int n = (rec.x >> PR_NE_SHIFT) & 127;
+    two = false; three = false; k1 = 1; k3 = 1; wA = (double)__int_as_float(rec.z); w1 = 0.0; w3 = 0.0;
+    if (rec.x & PR_TWO) {
+        two = true; k1 = (int)((unsigned)rec.y >> 16); w1 = (double)__int_as_float(rec.w);
+        if (rec.x & PR_THREE) { three = true; edge_at<LEFT>(rec, 2, site, k3, w3); }
+        return true;
+    }
+    if (n == 1) return (rec.y & 0xffff) == 1;
+    if (n == 3) {
+        const int e0 = rec.y & 0xffff, e1 = (int)((unsigned)rec.y >> 16);
+        const double f0 = wA, f1 = (double)__int_as_float(rec.w);
+        int e2; double f2;
+        edge_at<LEFT>(rec, 2, site, e2, f2);
+        two = true; three = true;
+        if (e0 == 1) { k1 = e1; w1 = f1; k3 = e2; w3 = f2; }
+        else if (e1 == 1) { wA = f1; k1 = e0; w1 = f0; k3 = e2; w3 = f2; }
+        else { wA = f2; k1 = e0; w1 = f0; k3 = e1; w3 = f1; }
+        return ((e0 == 1) + (e1 == 1) + (e2 == 1)) == 1;
+    }
+    return false;
+}
+// One cell's three scores from L2 as loads the compiler tracks (agent scope, as far_fetch's sc1): they may stay in flight
+// across other code -- the lock-step poll -- and the compiler waits where a value is first used.
+__device__ __forceinline__ void far_issue(gdouble_w sc, const FarAsk &a, unsigned long long (&q)[3]) {
+#ifdef PG_PIPE_STATS
+    // (as far_fetch8: a cell outside the job's score array sets the abort flag, and the arena's first cell is read instead)
+    const bool bad = a.need && (a.boff < 0 || a.boff + 24 > PM.far_limit);
+    if (__builtin_amdgcn_ballot_w64(bad) != 0 && PM.abort_flag == 0) PM.abort_flag = 0x7f000005;
+    PG_GLOBAL const unsigned long long *p = (PG_GLOBAL const unsigned long long *)((PG_GLOBAL const char *)sc + (a.need && !bad ? a.boff : 0ll));
+#else
+    PG_GLOBAL const unsigned long long *p = (PG_GLOBAL const unsigned long long *)((PG_GLOBAL const char *)sc + (a.need ? a.boff : 0ll));
+#endif
+    q[0] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    q[1] = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    q[2] = __hip_atomic_load(p + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 __device__ __noinline__ void wide_run7(WaveCtx &C_) {
     WCTX_IN(C_);
     WCTX_STATS(C_);
@@ -2671,6 +2716,16 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
     auto wpos = [&](int r_) { int q_ = r_ - wbase; q_ -= q_ >= wpos_n ? wpos_n : 0; q_ -= q_ >= wpos_n ? wpos_n : 0; return q_; };
     int n_hist1 = 0, n_hist2 = 0;                                  // stores issued in the previous step / the one before
     int lo_prev = cur.x;
+    // what a step need not work out again: the wide-ring row of the diagonal (d % wk, in bytes), the position of the lane's own
+    // row in it (in bytes; wbase moves by whole rings, so it changes at the hand-over only), and the lane's LEFT site -- a lane
+    // keeps its row, so the site is decoded when the lane meets the row (lrow: the row the values below belong to)
+    const int wring_bytes = wk * wrow_bytes;
+    int wsb = (d0 % wk) * wrow_bytes;
+    int wqb = wpos(wr) * 24;
+    int lrow = -1, lbits = 0;                                      // 1: batched shape and interior, 2: an other edge, 4: a second one, 8: a site with edges
+    pg_i4 gl = {0, 0, 0, 0};
+    int kL = 1, kL3 = 1;
+    double lwA = 0, lwS = 0, lwT = 0;                              // log weights: the previous-site edge's, the other edge's, the second other edge's
     for (;;) {
         const int lo = cur.x, hi = cur.y;
         if (lo - 2 * wage - 4 - wbase >= wpos_n) wbase += wpos_n;
@@ -2686,59 +2741,84 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
         // the records and the shape of the lane's cell do not depend on the other waves: before the flags
         // (the row the lane will hold after the hand-over below)
         const int r = wr < lo ? wr + PW7L : wr, j = d - r;
+        // the left site, when the lane's row is new to it: the run's first step, a row that has just come into the band (a lane
+        // takes its next row at the hand-over, 448 rows on and far below the band; the records are there once the band is)
+        if (__any(r <= hi && r != lrow)) {
+            if (r <= hi && r != lrow) {
+                lrow = r;
+                gl = PM.recL[r & (PRW - 1)];
+                bool two, three;
+                const bool easy = site7<true>(gl, r, two, three, kL, kL3, lwA, lwS, lwT);
+                // interior, and no edge in reach starts at site 0 (where the gap-open term differs): the row's half
+                const bool in = r >= 2 && r <= Lx - 2 && r - kL >= 1 && r - kL3 >= 1;
+                lbits = (easy && in ? 1 : 0) | (two ? 2 : 0) | (three ? 4 : 0) | (r > 0 && ((gl.x >> PR_NE_SHIFT) & 127) > 0 ? 8 : 0);
+            }
+        }
         int kind = 0;                                           // 0 outside the band, 1 batched, 2 general rules
-        pg_i4 gl = {0, 0, 0, 0}, gr = {0, 0, 0, 0};
-        bool l2 = false, r2 = false, l3 = false, r3 = false;   // the site has an other edge / a second other edge (three edges: the third pass below)
-        int kL = 1, kR = 1, kL3 = 1, kR3 = 1;
-        double lwA = 0, lwS = 0, lwT = 0, rwA = 0, rwS = 0, rwT = 0;       // log weights: the previous-site edge's, the other edge's, the second other edge's
+        pg_i4 gr = {0, 0, 0, 0};
+        bool r2_ = false, r3_ = false;
+        int kR = 1, kR3 = 1;
+        double rwA = 0, rwS = 0, rwT = 0;
         double tM = 0, tX = 0;
         if (r <= hi) {
-            gl = PM.recL[r & (PRW - 1)]; gr = PM.recR[j & (PRW - 1)];
-            const int nl = (gl.x >> PR_NE_SHIFT) & 127, nr = (gr.x >> PR_NE_SHIFT) & 127;
-            // one site's edges: exactly one from the previous site, beside it none, one or two others (three edges: the third from
-            // the edge window, rare -- one site in a thousand at the top of cfg4's tree, but half of the root's wide diagonals hold one,
-            // and the general rules it used to take are a loop of single fetches)
-            auto shape = [&](auto left_tag, const pg_i4 &rec, int site, int n, bool &two, bool &three, int &k1, int &k3, double &wA, double &w1, double &w3) -> bool {
-                constexpr bool LEFT = decltype(left_tag)::value;
-                const int e0 = rec.y & 0xffff, e1 = (int)((unsigned)rec.y >> 16);
-                const double f0 = (double)__int_as_float(rec.z), f1 = (double)__int_as_float(rec.w);
-                two = false; three = false; k1 = 1; k3 = 1; wA = f0; w1 = 0.0; w3 = 0.0;
-                if (n == 1) return e0 == 1;
-                if (n == 2) {
-                    two = true;
-                    if (e0 == 1) { wA = f0; k1 = e1; w1 = f1; } else { wA = f1; k1 = e0; w1 = f0; }
-                    return (e0 == 1) != (e1 == 1);
-                }
-                if (n == 3) {
-                    int e2; double f2;
-                    edge_at<LEFT>(rec, 2, site, e2, f2);
-                    two = true; three = true;
-                    if (e0 == 1) { wA = f0; k1 = e1; w1 = f1; k3 = e2; w3 = f2; }
-                    else if (e1 == 1) { wA = f1; k1 = e0; w1 = f0; k3 = e2; w3 = f2; }
-                    else { wA = f2; k1 = e0; w1 = f0; k3 = e1; w3 = f1; }
-                    return ((e0 == 1) + (e1 == 1) + (e2 == 1)) == 1;
-                }
-                return false;
-            };
-            bool l2_, l3_, r2_, r3_;
-            const bool easyL = shape(std::true_type(), gl, r, nl, l2_, l3_, kL, kL3, lwA, lwS, lwT);
-            const bool easyR = shape(std::false_type(), gr, j, nr, r2_, r3_, kR, kR3, rwA, rwS, rwT);
-            // interior, and no edge in reach starts at site 0 (where the gap-open term differs)
-            const bool inner = r >= 2 && r <= Lx - 2 && j >= 2 && j <= Ly - 2 && r - kL >= 1 && j - kR >= 1 && r - kL3 >= 1 && j - kR3 >= 1;
-            kind = (easyL && easyR && inner && !(l3_ && r3_)) ? 1 : 2;
-            if (kind == 1) { l2 = l2_; r2 = r2_; l3 = l3_; r3 = r3_; }
-            if (r > 0 && j > 0 && nl > 0 && nr > 0) {
+            gr = PM.recR[j & (PRW - 1)];
+            // (three edges: the third from the edge window, rare -- one site in a thousand at the top of cfg4's tree, but half of the
+            // root's wide diagonals hold one, and the general rules it used to take are a loop of single fetches)
+            const bool easyR = site7<false>(gr, j, r2_, r3_, kR, kR3, rwA, rwS, rwT);
+            const bool in = j >= 2 && j <= Ly - 2 && j - kR >= 1 && j - kR3 >= 1;
+            kind = ((lbits & 1) && easyR && in && !((lbits & 4) && r3_)) ? 1 : 2;
+            if ((lbits & 8) && j > 0 && ((gr.x >> PR_NE_SHIFT) & 127) > 0) {
                 const int ti_ = ((gl.x & 0xffff) + __umul24(gr.x & 0xffff, S)) & 255;
                 tM = PM.tab2[ti_][0]; tX = PM.tab2[ti_][1];
             }
         }
+        const bool b1 = kind == 1;
+        // the site has an other edge / a second other edge (three edges: the third pass below) -- of batched cells only
+        const bool l2 = b1 && (lbits & 2), l3 = b1 && (lbits & 4), r2 = b1 && r2_, r3 = b1 && r3_;
         // the next diagonal's descriptor: staged by the loader (the window runs PLOOK diagonals ahead of the slowest wave)
         if (diags_ld < d + 2 && d + 1 < nd) diags_ld = POLLX(&PM.loaded[2], d + 2, 5);
         const pg_i4 nxt = PM.dring[(d + 1) & (PDR - 1)];
         const int amax = d - d0 < wage ? d - d0 : wage;               // ages 1 .. amax are in the wide ring
-        const int wsb = (d % wk) * wrow_bytes;
         const long long soff = ((long long)cur.w << 32) | (unsigned)cur.z;
         PG_GLOBAL char *srow = (PG_GLOBAL char *)sc_out + soff;
+        // The batched cells' other-edge operands: (r - kL, d - kL), (r - kL, d - kL - 1), (r, d - kR), (r - 1, d - kR - 1),
+        // (r - kL, d - kL - kR).  Where each lies follows from the records and the descriptor window alone: in the wide ring
+        // (o_off: its byte offset there; the -inf cell for a lane without it) or, older than the ring holds, in L2 (o_f).
+        // An L2 cell is at least wage + 1 >= 8 diagonals old or from before the run, and every wave has completed d - 3 by now,
+        // with all but its last three steps' stores retired: it has landed.  So the loads go out HERE, in front of the lock
+        // step, and are waited for behind it beside the ring reads.  (Ages here are >= 2: wcell's age 1 rule never applies.)
+        // Wave-uniform shortcuts: an operand no lane has is skipped, and no load is issued while every lane's lies in the ring.
+        const int null_off = (int)offsetof(PipeSmem, null_cell) - (int)offsetof(PipeSmem, sc);
+        int o_off[5] = {null_off, null_off, null_off, null_off, null_off};
+        FarAsk o_f[5] = {{false, 0}, {false, 0}, {false, 0}, {false, 0}, {false, 0}};
+        bool o_any[5] = {false, false, false, false, false};
+        unsigned long long o_q[5][3];
+        bool any_far = false;
+        if (__any(l2 || r2)) {
+            auto plan = [&](int t, bool need, int age, int p_) {
+                if (!__any(need)) return;
+                o_any[t] = true;
+                if (need) {
+                    if (age <= amax) {
+                        int rb = wsb - age * wrow_bytes;
+                        rb += rb < 0 ? wring_bytes : 0;
+                        o_off[t] = rb + wpos(p_) * 24;
+                    } else o_f[t] = far_ask(psc, d, age, p_);      // (need = false outside the band: the slot keeps -inf)
+                }
+            };
+            plan(0, l2, kL, r - kL);
+            plan(1, l2, kL + 1, r - kL);
+            plan(2, r2, kR, r);
+            plan(3, r2, kR + 1, r - 1);
+            plan(4, l2 && r2, kL + kR, r - kL);
+            any_far = __any(o_f[0].need || o_f[1].need || o_f[2].need || o_f[3].need || o_f[4].need);
+        }
+#if !defined(PG_WIDE7_FETCH_BEHIND) && !defined(PG_EXP_WIDE_SKIP)
+        if (any_far) {
+#pragma unroll
+            for (int t = 0; t < 5; ++t) far_issue(sc_out, o_f[t], o_q[t]);
+        }
+#endif
         {   // lock step: lanes 0..6 look at one wave's flag each -- the wave above has completed d-1, every wave d-2
             int spins = 0;
             for (;;) {
@@ -2761,6 +2841,7 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
             flag_store(&PM.wflag[w7], d);
             if (w7 < PNW) flag_store(&PM.progress[w7], d);
             ++d; lo_prev = lo;
+            wsb += wrow_bytes; wsb = wsb == wring_bytes ? 0 : wsb;
             if (d >= run_end || flag_load(&PM.abort_flag) != 0) break;
             cur.x = __builtin_amdgcn_readfirstlane(nxt.x); cur.y = __builtin_amdgcn_readfirstlane(nxt.y);
             cur.z = __builtin_amdgcn_readfirstlane(nxt.z); cur.w = __builtin_amdgcn_readfirstlane(nxt.w);
@@ -2771,13 +2852,16 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
             // (row-1, j) on d-1: lane T-1's cell, lane 0 from the wide ring; the band's first row of d-1 has no row above it in
             // the band (for lane 0 as well: the position it read is another row's alias -- wide_run has the story)
             int rb1 = wsb - wrow_bytes;
-            rb1 += rb1 < 0 ? wk * wrow_bytes : 0;
-            const double *c = (const double *)((const char *)&PM.sc[0][0][0] + rb1 + wpos(wr - 1) * 24);
+            rb1 += rb1 < 0 ? wring_bytes : 0;
+            const double *c = (const double *)((const char *)&PM.sc[0][0][0] + rb1 + (wqb != 0 ? wqb : wrow_bytes) - 24);
             const double ax = dpp_shr1(Px, c[PG_X]), ay = dpp_shr1(Py, c[PG_Y]), am = dpp_shr1(Pm, c[PG_M]);
             const bool top = wr == lo_prev;
             Ux = top ? NIw : ax; Uy = top ? NIw : ay; Um = top ? NIw : am;
             // row hand-over: the lane's next row (448 on: far below the band) starts from -inf
-            if (wr < lo) { wr += PW7L; Px = NIw; Py = NIw; Pm = NIw; Cx = NIw; Cy = NIw; Cm = NIw; Ux = NIw; Uy = NIw; Um = NIw; }
+            if (wr < lo) {
+                wqb += PW7L * 24; wqb -= wqb >= wrow_bytes ? wrow_bytes : 0; wqb -= wqb >= wrow_bytes ? wrow_bytes : 0;
+                wr += PW7L; Px = NIw; Py = NIw; Pm = NIw; Cx = NIw; Cy = NIw; Cm = NIw; Ux = NIw; Uy = NIw; Um = NIw;
+            }
         }
         // one operand cell (p, d - age): read from the wide ring, or -- not there -- what to ask L2 for; -inf outside the band
         auto wcell = [&](bool need, int age, int p_, pg_d2 &xy, double &m) -> FarAsk {
@@ -2797,38 +2881,30 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
             }
             return far_ask(psc, d, age, p_);
         };
-        pg_d2 o_xy[8];
-        double o_m[8];
-        FarAsk o_f[8];
-        bool any_far = false;
+        // the other-edge operands: the ring's rows are final now; an L2 cell replaces what the lane read (the -inf cell)
+        pg_d2 o_xy[5];
+        double o_m[5];
 #pragma unroll
-        for (int t = 0; t < 8; ++t) { o_f[t].need = false; o_f[t].boff = 0; o_xy[t].x = NIw; o_xy[t].y = NIw; o_m[t] = NIw; }
-        const bool b1 = kind == 1;
-        if (__any(b1 && (l2 || r2))) {
-            // the batched cells' other-edge operands.  Wave-uniform shortcuts: an operand is skipped when no lane has it, and
-            // while every lane's lies in the wide ring the reads are plain LDS reads (no L2 path, no branches)
-            auto rd = [&](bool need, int age, int p_, pg_d2 &xy, double &m) {
-                int rb = wsb - age * wrow_bytes;
-                rb += rb < 0 ? wk * wrow_bytes : 0;
-                const int off = need ? rb + wpos(p_) * 24 : (int)offsetof(PipeSmem, null_cell) - (int)offsetof(PipeSmem, sc);
-                const double *c = (const double *)((const char *)&PM.sc[0][0][0] + off);
-                xy.x = c[PG_X]; xy.y = c[PG_Y]; m = c[PG_M];
-            };
-            auto fetch = [&](int t, bool need, int age, int p_) {
-                if (!__any(need)) return;
-                if (!__any(need && age > amax)) rd(need, age, p_, o_xy[t], o_m[t]);
-                else { o_f[t] = wcell(need, age, p_, o_xy[t], o_m[t]); any_far = true; }     // (-inf for the lanes without it)
-            };
-            fetch(3, b1 && l2, kL, r - kL);
-            fetch(4, b1 && l2, kL + 1, r - kL);
-            fetch(5, b1 && r2, kR, r);
-            fetch(6, b1 && r2, kR + 1, r - 1);
-            fetch(7, b1 && l2 && r2, kL + kR, r - kL);
+        for (int t = 0; t < 5; ++t) {
+            o_xy[t].x = NIw; o_xy[t].y = NIw; o_m[t] = NIw;
+            if (o_any[t]) {
+                const double *c = (const double *)((const char *)&PM.sc[0][0][0] + o_off[t]);
+                o_xy[t].x = c[PG_X]; o_xy[t].y = c[PG_Y]; o_m[t] = c[PG_M];
+            }
         }
 #ifdef PG_PIPE_STATS
         const long long st_t2 = __builtin_readcyclecounter();
 #endif
-        if (any_far) far_fetch8(sc_out, o_f, o_xy, o_m);           // (requests and wait in one statement; nothing if no lane asked)
+        if (any_far) {
+#ifdef PG_WIDE7_FETCH_BEHIND                                       // A/B build: the requests behind the lock step, as before round 6
+#pragma unroll
+            for (int t = 0; t < 5; ++t) far_issue(sc_out, o_f[t], o_q[t]);
+#endif
+#pragma unroll
+            for (int t = 0; t < 5; ++t) {
+                if (o_f[t].need) { o_xy[t].x = __longlong_as_double((long long)o_q[t][0]); o_xy[t].y = __longlong_as_double((long long)o_q[t][1]); o_m[t] = __longlong_as_double((long long)o_q[t][2]); }
+            }
+        }
 #ifdef PG_PIPE_STATS
         const long long st_t3 = __builtin_readcyclecounter();
 #endif
@@ -2837,8 +2913,8 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
         double bx = NIw, by = NIw, bm = NIw;
         unsigned px = PG_BP_NONE, py = PG_BP_NONE, pm = PG_BP_NONE;
         if (kind == 1) {
-            const pg_d2 lx_ = o_xy[3], lm_ = o_xy[4], ry_ = o_xy[5], rm_ = o_xy[6], lr_ = o_xy[7];
-            const double lxm = o_m[3], lmm = o_m[4], rym = o_m[5], rmm = o_m[6], lrm = o_m[7];
+            const pg_d2 lx_ = o_xy[0], lm_ = o_xy[1], ry_ = o_xy[2], rm_ = o_xy[3], lr_ = o_xy[4];
+            const double lxm = o_m[0], lmm = o_m[1], rym = o_m[2], rmm = o_m[3], lrm = o_m[4];
             // scores only (pg_backptr derives the back-pointers); the reference's candidates with the maxima regrouped
             // (tools/gen_hot_asm.py); absent operands are -inf
             auto gapv = [&](double own, double other, double m_) { return __builtin_fmax(own + ge, __builtin_fmax(other, m_ + ng) + go); };
@@ -2903,12 +2979,13 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
                      bx, by, bm, px, py, pm);
         }
         if (wr < lo + wpos_n) {                                  // (a row that many past the band's first: never in the band, and its position is another row's)
-            double *o = (double *)((char *)&PM.sc[0][0][0] + wsb + wpos(wr) * 24);
+            double *o = (double *)((char *)&PM.sc[0][0][0] + wsb + wqb);
             o[PG_X] = bx; o[PG_Y] = by; o[PG_M] = bm;
         }
         if (__any(kind != 0 && ((gl.x | gr.x) & PR_SRC))) { if (kind != 0) hist_append(gl, gr, r, j, bx, by, bm); }
         if (wpos_n > PW7L && wr < lo + wpos_n - PW7L) {           // (512 positions, 448 lanes: the positions of the rows lo + 448 .. lo + 511 -- -inf,
-            double *o = (double *)((char *)&PM.sc[0][0][0] + wsb + wpos(wr + PW7L) * 24);      //  what a read above an older diagonal's band lands on)
+            int q_ = wqb + PW7L * 24; q_ -= q_ >= wrow_bytes ? wrow_bytes : 0;                //  what a read above an older diagonal's band lands on)
+            double *o = (double *)((char *)&PM.sc[0][0][0] + wsb + q_);
             o[PG_X] = NIw; o[PG_Y] = NIw; o[PG_M] = NIw;
         }
         {   // all but the stores of the last two steps have retired (this step's are issued behind the flag)
@@ -2937,6 +3014,7 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
         }
 #endif
         ++d;
+        wsb += wrow_bytes; wsb = wsb == wring_bytes ? 0 : wsb;
         lo_prev = lo;
         if (d >= run_end || flag_load(&PM.abort_flag) != 0) break;
         cur.x = __builtin_amdgcn_readfirstlane(nxt.x); cur.y = __builtin_amdgcn_readfirstlane(nxt.y);
