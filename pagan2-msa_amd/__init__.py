@@ -545,6 +545,18 @@ def debug_far(left, right, band=None):
     return n, hfl, hfr, hb, cls
 
 
+def debug_descriptors(left, right, band=None, n_states=15):
+    """Diagnostic (host only): the descriptor words pg_fill_pipe would read for this job under a model of n_states states, as an
+    int32 array [diagonals, 8] (include/pagan_dp.h has the layout); [0, 8] for a job the planner does not give to pg_fill_pipe."""
+    import numpy as np
+    nd = left.n_sites + right.n_sites - 3
+    words = np.zeros((nd, 8), np.int32)
+    n = lib().pagan_dp_debug_descriptors(C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None,
+                                         int(n_states), words.ctypes.data_as(C.POINTER(C.c_int32)), words.size)
+    _check(min(n, 0), "pagan_dp_debug_descriptors")
+    return words[:n]
+
+
 def debug_plan(left, right, band=None, with_lead=False):
     """Diagnostic (host only): (classes[Lx+Ly-1] uint8, [awake intervals of wave 0..3]) the banded fill kernel
     would be given for this job; with_lead adds the per-diagonal downstream-progress requirement."""

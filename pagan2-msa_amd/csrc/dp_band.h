@@ -1,4 +1,4 @@
-// dp_band.h -- host-side helpers shared by the C-ABI layers (dp_abi.hip, dp_fb.hip): graph validation,
+// dp_band.h -- host-side helpers shared by the C-ABI layers (dp_abi.hip, dp_plan.cpp, dp_fb.hip): graph validation,
 // the tunnel as a clamped row band, and its per-anti-diagonal form (the device's cell index).
 #pragma once
 #include <cstdint>
@@ -7,9 +7,10 @@
 #include "../../include/pagan_dp.h"
 #include "dp_device.h"
 
-namespace {
+// (an inline named namespace, not an unnamed one: HostJob of dp_plan.h holds a DiagIndex and is one type in two translation units)
+inline namespace pg_band {
 
-int check_graph(const pagan_graph *g) {
+inline int check_graph(const pagan_graph *g) {
     if (!g || g->n_sites < 2 || g->n_edges < 0 || !g->state || !g->bwd_off) return PAGAN_E_GRAPH;
     if (g->bwd_off[0] != 0) return PAGAN_E_GRAPH;
     for (int s = 0; s < g->n_sites; ++s) {
@@ -81,4 +82,4 @@ struct DiagIndex {
     }
 };
 
-} // namespace
+} // namespace pg_band

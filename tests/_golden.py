@@ -7,7 +7,9 @@ import numpy as np
 from pagan2_msa_amd import abi
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-NAMES = sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(HERE, "*.npz")))
+# (pipe_descriptors.npz is no alignment vector: tests/test_descriptors_cpu.py reads it)
+NAMES = sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(HERE, "*.npz"))
+               if os.path.basename(p) != "pipe_descriptors.npz")
 
 
 def load(name):

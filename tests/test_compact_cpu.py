@@ -1,4 +1,4 @@
-"""Host logic of the dead-site compaction (dp_abi.hip: CompactSide, compact_band) through the host-only
+"""Host logic of the dead-site compaction (dp_plan.cpp: CompactSide, compact_band) through the host-only
 diagnostic entry point: which sites go (no bwd edge, or bwd edges from such sites only -- the cascade), which always stay
 (start, end, the last site before the end), which edges are dropped and what position the kept ones had in the caller's
 lists, and how a band is re-indexed.  Checked against a brute-force restatement in Python."""
@@ -80,7 +80,7 @@ def test_cascade_and_edges_from_dead_sites():
 
 
 def test_staircase_predicate():
-    """When the tiled kernel's dataflow launch may order a tile behind its three neighbours only (dp_abi.hip: tiles_staircase)."""
+    """When the tiled kernel's dataflow launch may order a tile behind its three neighbours only (dp_plan.cpp: tiles_staircase)."""
     full = [(a, b) for a in range(5) for b in range(6)]
     assert pg.debug_tiles_staircase(full)
     band = [(a, b) for a in range(8) for b in range(max(0, a - 1), min(8, a + 3))]

@@ -1,4 +1,4 @@
-"""Far histories and three-edge sites in the banded kernel's plan (dp_abi.hip: plan_far_hist, classify_diagonals; round 5).
+"""Far histories and three-edge sites in the banded kernel's plan (dp_plan.cpp: plan_far_hist, classify_diagonals; round 5).
 No GPU: pagan_dp_debug_far is host code.  Invariants the kernel's hist_tail / third_pass rest on:
 
   * a served far site is an easy two-edge site whose other edge reaches REACH - 1 .. PG_HIST_MAX_SPAN sites back; its start site

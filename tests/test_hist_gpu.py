@@ -1,5 +1,5 @@
 """Far histories and the third pass of the banded kernel's hand-scheduled loop (tools/gen_hot_asm.py: hist_tail, third_pass;
-dp_abi.hip: plan_far_hist) against the oracle: banded jobs whose plan serves far sites from history lines and keeps three-edge
+dp_plan.cpp: plan_far_hist) against the oracle: banded jobs whose plan serves far sites from history lines and keeps three-edge
 sites in the lanes -- asserted on the plan, so that the comparison is about those paths.  pagan_batch_fetch also re-evaluates
 every cell from its stored predecessors (PG_FLAG_SCORE_CHECK): a wrong cell anywhere in the band fails the call."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""Host-side planner of the banded fill kernel (dp_abi.hip: classify_diagonals, schedule_waves) against a
+"""Host-side planner of the banded fill kernel (dp_plan.cpp: classify_diagonals, schedule_waves) against a
 brute-force restatement of its rules.  No GPU: pagan_dp_debug_plan is host code."""
 import numpy as np
 import pytest
@@ -236,7 +236,7 @@ def test_a_tile_with_too_many_edges_is_not_tiled():
 
 @pytest.mark.parametrize("seed", range(4))
 def test_plan_over_several_threads_is_the_plan(monkeypatch, seed):
-    """round 5: the plan of one alignment runs over ranges of diagonals on several host threads (dp_abi.hip, par_ranges; the
+    """round 5: the plan of one alignment runs over ranges of diagonals on several host threads (dp_plan.cpp, par_ranges; the
     sliding windows restart at a range's first diagonal).  Classes, wave schedules and ring-row reuse are those of one thread.
     Long jobs only: a range has at least 4096 diagonals."""
     rng = np.random.default_rng(700 + seed)

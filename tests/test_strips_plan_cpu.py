@@ -1,4 +1,4 @@
-"""Host logic of the row strips (dp_abi.hip: plan_strips), no device: the strips of a wide job cover every cell of the job
+"""Host logic of the row strips (dp_plan.cpp: plan_strips), no device: the strips of a wide job cover every cell of the job
 exactly once and put every score where the job's diagonal index has it; a strip's rows never fall from one diagonal to the
 next; strip k > 0 is fed by the compute wave above its first row; the general steps are the few the design names; the bound on
 a diagonal's multi-edge sites refuses dense jobs."""

@@ -187,7 +187,7 @@ def test_band_whose_tiles_are_no_staircase(pg, oracle):
 @pytest.mark.parametrize("p_dead", [0.06, 0.3, 0.6])
 def test_many_dead_sites(pg, oracle, monkeypatch, compact, p_dead):
     """Sites without bwd edges make whole rows / columns -inf; from 5 % on the library aligns the compacted graphs and maps
-    the path back (dp_abi.hip: CompactJob).  Full matrix, wide band and a narrow band (the banded kernel), edges that start
+    the path back (dp_plan.h: CompactJob).  Full matrix, wide band and a narrow band (the banded kernel), edges that start
     at dead sites included; with PAGAN_DP_COMPACT=0 the same inputs go through uncompacted."""
     if compact == "off":
         monkeypatch.setenv("PAGAN_DP_COMPACT", "0")

@@ -1,5 +1,5 @@
 """A second reading, in plain Python, of how the segmented traceback cuts a path (dp_kernels.hip: pg_trace_spec,
-pg_trace_compose; dp_abi.hip, validate_job: how many boundaries a job gets).  Restated from the code, never calling it:
+pg_trace_compose; dp_plan.cpp, validate_job: how many boundaries a job gets).  Restated from the code, never calling it:
 given the cells a path visits and the width of every anti-diagonal, `plan` says which segments pg_trace_compose must
 record, which cells one lane walks serially, and which exit every table entry on the path took.
 

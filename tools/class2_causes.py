@@ -1,4 +1,4 @@
-"""Diagnostic: why the diagonals of the bench workload's upper nodes are class 2 (dp_abi.hip, classify_diagonals):
+"""Diagnostic: why the diagonals of the bench workload's upper nodes are class 2 (dp_plan.cpp, classify_diagonals):
 a site that is not 'easy' (more than two edges / no previous-site edge) or operands beyond the ring's reach.  Needs the GPU."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
