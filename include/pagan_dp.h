@@ -345,6 +345,31 @@ int  pagan_fb_site_marginals_batch(int32_t n, pagan_fb *const *fbs, double *cons
 /* device time of the handle's last gather (path support / posterior cells), row pass and column pass, milliseconds; a batch's
  * passes are booked at the first handle that took part, 0 at the others                                                    */
 int  pagan_fb_post_ms(const pagan_fb *fb, double ms[3]);
+/* ---- expected transition and emission counts (dp_fb_counts.inc) ----------------------------------
+ * The posterior over the TRANSITIONS of a finished pass: the sufficient statistics of the pair model, each the derivative of
+ * log_fwd by the matching log parameter.  States X = 0, Y = 1, M = 2.  An arc is one term of the forward recurrence with the
+ * weight the forward sweep uses: into X(i, j) from (p, j, X / Y / M) over the left bwd edges p -> i with l_ext / l_open /
+ * l_ng + l_open; into Y(i, j) the mirror over the right edges; into M(i, j) from (p, q, M / X / Y) over the edge pairs with
+ * 2 l_ng / l_ng / l_ng, plus ltab[a, b] + lwL + lwR.  Its share is exp(F[pred] + log w + B[cell] - log_fwd), the argument
+ * clamped to <= 0; 0 where F or B is -inf, where the predecessor is outside the band, and everywhere when log_fwd is -inf.
+ *   trans[3 * from + to]   the sum of the shares of all arcs from a cell of state `from` into a cell of state `to`;
+ *   trans[9], [10], [11]   the end transitions X-close, Y-close, M-end: exp(F[cell] + log w - log_fwd) over the terms of the
+ *                          forward end corner, each as often as that corner visits it (M-end: l_ng + lwL + lwR; a close: 0);
+ *                          they sum to 1 unless the full probability is 0;
+ *   emit[a + b * S]        (the score table's layout) the sum of post(M, i, j) over the in-band cells with i, j >= 1,
+ *                          state_left[i] = a, state_right[j] = b.  Provided for n_states <= 32 (DNA); the protein and codon
+ *                          tables are not: emit non-NULL on a larger model is PAGAN_E_ARG.  emit may be NULL.
+ * The sums are taken without atomics in a fixed order: two runs give the same bits, and a batch gives the bits of one call per
+ * pair.  F and B of any sweep schedule are read alike.  All handles of a batch are on one device; the calling thread is put on
+ * it and restored on exit.  PAGAN_E_ARG (before any device call): a NULL handle or trans, handles of different devices, emit
+ * with n_states > 32.                                                                                                       */
+int  pagan_fb_expected_counts(pagan_fb *fb, double trans[12], double *emit /* [S*S] or NULL */);
+/* trans: n pointers; emit: NULL or n pointers, any entry NULL.  One launch of pg_fb_counts serves the batch.                 */
+int  pagan_fb_expected_counts_batch(int32_t n, pagan_fb *const *fbs, double *const *trans, double *const *emit);
+/* device time of the handle's last counts pass (both launches), milliseconds: booked at the batch's first pair, 0 at the others */
+int  pagan_fb_counts_ms(const pagan_fb *fb, double *ms);
+/* Host only: the device bytes one pair's counts pass takes beside the pair itself (the row blocks' partial sums, the result) */
+int64_t pagan_fb_counts_predict_bytes(int32_t left_sites, int32_t right_sites, int32_t n_states);
 /* Host only: the device bytes pagan_fb_run takes for a pair (F and B at 24 B a cell each, the diagonals' index, the lists);
  * an estimate from above as far as the lists go (four edges a site).  A caller cuts a level's pairs into batches by it.      */
 int64_t pagan_fb_predict_bytes(int32_t left_sites, int32_t right_sites, const pagan_band *band);

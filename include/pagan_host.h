@@ -153,6 +153,33 @@ int     pagan_msa_set_sampler(pagan_msa *m, int32_t on_device);
  * a band whose full probability is 0 retried without the band.  Together with sample_path: PAGAN_E_ARG at align time; with the
  * test seam: PAGAN_E_NODEVICE.  gap_weight: a finite double >= 0 (0.5: a residue counts once).  Call before aligning.           */
 int     pagan_msa_set_decoder(pagan_msa *m, int32_t on, double gap_weight);
+/* Expected counts in the walk (a setter: pagan_msa_opts does not grow).  on = 1: wherever a node's forward/backward pass runs
+ * (full_probability, sample_path, the decoder) the node also keeps pagan_fb_expected_counts' trans[12] and, for DNA, emit[S * S]
+ * (pagan_dp.h); a sub-batch's counts are taken in one pagan_fb_expected_counts_batch before its matrices are released, and the
+ * device time is added to pagan_msa_node_fb's out[3] at the sub-batch's first node.  Without any such pass: PAGAN_E_ARG at align
+ * time.  Nothing else of the walk changes.  Call before aligning.                                                              */
+int     pagan_msa_set_counts(pagan_msa *m, int32_t on);
+/* node_counts (pagan_msa_set_counts): trans[12]; emit[S * S] or NULL (protein and codon walks keep no table: emit non-NULL is
+ * PAGAN_E_ARG there).  PAGAN_E_ARG for a node this process did not align, as for the support.                                 */
+int     pagan_msa_node_counts(const pagan_msa *m, int32_t k, double *trans, double *emit);
+/* The indel model of the walk, the reference's --ins-rate, --del-rate, --gap-extension, --end-gap-extension (settings.cpp:216-218,
+ * 266-267): the values replace the data type's defaults (DNA 0.01 / 0.01 / 0.8 / 0.95, protein 0.05 / 0.05 / 0.5 / 0.75, codon
+ * 0.01 / 0.01 / 0.5 / 0.75) in both model views -- gap_open = t = 1 - exp(-0.5 (ins + del) dist), non_gap = 1 - 2 t at a node's
+ * distance --; a negative value keeps the default; pileup_rates still replaces the two rates where it applies.  gap_ext and
+ * end_gap_ext are probabilities in (0, 1).  Call before aligning (after: PAGAN_E_ARG).  Rates that give 1 - 2 t <= 0 at some
+ * internal node's distance: PAGAN_E_ARG at align time.                                                                         */
+int     pagan_msa_set_indel_model(pagan_msa *m, double ins_rate, double del_rate, double gap_ext, double end_gap_ext);
+/* Host only, plain arithmetic: an indel rate and a gap extension probability from n nodes' distances dist[n] (the sum of the two
+ * child branches) and expected counts trans[n][12] -- "align, count, refit, realign".
+ *   gap_ext    = (n_XX + n_YY) / (n_XX + n_YY + n_XY + n_YX + n_XM + n_YM + n_Xend + n_Yend): the share of the steps out of a gap
+ *                cell that stay in the gap; 0 when no step out of a gap cell was counted.
+ *   indel_rate = r / 2, r = ins + del the maximiser of sum_k O_k log t_k + S_k log(1 - 2 t_k), t_k = 1 - exp(-0.5 r d_k),
+ *                O_k = n_MX + n_MY, S_k = n_MM + n_Mend, found by bisection on the derivative over 0 < r d_max < 2 ln 2 to
+ *                1e-13 relative (one node: t = O / (2 (O + S))); 0 when no node has dist > 0 and O + S > 0, or when every O is 0.
+ * A moment / pseudo-likelihood estimate: the reference's weights out of a gap state do not sum to 1 (gap_ext + gap_open + the
+ * close's 1), so this is NOT a maximum-likelihood fit of the model as scored, and no accuracy is claimed.  A negative or
+ * non-finite count or distance: PAGAN_E_ARG.                                                                                   */
+int     pagan_fit_indel(int32_t n, const double *dist, const double *trans, double *indel_rate, double *gap_ext);
 int  pagan_msa_n_internal(const pagan_msa *m);
 int  pagan_msa_node_info(const pagan_msa *m, int32_t k, pagan_node_info *out);
 /* Borrowed views (valid until pagan_msa_destroy) of what node k's alignment consumed and

@@ -96,6 +96,7 @@ class FullProbability:
         fb.sample_path(u)               Result with the shape of a Viterbi result
         fb.sample_paths(seed, node, K)  K paths drawn on the device (SampledPaths)
         fb.decode(gap_weight)           the maximum expected accuracy path (DecodedPath)
+        fb.expected_counts()            expected transition, end and emission counts (pg_fb_counts)
     """
 
     def __init__(self, left, right, model_prob, band=None, device=-1, _handle=None):
@@ -184,6 +185,17 @@ class FullProbability:
         """pagan_fb_decode: the maximum expected accuracy path of the pair's posteriors (cell weight: the posterior, times
         gap_weight in a gap state), found on the device.  Returns a DecodedPath."""
         return decode_batch([self], gap_weight, keep_matrix)[0]
+
+    def expected_counts(self, emissions=True):
+        """pagan_fb_expected_counts: {"trans": [3, 3] (from, to over X, Y, M), "end": [3] (X-close, Y-close, M-end),
+        "emit": [S, S] (left state, right state) or None}, summed on the device.  emissions=True needs n_states <= 32."""
+        return expected_counts_batch([self], emissions)[0]
+
+    def counts_ms(self):
+        """Device ms of the handle's last counts pass, booked at the batch's first pair."""
+        ms = C.c_double()
+        _check(self._L.pagan_fb_counts_ms(self._h, C.byref(ms)), "pagan_fb_counts_ms")
+        return ms.value
 
     def close(self):
         if self._h:
@@ -496,6 +508,33 @@ def site_marginals_batch(fbs, rows=True, columns=True):
     handles = (C.c_void_p * n)(*[fb._h for fb in fbs])
     _check(L.pagan_fb_site_marginals_batch(n, handles, *args), "pagan_fb_site_marginals_batch")
     return out
+
+
+def expected_counts_batch(fbs, emissions=True):
+    """pagan_fb_expected_counts_batch over FullProbability handles of one device (one launch of pg_fb_counts): a list of dicts
+    as FullProbability.expected_counts returns.  emissions: one switch for all pairs, or one per pair."""
+    import numpy as np
+    L = lib()
+    n = len(fbs)
+    f64p = C.POINTER(C.c_double)
+    want = [bool(emissions)] * n if isinstance(emissions, (bool, int)) else [bool(e) for e in emissions]
+    assert len(want) == n
+    trans = [np.zeros(12, np.float64) for _ in fbs]
+    emit = [np.zeros(fb.model.n_states ** 2, np.float64) if w else None for fb, w in zip(fbs, want)]
+    tp = (f64p * n)(*[t.ctypes.data_as(f64p) for t in trans])
+    ep = (f64p * n)(*[(e.ctypes.data_as(f64p) if e is not None else f64p()) for e in emit])
+    handles = (C.c_void_p * n)(*[fb._h for fb in fbs])
+    _check(L.pagan_fb_expected_counts_batch(n, handles, tp, ep), "pagan_fb_expected_counts_batch")
+    out = []
+    for k, fb in enumerate(fbs):
+        S = fb.model.n_states
+        out.append({"trans": trans[k][:9].reshape(3, 3).copy(), "end": trans[k][9:].copy(),
+                    "emit": emit[k].reshape(S, S).T.copy() if want[k] else None})      # emit[a + b * S] -> [a, b]
+    return out
+
+
+def fb_counts_predict_bytes(left_sites, right_sites, n_states):
+    return lib().pagan_fb_counts_predict_bytes(left_sites, right_sites, n_states)
 
 
 def path_cells(cols):

@@ -263,6 +263,14 @@ def declare(lib):
     lib.pagan_fb_site_marginals_batch.restype = C.c_int
     lib.pagan_fb_post_ms.argtypes = [C.c_void_p, f64p]
     lib.pagan_fb_post_ms.restype = C.c_int
+    lib.pagan_fb_expected_counts.argtypes = [C.c_void_p, f64p, f64p]
+    lib.pagan_fb_expected_counts.restype = C.c_int
+    lib.pagan_fb_expected_counts_batch.argtypes = [C.c_int32, C.POINTER(C.c_void_p), f64pp, f64pp]
+    lib.pagan_fb_expected_counts_batch.restype = C.c_int
+    lib.pagan_fb_counts_ms.argtypes = [C.c_void_p, f64p]
+    lib.pagan_fb_counts_ms.restype = C.c_int
+    lib.pagan_fb_counts_predict_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.pagan_fb_counts_predict_bytes.restype = C.c_int64
     lib.pagan_fb_predict_bytes.argtypes = [C.c_int32, C.c_int32, bp]
     lib.pagan_fb_predict_bytes.restype = C.c_int64
     lib.pagan_sample_uniforms.argtypes = [C.c_uint64, C.c_int32, C.c_int32, f64p]
@@ -324,4 +332,5 @@ EXPORTED = ["pagan_dp_align", "pagan_dp_align_batch", "pagan_result_free", "paga
             "pagan_fb_samples_visited_all", "pagan_fb_samples_result", "pagan_fb_samples_ms", "pagan_fb_sample_predict_bytes", "pagan_fb_samples_destroy",
             "pagan_fb_decode_batch", "pagan_fb_decode", "pagan_fb_decoded_summary", "pagan_fb_decoded_visited", "pagan_fb_decoded_result",
             "pagan_fb_decoded_dump", "pagan_fb_decoded_ms", "pagan_fb_debug_decode_route", "pagan_fb_decode_predict_bytes", "pagan_fb_decoded_destroy",
+            "pagan_fb_expected_counts", "pagan_fb_expected_counts_batch", "pagan_fb_counts_ms", "pagan_fb_counts_predict_bytes",
             "pagan_fb_destroy", "pagan_dp_version"]

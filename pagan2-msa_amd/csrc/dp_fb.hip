@@ -487,6 +487,7 @@ __global__ __launch_bounds__(FB_RG_THREADS) void pg_fb_backward_ring(const PgFbJ
 
 #include "dp_fb_deep.inc"
 #include "dp_fb_post.inc"
+#include "dp_fb_counts.inc"
 #include "dp_fb_sample.inc"
 #include "dp_fb_decode.inc"
 
@@ -1020,6 +1021,7 @@ struct pagan_fb {
     PgFbJob job{};                                      // the pair's job record (device pointers into the arena) ...
     const PgFbJob *d_job = nullptr;                     // ... and where it sits on the device
     float post_ms[3] = {0, 0, 0};                       // last pg_fb_gather, row pass, column pass (HIP events)
+    float counts_ms = 0;                                // last pg_fb_counts + pg_fb_counts_fold (booked at a batch's first pair)
     long long at(int i, int j) const { return dx.at(i, j); }
 };
 
@@ -1792,6 +1794,84 @@ static int fb_marginals(int32_t n, pagan_fb *const *fbs, void *const *const o[8]
     return PAGAN_OK;
 }
 
+// The expected counts of n handles of one device: pg_fb_counts over (work items of the longest pair, pairs), then pg_fb_counts_fold,
+// one workgroup a pair.  One buffer: the job records, the count records, the pairs' work items, then per pair the result and the
+// work items' partial sums.
+static size_t fb_counts_stride(const pagan_fb *fb, bool emit) { return 9 + (emit ? (size_t)fb->S * fb->S : 0); }
+// A pair's work items (first row of a row block, first diagonal, last diagonal + 1): per block of FB_CN_ROWS rows the diagonals that
+// hold a cell of the block -- for a monotone band imin and imax never fall (dp_band.h) --, in segments of FB_CN_SEG
+static void fb_counts_items(const pagan_fb *fb, std::vector<int> *items) {
+    const DiagIndex &dx = fb->dx;
+    const int nd = fb->Lx + fb->Ly - 1;
+    int d0 = 0, d1 = 0;
+    for (int r0 = 0; r0 < fb->Lx; r0 += FB_CN_ROWS) {
+        const int r1 = std::min(fb->Lx, r0 + FB_CN_ROWS) - 1;
+        while (d0 < nd && dx.imax[d0] < r0) ++d0;                  // the first diagonal whose last row is >= r0
+        d1 = std::max(d1, d0);
+        while (d1 < nd && dx.imin[d1] <= r1) ++d1;                 // the first diagonal whose first row is > r1
+        for (int d = d0; d < d1; d += FB_CN_SEG) { items->push_back(r0); items->push_back(d); items->push_back(std::min(d + FB_CN_SEG, d1)); }
+    }
+}
+static int fb_counts(int32_t n, pagan_fb *const *fbs, double *const *trans, double *const *emit) {
+    if (n < 0 || (n > 0 && (!fbs || !trans))) return PAGAN_E_ARG;
+    for (int k = 0; k < n; ++k) {
+        if (!fbs[k] || !trans[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
+        if (emit && emit[k] && fbs[k]->S > FB_CN_MAXS) return PAGAN_E_ARG;
+    }
+    if (n == 0) return PAGAN_OK;
+    FbDeviceScope on_device(fbs[0]->device);
+    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    size_t cur = 0;
+    auto take = [&](size_t bytes) { const size_t at = cur; cur = (cur + bytes + 255) / 256 * 256; return at; };
+    const size_t o_jobs = take((size_t)n * sizeof(PgFbJob)), o_recs = take((size_t)n * sizeof(PgFbCounts));
+    std::vector<std::vector<int>> items(n);
+    std::vector<size_t> o_items(n), o_out(n), o_part(n);
+    int widest = 0;
+    size_t lds = 0;
+    for (int k = 0; k < n; ++k) {
+        fb_counts_items(fbs[k], &items[k]);
+        o_items[k] = take(4 * items[k].size());
+        widest = std::max(widest, (int)(items[k].size() / 3));
+        if (emit && emit[k]) lds = std::max(lds, 8 * (size_t)FB_CN_ROWS * fbs[k]->S);
+    }
+    const size_t in_bytes = cur;
+    for (int k = 0; k < n; ++k) o_out[k] = take(8 * (fb_counts_stride(fbs[k], emit && emit[k]) + 3));   // the results: they come back in one copy
+    const size_t out_end = cur;
+    for (int k = 0; k < n; ++k) o_part[k] = take(8 * fb_counts_stride(fbs[k], emit && emit[k]) * (items[k].size() / 3));
+    std::vector<char> host(out_end, 0);
+    FbDevBuf buf;
+    FbEvent e0, e1;
+    FB_DO(buf.alloc(cur));
+    for (int k = 0; k < n; ++k) {
+        PgFbCounts R;
+        R.part = (double *)(buf.h + o_part[k]); R.out = (double *)(buf.h + o_out[k]);
+        R.items = (const int *)(buf.h + o_items[k]); R.n_items = (int)(items[k].size() / 3); R.emit = emit && emit[k] ? 1 : 0;
+        std::memcpy(host.data() + o_jobs + k * sizeof(PgFbJob), &fbs[k]->job, sizeof(PgFbJob));
+        std::memcpy(host.data() + o_recs + k * sizeof(PgFbCounts), &R, sizeof(R));
+        if (!items[k].empty()) std::memcpy(host.data() + o_items[k], items[k].data(), 4 * items[k].size());
+    }
+    FB_TRY(hipMemcpy(buf, host.data(), in_bytes, hipMemcpyHostToDevice));
+    FB_DO(e0.create()); FB_DO(e1.create());
+    const PgFbJob *jobs = (const PgFbJob *)(buf.h + o_jobs);
+    const PgFbCounts *recs = (const PgFbCounts *)(buf.h + o_recs);
+    FB_TRY(hipEventRecord(e0, nullptr));
+    if (widest > 0) {
+        hipLaunchKernelGGL(pg_fb_counts, dim3((unsigned)widest, (unsigned)n), dim3(FB_CN_ROWS), lds, nullptr, jobs, recs);
+        FB_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(pg_fb_counts_fold, dim3((unsigned)n), dim3(256), 0, nullptr, jobs, recs);
+    FB_TRY(hipGetLastError());
+    FB_TRY(hipEventRecord(e1, nullptr));
+    FB_TRY(hipMemcpy(host.data() + in_bytes, buf.h + in_bytes, out_end - in_bytes, hipMemcpyDeviceToHost));
+    for (int k = 0; k < n; ++k) fbs[k]->counts_ms = 0.0f;
+    (void)hipEventElapsedTime(&fbs[0]->counts_ms, e0, e1);
+    for (int k = 0; k < n; ++k) {
+        std::memcpy(trans[k], host.data() + o_out[k], 8 * 12);
+        if (emit && emit[k]) std::memcpy(emit[k], host.data() + o_out[k] + 8 * 12, 8 * (size_t)fbs[k]->S * fbs[k]->S);
+    }
+    return PAGAN_OK;
+}
+
 static uint64_t fb_splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -1855,6 +1935,33 @@ int pagan_fb_post_ms(const pagan_fb *fb, double ms[3]) {
     if (!fb || !ms) return PAGAN_E_ARG;
     for (int k = 0; k < 3; ++k) ms[k] = fb->post_ms[k];
     return PAGAN_OK;
+}
+
+// Expected transition and emission counts (dp_fb_counts.inc; include/pagan_dp.h has the definitions).
+int pagan_fb_expected_counts_batch(int32_t n, pagan_fb *const *fbs, double *const *trans, double *const *emit) {
+    return fb_counts(n, fbs, trans, emit);
+}
+
+int pagan_fb_expected_counts(pagan_fb *fb, double trans[12], double *emit) {
+    if (!fb || !trans) return PAGAN_E_ARG;
+    return fb_counts(1, &fb, &trans, &emit);
+}
+
+int pagan_fb_counts_ms(const pagan_fb *fb, double *ms) {
+    if (!fb || !ms) return PAGAN_E_ARG;
+    *ms = fb->counts_ms;
+    return PAGAN_OK;
+}
+
+// What fb_counts allocates for a pair, from above: a row block of 64 rows crosses at most right_sites + 62 diagonals, in segments
+// of FB_CN_SEG (a tunnel's row block crosses far fewer); per work item the partial sums (8 B an entry) and 12 B of the item
+// itself, then the result and the two records.
+int64_t pagan_fb_counts_predict_bytes(int32_t left_sites, int32_t right_sites, int32_t n_states) {
+    if (left_sites < 2 || right_sites < 2 || n_states < 1) return PAGAN_E_ARG;
+    const int64_t stride = 9 + (n_states <= FB_CN_MAXS ? (int64_t)n_states * n_states : 0);
+    const int64_t nb = ((int64_t)left_sites - 1 + FB_CN_ROWS - 1) / FB_CN_ROWS;
+    const int64_t segs = ((int64_t)right_sites - 1 + FB_CN_ROWS - 1 + FB_CN_SEG - 1) / FB_CN_SEG;
+    return (8 * stride + 12) * nb * segs + 8 * (stride + 3) + (int64_t)sizeof(PgFbJob) + (int64_t)sizeof(PgFbCounts) + 5 * 256;
 }
 
 // What fb_stage's arena takes: F and B (24 B a cell each), the per-diagonal index and plan (20 B a diagonal), the graphs' lists

@@ -136,6 +136,10 @@ struct NodeWork {                // everything one internal node's alignment con
     // posterior decoding (pagan_msa_set_decoder): the node's result is the replay of its maximum expected accuracy path
     bool has_dec = false;
     double dec_objective = 0, dec_steps = 0, dec_ms = 0;   // dec_ms: the sub-batch's fill + trace, booked at its first node
+    // expected counts (pagan_msa_set_counts): pagan_fb_expected_counts' trans[12] and, for DNA, emit[S * S]
+    bool has_counts = false;
+    double trans[12] = {0};
+    std::vector<double> emit;
 };
 
 } // namespace
@@ -166,6 +170,8 @@ struct pagan_msa {
     int sample_on_device = 0;            // pagan_msa_set_sampler: sample_path's paths come from pg_fb_sample (1) or the host's walk (0)
     int decode_on = 0;                   // pagan_msa_set_decoder: the nodes' results are their posteriors' maximum expected accuracy paths
     double decode_gap = 0.5;             // ... with this gap weight
+    bool indel_set = false;              // pagan_msa_set_indel_model replaced a rate of the data type's defaults
+    int counts_on = 0;                   // pagan_msa_set_counts: every forward/backward pass also leaves the node's expected counts
     std::atomic<int> parents_built{0};   // parent graphs this process has built (pagan_msa_parents_built)
     std::atomic<int> lazy_err{0};        // first error of a deferred parent build (an imported result that does not fit the child graphs)
     bool rows_built = false;             // m->rows are valid (pagan_msa_finish builds them at once, pagan_msa_finish_lazy on first use)
@@ -258,6 +264,7 @@ int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads,
                 need += more;
             } else
             if (sample && m->sample_on_device) need += pagan_fb_sample_predict_bytes(w.gl.n_sites, w.gr.n_sites, 1, 0);    // (the path's trace)
+            if (m->counts_on) need += pagan_fb_counts_predict_bytes(w.gl.n_sites, w.gr.n_sites, m->mf.S);
             if (need > budget) return PAGAN_E_MEMCAP;
             if (!which.empty() && used + need > budget) break;
             used += need;
@@ -347,10 +354,31 @@ int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads,
             rc = pagan_fb_site_marginals_batch(n, fbs.data(), pd[0].data(), pd[1].data(), pi[0].data(), pd[2].data(),
                                                pd[3].data(), pd[4].data(), pi[1].data(), pd[5].data());
         }
+        double cnt_ms = 0;
+        for (int q = 0; q < n; ++q) m->work[which[q]].has_counts = false;
+        if (rc == PAGAN_OK && m->counts_on) {
+            // one launch for the sub-batch, before the matrices are released; the emission table for DNA only
+            const bool em = m->mf.type == kDna;
+            std::vector<pagan_fb *> cf;
+            std::vector<double *> ct, ce;
+            for (int q = 0; q < n; ++q) {
+                if (again[q]) continue;
+                NodeWork &w = m->work[which[q]];
+                w.emit.assign(em ? (size_t)m->mf.S * m->mf.S : 0, 0.0);
+                cf.push_back(fbs[q]); ct.push_back(w.trans); ce.push_back(em ? w.emit.data() : nullptr);
+            }
+            if (!cf.empty()) {
+                rc = pagan_fb_expected_counts_batch((int32_t)cf.size(), cf.data(), ct.data(), ce.data());
+                if (rc == PAGAN_OK) rc = pagan_fb_counts_ms(cf[0], &cnt_ms);
+            }
+            for (int q = 0; q < n; ++q) m->work[which[q]].has_counts = rc == PAGAN_OK && !again[q];
+        }
+        bool first_kept = true;
         for (int q = 0; q < n; ++q) {
             NodeWork &w = m->work[which[q]];
             double ms[3] = {0, 0, 0};
             if (rc == PAGAN_OK && pagan_fb_post_ms(fbs[q], ms) == PAGAN_OK) w.fb_post_ms = ms[0] + ms[1] + ms[2] + (q == 0 ? smp_ms : 0.0);
+            if (rc == PAGAN_OK && !again[q] && first_kept) { w.fb_post_ms += cnt_ms; first_kept = false; }
             pagan_fb_samples_destroy(smp[q]);
             pagan_fb_decoded_destroy(dec[q]);
             w.has_fb = rc == PAGAN_OK && !again[q];
@@ -919,6 +947,21 @@ int64_t node_cost_estimate(const pagan_msa *m, int id) {
     return m->opts.use_anchors ? (lx + ly) * (int64_t)(2 * m->opts.anchors_offset + 16) : lx * ly;
 }
 
+// pagan_msa_set_indel_model: the rates give a positive non-gap probability 1 - 2 t, t = 1 - exp(-0.5 (ins + del) dist), at every
+// internal node's distance (the float expressions of ModelFactory::alignment_model)
+bool indel_model_fits(const pagan_msa *m) {
+    if (!m->indel_set) return true;
+    const bool pileup = m->opts.pileup_rates != 0;
+    const float ins = pileup ? 0.25f : m->mf.ins_rate, del = pileup ? 0.25f : m->mf.del_rate;
+    for (const TreeNode &t : m->tree) {
+        if (t.left < 0 || t.right < 0) continue;
+        const double dist = m->tree[t.left].dist + m->tree[t.right].dist;
+        const double tt = 1.0 - std::exp(-0.5 * (ins + del) * dist);
+        if (!(1.0 - 2 * tt > 0.0)) return false;
+    }
+    return true;
+}
+
 } // namespace
 
 extern "C" {
@@ -946,6 +989,8 @@ int64_t pagan_msa_node_cost(const pagan_msa *m, int32_t id) {
 int pagan_msa_align_nodes(pagan_msa *m, int32_t n_ids, const int32_t *ids) {
     if (!m || m->aligned || n_ids < 0 || (n_ids > 0 && !ids)) return PAGAN_E_ARG;
     if (m->decode_on && m->opts.sample_path) return PAGAN_E_ARG;        // (a node has one path: the decoded one or a sampled one)
+    if (m->counts_on && !(m->opts.full_probability || m->opts.sample_path || m->decode_on)) return PAGAN_E_ARG;   // (no pass to take the counts from)
+    if (!indel_model_fits(m)) return PAGAN_E_ARG;
     if (m->backend && (m->opts.full_probability || m->opts.sample_path || m->decode_on)) return PAGAN_E_NODEVICE;   // (the seam has no forward/backward pass: never skipped silently)
     for (int k = 0; k < n_ids; ++k)
         if (ids[k] < m->n_leaves || ids[k] >= 2 * m->n_leaves - 1 || !node_ready(m, ids[k])) return PAGAN_E_ARG;
@@ -1016,6 +1061,8 @@ int pagan_msa_parents_built(const pagan_msa *m) { return m ? m->parents_built.lo
 int pagan_msa_align(pagan_msa *m) {
     if (!m || m->aligned) return PAGAN_E_ARG;
     if (m->decode_on && m->opts.sample_path) return PAGAN_E_ARG;
+    if (m->counts_on && !(m->opts.full_probability || m->opts.sample_path || m->decode_on)) return PAGAN_E_ARG;   // (no pass to take the counts from)
+    if (!indel_model_fits(m)) return PAGAN_E_ARG;
     if (m->backend && (m->opts.full_probability || m->opts.sample_path || m->decode_on)) return PAGAN_E_NODEVICE;
     int ndev = m->opts.n_devices;
     int first_dev = m->opts.first_device;
@@ -1231,6 +1278,16 @@ int pagan_msa_node_decode(const pagan_msa *m, int32_t k, double out[3]) {
     if (!m || !out || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_dec) return PAGAN_E_ARG;
     const NodeWork &w = m->work[k];
     out[0] = w.dec_objective; out[1] = w.dec_steps; out[2] = w.dec_ms;
+    return PAGAN_OK;
+}
+
+// ... and the expected counts (pagan_msa_set_counts): trans[12], emit[S * S] (DNA; NULL: not wanted)
+int pagan_msa_node_counts(const pagan_msa *m, int32_t k, double *trans, double *emit) {
+    if (!m || !trans || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_fb || !m->work[k].has_counts) return PAGAN_E_ARG;
+    const NodeWork &w = m->work[k];
+    if (emit && w.emit.empty()) return PAGAN_E_ARG;                 // (protein and codon tables: not provided)
+    std::memcpy(trans, w.trans, sizeof(w.trans));
+    if (emit) std::memcpy(emit, w.emit.data(), 8 * w.emit.size());
     return PAGAN_OK;
 }
 
@@ -1586,6 +1643,68 @@ int pagan_msa_set_sampler(pagan_msa *m, int32_t on_device) {
 int pagan_msa_set_decoder(pagan_msa *m, int32_t on, double gap_weight) {
     if (!m || (on != 0 && on != 1) || !(gap_weight >= 0.0) || !(gap_weight < HUGE_VAL)) return PAGAN_E_ARG;
     m->decode_on = on; m->decode_gap = gap_weight;
+    return PAGAN_OK;
+}
+
+int pagan_msa_set_counts(pagan_msa *m, int32_t on) {
+    if (!m || (on != 0 && on != 1)) return PAGAN_E_ARG;
+    m->counts_on = on;
+    return PAGAN_OK;
+}
+
+// Before aligning: a negative value keeps the data type's default.  Both model views follow (ModelFactory::alignment_model reads
+// these fields); pileup_rates still replaces the two rates where it applies.
+int pagan_msa_set_indel_model(pagan_msa *m, double ins_rate, double del_rate, double gap_ext, double end_gap_ext) {
+    if (!m || m->aligned || m->rounds > 0) return PAGAN_E_ARG;
+    if (ins_rate != ins_rate || del_rate != del_rate || gap_ext != gap_ext || end_gap_ext != end_gap_ext) return PAGAN_E_ARG;
+    if (gap_ext >= 1.0 || gap_ext == 0.0 || end_gap_ext >= 1.0 || end_gap_ext == 0.0) return PAGAN_E_ARG;   // (a probability in (0, 1))
+    if ((ins_rate >= 0 || del_rate >= 0) && !((ins_rate >= 0 ? (float)ins_rate : m->mf.ins_rate) + (del_rate >= 0 ? (float)del_rate : m->mf.del_rate) > 0.0f)) return PAGAN_E_ARG;
+    if (ins_rate >= 0) { m->mf.ins_rate = (float)ins_rate; m->indel_set = true; }
+    if (del_rate >= 0) { m->mf.del_rate = (float)del_rate; m->indel_set = true; }
+    if (gap_ext > 0) m->mf.ext_prob = (float)gap_ext;
+    if (end_gap_ext > 0) m->mf.end_ext_prob = (float)end_gap_ext;
+    std::lock_guard<std::mutex> g(m->mu);
+    m->model_cache.clear();
+    return PAGAN_OK;
+}
+
+// A moment / pseudo-likelihood estimate of the indel model from the nodes' expected counts (include/pagan_host.h).
+int pagan_fit_indel(int32_t n, const double *dist, const double *trans, double *indel_rate, double *gap_ext) {
+    if (n < 0 || (n > 0 && (!dist || !trans)) || !indel_rate || !gap_ext) return PAGAN_E_ARG;
+    double stay = 0, leave = 0, d_max = 0;
+    std::vector<double> O(n), Sm(n);
+    bool any_open = false, any = false;
+    for (int k = 0; k < n; ++k) {
+        const double *t = trans + 12 * (size_t)k;
+        for (int q = 0; q < 12; ++q) if (!(t[q] >= 0.0) || !(t[q] < HUGE_VAL)) return PAGAN_E_ARG;
+        if (!(dist[k] >= 0.0) || !(dist[k] < HUGE_VAL)) return PAGAN_E_ARG;
+        stay += t[0] + t[4];                                        // n_XX + n_YY
+        leave += t[1] + t[3] + t[2] + t[5] + t[9] + t[10];          // n_XY + n_YX + n_XM + n_YM + n_Xend + n_Yend
+        O[k] = t[6] + t[7]; Sm[k] = t[8] + t[11];                   // n_MX + n_MY; n_MM + n_Mend
+        if (dist[k] > 0 && O[k] + Sm[k] > 0) { any = true; any_open = any_open || O[k] > 0; d_max = std::max(d_max, dist[k]); }
+    }
+    *gap_ext = stay + leave > 0 ? stay / (stay + leave) : 0.0;
+    *indel_rate = 0.0;
+    if (!any || !any_open) return PAGAN_OK;                         // (no transition out of a match seen, or no gap opened: rate 0)
+    // g(r) = sum_k d_k [ O_k (1 - t_k) / (2 t_k) - S_k (1 - t_k) / (1 - 2 t_k) ], t_k = 1 - exp(-0.5 r d_k): the derivative of the
+    // objective by r; it falls from +inf at r = 0 and reaches -inf where 1 - 2 t_k = 0 at the longest distance (r d_max = 2 ln 2),
+    // unless no node with d = d_max has S > 0, when the root may lie at the bound itself
+    auto g = [&](double r) {
+        double s = 0;
+        for (int k = 0; k < n; ++k) {
+            if (!(dist[k] > 0) || !(O[k] + Sm[k] > 0)) continue;
+            const double e = std::exp(-0.5 * r * dist[k]), tk = 1.0 - e;
+            s += dist[k] * (O[k] * e / (2 * tk) - Sm[k] * e / (1.0 - 2 * tk));
+        }
+        return s;
+    };
+    double lo = 0.0, hi = 2.0 * std::log(2.0) / d_max;
+    for (int it = 0; it < 200 && hi - lo > 1e-13 * hi; ++it) {
+        const double mid = 0.5 * (lo + hi);
+        const double v = g(mid);
+        if (v > 0) lo = mid; else hi = mid;                         // (NaN at the bound itself -- inf - inf -- counts as beyond the root)
+    }
+    *indel_rate = 0.25 * (lo + hi);                                 // r / 2
     return PAGAN_OK;
 }
 

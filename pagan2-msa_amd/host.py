@@ -211,6 +211,14 @@ def _lib():
         L.pagan_msa_node_model_prob.restype = C.c_int
         L.pagan_msa_support_row.argtypes = [vp, C.c_int32, _f32p]
         L.pagan_msa_support_row.restype = C.c_int
+        L.pagan_msa_set_counts.argtypes = [vp, C.c_int32]
+        L.pagan_msa_set_counts.restype = C.c_int
+        L.pagan_msa_node_counts.argtypes = [vp, C.c_int32, f64p, f64p]
+        L.pagan_msa_node_counts.restype = C.c_int
+        L.pagan_msa_set_indel_model.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double]
+        L.pagan_msa_set_indel_model.restype = C.c_int
+        L.pagan_fit_indel.argtypes = [C.c_int32, f64p, f64p, f64p, f64p]
+        L.pagan_fit_indel.restype = C.c_int
         _declared = True
     return L
 
@@ -232,7 +240,8 @@ HOST_EXPORTED = ["pagan_assign_units", "pagan_msa_default_opts", "pagan_msa_crea
                  "pagan_pileup_alignment_length", "pagan_pileup_alignment_row", "pagan_pileup_set_batch_backend",
                  "pagan_pileup_destroy",
                  "pagan_msa_node_fb", "pagan_msa_node_support", "pagan_msa_node_marginals", "pagan_msa_node_model_prob", "pagan_msa_support_row",
-                 "pagan_msa_set_sampler", "pagan_msa_set_decoder", "pagan_msa_node_decode"]
+                 "pagan_msa_set_sampler", "pagan_msa_set_decoder", "pagan_msa_node_decode",
+                 "pagan_msa_set_counts", "pagan_msa_node_counts", "pagan_msa_set_indel_model", "pagan_fit_indel"]
 
 
 def _ip(a):
@@ -482,6 +491,24 @@ def model_prob(data_type, dist, base_freq=None):
     return abi.ModelProb(score.reshape(S, S).T, *params)
 
 
+def fit_indel(dists, trans):
+    """pagan_fit_indel (host only): (indel_rate, gap_ext) from the nodes' distances [n] and expected counts [n, 12] -- trans[3 * from
+    + to] over X, Y, M, then X-close, Y-close, M-end (a [3, 3] and a [3] array per node are accepted as Msa.node_counts gives them).
+    A moment / pseudo-likelihood estimate (include/pagan_host.h), not a maximum-likelihood fit of the model as scored."""
+    d = np.ascontiguousarray(dists, np.float64).reshape(-1)
+    rows = [np.concatenate([np.asarray(t["trans"], np.float64).reshape(9), np.asarray(t["end"], np.float64).reshape(3)])
+            if isinstance(t, dict) else np.asarray(t, np.float64).reshape(12) for t in trans]
+    t = np.ascontiguousarray(np.array(rows, np.float64).reshape(-1, 12))
+    assert t.shape[0] == d.shape[0]
+    f64p = C.POINTER(C.c_double)
+    rate, ext = C.c_double(), C.c_double()
+    rc = _lib().pagan_fit_indel(int(d.shape[0]), d.ctypes.data_as(f64p), t.ctypes.data_as(f64p), C.byref(rate), C.byref(ext))
+    if rc != 0:
+        from . import PaganError
+        raise PaganError(rc, "pagan_fit_indel")
+    return rate.value, ext.value
+
+
 def sample_uniforms(seed, node, n):
     """pagan_sample_uniforms: the numbers the walk samples node `node`'s path with under sample_seed=seed."""
     from . import sample_uniforms as f
@@ -610,11 +637,14 @@ class Pileup:
 class Msa:
     """Progressive alignment of sequences on a rooted binary guide tree (Node mirror)."""
 
-    def __init__(self, names, seqs, newick, sample_on_device=0, posterior_decode=0, decode_gap_weight=0.5, **opts):
+    def __init__(self, names, seqs, newick, sample_on_device=0, posterior_decode=0, decode_gap_weight=0.5, expected_counts=0,
+                 indel_model=None, **opts):
         """opts: fields of pagan_msa_opts.  sample_on_device=1 (pagan_msa_set_sampler): with sample_path set, the nodes' paths
         are drawn by pg_fb_sample on the device instead of on the host behind a download of the forward matrix.
         posterior_decode=1 (pagan_msa_set_decoder): a node's result is the maximum expected accuracy path of its posteriors,
-        gaps weighted by decode_gap_weight."""
+        gaps weighted by decode_gap_weight.  expected_counts=1 (pagan_msa_set_counts): every node's forward/backward pass also
+        leaves its expected transition counts (node_counts, expected_counts).  indel_model=(ins_rate, del_rate, gap_ext,
+        end_gap_ext) (pagan_msa_set_indel_model): the walk's indel model; a negative entry keeps the data type's default."""
         L = _lib()
         o = CMsaOpts()
         L.pagan_msa_default_opts(C.byref(o))
@@ -641,6 +671,16 @@ class Msa:
             if rc != 0:
                 from . import PaganError
                 raise PaganError(rc, "pagan_msa_set_decoder")
+        if expected_counts:
+            rc = L.pagan_msa_set_counts(self._h, int(expected_counts))
+            if rc != 0:
+                from . import PaganError
+                raise PaganError(rc, "pagan_msa_set_counts")
+        if indel_model is not None:
+            rc = L.pagan_msa_set_indel_model(self._h, *[float(v) for v in indel_model])
+            if rc != 0:
+                from . import PaganError
+                raise PaganError(rc, "pagan_msa_set_indel_model")
 
     def align(self):
         rc = self._L.pagan_msa_align(self._h)
@@ -767,6 +807,35 @@ class Msa:
         out = (C.c_double * 3)()
         self._fb_check(self._L.pagan_msa_node_decode(self._h, k, out), "pagan_msa_node_decode")
         return tuple(out)
+
+    def node_counts(self, k, emissions=None):
+        """Node k's expected counts (expected_counts=1): the dict FullProbability.expected_counts returns.  emissions: None
+        takes the table where the walk keeps one (DNA)."""
+        v = abi.CModelProb()
+        self._fb_check(self._L.pagan_msa_node_model_prob(self._h, k, C.byref(v)), "pagan_msa_node_model_prob")
+        S = v.n_states
+        if emissions is None:
+            emissions = self.data_type == 1
+        f64p = C.POINTER(C.c_double)
+        trans = np.zeros(12, np.float64)
+        emit = np.zeros(S * S, np.float64) if emissions else None
+        self._fb_check(self._L.pagan_msa_node_counts(self._h, k, trans.ctypes.data_as(f64p), emit.ctypes.data_as(f64p) if emissions else None),
+                       "pagan_msa_node_counts")
+        return {"trans": trans[:9].reshape(3, 3).copy(), "end": trans[9:].copy(), "emit": emit.reshape(S, S).T.copy() if emissions else None}
+
+    def expected_counts(self):
+        """The sum of the expected counts over the nodes this process aligned: {"trans", "end", "emit", "nodes": [k, ...],
+        "dists": [node k's distance, ...], "node_counts": [node k's dict, ...]} -- the last two are what fit_indel takes."""
+        out = {"trans": np.zeros((3, 3)), "end": np.zeros(3), "emit": None, "nodes": [], "dists": [], "node_counts": []}
+        for k in range(self.n_internal):
+            if self.node_device(k) < 0:
+                continue
+            c = self.node_counts(k)
+            out["trans"] += c["trans"]; out["end"] += c["end"]
+            if c["emit"] is not None:
+                out["emit"] = c["emit"].copy() if out["emit"] is None else out["emit"] + c["emit"]
+            out["nodes"].append(k); out["dists"].append(self.node_info(k).dist); out["node_counts"].append(c)
+        return out
 
     def node_support(self, k):
         """Posterior of every column's own cell along node k's path; -1 at skip columns."""
