@@ -309,6 +309,14 @@ int  pagan_prefix_hits(const char *s1, const char *s2, int32_t min_length, int32
 /* diagnostic: how often the prefix-anchor finder ran on the device (csrc/dp_anchors.hip: suffix array by prefix doubling on the
  * GPU; PAGAN_ANCHORS=host keeps it on the host, which is also where it runs without a device)                               */
 long long pagan_anchors_device_calls(void);
+/* debug seam for the tests: the list pagan_prefix_hits starts from, before its sort by length and its overlap filter -- the
+ * adjacent cross-string pairs of the suffix array with a common prefix >= min_length, in suffix-array order
+ * (find_anchors.cpp:66-85).  hits: cap x 3 ints (start in s1, start in s2, length); cap = strlen(s1) + strlen(s2) + 1 always
+ * suffices.  Returns the number of pairs (those beyond cap are not written).  where = 0: the host's builder; where = 1: the
+ * device's (csrc/dp_anchors.hip) on the calling thread's anchor device, whatever the lengths and however many finders are in
+ * flight; PAGAN_E_NODEVICE where it declines (no device, a HIP error, a text of 2^20 - 1 symbols or more).  Does not count
+ * as a device call in pagan_anchors_device_calls.                                                                       */
+int  pagan_prefix_hits_raw(const char *s1, const char *s2, int32_t min_length, int32_t where, int32_t *hits, int32_t cap);
 int  pagan_drop_bad_hits(int32_t *hits, int32_t n, int32_t thr_total, int32_t thr_partly);
 int  pagan_define_tunnel_overlapping(const int32_t *hits, int32_t n, const char *gapped1, const char *gapped2, int32_t width,
                                      int32_t *upper, int32_t *lower, int32_t *blocks, int32_t cap);

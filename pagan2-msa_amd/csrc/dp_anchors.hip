@@ -15,8 +15,11 @@
 //   * the adjacent cross-string pairs with a common prefix >= min_length are selected in suffix-array order (a flag per
 //     rank, a library select) and written out as (start in a, start in b, length).
 // What follows in the reference -- the sort by length, the overlap filter (:87-126), check_hits_order_conflict and
-// define_tunnel -- stays with host_anchors.cpp: the hit list that enters it is the same, element for element
-// (tests/test_anchors_gpu.py compares the two on homologous sequences up to 2 x 100 kb).
+// define_tunnel -- stays with host_anchors.cpp: the hit list that enters it is the same, element for element.
+// tests/test_anchors_gpu.py takes the list as it leaves this file (pagan_prefix_hits_raw) and compares it, in order, with a
+// literal reading of :35-85 in Python (tests/pycheck_anchors.py) on small and degenerate inputs -- empty strings, one-letter
+// runs, identical strings, bytes >= 0x80, texts at launch-block boundaries -- and with the host's list up to the largest
+// accepted text, 2^20 - 2 symbols.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -174,7 +177,11 @@ bool prefix_hits_device(const std::string &a, const std::string &b, int min_leng
     char *m = S.mem;
     auto take = [&](size_t bytes) { char *p = m; m += up256(bytes); return p; };
     char *d_a = take(len1 + 1), *d_b = take(len2 + 1);
-    unsigned long long *key = (unsigned long long *)take(8 * (size_t)n), *key2 = (unsigned long long *)take(8 * (size_t)n);
+    // key and key2 are carved as ONE block: once the rounds are over it holds the emitted records (12 bytes per hit, and up to
+    // n - 3 hits -- identical strings with min_length 1 come close -- which is more than `key` alone holds)
+    const size_t key_stride = up256(8 * (size_t)n), out_cap = 2 * key_stride / (3 * sizeof(int));
+    char *keys = take(2 * key_stride);
+    unsigned long long *key = (unsigned long long *)keys, *key2 = (unsigned long long *)(keys + key_stride);
     int *idx = (int *)take(4 * (size_t)n), *sa = (int *)take(4 * (size_t)n), *flag = (int *)take(4 * (size_t)n), *fscan = (int *)take(4 * (size_t)n);
     int *lcp = (int *)take(4 * (size_t)n), *sel = (int *)take(4 * (size_t)n);
     int *rk[max_rounds + 1];
@@ -215,7 +222,8 @@ bool prefix_hits_device(const std::string &a, const std::string &b, int min_leng
     HIPA(hipStreamSynchronize(st));
     hits->clear();
     if (n_sel > 0) {
-        int *out = (int *)key;                                             // (the key array is free now: 3 ints per hit, n_sel <= n)
+        if ((size_t)n_sel > out_cap) return false;                         // (cannot happen: n_sel < n, and the block holds 16 n bytes)
+        int *out = (int *)keys;                                            // (both key arrays are free now: 3 ints per hit)
         hipLaunchKernelGGL(pa_emit, dim3((n_sel + B - 1) / B), dim3(B), 0, st, sel, n_sel, sa, lcp, len1, out);
         std::vector<int> h(3 * (size_t)n_sel);
         HIPA(hipMemcpyAsync(h.data(), out, h.size() * sizeof(int), hipMemcpyDeviceToHost, st));

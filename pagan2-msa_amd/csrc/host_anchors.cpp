@@ -91,29 +91,10 @@ static bool anchors_on_device() {
     return !(e && std::strcmp(e, "host") == 0);
 }
 
-void prefix_hits(const std::string &a, const std::string &b, int min_length, std::vector<Hit> *hits) {
+// The adjacent cross-string pairs of the suffix array with a common prefix >= min_length, in suffix-array order (:66-85): the
+// list before its sort by length and its overlap filter (pagan_prefix_hits_raw shows it to the tests).
+void prefix_hits_raw_host(const std::string &a, const std::string &b, int min_length, std::vector<Hit> *hits) {
     const int len1 = (int)a.size(), len2 = (int)b.size();
-    // The device's finder wins on long sequences (2 x 100 kb: 2.9 ms against 11 ms on one host thread) and loses on short ones
-    // (launch overheads: 2 x 3 kb 0.75 against 0.22 ms); a wide tree level prepares its nodes on as many host threads at once,
-    // which then beat a device they would have to share: at most four finders on the device at a time.
-    struct InFlight {
-        std::atomic<int> &c; const bool ok;
-        explicit InFlight(std::atomic<int> &c_) : c(c_), ok(c_.fetch_add(1) < 4) {}
-        ~InFlight() { c.fetch_sub(1); }
-    };
-    static std::atomic<int> on_device[64];                         // per device: the cap is about sharing ONE device
-    bool done = false;
-    if (anchors_on_device() && len1 + len2 >= 16384) {
-        const int dev = anchor_device();
-        InFlight slot(on_device[(dev < 0 ? 0 : dev) & 63]);
-        done = slot.ok && prefix_hits_device(a, b, min_length, hits, dev);
-    }
-    if (done) {
-        device_finder_calls.fetch_add(1);
-        std::sort(hits->begin(), hits->end(), [](Hit p, Hit q) { return p.len > q.len; });   // :87
-        drop_overlapping(hits, len1, len2);
-        return;
-    }
     hits->clear();
     const int n = len1 + len2 + 2;
     std::vector<int> t(n);
@@ -146,6 +127,27 @@ void prefix_hits(const std::string &a, const std::string &b, int min_length, std
         h.len = lcp[r]; h.score = lcp[r];
         hits->push_back(h);
     }
+}
+
+void prefix_hits(const std::string &a, const std::string &b, int min_length, std::vector<Hit> *hits) {
+    const int len1 = (int)a.size(), len2 = (int)b.size();
+    // The device's finder wins on long sequences (2 x 100 kb: 2.9 ms against 11 ms on one host thread) and loses on short ones
+    // (launch overheads: 2 x 3 kb 0.75 against 0.22 ms); a wide tree level prepares its nodes on as many host threads at once,
+    // which then beat a device they would have to share: at most four finders on the device at a time.
+    struct InFlight {
+        std::atomic<int> &c; const bool ok;
+        explicit InFlight(std::atomic<int> &c_) : c(c_), ok(c_.fetch_add(1) < 4) {}
+        ~InFlight() { c.fetch_sub(1); }
+    };
+    static std::atomic<int> on_device[64];                         // per device: the cap is about sharing ONE device
+    bool done = false;
+    if (anchors_on_device() && len1 + len2 >= 16384) {
+        const int dev = anchor_device();
+        InFlight slot(on_device[(dev < 0 ? 0 : dev) & 63]);
+        done = slot.ok && prefix_hits_device(a, b, min_length, hits, dev);
+    }
+    if (done) device_finder_calls.fetch_add(1);
+    else prefix_hits_raw_host(a, b, min_length, hits);
     std::sort(hits->begin(), hits->end(), [](Hit p, Hit q) { return p.len > q.len; });   // :87
     drop_overlapping(hits, len1, len2);
 }

@@ -24,6 +24,8 @@ struct AnchorSettings {
 };
 
 void prefix_hits(const std::string &a, const std::string &b, int min_length, std::vector<Hit> *hits);
+// the list before its sort by length and overlap filter (find_anchors.cpp:66-85), from the host's suffix array
+void prefix_hits_raw_host(const std::string &a, const std::string &b, int min_length, std::vector<Hit> *hits);
 // the same list before its sort by length and overlap filter, from a suffix array built on the device (dp_anchors.hip);
 // false where there is no device
 extern std::atomic<long long> device_finder_calls;    // how often prefix_hits took the device's finder

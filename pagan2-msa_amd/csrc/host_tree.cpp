@@ -1510,6 +1510,15 @@ int pagan_prefix_hits(const char *s1, const char *s2, int32_t min_length, int32_
     return (int)v.size();
 }
 
+int pagan_prefix_hits_raw(const char *s1, const char *s2, int32_t min_length, int32_t where, int32_t *hits, int32_t cap) {
+    if (!s1 || !s2 || min_length < 1 || cap < 0 || (cap > 0 && !hits) || (where != 0 && where != 1)) return PAGAN_E_ARG;
+    std::vector<Hit> v;
+    if (where == 0) prefix_hits_raw_host(s1, s2, min_length, &v);
+    else if (!prefix_hits_device(s1, s2, min_length, &v, anchor_device())) return PAGAN_E_NODEVICE;
+    for (size_t k = 0; k < v.size() && (int)k < cap; ++k) { hits[3 * k] = v[k].s1; hits[3 * k + 1] = v[k].s2; hits[3 * k + 2] = v[k].len; }
+    return (int)v.size();
+}
+
 long long pagan_anchors_device_calls(void) { return device_finder_calls.load(); }
 
 int pagan_drop_bad_hits(int32_t *hits, int32_t n, int32_t thr_total, int32_t thr_partly) {

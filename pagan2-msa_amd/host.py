@@ -119,6 +119,8 @@ def _lib():
         L.pagan_assign_units.restype = None
         L.pagan_prefix_hits.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, _i32p, C.c_int32]
         L.pagan_prefix_hits.restype = C.c_int
+        L.pagan_prefix_hits_raw.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, _i32p, C.c_int32]
+        L.pagan_prefix_hits_raw.restype = C.c_int
         L.pagan_anchors_device_calls.argtypes = []
         L.pagan_anchors_device_calls.restype = C.c_longlong
         L.pagan_drop_bad_hits.argtypes = [_i32p, C.c_int32, C.c_int32, C.c_int32]
@@ -229,7 +231,7 @@ HOST_EXPORTED = ["pagan_assign_units", "pagan_msa_default_opts", "pagan_msa_crea
                  "pagan_msa_node_graph", "pagan_msa_finish_lazy", "pagan_msa_parents_built",
                  "pagan_msa_destroy", "pagan_hgraph_leaf", "pagan_hgraph_parent", "pagan_hgraph_parent_device", "pagan_parents_device_calls", "pagan_hgraph_view",
                  "pagan_hgraph_attrs", "pagan_hgraph_fwd", "pagan_hgraph_string", "pagan_hgraph_free",
-                 "pagan_define_tunnel", "pagan_prefix_hits", "pagan_anchors_device_calls", "pagan_drop_bad_hits", "pagan_define_tunnel_overlapping",
+                 "pagan_define_tunnel", "pagan_prefix_hits", "pagan_prefix_hits_raw", "pagan_anchors_device_calls", "pagan_drop_bad_hits", "pagan_define_tunnel_overlapping",
                  "pagan_force_gap", "pagan_dna_model", "pagan_protein_model", "pagan_model_prob_table", "pagan_model_alphabets",
                  "pagan_codon_model", "pagan_codon_alphabet", "pagan_codon_states", "pagan_codon_translate", "pagan_hgraph_leaf_codon",
                  "pagan_eigen_qrev", "pagan_msa_ready", "pagan_msa_remaining", "pagan_msa_node_cost",
@@ -380,6 +382,23 @@ def prefix_hits(s1, s2, min_length=30):
     cap = max(len(s1), 1)
     out = np.zeros((cap, 4), np.int32)
     n = _lib().pagan_prefix_hits(s1.encode(), s2.encode(), min_length, _ip(out), cap)
+    return out[:n].copy()
+
+
+def prefix_hits_raw(s1, s2, min_length=30, device=False):
+    """The list prefix_hits() starts from, before its sort by length and its overlap filter: the adjacent cross-string pairs of
+    the suffix array in suffix-array order, [n, 3] int32 rows (start 1, start 2, length).  s1, s2: bytes, or str read as
+    latin-1 (no NUL).  device=True: the device's finder whatever the lengths (pagan_prefix_hits_raw, where = 1); raises
+    RuntimeError with the library's code where it declines."""
+    s1 = s1.encode("latin-1") if isinstance(s1, str) else bytes(s1)
+    s2 = s2.encode("latin-1") if isinstance(s2, str) else bytes(s2)
+    if b"\0" in s1 or b"\0" in s2:
+        raise ValueError("NUL ends a C string")
+    cap = len(s1) + len(s2) + 1
+    out = np.zeros((cap, 3), np.int32)
+    n = _lib().pagan_prefix_hits_raw(s1, s2, min_length, 1 if device else 0, _ip(out), cap)
+    if n < 0:
+        raise RuntimeError("pagan_prefix_hits_raw: error %d" % n)
     return out[:n].copy()
 
 
