@@ -33,6 +33,7 @@
 #include <condition_variable>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <thread>
 #include <vector>
 
@@ -484,6 +485,11 @@ __global__ __launch_bounds__(FB_RG_THREADS) void pg_fb_backward_ring(const PgFbJ
     if (threadIdx.x == 0) J.totals[1] = rd(J.B, cell_at(J, 0, 0), 2);
 }
 #undef FB_RING_THREADS
+
+// A path's summary, as pg_fb_sample and pg_fb_decode_trace write it and the path handles read it, FB_SUMMARY_INTS ints: the status
+// (0 a path, 1 full probability zero, 2 internal), the end cell (five ints: state, i, j, k1, k2), the steps, the steps by state,
+// a double in two ints (the sampler's log_q, the decoder's objective), four spare
+enum { FB_SUM_STATUS = 0, FB_SUM_END = 1, FB_SUM_STEPS = 6, FB_SUM_M = 7, FB_SUM_X = 8, FB_SUM_Y = 9, FB_SUM_VALUE = 10, FB_SUMMARY_INTS = 16 };
 
 #include "dp_fb_deep.inc"
 #include "dp_fb_post.inc"
@@ -1276,6 +1282,48 @@ struct FbLayout {
     }
 };
 
+static size_t fb_round256(size_t b) { return (b + 255) / 256 * 256; }
+
+// One call that reads finished passes of one device: the thread on that device for the call's length, one device buffer laid
+// out by take() -- first what goes UP (job records, launch records, small inputs), then what comes DOWN with the call (results,
+// summaries), then what only the DEVICE sees (partial sums, traces, pack buffers), every piece rounded up to 256 bytes --, the
+// host's copy of the first two regions, and the launches' times: begin() / end() around the launches of a span, any number of
+// spans, ms(k) once download() has waited for them.  The buffer is shared so that the handles a call makes can keep it.
+struct FbCall {
+    enum Region { UP, DOWN, DEVICE };
+    std::optional<FbDeviceScope> on_device;
+    std::shared_ptr<FbDevBuf> buf = std::make_shared<FbDevBuf>();
+    std::vector<char> host;
+    std::vector<FbEvent> ev;                 // a span's two events
+    size_t cur = 0, end_of[3] = {0, 0, 0};
+    int open(int32_t n, pagan_fb *const *fbs) {
+        for (int k = 0; k < n; ++k) if (!fbs[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
+        on_device.emplace(fbs[0]->device);
+        return on_device->ok ? PAGAN_OK : PAGAN_E_NODEVICE;
+    }
+    size_t take(Region r, size_t bytes) {
+        const size_t at = cur;
+        cur = fb_round256(cur + bytes);
+        for (int q = r; q < 3; ++q) end_of[q] = cur;
+        return at;
+    }
+    int alloc() { host.assign(end_of[DOWN], 0); return buf->alloc(cur); }
+    template <class T> T *dev(size_t off) const { return (T *)(buf->h + off); }
+    template <class T> void put(size_t off, const T &rec) { std::memcpy(host.data() + off, &rec, sizeof(T)); }
+    int upload() { FB_TRY(hipMemcpy(buf->h, host.data(), end_of[UP], hipMemcpyHostToDevice)); return PAGAN_OK; }
+    int begin() {
+        for (int q = 0; q < 2; ++q) { ev.emplace_back(); FB_DO(ev.back().create()); }
+        FB_TRY(hipEventRecord(ev[ev.size() - 2], nullptr));
+        return PAGAN_OK;
+    }
+    int end() { FB_TRY(hipGetLastError()); FB_TRY(hipEventRecord(ev.back(), nullptr)); return PAGAN_OK; }
+    int download() {
+        FB_TRY(hipMemcpy(host.data() + end_of[UP], buf->h + end_of[UP], end_of[DOWN] - end_of[UP], hipMemcpyDeviceToHost));
+        return PAGAN_OK;
+    }
+    float ms(int span) const { float v = 0; (void)hipEventElapsedTime(&v, ev[2 * span], ev[2 * span + 1]); return v; }
+};
+
 // One pair up to the upload of its inputs: validation, band index, lists, arena, the job record with its workgroup count
 // (`groups_cap`, `groups_cap_b`: what the caller's launch leaves this pair's forward / backward sweep).  What the handle does not
 // hold itself stays here.
@@ -1698,92 +1746,81 @@ namespace {
 // pg_fb_gather over one pair: the triples go up in one copy, the posteriors come back in one (state outside 0..2: -1)
 static int fb_gather(pagan_fb *fb, int32_t n, const int32_t *cells, double *post) {
     if (n == 0) return PAGAN_OK;
-    FbDeviceScope on_device(fb->device);
-    if (!on_device.ok) return PAGAN_E_NODEVICE;
-    const size_t o_cells = 256, o_out = o_cells + (12 * (size_t)n + 255) / 256 * 256, bytes = o_out + 8 * (size_t)n;
-    FbDevBuf buf;
-    FbEvent e0, e1;
-    FB_DO(buf.alloc(bytes));
-    std::vector<char> up(o_out, 0);
+    FbCall c;
+    FB_DO(c.open(1, &fb));
+    const size_t o_rec = c.take(FbCall::UP, sizeof(PgFbGather)), o_cells = c.take(FbCall::UP, 12 * (size_t)n);
+    const size_t o_out = c.take(FbCall::DOWN, 8 * (size_t)n);
+    FB_DO(c.alloc());
     PgFbGather G;
-    G.cells = (const int *)(buf.h + o_cells); G.out = (double *)(buf.h + o_out); G.n = n;
-    std::memcpy(up.data(), &G, sizeof(G));
-    std::memcpy(up.data() + o_cells, cells, 12 * (size_t)n);
-    FB_TRY(hipMemcpy(buf, up.data(), o_out, hipMemcpyHostToDevice));
-    FB_DO(e0.create()); FB_DO(e1.create());
-    FB_TRY(hipEventRecord(e0, nullptr));
+    G.cells = c.dev<const int>(o_cells); G.out = c.dev<double>(o_out); G.n = n;
+    c.put(o_rec, G);
+    std::memcpy(c.host.data() + o_cells, cells, 12 * (size_t)n);
+    FB_DO(c.upload());
+    FB_DO(c.begin());
     const unsigned blocks = (unsigned)std::min<long long>(((long long)n + 255) / 256, 4096);
-    hipLaunchKernelGGL(pg_fb_gather, dim3(blocks, 1), dim3(256), 0, nullptr, fb->d_job, (const PgFbGather *)buf.h);
-    FB_TRY(hipGetLastError());
-    FB_TRY(hipEventRecord(e1, nullptr));
-    FB_TRY(hipMemcpy(post, buf.h + o_out, 8 * (size_t)n, hipMemcpyDeviceToHost));
-    (void)hipEventElapsedTime(&fb->post_ms[0], e0, e1);
+    hipLaunchKernelGGL(pg_fb_gather, dim3(blocks, 1), dim3(256), 0, nullptr, fb->d_job, c.dev<const PgFbGather>(o_rec));
+    FB_DO(c.end());
+    FB_DO(c.download());
+    std::memcpy(post, c.host.data() + o_out, 8 * (size_t)n);
+    fb->post_ms[0] = c.ms(0);
     return PAGAN_OK;
 }
 
 // The two marginal passes over n handles of one device: one launch per pass, grid = (blocks of the longest pair, pairs that want
 // the pass).  o[0..3] rows (pX, pM, best_j, best_p), o[4..7] columns (pY, pM', best_i, best_p'): arrays of n pointers or null,
-// any entry null.  A pass none of whose outputs is wanted anywhere is not launched.  The launches' times go to the first handle.
+// any entry null.  A pass none of whose outputs is wanted anywhere is not launched.  A pass's time goes to the first handle that
+// wanted it.
 static int fb_marginals(int32_t n, pagan_fb *const *fbs, void *const *const o[8]) {
     if (n < 0 || (n > 0 && !fbs)) return PAGAN_E_ARG;
     if (n == 0) return PAGAN_OK;
-    for (int k = 0; k < n; ++k) if (!fbs[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
-    FbDeviceScope on_device(fbs[0]->device);
-    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    FbCall c;
+    FB_DO(c.open(n, fbs));
     auto wanted = [&](int k, int side) { for (int q = 4 * side; q < 4 * side + 4; ++q) if (o[q] && o[q][k]) return true; return false; };
     struct Side { std::vector<int> ks; std::vector<size_t> at; int blocks = 0; size_t o_jobs = 0, o_recs = 0; };
     Side sd[2];
-    size_t cur = 0;
-    auto take = [&](size_t bytes) { const size_t at = cur; cur = (cur + bytes + 255) / 256 * 256; return at; };
     for (int side = 0; side < 2; ++side) {
         for (int k = 0; k < n; ++k) if (wanted(k, side)) sd[side].ks.push_back(k);
-        sd[side].o_jobs = take(sd[side].ks.size() * sizeof(PgFbJob));
-        sd[side].o_recs = take(sd[side].ks.size() * sizeof(PgFbMarg));
+        sd[side].o_jobs = c.take(FbCall::UP, sd[side].ks.size() * sizeof(PgFbJob));
+        sd[side].o_recs = c.take(FbCall::UP, sd[side].ks.size() * sizeof(PgFbMarg));
     }
-    const size_t in_bytes = cur;
     for (int side = 0; side < 2; ++side)
         for (int k : sd[side].ks) {
             const int len = side ? fbs[k]->Ly : fbs[k]->Lx;
-            sd[side].at.push_back(take(28 * (size_t)len));          // three doubles and an int a site
+            sd[side].at.push_back(c.take(FbCall::DOWN, 28 * (size_t)len));          // three doubles and an int a site
             sd[side].blocks = std::max(sd[side].blocks, (len + FB_PM_ROWS - 1) / FB_PM_ROWS);
         }
     if (sd[0].ks.empty() && sd[1].ks.empty()) return PAGAN_OK;
-    FbDevBuf buf;
-    FbEvent ev[4];
-    FB_DO(buf.alloc(cur));
-    std::vector<char> host(cur, 0);
+    FB_DO(c.alloc());
     for (int side = 0; side < 2; ++side)
         for (size_t q = 0; q < sd[side].ks.size(); ++q) {
             const pagan_fb *fb = fbs[sd[side].ks[q]];
             const size_t len = side ? fb->Ly : fb->Lx;
-            char *base = buf.h + sd[side].at[q];
+            char *base = c.dev<char>(sd[side].at[q]);
             PgFbMarg M;
             M.gap = (double *)base; M.match = (double *)(base + 8 * len); M.best_p = (double *)(base + 16 * len); M.best = (int *)(base + 24 * len);
-            std::memcpy(host.data() + sd[side].o_jobs + q * sizeof(PgFbJob), &fb->job, sizeof(PgFbJob));
-            std::memcpy(host.data() + sd[side].o_recs + q * sizeof(PgFbMarg), &M, sizeof(M));
+            c.put(sd[side].o_jobs + q * sizeof(PgFbJob), fb->job);
+            c.put(sd[side].o_recs + q * sizeof(PgFbMarg), M);
         }
-    FB_TRY(hipMemcpy(buf, host.data(), in_bytes, hipMemcpyHostToDevice));
+    FB_DO(c.upload());
     for (int side = 0; side < 2; ++side) {
         if (sd[side].ks.empty()) continue;
-        FB_DO(ev[2 * side].create()); FB_DO(ev[2 * side + 1].create());
-        FB_TRY(hipEventRecord(ev[2 * side], nullptr));
+        FB_DO(c.begin());
         const dim3 grid((unsigned)sd[side].blocks, (unsigned)sd[side].ks.size());
-        const PgFbJob *jobs = (const PgFbJob *)(buf.h + sd[side].o_jobs);
-        const PgFbMarg *recs = (const PgFbMarg *)(buf.h + sd[side].o_recs);
+        const PgFbJob *jobs = c.dev<const PgFbJob>(sd[side].o_jobs);
+        const PgFbMarg *recs = c.dev<const PgFbMarg>(sd[side].o_recs);
         if (side) hipLaunchKernelGGL((pg_fb_marginals<true>), grid, dim3(FB_PM_ROWS), 0, nullptr, jobs, recs);
         else hipLaunchKernelGGL((pg_fb_marginals<false>), grid, dim3(FB_PM_ROWS), 0, nullptr, jobs, recs);
-        FB_TRY(hipGetLastError());
-        FB_TRY(hipEventRecord(ev[2 * side + 1], nullptr));
+        FB_DO(c.end());
     }
-    FB_TRY(hipMemcpy(host.data() + in_bytes, buf.h + in_bytes, cur - in_bytes, hipMemcpyDeviceToHost));
+    FB_DO(c.download());
     for (int k = 0; k < n; ++k) fbs[k]->post_ms[1] = fbs[k]->post_ms[2] = 0.0f;
     for (int side = 0; side < 2; ++side) {
         if (sd[side].ks.empty()) continue;
-        (void)hipEventElapsedTime(&fbs[sd[side].ks[0]]->post_ms[1 + side], ev[2 * side], ev[2 * side + 1]);
+        fbs[sd[side].ks[0]]->post_ms[1 + side] = c.ms(side && !sd[0].ks.empty() ? 1 : 0);   // (spans in the order of the passes launched)
         for (size_t q = 0; q < sd[side].ks.size(); ++q) {
             const int k = sd[side].ks[q];
             const size_t len = side ? fbs[k]->Ly : fbs[k]->Lx;
-            const char *base = host.data() + sd[side].at[q];
+            const char *base = c.host.data() + sd[side].at[q];
             void *const *const *oo = o + 4 * side;
             if (oo[0] && oo[0][k]) std::memcpy(oo[0][k], base, 8 * len);
             if (oo[1] && oo[1][k]) std::memcpy(oo[1][k], base + 8 * len, 8 * len);
@@ -1796,7 +1833,7 @@ static int fb_marginals(int32_t n, pagan_fb *const *fbs, void *const *const o[8]
 
 // The expected counts of n handles of one device: pg_fb_counts over (work items of the longest pair, pairs), then pg_fb_counts_fold,
 // one workgroup a pair.  One buffer: the job records, the count records, the pairs' work items, then per pair the result and the
-// work items' partial sums.
+// work items' partial sums.  The time goes to fbs[0].
 static size_t fb_counts_stride(const pagan_fb *fb, bool emit) { return 9 + (emit ? (size_t)fb->S * fb->S : 0); }
 // A pair's work items (first row of a row block, first diagonal, last diagonal + 1): per block of FB_CN_ROWS rows the diagonals that
 // hold a cell of the block -- for a monotone band imin and imax never fall (dp_band.h) --, in segments of FB_CN_SEG
@@ -1814,60 +1851,46 @@ static void fb_counts_items(const pagan_fb *fb, std::vector<int> *items) {
 }
 static int fb_counts(int32_t n, pagan_fb *const *fbs, double *const *trans, double *const *emit) {
     if (n < 0 || (n > 0 && (!fbs || !trans))) return PAGAN_E_ARG;
-    for (int k = 0; k < n; ++k) {
-        if (!fbs[k] || !trans[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
-        if (emit && emit[k] && fbs[k]->S > FB_CN_MAXS) return PAGAN_E_ARG;
-    }
+    for (int k = 0; k < n; ++k)
+        if (!fbs[k] || !trans[k] || (emit && emit[k] && fbs[k]->S > FB_CN_MAXS)) return PAGAN_E_ARG;
     if (n == 0) return PAGAN_OK;
-    FbDeviceScope on_device(fbs[0]->device);
-    if (!on_device.ok) return PAGAN_E_NODEVICE;
-    size_t cur = 0;
-    auto take = [&](size_t bytes) { const size_t at = cur; cur = (cur + bytes + 255) / 256 * 256; return at; };
-    const size_t o_jobs = take((size_t)n * sizeof(PgFbJob)), o_recs = take((size_t)n * sizeof(PgFbCounts));
+    FbCall c;
+    FB_DO(c.open(n, fbs));
+    const size_t o_jobs = c.take(FbCall::UP, (size_t)n * sizeof(PgFbJob)), o_recs = c.take(FbCall::UP, (size_t)n * sizeof(PgFbCounts));
     std::vector<std::vector<int>> items(n);
     std::vector<size_t> o_items(n), o_out(n), o_part(n);
     int widest = 0;
     size_t lds = 0;
     for (int k = 0; k < n; ++k) {
         fb_counts_items(fbs[k], &items[k]);
-        o_items[k] = take(4 * items[k].size());
+        o_items[k] = c.take(FbCall::UP, 4 * items[k].size());
         widest = std::max(widest, (int)(items[k].size() / 3));
         if (emit && emit[k]) lds = std::max(lds, 8 * (size_t)FB_CN_ROWS * fbs[k]->S);
     }
-    const size_t in_bytes = cur;
-    for (int k = 0; k < n; ++k) o_out[k] = take(8 * (fb_counts_stride(fbs[k], emit && emit[k]) + 3));   // the results: they come back in one copy
-    const size_t out_end = cur;
-    for (int k = 0; k < n; ++k) o_part[k] = take(8 * fb_counts_stride(fbs[k], emit && emit[k]) * (items[k].size() / 3));
-    std::vector<char> host(out_end, 0);
-    FbDevBuf buf;
-    FbEvent e0, e1;
-    FB_DO(buf.alloc(cur));
+    for (int k = 0; k < n; ++k) o_out[k] = c.take(FbCall::DOWN, 8 * (fb_counts_stride(fbs[k], emit && emit[k]) + 3));
+    for (int k = 0; k < n; ++k) o_part[k] = c.take(FbCall::DEVICE, 8 * fb_counts_stride(fbs[k], emit && emit[k]) * (items[k].size() / 3));
+    FB_DO(c.alloc());
     for (int k = 0; k < n; ++k) {
         PgFbCounts R;
-        R.part = (double *)(buf.h + o_part[k]); R.out = (double *)(buf.h + o_out[k]);
-        R.items = (const int *)(buf.h + o_items[k]); R.n_items = (int)(items[k].size() / 3); R.emit = emit && emit[k] ? 1 : 0;
-        std::memcpy(host.data() + o_jobs + k * sizeof(PgFbJob), &fbs[k]->job, sizeof(PgFbJob));
-        std::memcpy(host.data() + o_recs + k * sizeof(PgFbCounts), &R, sizeof(R));
-        if (!items[k].empty()) std::memcpy(host.data() + o_items[k], items[k].data(), 4 * items[k].size());
+        R.part = c.dev<double>(o_part[k]); R.out = c.dev<double>(o_out[k]);
+        R.items = c.dev<const int>(o_items[k]); R.n_items = (int)(items[k].size() / 3); R.emit = emit && emit[k] ? 1 : 0;
+        c.put(o_jobs + k * sizeof(PgFbJob), fbs[k]->job);
+        c.put(o_recs + k * sizeof(PgFbCounts), R);
+        if (!items[k].empty()) std::memcpy(c.host.data() + o_items[k], items[k].data(), 4 * items[k].size());
     }
-    FB_TRY(hipMemcpy(buf, host.data(), in_bytes, hipMemcpyHostToDevice));
-    FB_DO(e0.create()); FB_DO(e1.create());
-    const PgFbJob *jobs = (const PgFbJob *)(buf.h + o_jobs);
-    const PgFbCounts *recs = (const PgFbCounts *)(buf.h + o_recs);
-    FB_TRY(hipEventRecord(e0, nullptr));
-    if (widest > 0) {
-        hipLaunchKernelGGL(pg_fb_counts, dim3((unsigned)widest, (unsigned)n), dim3(FB_CN_ROWS), lds, nullptr, jobs, recs);
-        FB_TRY(hipGetLastError());
-    }
+    FB_DO(c.upload());
+    const PgFbJob *jobs = c.dev<const PgFbJob>(o_jobs);
+    const PgFbCounts *recs = c.dev<const PgFbCounts>(o_recs);
+    FB_DO(c.begin());
+    if (widest > 0) hipLaunchKernelGGL(pg_fb_counts, dim3((unsigned)widest, (unsigned)n), dim3(FB_CN_ROWS), lds, nullptr, jobs, recs);
     hipLaunchKernelGGL(pg_fb_counts_fold, dim3((unsigned)n), dim3(256), 0, nullptr, jobs, recs);
-    FB_TRY(hipGetLastError());
-    FB_TRY(hipEventRecord(e1, nullptr));
-    FB_TRY(hipMemcpy(host.data() + in_bytes, buf.h + in_bytes, out_end - in_bytes, hipMemcpyDeviceToHost));
+    FB_DO(c.end());
+    FB_DO(c.download());
     for (int k = 0; k < n; ++k) fbs[k]->counts_ms = 0.0f;
-    (void)hipEventElapsedTime(&fbs[0]->counts_ms, e0, e1);
+    fbs[0]->counts_ms = c.ms(0);
     for (int k = 0; k < n; ++k) {
-        std::memcpy(trans[k], host.data() + o_out[k], 8 * 12);
-        if (emit && emit[k]) std::memcpy(emit[k], host.data() + o_out[k] + 8 * 12, 8 * (size_t)fbs[k]->S * fbs[k]->S);
+        std::memcpy(trans[k], c.host.data() + o_out[k], 8 * 12);
+        if (emit && emit[k]) std::memcpy(emit[k], c.host.data() + o_out[k] + 8 * 12, 8 * (size_t)fbs[k]->S * fbs[k]->S);
     }
     return PAGAN_OK;
 }
@@ -1877,6 +1900,16 @@ static uint64_t fb_splitmix64(uint64_t x) {
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     return x ^ (x >> 31);
+}
+
+// The result of a pair whose full probability is 0: nothing to sample, nothing to decode
+static int fb_unreachable_result(const pagan_graph *L, const pagan_graph *R, long long cells, double log_fwd, pagan_result *out) {
+    int endcell[8] = {1, 0, 0, 0, -1, -1, 0, 0};
+    return pagan_internal_replay(L, R, cells, endcell, log_fwd, nullptr, out);
+}
+// A trace's first n records as `visited` has them: (i, j, state)
+static void fb_visited_of(const int *trace, int n, int32_t *visited) {
+    for (int t = 0; t < n; ++t) { visited[3 * t] = trace[3 * t]; visited[3 * t + 1] = trace[3 * t + 1]; visited[3 * t + 2] = trace[3 * t + 2] & 3; }
 }
 } // namespace
 
@@ -2039,11 +2072,8 @@ int pagan_fb_sample_path(pagan_fb *fb, const double *u, int32_t n_u, pagan_resul
     }
     if (used >= n_u) return PAGAN_E_ARG;
     int k = pick(u[used++]);
+    if (k < 0) return fb_unreachable_result(L, R, fb->dx.cells, fb->totals[0], out);
     int endcell[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (k < 0) {                                     // full probability 0: nothing to sample
-        endcell[0] = 1; endcell[4] = endcell[5] = -1;
-        return pagan_internal_replay(L, R, fb->dx.cells, endcell, fb->totals[0], nullptr, out);
-    }
     int state = c[k].state, i = c[k].i, j = c[k].j;
     endcell[1] = state; endcell[2] = i; endcell[3] = j; endcell[4] = c[k].k1; endcell[5] = c[k].k2;
     std::vector<int> trace;
@@ -2082,7 +2112,7 @@ int pagan_fb_sample_path(pagan_fb *fb, const double *u, int32_t n_u, pagan_resul
         state = c[k].state; i = c[k].i; j = c[k].j;
     }
     endcell[6] = (int)(trace.size() / 3);
-    if (visited) for (size_t t = 0; t < trace.size() / 3; ++t) { visited[3 * t] = trace[3 * t]; visited[3 * t + 1] = trace[3 * t + 1]; visited[3 * t + 2] = trace[3 * t + 2] & 3; }
+    if (visited) fb_visited_of(trace.data(), endcell[6], visited);
     if (n_visited) *n_visited = endcell[6];
     trace.resize(trace.size() + 3, 0);
     return pagan_internal_replay(L, R, fb->dx.cells, endcell, fb->totals[0], trace.data(), out);
@@ -2090,13 +2120,14 @@ int pagan_fb_sample_path(pagan_fb *fb, const double *u, int32_t n_u, pagan_resul
 
 } // extern "C"
 
-// ---- K sampled paths per pair on the device (pg_fb_sample, dp_fb_sample.inc) ----
+// ---- paths on the device: K sampled per pair (pg_fb_sample, dp_fb_sample.inc), or the decoded one (dp_fb_decode.inc) ----
 // One allocation serves a whole batch call -- the job records, the launch records, every pair's summaries, traces and pack
-// buffer -- and lives as long as any of the batch's handles does.
+// buffer -- and lives as long as any of the batch's handles does.  What the two handles share: the pair they are paths of, the
+// traces on the device, a summary per path, and the three ways of reading a path.
 
-struct pagan_fb_samples {
+struct FbPaths {
     int device = 0;
-    int Lx = 0, Ly = 0, n_paths = 0, max_steps = 0;
+    int Lx = 0, Ly = 0, n_paths = 1, max_steps = 0;
     uint32_t flags = 0;
     const pagan_graph *L = nullptr, *R = nullptr;       // borrowed from the pagan_fb: must outlive the handle for result()
     long long cells = 0;
@@ -2105,7 +2136,66 @@ struct pagan_fb_samples {
     const int *d_trace = nullptr;                       // [group][step][lane of the group][3]; null: PAGAN_SAMPLE_NO_TRACES
     int *d_pack = nullptr;                              // [max_steps][3]: one path out of a group of several (n_paths > 1)
     std::mutex pack_mu;
-    std::vector<int32_t> summary;                       // [n_paths][FS_SUMMARY_INTS], downloaded by the batch call
+    std::vector<int32_t> summary;                       // [n_paths][FB_SUMMARY_INTS], downloaded by the batch call
+
+    void bind(const pagan_fb *fb, int paths, uint32_t flags_, const FbCall &c) {
+        device = fb->device; Lx = fb->Lx; Ly = fb->Ly; n_paths = paths; max_steps = Lx + Ly; flags = flags_;
+        L = fb->L; R = fb->R; cells = fb->dx.cells; log_fwd = fb->totals[0];
+        buf = c.buf;
+    }
+    void keep_summary(const FbCall &c, size_t off) {
+        const int32_t *sm = (const int32_t *)(c.host.data() + off);
+        summary.assign(sm, sm + (size_t)FB_SUMMARY_INTS * n_paths);
+    }
+    const int32_t *sum(int path) const { return summary.data() + (size_t)FB_SUMMARY_INTS * path; }
+    // the steps of a path; of one that is none (status 1 or 2): 0
+    int steps(int path) const { return sum(path)[FB_SUM_STATUS] == 0 ? sum(path)[FB_SUM_STEPS] : 0; }
+    double value(int path) const { double v; std::memcpy(&v, sum(path) + FB_SUM_VALUE, 8); return v; }
+
+    // path `path`'s records, contiguous, three zero ints behind them (pagan_internal_replay's format)
+    int fetch(int path, std::vector<int> *trace, int *n_steps) {
+        const int n = steps(path);
+        if (n < 0 || n > max_steps) return PAGAN_E_INTERNAL;
+        trace->assign(3 * ((size_t)n + 1), 0);
+        *n_steps = n;
+        if (n == 0) return PAGAN_OK;
+        FbDeviceScope on_device(device);
+        if (!on_device.ok) return PAGAN_E_NODEVICE;
+        const int g = path / 64, lane = path % 64, width = std::min(64, n_paths - 64 * g);
+        const int *group = d_trace + 3 * (64ll * g * max_steps);
+        if (width == 1) {                                   // (one path a group: its records are one run already)
+            FB_TRY(hipMemcpy(trace->data(), group, 12 * (size_t)n, hipMemcpyDeviceToHost));
+            return PAGAN_OK;
+        }
+        std::lock_guard<std::mutex> lock(pack_mu);
+        hipLaunchKernelGGL(pg_fb_trace_pack, dim3((unsigned)std::min((n + 255) / 256, 1024)), dim3(256), 0, nullptr, group, width, lane, n, d_pack);
+        FB_TRY(hipGetLastError());
+        FB_TRY(hipMemcpy(trace->data(), d_pack, 12 * (size_t)n, hipMemcpyDeviceToHost));
+        return PAGAN_OK;
+    }
+    // the path's cells end -> start as (i, j, state), 3 * (Lx + Ly) ints at most: pagan_fb_sample_path's `visited`
+    int visited(int path, int32_t *visited, int32_t *n_visited) {
+        std::vector<int> trace;
+        int n = 0;
+        FB_DO(fetch(path, &trace, &n));
+        fb_visited_of(trace.data(), n, visited);
+        if (n_visited) *n_visited = n;
+        return PAGAN_OK;
+    }
+    // the replay of one trace: pagan_fb_sample_path's result (score = log full probability; status 1: the unreachable result)
+    int result(int path, pagan_result *out) {
+        const int32_t *sm = sum(path);
+        if (sm[FB_SUM_STATUS] == 1) return fb_unreachable_result(L, R, cells, log_fwd, out);
+        if (sm[FB_SUM_STATUS] != 0) return PAGAN_E_INTERNAL;
+        std::vector<int> trace;
+        int endcell[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        FB_DO(fetch(path, &trace, &endcell[6]));
+        for (int k = 0; k < 5; ++k) endcell[1 + k] = sm[FB_SUM_END + k];
+        return pagan_internal_replay(L, R, cells, endcell, log_fwd, trace.data(), out);
+    }
+};
+
+struct pagan_fb_samples : FbPaths {
     float ms = 0;                                       // pg_fb_sample (HIP events), at the batch's first pair
 };
 
@@ -2113,34 +2203,10 @@ namespace {
 // bytes of one pair's part of the allocation: summaries, traces, pack buffer (each rounded up to 256)
 struct FsSizes { size_t summary, trace, pack; };
 static FsSizes fs_sizes(int Lx, int Ly, int n_paths, uint32_t flags) {
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t steps = (size_t)Lx + Ly;
     const bool traces = !(flags & PAGAN_SAMPLE_NO_TRACES);
-    return {up(4 * (size_t)FS_SUMMARY_INTS * n_paths), traces ? up(12 * (size_t)n_paths * steps) : 0, traces && n_paths > 1 ? up(12 * steps) : 0};
-}
-
-// path `path`'s records, contiguous, three zero ints behind them (pagan_internal_replay's format); *n_steps of a path that was
-// not sampled (status 1 or 2): 0
-static int fs_fetch(pagan_fb_samples *s, int path, std::vector<int> *trace, int *n_steps) {
-    const int32_t *sm = s->summary.data() + (size_t)FS_SUMMARY_INTS * path;
-    const int n = sm[0] == 0 ? sm[6] : 0;
-    if (n < 0 || n > s->max_steps) return PAGAN_E_INTERNAL;
-    trace->assign(3 * ((size_t)n + 1), 0);
-    *n_steps = n;
-    if (n == 0) return PAGAN_OK;
-    FbDeviceScope on_device(s->device);
-    if (!on_device.ok) return PAGAN_E_NODEVICE;
-    const int g = path / 64, lane = path % 64, width = std::min(64, s->n_paths - 64 * g);
-    const int *group = s->d_trace + 3 * (64ll * g * s->max_steps);
-    if (width == 1) {                                   // (one path a group: its records are one run already)
-        FB_TRY(hipMemcpy(trace->data(), group, 12 * (size_t)n, hipMemcpyDeviceToHost));
-        return PAGAN_OK;
-    }
-    std::lock_guard<std::mutex> lock(s->pack_mu);
-    hipLaunchKernelGGL(pg_fb_trace_pack, dim3((unsigned)std::min((n + 255) / 256, 1024)), dim3(256), 0, nullptr, group, width, lane, n, s->d_pack);
-    FB_TRY(hipGetLastError());
-    FB_TRY(hipMemcpy(trace->data(), s->d_pack, 12 * (size_t)n, hipMemcpyDeviceToHost));
-    return PAGAN_OK;
+    return {fb_round256(4 * (size_t)FB_SUMMARY_INTS * n_paths), traces ? fb_round256(12 * (size_t)n_paths * steps) : 0,
+            traces && n_paths > 1 ? fb_round256(12 * steps) : 0};
 }
 } // namespace
 
@@ -2152,59 +2218,43 @@ int pagan_fb_sample_paths_batch(int32_t n, pagan_fb *const *fbs, uint64_t seed, 
                                 pagan_fb_samples **out) {
     if (n < 0 || n_paths < 1 || (flags & ~PAGAN_SAMPLE_NO_TRACES) || (n > 0 && (!fbs || !nodes || !out))) return PAGAN_E_ARG;
     for (int k = 0; k < n; ++k) out[k] = nullptr;
-    for (int k = 0; k < n; ++k) if (!fbs[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
     if (n == 0) return PAGAN_OK;
-    const int device = fbs[0]->device;
-    FbDeviceScope on_device(device);
-    if (!on_device.ok) return PAGAN_E_NODEVICE;
-    size_t cur = 0;
-    auto take = [&](size_t bytes) { const size_t at = cur; cur = (cur + bytes + 255) / 256 * 256; return at; };
-    const size_t o_jobs = take((size_t)n * sizeof(PgFbJob)), o_recs = take((size_t)n * sizeof(PgFbSample));
-    const size_t in_bytes = cur;
+    FbCall c;
+    FB_DO(c.open(n, fbs));
+    const size_t o_jobs = c.take(FbCall::UP, (size_t)n * sizeof(PgFbJob)), o_recs = c.take(FbCall::UP, (size_t)n * sizeof(PgFbSample));
     std::vector<size_t> o_sum(n), o_trace(n), o_pack(n);
-    for (int k = 0; k < n; ++k) o_sum[k] = take(fs_sizes(fbs[k]->Lx, fbs[k]->Ly, n_paths, flags).summary);
-    const size_t sum_end = cur;
+    for (int k = 0; k < n; ++k) o_sum[k] = c.take(FbCall::DOWN, fs_sizes(fbs[k]->Lx, fbs[k]->Ly, n_paths, flags).summary);
     for (int k = 0; k < n; ++k) {
         const FsSizes z = fs_sizes(fbs[k]->Lx, fbs[k]->Ly, n_paths, flags);
-        o_trace[k] = take(z.trace); o_pack[k] = take(z.pack);
+        o_trace[k] = c.take(FbCall::DEVICE, z.trace); o_pack[k] = c.take(FbCall::DEVICE, z.pack);
     }
-    std::shared_ptr<FbDevBuf> buf = std::make_shared<FbDevBuf>();
-    FB_DO(buf->alloc(cur));
+    FB_DO(c.alloc());
     const bool traces = !(flags & PAGAN_SAMPLE_NO_TRACES);
     const int groups = (n_paths + 63) / 64;
-    std::vector<char> host(sum_end, 0);
     for (int k = 0; k < n; ++k) {
         PgFbSample R;
         R.key = fb_splitmix64(fb_splitmix64(seed) ^ (uint64_t)(int64_t)nodes[k]);
         R.n_paths = n_paths; R.groups = groups; R.max_steps = fbs[k]->Lx + fbs[k]->Ly; R.pad = 0;
-        R.trace = traces ? (int *)(buf->h + o_trace[k]) : nullptr;
-        R.summary = (int *)(buf->h + o_sum[k]);
-        std::memcpy(host.data() + o_jobs + (size_t)k * sizeof(PgFbJob), &fbs[k]->job, sizeof(PgFbJob));
-        std::memcpy(host.data() + o_recs + (size_t)k * sizeof(PgFbSample), &R, sizeof(R));
+        R.trace = traces ? c.dev<int>(o_trace[k]) : nullptr;
+        R.summary = c.dev<int>(o_sum[k]);
+        c.put(o_jobs + (size_t)k * sizeof(PgFbJob), fbs[k]->job);
+        c.put(o_recs + (size_t)k * sizeof(PgFbSample), R);
     }
-    FbEvent e0, e1;
-    float ms = 0;
-    FB_TRY(hipMemcpy(buf->h, host.data(), in_bytes, hipMemcpyHostToDevice));
-    FB_DO(e0.create()); FB_DO(e1.create());
-    FB_TRY(hipEventRecord(e0, nullptr));
+    FB_DO(c.upload());
+    FB_DO(c.begin());
     for (int at = 0; at < n; at += 65535) {                    // (a grid's y extent)
         const dim3 grid((unsigned)groups, (unsigned)std::min(65535, n - at));
-        hipLaunchKernelGGL(pg_fb_sample, grid, dim3(64), 0, nullptr, (const PgFbJob *)(buf->h + o_jobs) + at, (const PgFbSample *)(buf->h + o_recs) + at);
+        hipLaunchKernelGGL(pg_fb_sample, grid, dim3(64), 0, nullptr, c.dev<const PgFbJob>(o_jobs) + at, c.dev<const PgFbSample>(o_recs) + at);
     }
-    FB_TRY(hipGetLastError());
-    FB_TRY(hipEventRecord(e1, nullptr));
-    FB_TRY(hipMemcpy(host.data() + in_bytes, buf->h + in_bytes, sum_end - in_bytes, hipMemcpyDeviceToHost));
-    (void)hipEventElapsedTime(&ms, e0, e1);
+    FB_DO(c.end());
+    FB_DO(c.download());
     for (int k = 0; k < n; ++k) {
         pagan_fb_samples *s = new pagan_fb_samples();
-        s->device = device; s->Lx = fbs[k]->Lx; s->Ly = fbs[k]->Ly; s->n_paths = n_paths; s->max_steps = s->Lx + s->Ly; s->flags = flags;
-        s->L = fbs[k]->L; s->R = fbs[k]->R; s->cells = fbs[k]->dx.cells; s->log_fwd = fbs[k]->totals[0];
-        s->buf = buf;
-        s->d_trace = traces ? (const int *)(buf->h + o_trace[k]) : nullptr;
-        s->d_pack = traces && n_paths > 1 ? (int *)(buf->h + o_pack[k]) : nullptr;
-        const int32_t *sm = (const int32_t *)(host.data() + o_sum[k]);
-        s->summary.assign(sm, sm + (size_t)FS_SUMMARY_INTS * n_paths);
-        s->ms = k == 0 ? ms : 0.0f;
+        s->bind(fbs[k], n_paths, flags, c);
+        s->d_trace = traces ? c.dev<const int>(o_trace[k]) : nullptr;
+        s->d_pack = traces && n_paths > 1 ? c.dev<int>(o_pack[k]) : nullptr;
+        s->keep_summary(c, o_sum[k]);
+        s->ms = k == 0 ? c.ms(0) : 0.0f;
         out[k] = s;
     }
     return PAGAN_OK;
@@ -2219,27 +2269,20 @@ int pagan_fb_samples_summary(const pagan_fb_samples *s, int32_t *status, int32_t
                              double *log_q) {
     if (!s) return PAGAN_E_ARG;
     for (int p = 0; p < s->n_paths; ++p) {
-        const int32_t *sm = s->summary.data() + (size_t)FS_SUMMARY_INTS * p;
-        if (status) status[p] = sm[0];
-        if (n_steps) n_steps[p] = sm[6];
-        if (n_m) n_m[p] = sm[7];
-        if (n_x) n_x[p] = sm[8];
-        if (n_y) n_y[p] = sm[9];
-        if (log_q) std::memcpy(&log_q[p], sm + 10, 8);
+        const int32_t *sm = s->sum(p);
+        if (status) status[p] = sm[FB_SUM_STATUS];
+        if (n_steps) n_steps[p] = sm[FB_SUM_STEPS];
+        if (n_m) n_m[p] = sm[FB_SUM_M];
+        if (n_x) n_x[p] = sm[FB_SUM_X];
+        if (n_y) n_y[p] = sm[FB_SUM_Y];
+        if (log_q) log_q[p] = s->value(p);
     }
     return PAGAN_OK;
 }
 
-// the path's cells end -> start as (i, j, state), 3 * (Lx + Ly) ints at most: pagan_fb_sample_path's `visited`
 int pagan_fb_samples_visited(pagan_fb_samples *s, int32_t path, int32_t *visited, int32_t *n_visited) {
     if (!s || !s->d_trace || path < 0 || path >= s->n_paths || !visited) return PAGAN_E_ARG;
-    std::vector<int> trace;
-    int n = 0;
-    const int rc = fs_fetch(s, path, &trace, &n);
-    if (rc != PAGAN_OK) return rc;
-    for (int t = 0; t < n; ++t) { visited[3 * t] = trace[3 * t]; visited[3 * t + 1] = trace[3 * t + 1]; visited[3 * t + 2] = trace[3 * t + 2] & 3; }
-    if (n_visited) *n_visited = n;
-    return PAGAN_OK;
+    return s->visited(path, visited, n_visited);
 }
 
 // every path's cells in ONE copy of the trace buffer: visited [n_paths][Lx + Ly][3] (rows behind a path's last step: 0),
@@ -2252,8 +2295,7 @@ int pagan_fb_samples_visited_all(pagan_fb_samples *s, int32_t *visited, int32_t 
     std::vector<int32_t> raw(3 * (size_t)s->n_paths * ms);
     if (!raw.empty()) FB_TRY(hipMemcpy(raw.data(), s->d_trace, 4 * raw.size(), hipMemcpyDeviceToHost));
     for (int p = 0; p < s->n_paths; ++p) {
-        const int32_t *sm = s->summary.data() + (size_t)FS_SUMMARY_INTS * p;
-        const int n = sm[0] == 0 ? sm[6] : 0;
+        const int n = s->steps(p);
         if (n < 0 || n > s->max_steps) return PAGAN_E_INTERNAL;
         const int g = p / 64, lane = p % 64, width = std::min(64, s->n_paths - 64 * g);
         const int32_t *group = raw.data() + 3 * (64 * (size_t)g * ms);
@@ -2268,23 +2310,9 @@ int pagan_fb_samples_visited_all(pagan_fb_samples *s, int32_t *visited, int32_t 
     return PAGAN_OK;
 }
 
-// the replay of one trace: pagan_fb_sample_path's result (score = log full probability; status 1: the unreachable result)
 int pagan_fb_samples_result(pagan_fb_samples *s, int32_t path, pagan_result *out) {
     if (!s || !s->d_trace || path < 0 || path >= s->n_paths || !out) return PAGAN_E_ARG;
-    const int32_t *sm = s->summary.data() + (size_t)FS_SUMMARY_INTS * path;
-    int endcell[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (sm[0] == 1) {
-        endcell[0] = 1; endcell[4] = endcell[5] = -1;
-        return pagan_internal_replay(s->L, s->R, s->cells, endcell, s->log_fwd, nullptr, out);
-    }
-    if (sm[0] != 0) return PAGAN_E_INTERNAL;
-    std::vector<int> trace;
-    int n = 0;
-    const int rc = fs_fetch(s, path, &trace, &n);
-    if (rc != PAGAN_OK) return rc;
-    for (int k = 1; k <= 5; ++k) endcell[k] = sm[k];
-    endcell[6] = n;
-    return pagan_internal_replay(s->L, s->R, s->cells, endcell, s->log_fwd, trace.data(), out);
+    return s->result(path, out);
 }
 
 int pagan_fb_samples_ms(const pagan_fb_samples *s, double *ms) {
@@ -2313,41 +2341,23 @@ void pagan_fb_destroy(pagan_fb *fb) {
 
 // ---- posterior decoding: the maximum expected accuracy path of a finished pass (dp_fb_decode.inc) ----
 // A pair's score matrix A (24 B a cell) is an arena of its own from fb_arena_pool: it goes back to the pool behind the trace
-// unless the caller keeps it (PAGAN_DECODE_KEEP_MATRIX).  One further allocation serves a whole batch call -- the job records,
-// the launch records, every pair's summary and trace -- and lives as long as any of the batch's handles does.
+// unless the caller keeps it (PAGAN_DECODE_KEEP_MATRIX).  The handle is a path handle of one path, [max_steps][3].
 
-struct pagan_fb_decoded {
-    int device = 0;
-    int Lx = 0, Ly = 0, max_steps = 0;
-    uint32_t flags = 0;
-    const pagan_graph *L = nullptr, *R = nullptr;       // borrowed from the pagan_fb: must outlive the handle for result()
-    long long cells = 0;
-    double log_fwd = 0;
+struct pagan_fb_decoded : FbPaths {
     DiagIndex dx;                                       // kept matrix only: where a cell sits (pagan_fb_decoded_dump)
     char *arena = nullptr;                              // A; null once it went back to the pool
     size_t arena_cap = 0;
-    std::shared_ptr<FbDevBuf> buf;
-    const int *d_trace = nullptr;                       // [max_steps][3]
-    int32_t summary[FD_SUMMARY_INTS] = {0};
     float ms[2] = {0, 0};                               // fill, trace (HIP events), at the batch's first pair
     int schedule = 0;                                   // 0 pg_fb_decode_fill, 1 pg_fb_ring_decode
     ~pagan_fb_decoded() { if (arena) fb_arena_pool.give(device, arena, arena_cap); }
 };
 
 namespace {
-// the trace's records, three zero ints behind them (pagan_internal_replay's format)
-static int fd_fetch(pagan_fb_decoded *d, std::vector<int> *trace, int *n_steps) {
-    const int n = d->summary[0] == 0 ? d->summary[6] : 0;
-    if (n < 0 || n > d->max_steps) return PAGAN_E_INTERNAL;
-    trace->assign(3 * ((size_t)n + 1), 0);
-    *n_steps = n;
-    if (n == 0) return PAGAN_OK;
-    FbDeviceScope on_device(d->device);
-    if (!on_device.ok) return PAGAN_E_NODEVICE;
-    FB_TRY(hipMemcpy(trace->data(), d->d_trace, 12 * (size_t)n, hipMemcpyDeviceToHost));
-    return PAGAN_OK;
+// bytes a pair's decode takes: the matrix A (an arena of the pool's), and of the call's allocation the summary and the trace
+struct FdSizes { size_t matrix, summary, trace; };
+static FdSizes fd_sizes(long long cells, int Lx, int Ly) {
+    return {24 * (size_t)cells, fb_round256(4 * FB_SUMMARY_INTS), fb_round256(12 * ((size_t)Lx + Ly))};
 }
-static size_t fd_up(size_t b) { return (b + 255) / 256 * 256; }
 // waits for the default stream when a call leaves, by whichever return: a handle's matrix must not reach fb_arena_pool (whose next
 // take would hand it out) while a kernel may still be writing it
 struct FdStreamWait { ~FdStreamWait() { (void)hipStreamSynchronize(nullptr); } };
@@ -2360,11 +2370,9 @@ extern "C" {
 int pagan_fb_decode_batch(int32_t n, pagan_fb *const *fbs, double gap_weight, uint32_t flags, pagan_fb_decoded **out) {
     if (n < 0 || (flags & ~PAGAN_DECODE_KEEP_MATRIX) || !(gap_weight >= 0.0) || !(gap_weight < HUGE_VAL) || (n > 0 && (!fbs || !out))) return PAGAN_E_ARG;
     for (int k = 0; k < n; ++k) out[k] = nullptr;
-    for (int k = 0; k < n; ++k) if (!fbs[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
     if (n == 0) return PAGAN_OK;
-    const int device = fbs[0]->device;
-    FbDeviceScope on_device(device);
-    if (!on_device.ok) return PAGAN_E_NODEVICE;
+    FbCall c;
+    FB_DO(c.open(n, fbs));
     // launch order: the fill pairs, then the ring pairs by workgroup size and by whether their score table needs looking at
     std::vector<int> block(n, 0), order(n), tabfin(n, 1);
     for (int k = 0; k < n; ++k) {
@@ -2378,50 +2386,39 @@ int pagan_fb_decode_batch(int32_t n, pagan_fb *const *fbs, double gap_weight, ui
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return launch_key(a) < launch_key(b); });
     std::vector<std::unique_ptr<pagan_fb_decoded>> hs(n);
     FdStreamWait wait_on_exit;                                   // (declared behind the handles: runs before they are destroyed)
-    size_t cur = 0;
-    auto take = [&](size_t bytes) { const size_t at = cur; cur = fd_up(cur + bytes); return at; };
-    const size_t o_jobs = take((size_t)n * sizeof(PgFbJob)), o_recs = take((size_t)n * sizeof(PgFbDecode));
-    const size_t in_bytes = cur;
+    const size_t o_jobs = c.take(FbCall::UP, (size_t)n * sizeof(PgFbJob)), o_recs = c.take(FbCall::UP, (size_t)n * sizeof(PgFbDecode));
     std::vector<size_t> o_sum(n), o_trace(n);
-    for (int k = 0; k < n; ++k) o_sum[k] = take(4 * FD_SUMMARY_INTS);
-    const size_t sum_end = cur;
-    for (int k = 0; k < n; ++k) o_trace[k] = take(12 * ((size_t)fbs[k]->Lx + fbs[k]->Ly));
-    std::shared_ptr<FbDevBuf> buf = std::make_shared<FbDevBuf>();
-    FB_DO(buf->alloc(cur));
-    std::vector<char> host(sum_end, 0);
+    for (int k = 0; k < n; ++k) o_sum[k] = c.take(FbCall::DOWN, fd_sizes(fbs[k]->dx.cells, fbs[k]->Lx, fbs[k]->Ly).summary);
+    for (int k = 0; k < n; ++k) o_trace[k] = c.take(FbCall::DEVICE, fd_sizes(fbs[k]->dx.cells, fbs[k]->Lx, fbs[k]->Ly).trace);
+    FB_DO(c.alloc());
     int fill_block = 64, n_fill = 0;
     for (int q = 0; q < n; ++q) {
         const int k = order[q];
         const pagan_fb *fb = fbs[k];
         hs[k].reset(new pagan_fb_decoded());
         pagan_fb_decoded *d = hs[k].get();
-        d->device = device; d->Lx = fb->Lx; d->Ly = fb->Ly; d->max_steps = fb->Lx + fb->Ly; d->flags = flags;
-        d->L = fb->L; d->R = fb->R; d->cells = fb->dx.cells; d->log_fwd = fb->totals[0];
+        d->bind(fb, 1, flags, c);
         d->schedule = block[k] ? 1 : 0;
-        d->arena = fb_arena_pool.take(device, 24 * (size_t)fb->dx.cells, &d->arena_cap);
+        d->arena = fb_arena_pool.take(d->device, fd_sizes(fb->dx.cells, fb->Lx, fb->Ly).matrix, &d->arena_cap);
         if (!d->arena) return PAGAN_E_NOMEM;
         if (flags & PAGAN_DECODE_KEEP_MATRIX) d->dx = fb->dx;
-        d->buf = buf;
-        d->d_trace = (const int *)(buf->h + o_trace[k]);
+        d->d_trace = c.dev<const int>(o_trace[k]);
         PgFbDecode R;
-        R.g = gap_weight; R.A = (double *)d->arena; R.trace = (int *)(buf->h + o_trace[k]); R.summary = (int *)(buf->h + o_sum[k]);
+        R.g = gap_weight; R.A = (double *)d->arena; R.trace = c.dev<int>(o_trace[k]); R.summary = c.dev<int>(o_sum[k]);
         R.max_steps = d->max_steps;
         R.tab_finite = tabfin[k];
-        std::memcpy(host.data() + o_jobs + (size_t)q * sizeof(PgFbJob), &fb->job, sizeof(PgFbJob));
-        std::memcpy(host.data() + o_recs + (size_t)q * sizeof(PgFbDecode), &R, sizeof(R));
+        c.put(o_jobs + (size_t)q * sizeof(PgFbJob), fb->job);
+        c.put(o_recs + (size_t)q * sizeof(PgFbDecode), R);
         if (!block[k]) {
             const int mw = fb->dx.max_width;
             fill_block = std::max(fill_block, mw >= 768 ? 1024 : mw >= 384 ? 512 : mw >= 192 ? 256 : (mw >= 96 ? 128 : 64));
             ++n_fill;
         }
     }
-    const PgFbJob *jobs = (const PgFbJob *)(buf->h + o_jobs);
-    const PgFbDecode *recs = (const PgFbDecode *)(buf->h + o_recs);
-    FbEvent e0, e1, e2;
-    float ms[2] = {0, 0};
-    FB_TRY(hipMemcpy(buf->h, host.data(), in_bytes, hipMemcpyHostToDevice));
-    FB_DO(e0.create()); FB_DO(e1.create()); FB_DO(e2.create());
-    FB_TRY(hipEventRecord(e0, nullptr));
+    const PgFbJob *jobs = c.dev<const PgFbJob>(o_jobs);
+    const PgFbDecode *recs = c.dev<const PgFbDecode>(o_recs);
+    FB_DO(c.upload());
+    FB_DO(c.begin());
     if (n_fill > 0) hipLaunchKernelGGL(pg_fb_decode_fill, dim3((unsigned)n_fill), dim3((unsigned)fill_block), 0, nullptr, jobs, recs);
     for (int q = n_fill; q < n;) {
         const int b = block[order[q]], key = launch_key(order[q]);
@@ -2434,19 +2431,16 @@ int pagan_fb_decode_batch(int32_t n, pagan_fb *const *fbs, double gap_weight, ui
         else hipLaunchKernelGGL((pg_fb_ring_decode<512, true>), grid, blk, 0, nullptr, jobs + q, recs + q);
         q = e;
     }
-    FB_TRY(hipGetLastError());
-    FB_TRY(hipEventRecord(e1, nullptr));
+    FB_DO(c.end());
+    FB_DO(c.begin());
     hipLaunchKernelGGL(pg_fb_decode_trace, dim3((unsigned)n), dim3(64), 0, nullptr, jobs, recs);
-    FB_TRY(hipGetLastError());
-    FB_TRY(hipEventRecord(e2, nullptr));
-    FB_TRY(hipMemcpy(host.data() + in_bytes, buf->h + in_bytes, sum_end - in_bytes, hipMemcpyDeviceToHost));
-    (void)hipEventElapsedTime(&ms[0], e0, e1);
-    (void)hipEventElapsedTime(&ms[1], e1, e2);
+    FB_DO(c.end());
+    FB_DO(c.download());
     for (int k = 0; k < n; ++k) {
         pagan_fb_decoded *d = hs[k].get();
-        std::memcpy(d->summary, host.data() + o_sum[k], 4 * FD_SUMMARY_INTS);
-        if (k == 0) { d->ms[0] = ms[0]; d->ms[1] = ms[1]; }
-        if (!(flags & PAGAN_DECODE_KEEP_MATRIX)) { fb_arena_pool.give(device, d->arena, d->arena_cap); d->arena = nullptr; }
+        d->keep_summary(c, o_sum[k]);
+        if (k == 0) { d->ms[0] = c.ms(0); d->ms[1] = c.ms(1); }
+        if (!(flags & PAGAN_DECODE_KEEP_MATRIX)) { fb_arena_pool.give(d->device, d->arena, d->arena_cap); d->arena = nullptr; }
     }
     for (int k = 0; k < n; ++k) out[k] = hs[k].release();
     return PAGAN_OK;
@@ -2460,42 +2454,23 @@ int pagan_fb_decode(pagan_fb *fb, double gap_weight, uint32_t flags, pagan_fb_de
 int pagan_fb_decoded_summary(const pagan_fb_decoded *d, int32_t *status, double *objective, int32_t *n_steps, int32_t counts[3],
                              int32_t *schedule) {
     if (!d) return PAGAN_E_ARG;
-    if (status) *status = d->summary[0];
-    if (objective) std::memcpy(objective, d->summary + 10, 8);
-    if (n_steps) *n_steps = d->summary[6];
-    if (counts) { counts[0] = d->summary[7]; counts[1] = d->summary[8]; counts[2] = d->summary[9]; }
+    const int32_t *sm = d->sum(0);
+    if (status) *status = sm[FB_SUM_STATUS];
+    if (objective) *objective = d->value(0);
+    if (n_steps) *n_steps = sm[FB_SUM_STEPS];
+    if (counts) { counts[0] = sm[FB_SUM_M]; counts[1] = sm[FB_SUM_X]; counts[2] = sm[FB_SUM_Y]; }
     if (schedule) *schedule = d->schedule;
     return PAGAN_OK;
 }
 
-// the path's cells end -> start as (i, j, state), 3 * (Lx + Ly) ints at most: pagan_fb_sample_path's `visited`
 int pagan_fb_decoded_visited(pagan_fb_decoded *d, int32_t *visited, int32_t *n_visited) {
     if (!d || !visited) return PAGAN_E_ARG;
-    std::vector<int> trace;
-    int n = 0;
-    const int rc = fd_fetch(d, &trace, &n);
-    if (rc != PAGAN_OK) return rc;
-    for (int t = 0; t < n; ++t) { visited[3 * t] = trace[3 * t]; visited[3 * t + 1] = trace[3 * t + 1]; visited[3 * t + 2] = trace[3 * t + 2] & 3; }
-    if (n_visited) *n_visited = n;
-    return PAGAN_OK;
+    return d->visited(0, visited, n_visited);
 }
 
-// the replay of the trace: a result of a sampled path's shape (score = log full probability; status 1: the unreachable result)
 int pagan_fb_decoded_result(pagan_fb_decoded *d, pagan_result *out) {
     if (!d || !out) return PAGAN_E_ARG;
-    int endcell[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (d->summary[0] == 1) {
-        endcell[0] = 1; endcell[4] = endcell[5] = -1;
-        return pagan_internal_replay(d->L, d->R, d->cells, endcell, d->log_fwd, nullptr, out);
-    }
-    if (d->summary[0] != 0) return PAGAN_E_INTERNAL;
-    std::vector<int> trace;
-    int n = 0;
-    const int rc = fd_fetch(d, &trace, &n);
-    if (rc != PAGAN_OK) return rc;
-    for (int k = 1; k <= 5; ++k) endcell[k] = d->summary[k];
-    endcell[6] = n;
-    return pagan_internal_replay(d->L, d->R, d->cells, endcell, d->log_fwd, trace.data(), out);
+    return d->result(0, out);
 }
 
 // dst [Lx][Ly][3] row-major, state order X, Y, M; -inf outside the band
@@ -2535,13 +2510,13 @@ int pagan_fb_debug_decode_route(const pagan_graph *left, const pagan_graph *righ
     return fb_decode_route(left, right, Lx, Ly, dx);
 }
 
-// What a decode takes beside the pair's own arena: A (24 B a cell, with the pool's allowance of a sixteenth), 12 B a path step,
-// the summary and the records.
+// What a decode takes beside the pair's own arena: A with the pool's allowance of a sixteenth (FbArenaPool::take), 12 B a path
+// step, the summary and the records.
 int64_t pagan_fb_decode_predict_bytes(int32_t left_sites, int32_t right_sites, const pagan_band *band) {
     const int64_t cells = pagan_dp_count_cells(left_sites, right_sites, band);
     if (cells < 0) return cells;
-    const int64_t a = 24 * cells;
-    return a + a / 16 + (int64_t)fd_up(12 * ((size_t)left_sites + right_sites - 2)) + (int64_t)(fd_up(4 * FD_SUMMARY_INTS) + sizeof(PgFbJob) + sizeof(PgFbDecode) + 1024);
+    const FdSizes z = fd_sizes(cells, left_sites - 1, right_sites - 1);
+    return (int64_t)(z.matrix + z.matrix / 16 + z.trace + z.summary + sizeof(PgFbJob) + sizeof(PgFbDecode) + 1024);
 }
 
 void pagan_fb_decoded_destroy(pagan_fb_decoded *d) { delete d; }

@@ -18,14 +18,13 @@
 // FD_PRE diagonals ahead.  pg_fb_decode_trace: the walk back, one wave a pair and one lane walking; it re-derives every maximum
 // from A (same candidates, same rule) and writes the records pagan_internal_replay takes.
 
-#define FD_SUMMARY_INTS 16           // status, end state, i, j, k1, k2, steps, n_m, n_x, n_y, objective (two ints), four spare
 #define FD_PRE 4                     // diagonals a ring step's own F / B are requested ahead of their use (divides FB_RG_REFILL)
 
 struct PgFbDecode {
     double g;                        // gap weight
     double *A;                       // [cells][3]
     int *trace;                      // [max_steps][3]
-    int *summary;                    // [FD_SUMMARY_INTS]
+    int *summary;                    // [FB_SUMMARY_INTS]: pg_fb_sample's layout, the objective where that has log_q
     int max_steps;                   // Lx + Ly
     int tab_finite;                  // every entry of the score table has a finite log (then no step looks one up)
 };
@@ -327,9 +326,10 @@ __global__ __launch_bounds__(64) void pg_fb_decode_trace(const PgFbJob *jobs, co
         n_m += state == PAGAN_M_MAT; n_x += state == PAGAN_X_MAT; n_y += state == PAGAN_Y_MAT;
         state = ps; i = pi; j = pj;
     }
-    out[0] = status; out[1] = e_state; out[2] = e_i; out[3] = e_j; out[4] = e_k1; out[5] = e_k2;
-    out[6] = steps; out[7] = n_m; out[8] = n_x; out[9] = n_y;
+    out[FB_SUM_STATUS] = status;
+    out[FB_SUM_END] = e_state; out[FB_SUM_END + 1] = e_i; out[FB_SUM_END + 2] = e_j; out[FB_SUM_END + 3] = e_k1; out[FB_SUM_END + 4] = e_k2;
+    out[FB_SUM_STEPS] = steps; out[FB_SUM_M] = n_m; out[FB_SUM_X] = n_x; out[FB_SUM_Y] = n_y;
     const long long ob = __double_as_longlong(objective);
-    out[10] = (int)(unsigned)(ob & 0xffffffffll); out[11] = (int)(unsigned)((unsigned long long)ob >> 32);
+    out[FB_SUM_VALUE] = (int)(unsigned)(ob & 0xffffffffll); out[FB_SUM_VALUE + 1] = (int)(unsigned)((unsigned long long)ob >> 32);
     out[12] = out[13] = out[14] = out[15] = 0;
 }

@@ -24,19 +24,17 @@
 // Outputs.  Per path and step one record (i, j, word), word = state | k1 << 4 | k2 << 18 as the host packs it: what
 // pagan_internal_replay takes.  Trace layout: [group][step][lane of the group], a group of w = min(64, K - 64 g) paths holding
 // w * max_steps records from record 64 g * max_steps on -- the lanes at one step write one contiguous run, K paths take exactly
-// 12 K (Lx + Ly) bytes, and a single path (the tree walk's) is contiguous.  Per path a summary of FS_SUMMARY_INTS ints: status
+// 12 K (Lx + Ly) bytes, and a single path (the tree walk's) is contiguous.  Per path a summary of FB_SUMMARY_INTS ints (dp_fb.hip names them): status
 // (0 sampled, 1 full probability zero, 2 internal: no candidate, or more than Lx + Ly steps), the end cell (state, i, j, k1, k2),
 // the step count, the counts of M, X and Y steps, and log_q = the sum over the picks, the end corner's included, of
 // (lw_k - hi) - log(total) = log(exp(lw_k - hi) / total): the log posterior probability of the path.
-
-#define FS_SUMMARY_INTS 16           // status, end state, i, j, k1, k2, steps, n_m, n_x, n_y, log_q (two ints), four spare
 
 struct PgFbSample {
     unsigned long long key;          // mix(mix(seed) ^ node)
     int n_paths, groups, max_steps;  // K, ceil(K / 64), Lx + Ly
     int pad;
     int *trace;                      // null: summaries only (PAGAN_SAMPLE_NO_TRACES)
-    int *summary;                    // [n_paths][FS_SUMMARY_INTS]
+    int *summary;                    // [n_paths][FB_SUMMARY_INTS]
 };
 
 typedef const __attribute__((address_space(1))) int *fs_gi;
@@ -197,7 +195,7 @@ __global__ __launch_bounds__(64) void pg_fb_sample(const PgFbJob *jobs, const Pg
     if (path >= R.n_paths) return;
     const int width = min(64, R.n_paths - 64 * (int)blockIdx.x);   // paths of this group
     const fs_go trace = R.trace ? (fs_go)(unsigned long long)R.trace + 3 * (64ll * blockIdx.x * R.max_steps + lane) : (fs_go)0;
-    const fs_go out = (fs_go)(unsigned long long)R.summary + (long long)FS_SUMMARY_INTS * path;
+    const fs_go out = (fs_go)(unsigned long long)R.summary + (long long)FB_SUMMARY_INTS * path;
     const double NI = ninf();
     double log_q = 0.0, tot_prod = 1.0;
     int status = 0, steps = 0, n_m = 0, n_x = 0, n_y = 0;
@@ -268,10 +266,11 @@ __global__ __launch_bounds__(64) void pg_fb_sample(const PgFbJob *jobs, const Pg
         state = P.state; i = P.i; j = P.j;
     }
     log_q -= log(tot_prod);
-    out[0] = status; out[1] = e_state; out[2] = e_i; out[3] = e_j; out[4] = e_k1; out[5] = e_k2;
-    out[6] = steps; out[7] = n_m; out[8] = n_x; out[9] = n_y;
+    out[FB_SUM_STATUS] = status;
+    out[FB_SUM_END] = e_state; out[FB_SUM_END + 1] = e_i; out[FB_SUM_END + 2] = e_j; out[FB_SUM_END + 3] = e_k1; out[FB_SUM_END + 4] = e_k2;
+    out[FB_SUM_STEPS] = steps; out[FB_SUM_M] = n_m; out[FB_SUM_X] = n_x; out[FB_SUM_Y] = n_y;
     const long long lq = __double_as_longlong(log_q);
-    out[10] = (int)(unsigned)(lq & 0xffffffffll); out[11] = (int)(unsigned)((unsigned long long)lq >> 32);
+    out[FB_SUM_VALUE] = (int)(unsigned)(lq & 0xffffffffll); out[FB_SUM_VALUE + 1] = (int)(unsigned)((unsigned long long)lq >> 32);
     out[12] = out[13] = out[14] = out[15] = 0;
 }
 

@@ -242,153 +242,193 @@ int host_threads_of(const pagan_msa *m);
 // Posterior decoding (pagan_msa_set_decoder): no Viterbi batch either; the sub-batches are cut by pagan_fb_predict_bytes +
 // pagan_fb_decode_predict_bytes, each goes through one pagan_fb_decode_batch behind its sweeps, and a node's result is the
 // replay of its decoded path (score = log full probability, support along that path, the same retry without the band).
+// In four steps: fb_cut, fb_sweeps, fb_paths + fb_node, fb_readers.
+
+// what the pass does beside the sweeps: where a node's path comes from (path: from this pass at all), which readers run
+struct FbMode {
+    bool decode, path, device_sampler, marg, counts;
+    explicit FbMode(const pagan_msa *m)
+        : decode(m->decode_on != 0), path(m->opts.sample_path != 0 || decode), device_sampler(path && !decode && m->sample_on_device != 0),
+          marg(m->opts.full_probability == 2), counts(m->counts_on != 0) {}
+};
+
+// A sub-batch: its nodes (indices into m->work) and their handles, destroyed with it on every exit
+struct FbSub {
+    std::vector<int> which;
+    std::vector<pagan_fb *> fbs;
+    std::vector<pagan_fb_samples *> smp;
+    std::vector<pagan_fb_decoded *> dec;
+    std::vector<char> again;                 // banded, full probability 0: goes to `retry`
+    double smp_ms = 0, dec_ms = 0;
+    explicit FbSub(const std::vector<int> &nodes)
+        : which(nodes), fbs(nodes.size(), nullptr), smp(nodes.size(), nullptr), dec(nodes.size(), nullptr), again(nodes.size(), 0) {}
+    FbSub(const FbSub &) = delete;
+    ~FbSub() {                               // the path handles before the passes they are paths of
+        for (pagan_fb_decoded *d : dec) pagan_fb_decoded_destroy(d);
+        for (pagan_fb_samples *s : smp) pagan_fb_samples_destroy(s);
+        for (pagan_fb *fb : fbs) pagan_fb_destroy(fb);
+    }
+};
+
+// the nodes of ks from *at on that fit the budget together (one at least), by the sum of the mode's predictors
+int fb_cut(const pagan_msa *m, const FbMode &md, const std::vector<int> &ks, size_t *at, int64_t budget, std::vector<int> *which) {
+    int64_t used = 0;
+    for (; *at < ks.size(); ++*at) {
+        const NodeWork &w = m->work[ks[*at]];
+        const pagan_band *band = w.banded ? &w.pb : nullptr;
+        int64_t need = pagan_fb_predict_bytes(w.gl.n_sites, w.gr.n_sites, band);
+        if (need < 0) return (int)need;
+        if (md.decode) {
+            const int64_t more = pagan_fb_decode_predict_bytes(w.gl.n_sites, w.gr.n_sites, band);
+            if (more < 0) return (int)more;
+            need += more;
+        } else if (md.device_sampler) need += pagan_fb_sample_predict_bytes(w.gl.n_sites, w.gr.n_sites, 1, 0);    // (the path's trace)
+        if (md.counts) need += pagan_fb_counts_predict_bytes(w.gl.n_sites, w.gr.n_sites, m->mf.S);
+        if (need > budget) return PAGAN_E_MEMCAP;
+        if (!which->empty() && used + need > budget) break;
+        used += need;
+        which->push_back(ks[*at]);
+    }
+    return PAGAN_OK;
+}
+
+int fb_sweeps(pagan_msa *m, FbSub &sb, int dev) {
+    const int n = (int)sb.which.size();
+    pagan_opts po;
+    po.flags = 0; po.device = dev;
+    std::vector<pagan_model_prob> mp(n);
+    std::vector<const pagan_graph *> gl(n), gr(n);
+    std::vector<const pagan_model_prob *> mpp(n);
+    std::vector<const pagan_band *> bd(n);
+    for (int q = 0; q < n; ++q) {
+        NodeWork &w = m->work[sb.which[q]];
+        mp[q] = w.model->prob_view();
+        gl[q] = &w.gl; gr[q] = &w.gr; mpp[q] = &mp[q]; bd[q] = w.banded ? &w.pb : nullptr;
+    }
+    return pagan_fb_run_batch(n, gl.data(), gr.data(), mpp.data(), bd.data(), &po, sb.fbs.data());
+}
+
+// the sub-batch's paths where the device makes them: one call of the decoder or of the sampler, and its time
+int fb_paths(pagan_msa *m, const FbMode &md, FbSub &sb) {
+    const int n = (int)sb.which.size();
+    int rc = PAGAN_OK;
+    if (md.decode) {
+        double dms[2] = {0, 0};
+        rc = pagan_fb_decode_batch(n, sb.fbs.data(), m->decode_gap, 0, sb.dec.data());
+        if (rc == PAGAN_OK) rc = pagan_fb_decoded_ms(sb.dec[0], dms);
+        sb.dec_ms = dms[0] + dms[1];
+    } else if (md.device_sampler) {
+        std::vector<int32_t> ids(n);
+        for (int q = 0; q < n; ++q) ids[q] = m->work[sb.which[q]].node;
+        rc = pagan_fb_sample_paths_batch(n, sb.fbs.data(), m->opts.sample_seed, ids.data(), 1, 0, sb.smp.data());
+        if (rc == PAGAN_OK) rc = pagan_fb_samples_ms(sb.smp[0], &sb.smp_ms);
+    }
+    return rc;
+}
+
+// node q: the totals; where this pass gives the path, the result from its source (the decoder, the device's sampler, the host's);
+// the support of the path's columns
+int fb_node(pagan_msa *m, const FbMode &md, FbSub &sb, int q) {
+    NodeWork &w = m->work[sb.which[q]];
+    double ms[2] = {0, 0};
+    int r = pagan_fb_totals(sb.fbs[q], &w.log_fwd, &w.log_bwd, nullptr);
+    if (r == PAGAN_OK) r = pagan_fb_kernel_ms(sb.fbs[q], ms);
+    w.fb_sweep_ms = ms[0] + ms[1]; w.fb_post_ms = 0;
+    w.has_marg = false; w.support.clear(); w.has_dec = false;
+    if (r == PAGAN_OK && md.path) {
+        if (w.has_res) { pagan_result_free(&w.res); w.has_res = false; }
+        if (!(w.log_fwd > -HUGE_VAL) && w.banded) { sb.again[q] = 1; return PAGAN_OK; }
+        if (sb.dec[q]) {
+            int32_t steps = 0;
+            r = pagan_fb_decoded_summary(sb.dec[q], nullptr, &w.dec_objective, &steps, nullptr, nullptr);
+            if (r == PAGAN_OK) r = pagan_fb_decoded_result(sb.dec[q], &w.res);
+            w.dec_steps = steps; w.dec_ms = q == 0 ? sb.dec_ms : 0.0;
+            w.has_dec = r == PAGAN_OK;
+        } else if (sb.smp[q]) {
+            r = pagan_fb_samples_result(sb.smp[q], 0, &w.res);
+        } else {
+            const int n_u = w.gl.n_sites + w.gr.n_sites - 1;                 // Lx + Ly + 1
+            std::vector<double> u((size_t)n_u);
+            r = pagan_sample_uniforms(m->opts.sample_seed, w.node, n_u, u.data());
+            if (r == PAGAN_OK) r = pagan_fb_sample_path(sb.fbs[q], u.data(), n_u, &w.res, nullptr, nullptr);
+        }
+        w.has_res = r == PAGAN_OK;
+    }
+    if (r == PAGAN_OK && w.res.status == PAGAN_DP_REACHED) {
+        w.support.assign((size_t)w.res.n_cols, 0.0);
+        r = pagan_fb_path_support(sb.fbs[q], w.res.cols, w.res.n_cols, w.support.data());
+    }
+    return r;
+}
+
+// The readers over the whole sub-batch, one launch each (not for a node that goes to `retry`), while rc is PAGAN_OK; then what the
+// sub-batch leaves at its nodes either way.  Times: a node's own gather and marginal passes; the sampler's at the first node, the
+// counts' at the first node that stays.
+int fb_readers(pagan_msa *m, const FbMode &md, const FbSub &sb, int rc, std::vector<int> *retry) {
+    const int n = (int)sb.which.size();
+    if (rc == PAGAN_OK && md.marg) {
+        std::vector<double *> pd[6];
+        std::vector<int32_t *> pi[2];
+        for (int q = 0; q < n; ++q) {
+            NodeWork &w = m->work[sb.which[q]];
+            const size_t Lx = (size_t)w.gl.n_sites - 1, Ly = (size_t)w.gr.n_sites - 1;
+            for (int a = 0; a < 6; ++a) { w.mg_d[a].assign(a < 3 ? Lx : Ly, 0.0); pd[a].push_back(sb.again[q] ? nullptr : w.mg_d[a].data()); }
+            for (int a = 0; a < 2; ++a) { w.mg_i[a].assign(a < 1 ? Lx : Ly, 0); pi[a].push_back(sb.again[q] ? nullptr : w.mg_i[a].data()); }
+            w.has_marg = !sb.again[q];
+        }
+        rc = pagan_fb_site_marginals_batch(n, sb.fbs.data(), pd[0].data(), pd[1].data(), pi[0].data(), pd[2].data(),
+                                           pd[3].data(), pd[4].data(), pi[1].data(), pd[5].data());
+    }
+    double cnt_ms = 0;
+    for (int q = 0; q < n; ++q) m->work[sb.which[q]].has_counts = false;
+    if (rc == PAGAN_OK && md.counts) {
+        // before the matrices are released; the emission table for DNA only
+        const bool em = m->mf.type == kDna;
+        std::vector<pagan_fb *> cf;
+        std::vector<double *> ct, ce;
+        for (int q = 0; q < n; ++q) {
+            if (sb.again[q]) continue;
+            NodeWork &w = m->work[sb.which[q]];
+            w.emit.assign(em ? (size_t)m->mf.S * m->mf.S : 0, 0.0);
+            cf.push_back(sb.fbs[q]); ct.push_back(w.trans); ce.push_back(em ? w.emit.data() : nullptr);
+        }
+        if (!cf.empty()) {
+            rc = pagan_fb_expected_counts_batch((int32_t)cf.size(), cf.data(), ct.data(), ce.data());
+            if (rc == PAGAN_OK) rc = pagan_fb_counts_ms(cf[0], &cnt_ms);
+        }
+        for (int q = 0; q < n; ++q) m->work[sb.which[q]].has_counts = rc == PAGAN_OK && !sb.again[q];
+    }
+    bool first_kept = true;
+    for (int q = 0; q < n; ++q) {
+        NodeWork &w = m->work[sb.which[q]];
+        double ms[3] = {0, 0, 0};
+        if (rc == PAGAN_OK && pagan_fb_post_ms(sb.fbs[q], ms) == PAGAN_OK) w.fb_post_ms = ms[0] + ms[1] + ms[2] + (q == 0 ? sb.smp_ms : 0.0);
+        if (rc == PAGAN_OK && !sb.again[q] && first_kept) { w.fb_post_ms += cnt_ms; first_kept = false; }
+        w.has_fb = rc == PAGAN_OK && !sb.again[q];
+        w.has_dec = w.has_dec && w.has_fb;
+        if (sb.again[q]) retry->push_back(sb.which[q]);
+    }
+    return rc;
+}
+
 int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads, std::vector<int> *retry) {
     int64_t budget = 0;
     int rc = device_budget(m, dev, &budget);
-    if (rc != PAGAN_OK) return rc;
-    pagan_opts po;
-    po.flags = 0; po.device = dev;
-    const bool decode = m->decode_on != 0;
-    const bool sample = m->opts.sample_path != 0 || decode, marg = m->opts.full_probability == 2;   // sample: the node's path comes from this pass
-    size_t at = 0;
-    while (at < ks.size()) {
+    const FbMode md(m);
+    for (size_t at = 0; rc == PAGAN_OK && at < ks.size();) {
         std::vector<int> which;
-        int64_t used = 0;
-        while (at < ks.size()) {
-            NodeWork &w = m->work[ks[at]];
-            int64_t need = pagan_fb_predict_bytes(w.gl.n_sites, w.gr.n_sites, w.banded ? &w.pb : nullptr);
-            if (need < 0) return (int)need;
-            if (decode) {
-                const int64_t more = pagan_fb_decode_predict_bytes(w.gl.n_sites, w.gr.n_sites, w.banded ? &w.pb : nullptr);
-                if (more < 0) return (int)more;
-                need += more;
-            } else
-            if (sample && m->sample_on_device) need += pagan_fb_sample_predict_bytes(w.gl.n_sites, w.gr.n_sites, 1, 0);    // (the path's trace)
-            if (m->counts_on) need += pagan_fb_counts_predict_bytes(w.gl.n_sites, w.gr.n_sites, m->mf.S);
-            if (need > budget) return PAGAN_E_MEMCAP;
-            if (!which.empty() && used + need > budget) break;
-            used += need;
-            which.push_back(ks[at]); ++at;
-        }
-        const int n = (int)which.size();
-        std::vector<pagan_model_prob> mp(n);
-        std::vector<const pagan_graph *> gl(n), gr(n);
-        std::vector<const pagan_model_prob *> mpp(n);
-        std::vector<const pagan_band *> bd(n);
-        for (int q = 0; q < n; ++q) {
-            NodeWork &w = m->work[which[q]];
-            mp[q] = w.model->prob_view();
-            gl[q] = &w.gl; gr[q] = &w.gr; mpp[q] = &mp[q]; bd[q] = w.banded ? &w.pb : nullptr;
-        }
-        std::vector<pagan_fb *> fbs(n, nullptr);
-        rc = pagan_fb_run_batch(n, gl.data(), gr.data(), mpp.data(), bd.data(), &po, fbs.data());
-        if (rc != PAGAN_OK) return rc;
-        std::vector<int> rcs(n, PAGAN_OK);
-        std::vector<char> again(n, 0);
-        std::vector<pagan_fb_samples *> smp(n, nullptr);
-        double smp_ms = 0, dec_ms = 0;
-        std::vector<pagan_fb_decoded *> dec(n, nullptr);
-        if (decode) {
-            double dms[2] = {0, 0};
-            rc = pagan_fb_decode_batch(n, fbs.data(), m->decode_gap, 0, dec.data());
-            if (rc == PAGAN_OK) rc = pagan_fb_decoded_ms(dec[0], dms);
-            if (rc != PAGAN_OK) {
-                for (int q = 0; q < n; ++q) { pagan_fb_decoded_destroy(dec[q]); pagan_fb_destroy(fbs[q]); }
-                return rc;
-            }
-            dec_ms = dms[0] + dms[1];
-        } else
-        if (sample && m->sample_on_device) {
-            std::vector<int32_t> ids(n);
-            for (int q = 0; q < n; ++q) ids[q] = m->work[which[q]].node;
-            rc = pagan_fb_sample_paths_batch(n, fbs.data(), m->opts.sample_seed, ids.data(), 1, 0, smp.data());
-            if (rc == PAGAN_OK) rc = pagan_fb_samples_ms(smp[0], &smp_ms);
-            if (rc != PAGAN_OK) {
-                for (int q = 0; q < n; ++q) { pagan_fb_samples_destroy(smp[q]); pagan_fb_destroy(fbs[q]); }
-                return rc;
-            }
-        }
-        parallel_for(n, threads, [&](int q) {
-            NodeWork &w = m->work[which[q]];
-            double ms[2] = {0, 0};
-            int r = pagan_fb_totals(fbs[q], &w.log_fwd, &w.log_bwd, nullptr);
-            if (r == PAGAN_OK) r = pagan_fb_kernel_ms(fbs[q], ms);
-            w.fb_sweep_ms = ms[0] + ms[1]; w.fb_post_ms = 0;
-            w.has_marg = false; w.support.clear(); w.has_dec = false;
-            if (r == PAGAN_OK && sample) {
-                if (w.has_res) { pagan_result_free(&w.res); w.has_res = false; }
-                if (!(w.log_fwd > -HUGE_VAL) && w.banded) { again[q] = 1; rcs[q] = PAGAN_OK; return; }
-                if (dec[q]) {
-                    int32_t steps = 0;
-                    r = pagan_fb_decoded_summary(dec[q], nullptr, &w.dec_objective, &steps, nullptr, nullptr);
-                    if (r == PAGAN_OK) r = pagan_fb_decoded_result(dec[q], &w.res);
-                    w.dec_steps = steps; w.dec_ms = q == 0 ? dec_ms : 0.0;
-                    w.has_dec = r == PAGAN_OK;
-                } else if (smp[q]) {
-                    r = pagan_fb_samples_result(smp[q], 0, &w.res);
-                } else {
-                    const int n_u = w.gl.n_sites + w.gr.n_sites - 1;                 // Lx + Ly + 1
-                    std::vector<double> u((size_t)n_u);
-                    r = pagan_sample_uniforms(m->opts.sample_seed, w.node, n_u, u.data());
-                    if (r == PAGAN_OK) r = pagan_fb_sample_path(fbs[q], u.data(), n_u, &w.res, nullptr, nullptr);
-                }
-                w.has_res = r == PAGAN_OK;
-            }
-            if (r == PAGAN_OK && w.res.status == PAGAN_DP_REACHED) {
-                w.support.assign((size_t)w.res.n_cols, 0.0);
-                r = pagan_fb_path_support(fbs[q], w.res.cols, w.res.n_cols, w.support.data());
-            }
-            rcs[q] = r;
-        });
-        for (int q = 0; q < n && rc == PAGAN_OK; ++q) rc = rcs[q];
-        if (rc == PAGAN_OK && marg) {
-            std::vector<double *> pd[6];
-            std::vector<int32_t *> pi[2];
-            for (int q = 0; q < n; ++q) {
-                NodeWork &w = m->work[which[q]];
-                const size_t Lx = (size_t)w.gl.n_sites - 1, Ly = (size_t)w.gr.n_sites - 1;
-                for (int a = 0; a < 6; ++a) { w.mg_d[a].assign(a < 3 ? Lx : Ly, 0.0); pd[a].push_back(again[q] ? nullptr : w.mg_d[a].data()); }
-                for (int a = 0; a < 2; ++a) { w.mg_i[a].assign(a < 1 ? Lx : Ly, 0); pi[a].push_back(again[q] ? nullptr : w.mg_i[a].data()); }
-                w.has_marg = !again[q];
-            }
-            rc = pagan_fb_site_marginals_batch(n, fbs.data(), pd[0].data(), pd[1].data(), pi[0].data(), pd[2].data(),
-                                               pd[3].data(), pd[4].data(), pi[1].data(), pd[5].data());
-        }
-        double cnt_ms = 0;
-        for (int q = 0; q < n; ++q) m->work[which[q]].has_counts = false;
-        if (rc == PAGAN_OK && m->counts_on) {
-            // one launch for the sub-batch, before the matrices are released; the emission table for DNA only
-            const bool em = m->mf.type == kDna;
-            std::vector<pagan_fb *> cf;
-            std::vector<double *> ct, ce;
-            for (int q = 0; q < n; ++q) {
-                if (again[q]) continue;
-                NodeWork &w = m->work[which[q]];
-                w.emit.assign(em ? (size_t)m->mf.S * m->mf.S : 0, 0.0);
-                cf.push_back(fbs[q]); ct.push_back(w.trans); ce.push_back(em ? w.emit.data() : nullptr);
-            }
-            if (!cf.empty()) {
-                rc = pagan_fb_expected_counts_batch((int32_t)cf.size(), cf.data(), ct.data(), ce.data());
-                if (rc == PAGAN_OK) rc = pagan_fb_counts_ms(cf[0], &cnt_ms);
-            }
-            for (int q = 0; q < n; ++q) m->work[which[q]].has_counts = rc == PAGAN_OK && !again[q];
-        }
-        bool first_kept = true;
-        for (int q = 0; q < n; ++q) {
-            NodeWork &w = m->work[which[q]];
-            double ms[3] = {0, 0, 0};
-            if (rc == PAGAN_OK && pagan_fb_post_ms(fbs[q], ms) == PAGAN_OK) w.fb_post_ms = ms[0] + ms[1] + ms[2] + (q == 0 ? smp_ms : 0.0);
-            if (rc == PAGAN_OK && !again[q] && first_kept) { w.fb_post_ms += cnt_ms; first_kept = false; }
-            pagan_fb_samples_destroy(smp[q]);
-            pagan_fb_decoded_destroy(dec[q]);
-            w.has_fb = rc == PAGAN_OK && !again[q];
-            w.has_dec = w.has_dec && w.has_fb;
-            if (again[q]) retry->push_back(which[q]);
-            pagan_fb_destroy(fbs[q]);
-        }
-        if (rc != PAGAN_OK) return rc;
+        rc = fb_cut(m, md, ks, &at, budget, &which);
+        if (rc != PAGAN_OK) break;
+        FbSub sb(which);
+        rc = fb_sweeps(m, sb, dev);
+        if (rc == PAGAN_OK) rc = fb_paths(m, md, sb);
+        if (rc != PAGAN_OK) break;
+        std::vector<int> rcs(which.size(), PAGAN_OK);
+        parallel_for((int)which.size(), threads, [&](int q) { rcs[q] = fb_node(m, md, sb, q); });
+        for (size_t q = 0; q < rcs.size() && rc == PAGAN_OK; ++q) rc = rcs[q];
+        rc = fb_readers(m, md, sb, rc, retry);
     }
-    return PAGAN_OK;
+    return rc;
 }
 
 void build_rows(pagan_msa *m) {

@@ -158,7 +158,33 @@ def test_predict_bytes_grows_by_24_bytes_a_cell(pg):
     assert pgm.fb_decode_predict_bytes(1, 5) < 0
 
 
-NEW_DP = ["pagan_fb_decode_batch", "pagan_fb_decode", "pagan_fb_decoded_summary", "pagan_fb_decoded_visited", "pagan_fb_decoded_result",
+# (left_sites, right_sites, band half-width or None) -> pagan_fb_predict_bytes, pagan_fb_decode_predict_bytes,
+# pagan_fb_sample_predict_bytes for (n_paths, traces) = (1, on), (1, off), (65, on), (65, off), pagan_fb_counts_predict_bytes for
+# S = 15, 211.  The literals were recorded by running the library of the commit before the readers' sizes came from one
+# function each: the predictors' values are part of the interface (the walk cuts its sub-batches by them).
+PINNED_BYTES = [
+    ((2, 2, None), 566240, 1889, (1864, 1608, 7752, 5704), (5380, 1780)),
+    ((301, 281, None), 4921427, 2150776, (8776, 1608, 465480, 5704), (22336, 2536)),
+    ((1001, 11, None), 1200425, 268896, (13896, 1608, 805960, 5704), (33640, 3040)),
+    ((301, 281, 12), 1011359, 195742, (8776, 1608, 465480, 5704), (22336, 2536)),
+]
+
+
+def test_the_predictors_values_are_pinned(pg):
+    for (lx, ly, half), fb, decode, sample, counts in PINNED_BYTES:
+        band = None
+        if half is not None:                                                      # a band of constant half-width about the diagonal
+            centre = np.arange(lx - 1) * (ly - 2) // (lx - 2)
+            band = abi.Band(np.maximum(centre - half, 0).astype(np.int32), np.minimum(centre + half, ly - 2).astype(np.int32))
+        what = (lx, ly, half)
+        assert pgm.fb_predict_bytes(lx, ly, band) == fb, what
+        assert pgm.fb_decode_predict_bytes(lx, ly, band) == decode, what
+        got = tuple(pgm.fb_sample_predict_bytes(lx, ly, k, traces=t) for k in (1, 65) for t in (True, False))
+        assert got == sample, (what, got)
+        assert tuple(pgm.fb_counts_predict_bytes(lx, ly, s) for s in (15, 211)) == counts, what
+
+
+NEW_DP = ["pagan_fb_decode_batch","pagan_fb_decode", "pagan_fb_decoded_summary", "pagan_fb_decoded_visited", "pagan_fb_decoded_result",
           "pagan_fb_decoded_dump", "pagan_fb_decoded_ms", "pagan_fb_debug_decode_route", "pagan_fb_decode_predict_bytes",
           "pagan_fb_decoded_destroy"]
 

@@ -1,6 +1,9 @@
 """GPU: the forward/backward pass inside the tree walk (host_tree.cpp: full_probability, sample_path, sample_seed) -- the
 walk's per-node totals, column support and site marginals against the same calls made pair by pair on the node's job, the
-alignment untouched by full_probability, and sampled walks that depend on (seed, node) only."""
+alignment untouched by full_probability, sampled walks that depend on (seed, node) only, and the pass's sub-batches: a walk
+whose memory budget admits one node at a time leaves what the uncut walk leaves."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -120,3 +123,72 @@ def test_sampled_walks_depend_on_seed_and_node_only(pg, walks):
             # every site of both children is used once, in order
             assert [x for x in res.cols[:, 0] if x >= 0] == list(range(1, left.n_sites - 1))
             assert [x for x in res.cols[:, 1] if x >= 0] == list(range(1, right.n_sites - 1))
+
+
+# ---- the sub-batch cut ----
+
+CUT_MODES = {
+    "marginals": {"full_probability": 2, "expected_counts": 1},
+    "device_sampler": {"sample_path": 1, "sample_on_device": 1, "expected_counts": 1},
+    "host_sampler": {"sample_path": 1},
+    "decoder": {"posterior_decode": 1, "expected_counts": 1},
+}
+
+
+@pytest.fixture(scope="module")
+def cut_tree():
+    """4 leaves x 300 sites, balanced: two leaf-level nodes of near-equal size in one round, the smallest walk a cut can happen in.
+    Few indels, so that the root (the largest node: it sets the budget) is not a tenth longer than its grandchildren -- then the
+    budget for the root alone would admit both leaf-level nodes at once in every mode but the decoder's."""
+    return synth.evolve_balanced(4, 300, branch=0.05, sub=0.05, indel_start=0.002, mean_len=4, seed=33)
+
+
+def _pass_bytes(msa, k, kw):
+    """(what the forward/backward pass of node k takes under the mode: the sum the walk cuts by, the node's Viterbi batch)"""
+    left, right, _model, band = msa.node_job(k)
+    l, r = left.n_sites, right.n_sites
+    need = pgm.fb_predict_bytes(l, r, band)
+    if kw.get("posterior_decode"):
+        need += pgm.fb_decode_predict_bytes(l, r, band)
+    elif kw.get("sample_on_device"):
+        need += pgm.fb_sample_predict_bytes(l, r, 1)
+    if kw.get("expected_counts"):
+        need += pgm.fb_counts_predict_bytes(l, r, msa.node_model_prob(k).n_states)
+    dp = pgm.lib().pagan_dp_predict_bytes(l, r, C.byref(band.c) if band is not None else None)
+    assert need > 0 and dp > 0
+    return need, dp
+
+
+@pytest.mark.parametrize("mode", sorted(CUT_MODES))
+def test_a_budget_for_one_node_at_a_time_changes_nothing(pg, cut_tree, mode):
+    names, seqs, nwk = cut_tree
+    # full matrices: behind a band a node of 300 sites takes little more than the predictors' constants, and two fit wherever one does
+    kw = dict(CUT_MODES[mode], use_anchors=0)
+    whole = host.Msa(names, seqs, nwk, **kw).align()
+    assert whole.n_internal == 3
+    leaf_level = [k for k in range(3) if whole.node_info(k).level == whole.node_info(0).level]
+    assert leaf_level == [0, 1] and whole.node_info(2).level != whole.node_info(0).level
+    needs = [_pass_bytes(whole, k, kw) for k in range(3)]
+    budget = max(fb + dp for fb, dp in needs) + 1            # every node fits alone, its Viterbi batch included
+    assert 2 * min(needs[k][0] for k in leaf_level) > budget                    # ... and the two leaf-level passes do not fit together
+    tight = host.Msa(names, seqs, nwk, device_mem_budget=budget, **kw).align()
+    assert tight.alignment_all() == whole.alignment_all()
+    for k in range(3):
+        a, b = whole.node_result(k), tight.node_result(k)
+        assert a.same_alignment(b) and a.status == b.status, k
+        assert np.array_equal(a.left_used, b.left_used) and np.array_equal(a.right_used, b.right_used), k
+        assert np.float64(whole.node_info(k).score).tobytes() == np.float64(tight.node_info(k).score).tobytes(), k
+        assert np.array(whole.node_fb(k)[:2]).tobytes() == np.array(tight.node_fb(k)[:2]).tobytes(), k
+        assert whole.node_support(k).tobytes() == tight.node_support(k).tobytes(), k
+        if kw.get("full_probability") == 2:
+            want, got = whole.node_marginals(k), tight.node_marginals(k)
+            assert set(want) == set(got) and all(want[name].tobytes() == got[name].tobytes() for name in want), k
+        if kw.get("expected_counts"):
+            want, got = whole.node_counts(k), tight.node_counts(k)
+            assert all(want[name].tobytes() == got[name].tobytes() for name in ("trans", "end", "emit")), k
+        if kw.get("posterior_decode"):
+            assert np.array(whole.node_decode(k)[:2]).tobytes() == np.array(tight.node_decode(k)[:2]).tobytes(), k
+    if kw.get("posterior_decode"):
+        # the decoder's time is booked at a sub-batch's first node: the cut walk has a sub-batch per leaf-level node, the uncut one
+        assert all(tight.node_decode(k)[2] > 0 for k in leaf_level)
+        assert sorted(whole.node_decode(k)[2] > 0 for k in leaf_level) == [False, True]
