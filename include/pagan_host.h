@@ -358,6 +358,64 @@ int  pagan_model_alphabets(int32_t data_type, char *leaf_alphabet, char *ancestr
  * Q = U diag(root) V.  Exposed for the tests.                                                     */
 int  pagan_eigen_qrev(const double *Q, const double *pi, int32_t n, double *root, double *U, double *V);
 
+/* ---- guide tree from the sequences alone: k-mer distances on the device, UPGMA on the host --------------------
+ * (csrc/dp_guide.hip, csrc/host_guide.cpp; DESIGN.md "Guide tree").  The reference leaves this to external programs.
+ *
+ * Cleaning: exactly pagan_msa_create's -- upper case; '-', CR, LF dropped; data_type 0 guesses as the walk does, 1 DNA,
+ * 2 protein, 3 codon (read as DNA over its nucleotides); DNA U -> T, protein U -> X; letters outside the full alphabet dropped.
+ * k-mer: a window of k consecutive cleaned letters, all of them core letters (ACGT / the 20 amino acids); any other window
+ * contributes nothing.  2 bits a letter for DNA (k <= 31), 5 bits for protein (k <= 12), packed in a u64; "no k-mer here" is
+ * all ones, which no code takes.  k = 0: pagan_guide_kmer_length of the longest cleaned sequence.
+ * Distance of x, y with k-mer multisets n_x, n_y: S = sum_t min(n_x(t), n_y(t)) (an integer), m = min(|n_x|, |n_y|),
+ * F = S / m (0 when m = 0), p = 1 - F^(1/k) (1 when F = 0; d = 0 when p = 0); DNA / codon: p <= 0.7, d = -0.75 ln(1 - p / 0.75);
+ * protein: p <= 0.85, d = -ln(1 - p - 0.2 p^2).  fp64 on the host from the integers the device counted.
+ *
+ * Limits (refused with PAGAN_E_ARG before anything is allocated): n <= PAGAN_GUIDE_MAX_SEQS (the number of pairs
+ * n (n - 1) / 2 stays below 2^31: a pair's sum is addressed with its index, and the pair kernel's launch is at most 2^20
+ * workgroups that stride over the pairs, so no launch dimension depends on n), cleaned letters in total <=
+ * PAGAN_GUIDE_MAX_POSITIONS (32-bit positions, a thread a position).  The device entries run on the caller's current device and
+ * leave it current; without a device they return PAGAN_E_NODEVICE (there is no host path); a HIP error on a device that is
+ * there is PAGAN_E_NOMEM (out of memory) or PAGAN_E_INTERNAL.                                                         */
+#define PAGAN_GUIDE_MAX_SEQS       65536
+#define PAGAN_GUIDE_MAX_POSITIONS  2147483000LL
+#define PAGAN_GUIDE_PAIR_CHUNK     64      /* list entries a wave of the pair kernel takes at a time */
+typedef struct pagan_guide_info {
+    int32_t k;                   /* the k used                                                                   */
+    int32_t data_type;           /* 1 DNA, 2 protein, 3 codon: what 0 was resolved to                            */
+    int32_t pair_chunk;          /* PAGAN_GUIDE_PAIR_CHUNK                                                       */
+    int32_t waves_per_pair;      /* waves of the workgroup that owns a pair's sum                                */
+    int64_t positions;           /* cleaned letters in total = keys packed and sorted                            */
+    int64_t entries;             /* (code, count) entries of all lists                                           */
+    int64_t pairs;               /* n (n - 1) / 2                                                                */
+    int64_t device_bytes;        /* what the call allocated on the device                                        */
+    double  pack_ms, sort_ms, compress_ms, pairs_ms;   /* device time of the stages (events around their launches; no stage
+                                                          waits for the host)                                      */
+    double  upgma_ms;            /* host time of the tree builder (pagan_guide_tree), 0 otherwise                */
+} pagan_guide_info;
+/* shared [n * n]: S(x, y), the diagonal |n_x|; kmers [n]: |n_x|; dist [n * n]: d, the diagonal 0.  Any of the three may be NULL. */
+int     pagan_guide_distances(int32_t n, const char *const *seqs, int32_t data_type, int32_t k, int64_t *shared, int64_t *kmers,
+                              double *dist, pagan_guide_info *info);
+/* The distances, then pagan_guide_upgma.  Returns the bytes the string needs with its NUL (> cap: nothing was written, call
+ * again with that much) or a negative code.                                                                             */
+int64_t pagan_guide_tree(int32_t n, const char *const *names, const char *const *seqs, int32_t data_type, int32_t k,
+                         char *newick_out, int64_t cap, pagan_guide_info *info);
+/* Host only.  kmer_length: the smallest k with A^k >= 16 max_len (A = 4 for data_type 1 and 3, 20 for 2), clamped to 8..31
+ * resp. 3..12; PAGAN_E_ARG for another data_type or max_len < 0.  distance_of: d from S, m, k as above, NaN for arguments
+ * outside 0 <= S <= m, 1 <= k <= 31 resp. 12, data_type 1..3.                                                          */
+int     pagan_guide_kmer_length(int32_t data_type, int64_t max_len);
+double  pagan_guide_distance_of(int64_t shared, int64_t m, int32_t k, int32_t data_type);
+/* UPGMA over dist [n * n] (read at [i * n + j], i < j; finite, >= 0).  Leaves are clusters 0..n-1, the cluster of step t is
+ * n + t; a step merges the active pair of smallest distance (ties: lowest first id, then lowest second id), height d / 2, the
+ * distance to every other active c is (n_a d(a,c) + n_b d(b,c)) / (n_a + n_b) in exactly that form, the left child is the
+ * lower id, a branch is max(0, h(parent) - h(child)) printed %.17g.  Names that are empty or hold any of "(),:;" or white
+ * space: PAGAN_E_ARG (pagan_msa_create's reader could not read them back).  Returns as pagan_guide_tree.                 */
+int64_t pagan_guide_upgma(int32_t n, const char *const *names, const double *dist, char *newick_out, int64_t cap);
+/* Device bytes pagan_guide_distances allocates for n sequences of total_len cleaned letters in total: exact for the call's own
+ * buffers (the lists are sized for one entry per position), an ESTIMATE for the sort's and the scan's temporary storage (a
+ * second key buffer, index arrays over the sequences, 1 MiB: what rocPRIM asks for is known only with a device, and a call takes
+ * that if it is more; pagan_guide_info.device_bytes is what a call did allocate).  PAGAN_E_ARG beyond the limits above.    */
+int64_t pagan_guide_predict_bytes(int32_t n, int64_t total_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,16 @@ class CPileupStep(C.Structure):
                 ("cells", C.c_int64)]
 
 
+class CGuideInfo(C.Structure):
+    _fields_ = [("k", C.c_int32), ("data_type", C.c_int32), ("pair_chunk", C.c_int32), ("waves_per_pair", C.c_int32),
+                ("positions", C.c_int64), ("entries", C.c_int64), ("pairs", C.c_int64), ("device_bytes", C.c_int64),
+                ("pack_ms", C.c_double), ("sort_ms", C.c_double), ("compress_ms", C.c_double), ("pairs_ms", C.c_double),
+                ("upgma_ms", C.c_double)]
+
+
+GUIDE_MAX_SEQS = 65536
+GUIDE_PAIR_CHUNK = 64
+
 _declared = False
 
 
@@ -221,6 +231,19 @@ def _lib():
         L.pagan_msa_set_indel_model.restype = C.c_int
         L.pagan_fit_indel.argtypes = [C.c_int32, f64p, f64p, f64p, f64p]
         L.pagan_fit_indel.restype = C.c_int
+        i64p, cpp = C.POINTER(C.c_int64), C.POINTER(C.c_char_p)
+        L.pagan_guide_distances.argtypes = [C.c_int32, cpp, C.c_int32, C.c_int32, i64p, i64p, f64p, C.POINTER(CGuideInfo)]
+        L.pagan_guide_distances.restype = C.c_int
+        L.pagan_guide_tree.argtypes = [C.c_int32, cpp, cpp, C.c_int32, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(CGuideInfo)]
+        L.pagan_guide_tree.restype = C.c_int64
+        L.pagan_guide_kmer_length.argtypes = [C.c_int32, C.c_int64]
+        L.pagan_guide_kmer_length.restype = C.c_int
+        L.pagan_guide_distance_of.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32]
+        L.pagan_guide_distance_of.restype = C.c_double
+        L.pagan_guide_upgma.argtypes = [C.c_int32, cpp, f64p, C.c_char_p, C.c_int64]
+        L.pagan_guide_upgma.restype = C.c_int64
+        L.pagan_guide_predict_bytes.argtypes = [C.c_int32, C.c_int64]
+        L.pagan_guide_predict_bytes.restype = C.c_int64
         _declared = True
     return L
 
@@ -243,7 +266,9 @@ HOST_EXPORTED = ["pagan_assign_units", "pagan_msa_default_opts", "pagan_msa_crea
                  "pagan_pileup_destroy",
                  "pagan_msa_node_fb", "pagan_msa_node_support", "pagan_msa_node_marginals", "pagan_msa_node_model_prob", "pagan_msa_support_row",
                  "pagan_msa_set_sampler", "pagan_msa_set_decoder", "pagan_msa_node_decode",
-                 "pagan_msa_set_counts", "pagan_msa_node_counts", "pagan_msa_set_indel_model", "pagan_fit_indel"]
+                 "pagan_msa_set_counts", "pagan_msa_node_counts", "pagan_msa_set_indel_model", "pagan_fit_indel",
+                 "pagan_guide_distances", "pagan_guide_tree", "pagan_guide_kmer_length", "pagan_guide_distance_of",
+                 "pagan_guide_upgma", "pagan_guide_predict_bytes"]
 
 
 def _ip(a):
@@ -561,6 +586,88 @@ def eigen_qrev(Q, pi):
     return root, U, V
 
 
+def _guide_check(rc, what):
+    if rc < 0:
+        from . import PaganError
+        raise PaganError(int(rc), what)
+    return rc
+
+
+def _c_strings(strings):
+    return (C.c_char_p * len(strings))(*[s.encode() if isinstance(s, str) else bytes(s) for s in strings])
+
+
+def _guide_info(ci):
+    return {name: getattr(ci, name) for name, _ in CGuideInfo._fields_}
+
+
+def guide_kmer_length(data_type, max_len):
+    """pagan_guide_kmer_length (host only): the default k for sequences of at most max_len cleaned letters."""
+    return _guide_check(_lib().pagan_guide_kmer_length(int(data_type), int(max_len)), "pagan_guide_kmer_length")
+
+
+def guide_distance_of(shared, m, k, data_type):
+    """pagan_guide_distance_of (host only): the distance from S, m = min(|n_x|, |n_y|) and k; NaN for arguments outside the domain."""
+    return float(_lib().pagan_guide_distance_of(int(shared), int(m), int(k), int(data_type)))
+
+
+def guide_predict_bytes(n, total_len):
+    """pagan_guide_predict_bytes (host only): device bytes guide_distances allocates at most."""
+    return _guide_check(_lib().pagan_guide_predict_bytes(int(n), int(total_len)), "pagan_guide_predict_bytes")
+
+
+def guide_distances(seqs, data_type=0, k=0):
+    """pagan_guide_distances: (shared [n, n] int64, kmers [n] int64, dist [n, n] float64, info dict) -- the k-mers every pair of
+    sequences shares, counted on the current device, and the distances made of them (include/pagan_host.h)."""
+    n = len(seqs)
+    shared = np.zeros((n, n), np.int64)
+    kmers = np.zeros(n, np.int64)
+    dist = np.zeros((n, n), np.float64)
+    ci = CGuideInfo()
+    i64p, f64p = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+    _guide_check(_lib().pagan_guide_distances(n, _c_strings(seqs), int(data_type), int(k), shared.ctypes.data_as(i64p),
+                                              kmers.ctypes.data_as(i64p), dist.ctypes.data_as(f64p), C.byref(ci)),
+                 "pagan_guide_distances")
+    return shared, kmers, dist, _guide_info(ci)
+
+
+def _newick_call(call, what, names):
+    cap = sum(len(s) for s in names) + 64 * len(names) + 64        # (a branch prints as at most 24 characters)
+    for _ in range(2):
+        buf = C.create_string_buffer(cap)
+        need = _guide_check(call(buf, cap), what)
+        if need <= cap:
+            return buf.value.decode()
+        cap = need
+    raise RuntimeError("%s: the string's size changed between two calls" % what)
+
+
+def guide_tree(names, seqs, data_type=0, k=0, with_info=False):
+    """pagan_guide_tree: the rooted binary UPGMA tree over guide_distances' matrix as a Newick string (with_info: and the info
+    dict), ready for Msa."""
+    n = len(names)
+    if len(seqs) != n:
+        raise ValueError("names and sequences differ in number")
+    na, sa = _c_strings(names), _c_strings(seqs)
+    ci = CGuideInfo()
+    L = _lib()
+    newick = _newick_call(lambda buf, cap: L.pagan_guide_tree(n, na, sa, int(data_type), int(k), buf, cap, C.byref(ci)),
+                          "pagan_guide_tree", names)
+    return (newick, _guide_info(ci)) if with_info else newick
+
+
+def guide_upgma(names, dist):
+    """pagan_guide_upgma (host only): the UPGMA tree over a distance matrix [n, n] (its upper triangle is read) as Newick."""
+    n = len(names)
+    d = np.ascontiguousarray(dist, np.float64)
+    if d.shape != (n, n):
+        raise ValueError("dist must be [%d, %d]" % (n, n))
+    na = _c_strings(names)
+    L = _lib()
+    return _newick_call(lambda buf, cap: L.pagan_guide_upgma(n, na, d.ctypes.data_as(C.POINTER(C.c_double)), buf, cap),
+                        "pagan_guide_upgma", names)
+
+
 def _job_copy(j):
     """(Graph, Graph, Model, Band|None) copies of a borrowed CJob."""
     left, right = _graph_from_view(j.left.contents), _graph_from_view(j.right.contents)
@@ -656,9 +763,11 @@ class Pileup:
 class Msa:
     """Progressive alignment of sequences on a rooted binary guide tree (Node mirror)."""
 
-    def __init__(self, names, seqs, newick, sample_on_device=0, posterior_decode=0, decode_gap_weight=0.5, expected_counts=0,
+    def __init__(self, names, seqs, newick=None, sample_on_device=0, posterior_decode=0, decode_gap_weight=0.5, expected_counts=0,
                  indel_model=None, **opts):
-        """opts: fields of pagan_msa_opts.  sample_on_device=1 (pagan_msa_set_sampler): with sample_path set, the nodes' paths
+        """newick=None: the guide tree is made from the sequences (guide_tree with the walk's data_type, on the current
+        device); either way the tree walked is kept as self.newick.
+        opts: fields of pagan_msa_opts.  sample_on_device=1 (pagan_msa_set_sampler): with sample_path set, the nodes' paths
         are drawn by pg_fb_sample on the device instead of on the host behind a download of the forward matrix.
         posterior_decode=1 (pagan_msa_set_decoder): a node's result is the maximum expected accuracy path of its posteriors,
         gaps weighted by decode_gap_weight.  expected_counts=1 (pagan_msa_set_counts): every node's forward/backward pass also
@@ -672,9 +781,12 @@ class Msa:
                 raise TypeError("unknown option %s" % k)
             setattr(o, k, v)
         self.n = len(names)
+        self._h = C.c_void_p()
+        if newick is None:
+            newick = guide_tree(names, seqs, data_type=o.data_type)
+        self.newick = newick
         na = (C.c_char_p * self.n)(*[s.encode() for s in names])
         sa = (C.c_char_p * self.n)(*[s.encode() for s in seqs])
-        self._h = C.c_void_p()
         rc = L.pagan_msa_create(self.n, na, sa, newick.encode(), C.byref(o), C.byref(self._h))
         if rc != 0:
             from . import PaganError
