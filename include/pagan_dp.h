@@ -310,6 +310,21 @@ int  pagan_fb_schedule(const pagan_fb *fb);
  * [6] cells with a far predecessor (further back than the segment's ring holds; forward sweep), [7] diagonals marked far;
  * [2], [3], [6], [7] are 0 unless the code is 3.                                                                          */
 int  pagan_fb_debug_route(const pagan_graph *left, const pagan_graph *right, const pagan_band *band, int32_t info[8]);
+/* Host only, no device needed: everything the plan of a pair fixes under the current environment (dp_fb_plan.cpp: fb_plan_pair,
+ * what pagan_fb_run stages), for a model of n_states character states and a launch that leaves the pair's forward / backward
+ * tiled sweep groups_cap / groups_cap_b workgroups.  Returns the schedule code or a negative PAGAN_E_*.  head: [0] schedule code,
+ * [1] workgroups of a tiled sweep before the caps (1: not tiled), [2] forward and [3] backward within them, [4] threads of a
+ * workgroup -- for schedule 2 its rows B --, [5] threads a row (schedule 2: 3, 2 or 1), [6] n_init, the assignments of the
+ * backward sweep's corner initialisation, [7] init_dmin, the first cell diagonal that holds one (the number of diagonals: none),
+ * [8] segments of the deep-ring plan, [9] entries of dfar (the cell diagonals; both 0 unless the code is 3), [10] the decode
+ * route (pagan_fb_debug_decode_route), [11] rows (route 1) or threads (route 0) of the decode fill's workgroup for this pair,
+ * [12] 1: the score table sits in LDS, [13..15] 0.  The arrays may be NULL (a first call for the counts in head); each gets at
+ * most its cap: init_at [init_cap] 3 * cell + state of every assignment; seg_start [seg_cap + 1] first diagonal of a segment,
+ * then the number of diagonals; seg_B [seg_cap] rows B of the segment | 1 << 16: it holds a far cell; dfar [dfar_cap] bit 0: the
+ * diagonal holds a cell with a far predecessor, bit 1: a far successor.                                                      */
+int  pagan_fb_debug_plan(const pagan_graph *left, const pagan_graph *right, const pagan_band *band, int32_t n_states,
+                         int32_t groups_cap, int32_t groups_cap_b, int32_t head[16], int64_t *init_at, int32_t init_cap,
+                         int32_t *seg_start, int32_t *seg_B, int32_t seg_cap, int32_t *dfar, int32_t dfar_cap);
 /* which: 0 log forward, 1 log backward, 2 posterior (compute_posterior_score, VA:1029-1034);
  * dst [Lx][Ly][3] row-major, states X, Y, M; outside the tunnel -inf / 0.                                  */
 int  pagan_fb_dump(pagan_fb *fb, int32_t which, double *dst);

@@ -466,6 +466,28 @@ def fb_route(left, right, band=None):
     return rc, dict(zip(FB_ROUTE_INFO, (int(v) for v in info)))
 
 
+FB_PLAN_HEAD = ("schedule", "groups", "groups_fwd", "groups_bwd", "block", "nsplit", "n_init", "init_dmin", "segments", "n_dfar",
+                "decode_route", "decode_block", "table_in_lds")
+
+
+def fb_plan(left, right, band=None, n_states=4, groups_cap=64, groups_cap_b=64):
+    """pagan_fb_debug_plan (host only): everything FullProbability's plan fixes for the pair under the current environment -- a
+    dict of the head words (FB_PLAN_HEAD) and the arrays init_at, seg_start, seg_B, dfar."""
+    import numpy as np
+    L = lib()
+    p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    args = (C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None, n_states, groups_cap, groups_cap_b)
+    head = np.zeros(16, np.int32)
+    _check(min(L.pagan_fb_debug_plan(*args, head.ctypes.data_as(p32), None, 0, None, None, 0, None, 0), 0), "pagan_fb_debug_plan")
+    out = dict(zip(FB_PLAN_HEAD, (int(v) for v in head)))
+    n_init, nseg, n_dfar = out["n_init"], out["segments"], out["n_dfar"]
+    init_at = np.zeros(n_init, np.int64); seg_start = np.zeros(nseg + 1, np.int32); seg_B = np.zeros(nseg, np.int32); dfar = np.zeros(n_dfar, np.int32)
+    _check(min(L.pagan_fb_debug_plan(*args, head.ctypes.data_as(p32), init_at.ctypes.data_as(p64), n_init, seg_start.ctypes.data_as(p32),
+                                     seg_B.ctypes.data_as(p32), nseg, dfar.ctypes.data_as(p32), n_dfar), 0), "pagan_fb_debug_plan")
+    out.update(init_at=init_at, seg_start=seg_start[:nseg + 1 if nseg else 0], seg_B=seg_B, dfar=dfar)
+    return out
+
+
 def full_probability_batch(pairs, device=-1):
     """pagan_fb_run_batch: [(left, right, model_prob, band or None), ...] -> [FullProbability, ...]; the wide pairs' forward sweeps
     run in one launch and their backward sweeps in another (all pairs side by side on the device)."""

@@ -246,6 +246,8 @@ def declare(lib):
     lib.pagan_fb_schedule.restype = C.c_int
     lib.pagan_fb_debug_route.argtypes = [gp, gp, bp, _i32p]
     lib.pagan_fb_debug_route.restype = C.c_int
+    lib.pagan_fb_debug_plan.argtypes = [gp, gp, bp, C.c_int32, C.c_int32, C.c_int32, _i32p, C.POINTER(C.c_int64), C.c_int32, _i32p, _i32p, C.c_int32, _i32p, C.c_int32]
+    lib.pagan_fb_debug_plan.restype = C.c_int
     lib.pagan_fb_dump.argtypes = [C.c_void_p, C.c_int32, f64p]
     lib.pagan_fb_dump.restype = C.c_int
     lib.pagan_fb_posterior_cells.argtypes = [C.c_void_p, C.c_int32, _i32p, f64p]
@@ -326,7 +328,7 @@ EXPORTED = ["pagan_dp_align", "pagan_dp_align_batch", "pagan_result_free", "paga
             "pagan_dp_count_cells", "pagan_dp_device_count", "pagan_dp_select_device", "pagan_batch_create",
             "pagan_batch_run", "pagan_batch_sync", "pagan_batch_fetch", "pagan_batch_last_ms",
             "pagan_batch_cells", "pagan_batch_last_ms_detail", "pagan_batch_destroy", "pagan_batch_debug_trace", "pagan_batch_debug_segments", "pagan_dp_debug_plan", "pagan_dp_debug_far", "pagan_dp_debug_descriptors", "pagan_dp_debug_strips", "pagan_dp_debug_tiles", "pagan_dp_debug_compact", "pagan_dp_debug_tiles_staircase", "pagan_dp_release_cache", "pagan_dp_cached_device_bytes", "pagan_dp_debug_route", "pagan_batch_debug_scores", "pagan_batch_debug_backptrs", "pagan_batch_debug_poison", "pagan_batch_debug_followed", "pagan_batch_debug_poke_bp", "pagan_batch_debug_reruns",
-            "pagan_fb_run", "pagan_fb_run_batch", "pagan_fb_totals", "pagan_fb_kernel_ms", "pagan_fb_groups", "pagan_fb_schedule", "pagan_fb_debug_route", "pagan_fb_dump", "pagan_fb_posterior_cells", "pagan_fb_sample_path",
+            "pagan_fb_run", "pagan_fb_run_batch", "pagan_fb_totals", "pagan_fb_kernel_ms", "pagan_fb_groups", "pagan_fb_schedule", "pagan_fb_debug_route", "pagan_fb_debug_plan", "pagan_fb_dump", "pagan_fb_posterior_cells", "pagan_fb_sample_path",
             "pagan_path_cells", "pagan_fb_path_support", "pagan_fb_site_marginals", "pagan_fb_site_marginals_batch", "pagan_fb_post_ms", "pagan_fb_predict_bytes", "pagan_sample_uniforms",
             "pagan_sample_uniforms_path", "pagan_fb_sample_paths_batch", "pagan_fb_sample_paths", "pagan_fb_samples_summary", "pagan_fb_samples_visited",
             "pagan_fb_samples_visited_all", "pagan_fb_samples_result", "pagan_fb_samples_ms", "pagan_fb_sample_predict_bytes", "pagan_fb_samples_destroy",

@@ -20,6 +20,10 @@
 // use gap_ext for every gap (no end-gap extension) and the plain gap-open probability; edge weights enter matches only;
 // the end corner visits the Y-close term of a non-first right edge once per left edge.  Cells outside the tunnel hold
 // probability 0.
+//
+// What a pair runs on is not decided here: dp_fb_plan.cpp (plain C++, no HIP) reads the PAGAN_FB_* switches (FbSwitches) and plans a
+// pair (fb_plan_pair -> FbPlan: band index, corner initialisation, forward lists, schedule, deep-ring segments, workgroup sizes,
+// decode route); dp_fb_plan.h also holds PgFbJob and the constants plan and kernels share.  This file stages and launches the plan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,30 +43,9 @@
 
 #include "../../include/pagan_dp.h"
 #include "dp_band.h"
+#include "dp_fb_plan.h"
 
-struct PgFbJob {
-    int Lx, Ly, nd, S;
-    double l_ext, l_open, l_ng;              // logs of gap_ext, gap_open, non_gap
-    const int *stL, *offL, *srcL; const float *lwL;      // bwd lists (log weights as the CSR carries them)
-    const int *stR, *offR, *srcR; const float *lwR;
-    const int *foffL, *fdstL; const float *flwL;         // fwd lists
-    const int *foffR, *fdstR; const float *flwR;
-    const double *ltab;                      // log((double) score[a + b*S])
-    const int *imin, *imax; const long long *doff;
-    long long cells;
-    double *F, *B;                           // [cells][3] log forward / log backward
-    int n_init; const long long *init_at; const double *init_val;   // initialise_array_corner_bwd
-    double *totals;                          // [2]: log fwd_end, log bwd(M,0,0)
-    // the tiled sweeps (round 5: one launch may carry the sweeps of SEVERAL pairs, grid = (most workgroups of any pair, pairs) --
-    // pagan_fb_run_batch): the pair's own workgroup count and barrier words
-    int groups, groups_b;                    // workgroups of this pair's forward / backward sweep (blockIdx.x beyond: nothing to do)
-    int *sync;                               // [64] ints: forward barrier at [0..7], backward at [8..15], diagnostics behind
-    int init_dmin;                           // the first cell diagonal that holds a cell of init_at (nd: none)
-    // the deep-ring sweeps (graph pairs inside a tunnel, dp_fb_deep.inc): the segments of the pair's diagonals
-    int nseg; const int *seg_start;          // [nseg + 1] first diagonal of a segment, then nd
-    const int *seg_B;                        // [nseg] rows B of the segment's workgroup layout | 1 << 16: the segment holds a far cell
-    const int *dfar;                         // [nd] bit 0: the diagonal holds a cell with a far predecessor (forward), bit 1: a far successor (backward)
-};
+using namespace fbplan;
 
 namespace {
 
@@ -75,11 +58,7 @@ namespace {
         }                                                                                                    \
     } while (0)
 
-// the environment's switches: is `name` set to 0; `name` as an integer, or `dflt` where it is not set
-static bool fb_env_off(const char *name) { const char *e = std::getenv(name); return e && std::strcmp(e, "0") == 0; }
-static int fb_env_int(const char *name, int dflt) { const char *e = std::getenv(name); return e ? std::atoi(e) : dflt; }
-
-// ... and for a call that answers with a PAGAN_* code of its own
+// a call that answers with a PAGAN_* code of its own
 #define FB_DO(call) do { const int rc_ = (call); if (rc_ != PAGAN_OK) return rc_; } while (0)
 
 __device__ __forceinline__ double ninf() { return -__builtin_huge_val(); }
@@ -280,9 +259,6 @@ __global__ __launch_bounds__(1024) void pg_fb_backward(const PgFbJob *jobs) {
 // list) inside a tunnel take the deep-ring sweeps of dp_fb_deep.inc; diagonals wider than 1,024 cells keep the block schedule.
 #define FB_RG_COLS 1024          // columns / rows in the LDS windows (>= B + 2 * FB_RG_REFILL) up to B = 512; 2,048 for B = 1,024
 #define FB_RG_REFILL 256
-#define FB_RG_MAXB 1024         // rows of the widest diagonal a ring sweep takes
-#define FB_RG_INIT 32           // assignments of initialise_array_corner_bwd a ring sweep holds (a pair with more takes the block schedule)
-#define FB_RG_THREADS 1024       // B = 64 ... 256: three threads a row, one per state; B = 512: two (X and Y; M)
 // Who a thread is.  A cell's three states are three independent log-sum-exps of the same size -- the step's latency is one wave's
 // way through them --, so up to B = 256 a row has THREE threads, one per state (NSPLIT = 3, blockDim = 3 B), and with B = 512 two
 // (NSPLIT = 2: X and Y in one, M in the other; 1,024 threads is what a workgroup holds): wave w works on part w % NSPLIT of the
@@ -509,10 +485,8 @@ enum { FB_SUM_STATUS = 0, FB_SUM_END = 1, FB_SUM_STEPS = 6, FB_SUM_M = 7, FB_SUM
 // Barrier (MI355X_MICROARCH.md, "Valid forms", producer / consumer with fences): the wave's s_waitcnt vmcnt(0), the
 // workgroup barrier, lane 0's agent release + wait, its relaxed agent add; lane 0 polls (relaxed, agent), then agent
 // acquire + wait, workgroup barrier, plain loads.
-#define FB_T 64
 #define FB_RING 12
 #define FB_H 8                   // halo depth: rows above / columns left of a block (forward), below / right of it (backward) kept in LDS
-#define FB_MAX_GROUPS 64
 #define FB_SPIN_LIMIT (1 << 22)
 typedef __attribute__((address_space(1))) int *fb_gi;
 
@@ -934,24 +908,6 @@ __global__ __launch_bounds__(64) void pg_fb_backward_tiled(const PgFbJob *jobs) 
     if (blockIdx.x == 0 && threadIdx.x == 0) J.totals[1] = rd(J.B, cell_at(J, 0, 0), 2);
 }
 
-struct FwdLists { std::vector<int> off, dst, slot; std::vector<float> lw; };
-
-// A site's fwd list = its outgoing edges in creation order (Edge::index); the log weight is the bwd CSR's.
-FwdLists forward_lists(const pagan_graph *g) {
-    struct E { int src, dst, eid; float lw; };
-    std::vector<E> es;
-    es.reserve(g->bwd_off[g->n_sites]);
-    for (int s = 0; s < g->n_sites; ++s)
-        for (int k = g->bwd_off[s]; k < g->bwd_off[s + 1]; ++k) es.push_back({g->bwd_src[k], s, g->bwd_eid[k], g->bwd_logw[k]});
-    std::stable_sort(es.begin(), es.end(), [](const E &a, const E &b) { return a.src != b.src ? a.src < b.src : a.eid < b.eid; });
-    FwdLists f;
-    f.off.assign(g->n_sites + 1, 0);
-    for (const E &e : es) f.off[e.src + 1]++;
-    for (int s = 0; s < g->n_sites; ++s) f.off[s + 1] += f.off[s];
-    for (const E &e : es) { f.dst.push_back(e.dst); f.lw.push_back(e.lw); }
-    return f;
-}
-
 } // namespace
 
 int pagan_internal_replay(const pagan_graph *L, const pagan_graph *R, int64_t cells, const int *endcell, double endscore,
@@ -1030,192 +986,6 @@ struct pagan_fb {
     float counts_ms = 0;                                // last pg_fb_counts + pg_fb_counts_fold (booked at a batch's first pair)
     long long at(int i, int j) const { return dx.at(i, j); }
 };
-
-namespace {
-// initialise_array_corner_bwd (VA:740-854): assignments onto the cells the end corner reads
-static void fb_corner_init(const pagan_graph *left, const pagan_graph *right, int Lx, int Ly, const DiagIndex &dx, double l_ng,
-                           std::vector<long long> &init_at, std::vector<double> &init_val, int &init_dmin) {
-    init_dmin = Lx + Ly - 1;
-    auto put_init = [&](int i, int j, int s, double v) {
-        const long long a = dx.at(i, j);
-        if (a < 0) return;
-        init_dmin = std::min(init_dmin, i + j);
-        for (size_t k = 0; k < init_at.size(); ++k) if (init_at[k] == 3 * a + s) { init_val[k] = v; return; }   // later assignment wins
-        init_at.push_back(3 * a + s); init_val.push_back(v);
-    };
-    put_init(Lx - 1, Ly - 1, PAGAN_M_MAT, l_ng);
-    const int l0 = left->bwd_off[Lx], l1 = left->bwd_off[Lx + 1], r0 = right->bwd_off[Ly], r1 = right->bwd_off[Ly + 1];
-    if (l1 > l0 && r1 > r0)
-        for (int k1 = l0; k1 < l1; ++k1)
-            for (int k2 = r0; k2 < r1; ++k2)
-                put_init(left->bwd_src[k1], right->bwd_src[k2], PAGAN_M_MAT, l_ng + (double)left->bwd_logw[k1] + (double)right->bwd_logw[k2]);
-    for (int k1 = l0; k1 < l1; ++k1) put_init(left->bwd_src[k1], Ly - 1, PAGAN_X_MAT, 0.0);
-    for (int k2 = r0; k2 < r1; ++k2) put_init(Lx - 1, right->bwd_src[k2], PAGAN_Y_MAT, 0.0);
-}
-
-// Which schedule a pair's sweeps take, decided in ONE place (fb_stage and pagan_fb_debug_route both call this), and for the deep-ring
-// sweeps their plan: the segments and the diagonals that hold a far cell.
-struct FbRoute {
-    int groups = 1;                          // workgroups of a tiled sweep before the caller's caps (1: not tiled)
-    bool ring = false, deep = false;
-    int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // see pagan_fb_debug_route
-    std::vector<int> seg_start, seg_B, dfar;
-    int deep_block = 64;                     // threads of a deep-ring workgroup
-    int schedule() const { return deep ? 3 : (ring && groups == 1 ? 2 : (groups > 1 ? 1 : 0)); }
-};
-
-// v[k] := max of v over [k - before, k + after]
-static void fb_window_max(std::vector<int> &v, int before, int after) {
-    const int n = (int)v.size();
-    std::vector<int> out(n), dq(n);
-    int head = 0, tail = 0, nxt = 0;
-    for (int k = 0; k < n; ++k) {
-        for (; nxt < n && nxt <= k + after; ++nxt) { while (tail > head && v[dq[tail - 1]] <= v[nxt]) --tail; dq[tail++] = nxt; }
-        while (dq[head] < k - before) ++head;
-        out[k] = v[dq[head]];
-    }
-    v.swap(out);
-}
-
-// The deep-ring plan.  A diagonal needs B >= its own width and that of the FB_DP_HALO diagonals either side of it (the ring of a
-// segment is rebuilt from them at its boundary, in either direction).  Segments: greedy, a segment's B only grows while it is
-// shorter than FB_DP_MINSEG diagonals, ends where a wider diagonal comes, and where the next FB_DP_MINSEG diagonals all fit a smaller B.
-static void fb_deep_plan(int Lx, int Ly, const DiagIndex &dx, const std::vector<int> &rL, const std::vector<int> &rR,
-                         const std::vector<int> &sL, const std::vector<int> &sR, FbRoute *R) {
-    const int nd = Lx + Ly - 1;
-    std::vector<int> need(nd);
-    for (int d = 0; d < nd; ++d) { const int w = dx.imax[d] - dx.imin[d] + 1; need[d] = w > 512 ? 1024 : (w > 256 ? 512 : (w > 128 ? 256 : (w > 64 ? 128 : 64))); }
-    fb_window_max(need, FB_DP_HALO, FB_DP_HALO);
-    std::vector<int> ahead(need);
-    fb_window_max(ahead, 0, FB_DP_MINSEG - 1);
-    R->seg_start.clear(); R->seg_B.clear();
-    int maxB = 64, minD = FB_DP_CELLS / 64;
-    for (int s = 0; s < nd;) {
-        int B = need[s], e = s + 1;
-        for (; e < nd; ++e) {
-            const int nb = need[e];
-            if (nb == B) continue;
-            if (e - s < FB_DP_MINSEG) { B = std::max(B, nb); continue; }
-            if (nb > B || ahead[e] < B) break;
-        }
-        R->seg_start.push_back(s); R->seg_B.push_back(B);
-        maxB = std::max(maxB, B); minD = std::min(minD, FB_DP_CELLS / B);
-        s = e;
-    }
-    R->seg_start.push_back(nd);
-    // far cells: a predecessor (forward: reaches rL / rR of the bwd lists) or successor (backward: sL / sR of the fwd lists) D or more diagonals away
-    R->dfar.assign(nd, 0);
-    long long far_cells = 0; int far_diags = 0;
-    for (size_t g = 0; g + 1 < R->seg_start.size(); ++g) {
-        const int D = FB_DP_CELLS / R->seg_B[g];
-        int any = 0;
-        for (int d = R->seg_start[g]; d < R->seg_start[g + 1]; ++d) {
-            int f = 0;
-            for (int i = dx.imin[d]; i <= dx.imax[d]; ++i) {
-                const int j = d - i;
-                const int a = i > 0 ? rL[i] : 0, b = j > 0 ? rR[j] : 0;
-                if (a >= D || b >= D || (a > 0 && b > 0 && a + b >= D)) { ++far_cells; f |= 1; }
-                if (sL[i] >= D || sR[j] >= D || (sL[i] > 0 && sR[j] > 0 && sL[i] + sR[j] >= D)) f |= 2;
-            }
-            R->dfar[d] = f; any |= f;
-            if (f & 1) ++far_diags;
-        }
-        if (any) R->seg_B[g] |= 1 << 16;
-    }
-    R->deep_block = std::min(FB_RG_THREADS, 3 * maxB);
-    R->info[2] = (int)R->seg_B.size(); R->info[3] = minD;
-    R->info[6] = (int)std::min<long long>(far_cells, 0x7fffffff); R->info[7] = far_diags;
-}
-
-// a plain sequence: every site has exactly one edge, from the site before it
-static bool fb_plain(const pagan_graph *g) {
-    for (int sidx = 1; sidx < g->n_sites; ++sidx)
-        if (g->bwd_off[sidx + 1] - g->bwd_off[sidx] != 1 || g->bwd_src[g->bwd_off[sidx]] != sidx - 1) return false;
-    return g->bwd_off[1] == 0;
-}
-// no cell diagonal without a cell
-static bool fb_gapless(const DiagIndex &dx, int nd) {
-    for (int d = 0; d < nd; ++d) if (dx.imax[d] < dx.imin[d]) return false;
-    return true;
-}
-
-// Which kernel fills a pair's decode matrix, decided in ONE place (pagan_fb_decode_batch and pagan_fb_debug_decode_route both call
-// this): 1 = pg_fb_ring_decode -- two plain sequences whose widest diagonal fits a workgroup, the predicate of fb_route's schedule 2
-// without its shortest-pair rule (there is no tiled alternative to win on a short pair) --, 0 = pg_fb_decode_fill.
-// PAGAN_FB_DECODE_RING=0 switches the ring off.  Which sweep schedule wrote F and B does not matter: the layout is one.
-static int fb_decode_route(const pagan_graph *left, const pagan_graph *right, int Lx, int Ly, const DiagIndex &dx) {
-    if (fb_env_off("PAGAN_FB_DECODE_RING")) return 0;
-    if (!(dx.max_width <= FB_RG_MAXB && Lx >= 2 && Ly >= 2)) return 0;
-    return fb_plain(left) && fb_plain(right) && fb_gapless(dx, Lx + Ly - 1) ? 1 : 0;
-}
-
-static void fb_route(const pagan_graph *left, const pagan_graph *right, int Lx, int Ly, const DiagIndex &dx, bool has_band, int n_init,
-                     const FwdLists &fl, const FwdLists &fr, FbRoute *R) {
-    const int nd = Lx + Ly - 1, mw = dx.max_width;
-    // wide diagonals: 64 x 64 blocks over as many workgroups as a block anti-diagonal has blocks; PAGAN_FB_GROUPS=1 keeps the
-    // one-workgroup sweeps
-    int groups = mw > 256 ? std::min({FB_MAX_GROUPS, (Lx + FB_T - 1) / FB_T, (Ly + FB_T - 1) / FB_T}) : 1;
-    // A long tunnel (round 5; the leaf pairs of 32 x 100 kb: 2e5 diagonals of ~25 cells) on the block schedule as well: its one
-    // workgroup paid a __syncthreads() and a round trip to L2 per cell diagonal (2.7 us: 0.55 s a sweep); as blocks it is the few
-    // blocks the band has on a block anti-diagonal (fb_live_rows), a wave each, operands in registers / LDS, one counter barrier per
-    // 64 diagonals.  Workgroups: the blocks a diagonal of `mw` cells can lie in while it moves through 127 diagonals.
-    // PAGAN_FB_BAND_MIN_ND: the shortest pair (in cell diagonals) that takes this path (tests: 0; "off": none).
-    // ... and a long tunnel between plain sequences (every site one edge, from the site before it: leaves) on the LDS-ring sweeps
-    // (pg_fb_forward_ring): PAGAN_FB_RING=0 switches them off, PAGAN_FB_RING_MIN_ND is their shortest pair (default 256 diagonals)
-    // ... and a graph pair (any other edge lists) inside a tunnel on the deep-ring sweeps (pg_fb_forward_deep, dp_fb_deep.inc):
-    // PAGAN_FB_DEEP=0 switches them off, PAGAN_FB_DEEP_MIN_ND is their shortest pair (default 4,096 diagonals)
-    const bool gapless = fb_gapless(dx, nd);
-    const bool both_plain = fb_plain(left) && fb_plain(right);
-    const bool shape_ok = mw <= FB_RG_MAXB && Lx >= 2 && Ly >= 2 && n_init <= FB_RG_INIT && gapless;
-    bool ring = false, deep = false;
-    {
-        const int min_nd = fb_env_int("PAGAN_FB_RING_MIN_ND", 256);   // (a step of the ring sweeps is 1 us against the one-workgroup kernels' 2.7: worth it from a few hundred diagonals on)
-        ring = !fb_env_off("PAGAN_FB_RING") && nd >= min_nd && shape_ok && both_plain;
-        if (ring && !std::getenv("PAGAN_FB_GROUPS")) groups = 1;
-    }
-    // the longest reach of a site's lists: bwd (the forward sweep's predecessors), fwd without the edges into the end site (the backward sweep's successors)
-    std::vector<int> rL, rR, sL, sR;
-    if (!both_plain) { rL.assign(Lx + 1, 0); rR.assign(Ly + 1, 0); sL.assign(Lx + 1, 0); sR.assign(Ly + 1, 0); }
-    // (two plain sequences: every reach is 1, and nothing below reads the arrays -- such a pair is never a deep-ring pair)
-    auto reaches = [&](const pagan_graph *g, const FwdLists &f, int n, std::vector<int> &r, std::vector<int> &s) {
-        int longest = 0;
-        if (both_plain) return n > 1 ? 1 : 0;
-        for (int v = 1; v < n; ++v) {
-            for (int k = g->bwd_off[v]; k < g->bwd_off[v + 1]; ++k) r[v] = std::max(r[v], v - g->bwd_src[k]);
-            longest = std::max(longest, r[v]);
-        }
-        for (int v = 0; v < n; ++v)
-            for (int k = f.off[v]; k < f.off[v + 1]; ++k) if (f.dst[k] < n) s[v] = std::max(s[v], f.dst[k] - v);
-        return longest;
-    };
-    R->info[0] = nd; R->info[1] = mw;
-    R->info[4] = reaches(left, fl, Lx, rL, sL); R->info[5] = reaches(right, fr, Ly, rR, sR);
-    {
-        const int min_nd = fb_env_int("PAGAN_FB_DEEP_MIN_ND", 4096);
-        // the list windows hold FB_DP_E entries of any FB_DP_W consecutive sites
-        auto lists_fit = [](const int *off, int n_sites) {
-            for (int v = 0; v < n_sites; ++v) if (off[std::min(n_sites, v + FB_DP_W)] - off[v] > FB_DP_E) return false;
-            return true;
-        };
-        deep = !fb_env_off("PAGAN_FB_DEEP") && !std::getenv("PAGAN_FB_GROUPS") && has_band && nd >= min_nd && shape_ok && !both_plain &&
-               lists_fit(left->bwd_off, left->n_sites) && lists_fit(right->bwd_off, right->n_sites) &&
-               lists_fit(fl.off.data(), left->n_sites) && lists_fit(fr.off.data(), right->n_sites);
-        if (deep) { groups = 1; ring = false; fb_deep_plan(Lx, Ly, dx, rL, rR, sL, sR, R); }
-    }
-    {
-        const char *e = std::getenv("PAGAN_FB_BAND_MIN_ND");
-        const int min_nd = e && std::strcmp(e, "off") == 0 ? 0x7fffffff : fb_env_int("PAGAN_FB_BAND_MIN_ND", 4096);
-        if (ring || deep) {}
-        else if (groups == 1 && nd >= min_nd && Lx >= 2 && Ly >= 2)
-            groups = std::max(2, std::min({FB_MAX_GROUPS, (mw + FB_T - 1) / FB_T + 2, (Lx + FB_T - 1) / FB_T, (Ly + FB_T - 1) / FB_T}));
-        // (and a pair that is "wide" by a box of its tunnel -- one of the 16 leaf pairs has a diagonal of 295 cells -- does not need
-        //  the 64 workgroups of a full matrix at every barrier: a diagonal of mw cells lies in mw / 64 + 2 blocks at most)
-        else if (groups > 1) groups = std::max(2, std::min(groups, (mw + FB_T - 1) / FB_T + 2));
-    }
-    if (std::getenv("PAGAN_FB_GROUPS")) { groups = std::max(1, std::min(FB_MAX_GROUPS, fb_env_int("PAGAN_FB_GROUPS", 1))); ring = false; }
-    R->groups = groups; R->ring = ring; R->deep = deep;
-}
-} // namespace
 
 namespace {
 // The calling thread on `device` (negative: the one it is on) for the length of a call, back on the device it came with afterwards.
@@ -1324,30 +1094,35 @@ struct FbCall {
     float ms(int span) const { float v = 0; (void)hipEventElapsedTime(&v, ev[2 * span], ev[2 * span + 1]); return v; }
 };
 
-// One pair up to the upload of its inputs: validation, band index, lists, arena, the job record with its workgroup count
-// (`groups_cap`, `groups_cap_b`: what the caller's launch leaves this pair's forward / backward sweep).  What the handle does not
-// hold itself stays here.
+// One planned pair up to the upload of its inputs: the arena, the job record with its workgroup count
+// (`groups_cap`, `groups_cap_b`: what the caller's launch leaves this pair's forward / backward sweep).  Nothing is decided here:
+// the schedule, the workgroup and every array but the score table come with the plan, whose band index the handle keeps.
 struct FbStaged {
     std::unique_ptr<pagan_fb, void (*)(pagan_fb *)> fb{nullptr, pagan_fb_destroy};
     int groups_b = 1;                        // workgroups of the backward tiled sweep (the forward sweep's: fb->groups)
-    int block = 64;                          // threads of a workgroup; ring sweeps: their rows B
+    int block = 64, nsplit = 1;              // FbPlan's
     double t_host[3] = {0, 0, 0};            // band index + lists, arena, upload (seconds)
     size_t arena_bytes = 0;
 };
 static double fb_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pagan_model_prob *model, const pagan_band *band,
-                    const pagan_opts *opts, int groups_cap, int groups_cap_b, FbStaged *st) {
-    if (!left || !right || !model || !st || !model->score || model->n_states < 1) return PAGAN_E_ARG;
+// what fb_plan_pair does not look at, in the order the errors have always come in: the arguments, the graphs, the model, a device
+static int fb_check_pair(const pagan_graph *left, const pagan_graph *right, const pagan_model_prob *model) {
+    if (!left || !right || !model || !model->score || model->n_states < 1) return PAGAN_E_ARG;
     int rc = check_graph(left);
     if (rc == PAGAN_OK) rc = check_graph(right);
     if (rc != PAGAN_OK) return rc;
-    const int Lx = left->n_sites - 1, Ly = right->n_sites - 1, S = model->n_states;
-    const double th0 = fb_now();
-    for (int s = 1; s < Lx; ++s) if (left->state[s] < 0 || left->state[s] >= S) return PAGAN_E_MODEL;
-    for (int s = 1; s < Ly; ++s) if (right->state[s] < 0 || right->state[s] >= S) return PAGAN_E_MODEL;
+    const int S = model->n_states;
+    for (int s = 1; s < left->n_sites - 1; ++s) if (left->state[s] < 0 || left->state[s] >= S) return PAGAN_E_MODEL;
+    for (int s = 1; s < right->n_sites - 1; ++s) if (right->state[s] < 0 || right->state[s] >= S) return PAGAN_E_MODEL;
     if (!(model->gap_open > 0) || !(model->gap_ext > 0) || !(model->non_gap > 0)) return PAGAN_E_MODEL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return PAGAN_E_NODEVICE;
+    return PAGAN_OK;
+}
+static int fb_stage(FbPlan &plan, const pagan_graph *left, const pagan_graph *right, const pagan_model_prob *model,
+                    const pagan_opts *opts, int groups_cap, int groups_cap_b, FbStaged *st) {
+    const int Lx = plan.Lx, Ly = plan.Ly, S = model->n_states;
+    const double th0 = fb_now();
     st->fb.reset(new pagan_fb());            // (st owns the handle: an error from here on destroys it with st)
     pagan_fb *fb = st->fb.get();
     if (opts && opts->device >= 0) { FB_TRY(hipSetDevice(opts->device)); fb->device = opts->device; }
@@ -1355,32 +1130,20 @@ static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pag
     fb->Lx = Lx; fb->Ly = Ly; fb->S = S; fb->L = left; fb->R = right;
     fb->score.assign(model->score, model->score + (size_t)S * S);
     fb->gap_open = model->gap_open; fb->gap_ext = model->gap_ext; fb->non_gap = model->non_gap;
-    rc = fb->rb.build(Lx, Ly, band);
-    if (rc != PAGAN_OK) return rc;
-    fb->dx.build(Lx, Ly, fb->rb);
+    fb->rb = std::move(plan.rb); fb->dx = std::move(plan.dx);
     const long long cells = fb->dx.cells;
-    const int nd = Lx + Ly - 1;
-    const FwdLists fl = forward_lists(left), fr = forward_lists(right);
     std::vector<double> ltab((size_t)S * S);
     for (size_t k = 0; k < ltab.size(); ++k) ltab[k] = std::log((double)model->score[k]);
-    std::vector<long long> init_at;
-    std::vector<double> init_val;
-    const double l_ng = std::log((double)model->non_gap);
-    int init_dmin = nd;
-    fb_corner_init(left, right, Lx, Ly, fb->dx, l_ng, init_at, init_val, init_dmin);
-    FbRoute route;
-    fb_route(left, right, Lx, Ly, fb->dx, band != nullptr, (int)init_at.size(), fl, fr, &route);
-    // the schedule: fb_route above, the tiled sweeps' workgroups within the caller's caps
-    const int mw = fb->dx.max_width;
-    fb->groups = route.groups > 1 ? std::max(2, std::min(route.groups, groups_cap)) : route.groups;
-    st->groups_b = route.groups > 1 ? std::max(2, std::min(route.groups, groups_cap_b)) : 1;
+    fb->groups = plan.groups_within(groups_cap); st->groups_b = plan.groups_within(groups_cap_b);
+    fb->ring = plan.ring; fb->deep = plan.deep;
+    st->block = plan.block; st->nsplit = plan.nsplit;
     PgFbJob &J = fb->job;
-    J.Lx = Lx; J.Ly = Ly; J.nd = nd; J.S = S;
-    J.l_ext = std::log((double)model->gap_ext); J.l_open = std::log((double)model->gap_open); J.l_ng = l_ng;
+    J.Lx = Lx; J.Ly = Ly; J.nd = plan.nd; J.S = S;
+    J.l_ext = std::log((double)model->gap_ext); J.l_open = std::log((double)model->gap_open); J.l_ng = std::log((double)model->non_gap);
     J.cells = cells;
-    J.n_init = (int)init_at.size(); J.init_dmin = init_dmin;
+    J.n_init = (int)plan.init_at.size(); J.init_dmin = plan.init_dmin;
     J.groups = fb->groups; J.groups_b = st->groups_b;
-    J.nseg = (int)route.seg_B.size();
+    J.nseg = (int)plan.seg_B.size();
     // one arena: the job record and the inputs, then F and B (pagan_fb_predict_bytes and the pool's fit rule know this layout)
     FbLayout lay;
     auto vec = [&](const auto &v, auto **field) { lay.add(v.data(), sizeof(v[0]) * v.size(), field); };
@@ -1388,12 +1151,12 @@ static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pag
     lay.add(&J, sizeof(PgFbJob), &fb->d_job);
     lay.add(left->state, 4 * nL, &J.stL); lay.add(left->bwd_off, 4 * (nL + 1), &J.offL); lay.add(left->bwd_src, 4 * nbL, &J.srcL); lay.add(left->bwd_logw, 4 * nbL, &J.lwL);
     lay.add(right->state, 4 * nR, &J.stR); lay.add(right->bwd_off, 4 * (nR + 1), &J.offR); lay.add(right->bwd_src, 4 * nbR, &J.srcR); lay.add(right->bwd_logw, 4 * nbR, &J.lwR);
-    vec(fl.off, &J.foffL); vec(fl.dst, &J.fdstL); vec(fl.lw, &J.flwL);
-    vec(fr.off, &J.foffR); vec(fr.dst, &J.fdstR); vec(fr.lw, &J.flwR);
+    vec(plan.fl.off, &J.foffL); vec(plan.fl.dst, &J.fdstL); vec(plan.fl.lw, &J.flwL);
+    vec(plan.fr.off, &J.foffR); vec(plan.fr.dst, &J.fdstR); vec(plan.fr.lw, &J.flwR);
     vec(ltab, &J.ltab);
     vec(fb->dx.imin, &J.imin); vec(fb->dx.imax, &J.imax); vec(fb->dx.doff, &J.doff);
-    vec(init_at, &J.init_at); vec(init_val, &J.init_val);
-    vec(route.seg_start, &J.seg_start); vec(route.seg_B, &J.seg_B); vec(route.dfar, &J.dfar);
+    vec(plan.init_at, &J.init_at); vec(plan.init_val, &J.init_val);
+    vec(plan.seg_start, &J.seg_start); vec(plan.seg_B, &J.seg_B); vec(plan.dfar, &J.dfar);
     lay.add(nullptr, 16, &J.totals);
     lay.add(nullptr, 256, &J.sync);                       // two barrier counters + give-up words of the wide sweeps (zero)
     const size_t in_bytes = lay.cur;
@@ -1406,14 +1169,7 @@ static int fb_stage(const pagan_graph *left, const pagan_graph *right, const pag
     fb->dF = J.F; fb->dB = J.B;
     const double th2 = fb_now();
     FB_TRY(hipMemcpy(fb->arena, stage.data(), in_bytes, hipMemcpyHostToDevice));
-    // a thread per cell of the widest diagonal, up to the 1024 of a workgroup (a cell is ~20 exp / log1p calls: a thread with
-    // eight cells of a 2,000-cell diagonal was the whole sweep's pace)
-    st->block = mw >= 768 ? 1024 : mw >= 384 ? 512 : mw >= 192 ? 256 : (mw >= 96 ? 128 : 64);
-    fb->ring = route.ring && fb->groups == 1;
-    if (fb->ring) st->block = mw > 512 ? 1024 : (mw > 256 ? 512 : (mw > 128 ? 256 : (mw > 64 ? 128 : 64)));     // a thread per row of the widest diagonal
-    fb->deep = route.deep;
-    if (fb->deep) st->block = route.deep_block;
-    st->t_host[0] = th1 - th0; st->t_host[1] = th2 - th1; st->t_host[2] = fb_now() - th2;
+    st->t_host[0] += th1 - th0; st->t_host[1] = th2 - th1; st->t_host[2] = fb_now() - th2;
     st->arena_bytes = lay.cur;
     return PAGAN_OK;
 }
@@ -1449,15 +1205,14 @@ struct FbSlots {
 };
 static FbSlots fb_slots_of[64];
 struct FbSlotLease { FbSlots *s; int n; ~FbSlotLease() { if (n > 0) s->give(n); } };
-static int fb_slot_cap(int device) {
+static int fb_slot_cap(int device, const FbSwitches &sw) {
     int n_cu = 0;
-    const int per_cu_x16 = std::max(8, std::min(48, fb_env_int("PAGAN_FB_SLOTS_X16", 46)));   // 2.9 workgroups per compute unit of the 3 that fit (A/B; 2.5 until round 5)
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0) return per_cu_x16 * n_cu / 16;
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0) return sw.slots_x16 * n_cu / 16;
     return 512;
 }
 
 // The four schedules' kernels behind one launch.  `block`: the threads of a one-workgroup, tiled or deep-ring workgroup, the rows
-// B of a ring sweep's -- its workgroup has three threads a row up to B = 256, two with 512 (PAGAN_FB_RING_SPLIT=0: one), see
+// B of a ring sweep's -- its workgroup has `nsplit` threads a row: three up to B = 256, two with 512 (PAGAN_FB_RING_SPLIT=0: one), see
 // FB_RING_THREADS; 1,024 threads is what a workgroup holds.  all_lds: every pair's score table fits LDS (the kernels without the
 // table's load from memory; the one-workgroup kernels have one form).
 enum FbKind { FB_K_SMALL = 0, FB_K_TILED = 1, FB_K_RING = 2, FB_K_DEEP = 3 };      // (pagan_fb_schedule's codes)
@@ -1472,8 +1227,7 @@ static FbKernel fb_kernel(FbKind kind, bool fwd, int block, int nsplit) {
     if (nsplit == 2) return fwd ? pg_fb_forward_ring<ALL_LDS, 2, 512> : pg_fb_backward_ring<ALL_LDS, 2, 512>;
     return fwd ? pg_fb_forward_ring<ALL_LDS, 1, 512> : pg_fb_backward_ring<ALL_LDS, 1, 512>;
 }
-static void fb_launch(FbKind kind, bool fwd, bool all_lds, dim3 grid, int block, hipStream_t stream, const PgFbJob *jobs) {
-    const int nsplit = kind != FB_K_RING || fb_env_off("PAGAN_FB_RING_SPLIT") ? 1 : (block <= 256 ? 3 : (block <= 512 ? 2 : 1));
+static void fb_launch(FbKind kind, bool fwd, bool all_lds, dim3 grid, int block, int nsplit, hipStream_t stream, const PgFbJob *jobs) {
     const FbKernel k = all_lds ? fb_kernel<true>(kind, fwd, block, nsplit) : fb_kernel<false>(kind, fwd, block, nsplit);
     hipLaunchKernelGGL(k, grid, dim3((unsigned)(nsplit * block)), 0, stream, jobs);
 }
@@ -1485,7 +1239,7 @@ static void fb_launch(FbKind kind, bool fwd, bool all_lds, dim3 grid, int block,
 // per (workgroup size, table in LDS or not) -- a handful at most; a one-workgroup pair is a group and a span of its own.
 // (Only the tiled group is charged to the slot budget: see ADVICE.md's fourth finding; this list is where the others would be.)
 struct FbGroup {
-    FbKind kind; bool all_lds; int block;
+    FbKind kind; bool all_lds; int block, nsplit;
     unsigned gx, gx_b, gy;                   // the grid: x of the forward / of the backward launch, y
     std::vector<int> ks;                     // its pairs, in the order of its job records
     const PgFbJob *jobs;                     // ... which are here on the device
@@ -1511,7 +1265,7 @@ static int fb_launch_span(FbChunkRes &res, const std::vector<FbGroup> &groups, F
             hipStream_t s = S.lane[dir];
             if (g > S.a) FB_DO(res.stream(&s));
             else if (S.timed) FB_TRY(hipEventRecord(S.ev[2 * dir], s));
-            fb_launch(G.kind, dir == 0, G.all_lds, dim3(dir ? G.gx_b : G.gx, G.gy), G.block, s, G.jobs);
+            fb_launch(G.kind, dir == 0, G.all_lds, dim3(dir ? G.gx_b : G.gx, G.gy), G.block, G.nsplit, s, G.jobs);
             if (g > S.a) {
                 hipEvent_t done = nullptr;
                 FB_DO(res.event(false, &done));
@@ -1527,16 +1281,22 @@ static int fb_launch_span(FbChunkRes &res, const std::vector<FbGroup> &groups, F
 // caller's to hand back or to destroy -- after this function has returned, that is after every stream of the chunk has been
 // synchronised by its owner, whichever way the function was left.  `only_pair`: the chunk is the call's one pair.
 static int fb_run_chunk(int chunk, const pagan_graph *const *left, const pagan_graph *const *right, const pagan_model_prob *const *model,
-                        const pagan_band *const *band, const pagan_opts *opts, bool only_pair, int cap, FbStaged *st) {
+                        const pagan_band *const *band, const pagan_opts *opts, bool only_pair, int cap, const FbSwitches &sw, FbStaged *st) {
     const int device = opts->device;
     // the backward sweep is the slower of the two when a block anti-diagonal takes several turns: it gets the larger share
     // of the slots (PAGAN_FB_SPLIT: the forward sweeps' per cent, A/B).  A single pair's caps come out at or above FB_MAX_GROUPS
     // at the default budget; with PAGAN_FB_SLOTS_X16 near its minimum they can cut a single pair's sweeps too.
-    const int split = std::max(20, std::min(80, fb_env_int("PAGAN_FB_SPLIT", 40)));
     const int per_pair = std::max(4, cap / chunk);            // slots of one pair, both sweeps
-    const int groups_cap = std::max(2, (per_pair * split + 50) / 100), groups_cap_b = std::max(2, per_pair - groups_cap);
+    const int groups_cap = std::max(2, (per_pair * sw.split + 50) / 100), groups_cap_b = std::max(2, per_pair - groups_cap);
     std::vector<int> rcs(chunk, PAGAN_OK);
-    auto stage = [&](int q) { rcs[q] = fb_stage(left[q], right[q], model[q], band ? band[q] : nullptr, opts, groups_cap, groups_cap_b, &st[q]); };
+    auto stage = [&](int q) {
+        if ((rcs[q] = fb_check_pair(left[q], right[q], model[q])) != PAGAN_OK) return;
+        const double t0 = fb_now();
+        FbPlan plan;
+        if ((rcs[q] = fb_plan_pair(left[q], right[q], band ? band[q] : nullptr, sw, &plan, std::log((double)model[q]->non_gap))) != PAGAN_OK) return;
+        st[q].t_host[0] = fb_now() - t0;
+        rcs[q] = fb_stage(plan, left[q], right[q], model[q], opts, groups_cap, groups_cap_b, &st[q]);
+    };
     if (chunk == 1) stage(0);        // on the calling thread: a caller with a thread per pair makes no second thread per call
     else {
         std::vector<std::thread> pool;
@@ -1553,7 +1313,7 @@ static int fb_run_chunk(int chunk, const pagan_graph *const *left, const pagan_g
     for (int q = 0; q < chunk; ++q) if (st[q].fb->device != device) return PAGAN_E_INTERNAL;      // (every pair's arena is on the launches' device)
     const double th3 = fb_now();
     // the launch groups, in the order they go out: tiled, ring, one-workgroup, and the deep-ring groups last (below)
-    auto lds = [&](int q) { return st[q].fb->S * st[q].fb->S <= 256; };
+    auto lds = [&](int q) { return fb_table_in_lds(st[q].fb->S); };
     auto key = [&](int q) { return 2 * st[q].block + (lds(q) ? 1 : 0); };              // workgroup size, table in LDS
     std::vector<int> of[4];
     for (int q = 0; q < chunk; ++q) of[st[q].fb->groups > 1 ? FB_K_TILED : (st[q].fb->deep ? FB_K_DEEP : (st[q].fb->ring ? FB_K_RING : FB_K_SMALL))].push_back(q);
@@ -1567,7 +1327,7 @@ static int fb_run_chunk(int chunk, const pagan_graph *const *left, const pagan_g
         for (size_t a = 0, z; a < ks.size(); a = z) {
             z = kind == FB_K_TILED ? ks.size() : a + 1;
             while (kind != FB_K_SMALL && z < ks.size() && key(ks[z]) == key(ks[a])) ++z;
-            FbGroup G{kind, true, kind == FB_K_TILED ? 64 : st[ks[a]].block, (unsigned)(z - a), (unsigned)(z - a), 1, {ks.begin() + a, ks.begin() + z}, st[ks[a]].fb->d_job};
+            FbGroup G{kind, true, st[ks[a]].block, st[ks[a]].nsplit, (unsigned)(z - a), (unsigned)(z - a), 1, {ks.begin() + a, ks.begin() + z}, st[ks[a]].fb->d_job};
             if (kind == FB_K_TILED) { G.gx = G.gx_b = 0; G.gy = (unsigned)(z - a); }
             for (int q : G.ks) {
                 G.all_lds = G.all_lds && lds(q);
@@ -1594,7 +1354,6 @@ static int fb_run_chunk(int chunk, const pagan_graph *const *left, const pagan_g
     }
     // the lease is taken before the tiled launches and given back at the end of the chunk
     if (slots_needed > 0) { lease.s->take(slots_needed, cap); lease.n = slots_needed; }
-    const bool bwd_first = std::getenv("PAGAN_FB_BWD_FIRST") != nullptr;      // (A/B: which tiled sweep's workgroups are dealt out first)
     for (FbSpan &S : spans) {
         const FbKind kind = groups[S.a].kind;
         if (kind == FB_K_DEEP) {
@@ -1604,7 +1363,7 @@ static int fb_run_chunk(int chunk, const pagan_graph *const *left, const pagan_g
             FB_TRY(hipGetLastError());
             if (groups[0].kind == FB_K_TILED) { FB_TRY(hipStreamSynchronize(spans[0].lane[0])); FB_TRY(hipStreamSynchronize(spans[0].lane[1])); }
         }
-        FB_DO(fb_launch_span(res, groups, S, bwd_first && kind == FB_K_TILED));
+        FB_DO(fb_launch_span(res, groups, S, sw.bwd_first && kind == FB_K_TILED));      // (A/B: which tiled sweep's workgroups are dealt out first)
     }
     FB_TRY(hipGetLastError());
     const double th4 = fb_now();
@@ -1621,7 +1380,7 @@ static int fb_run_chunk(int chunk, const pagan_graph *const *left, const pagan_g
                 FB_DO(fb_finish(&st[q], first ? ms[0] : 0.0f, first ? ms[1] : 0.0f));
             }
     }
-    if (std::getenv("PAGAN_DP_VERBOSE")) {
+    if (sw.verbose) {
         double t[3] = {0, 0, 0}, mb = 0;
         for (int q = 0; q < chunk; ++q) { for (int k = 0; k < 3; ++k) t[k] += st[q].t_host[k]; mb += st[q].arena_bytes / 1048576.0; }
         std::fprintf(stderr, "pagan_fb: host: %d pair(s): band index + lists %.1f ms, arena (%.0f MB) %.1f ms, upload %.1f ms, streams + launch (+ slot wait) %.1f ms, kernels %.1f ms, rest %.1f ms\n",
@@ -1652,12 +1411,13 @@ int pagan_fb_run_batch(int32_t n, const pagan_graph *const *left, const pagan_gr
     pagan_opts staged_opts;
     staged_opts.flags = opts ? opts->flags : 0u;
     staged_opts.device = on_device.device;
-    const int cap = fb_slot_cap(staged_opts.device);
+    const FbSwitches sw = FbSwitches::read();
+    const int cap = fb_slot_cap(staged_opts.device, sw);
     std::vector<FbStaged> st(n);         // owns the handles until they are handed back
     // chunks of pairs whose tiled sweeps fit the slot budget with at least eight workgroups a sweep
     for (int done = 0, chunk; done < n; done += chunk) {
         chunk = std::min(n - done, std::max(1, cap / 16));
-        FB_DO(fb_run_chunk(chunk, left + done, right + done, model + done, band ? band + done : nullptr, &staged_opts, n == 1, cap, &st[done]));
+        FB_DO(fb_run_chunk(chunk, left + done, right + done, model + done, band ? band + done : nullptr, &staged_opts, n == 1, cap, sw, &st[done]));
     }
     for (int k = 0; k < n; ++k) out[k] = st[k].fb.release();
     return PAGAN_OK;
@@ -1680,29 +1440,6 @@ int pagan_fb_kernel_ms(const pagan_fb *fb, double ms[2]) {
 int pagan_fb_groups(const pagan_fb *fb) { return fb ? (fb->ring || fb->deep ? 0 : fb->groups) : PAGAN_E_ARG; }
 
 int pagan_fb_schedule(const pagan_fb *fb) { return fb ? (fb->deep ? 3 : (fb->ring ? 2 : (fb->groups > 1 ? 1 : 0))) : PAGAN_E_ARG; }
-
-// Host only: what fb_stage would decide for this pair under the current environment (it calls the same fb_route).
-int pagan_fb_debug_route(const pagan_graph *left, const pagan_graph *right, const pagan_band *band, int32_t info[8]) {
-    if (!left || !right) return PAGAN_E_ARG;
-    int rc = check_graph(left);
-    if (rc == PAGAN_OK) rc = check_graph(right);
-    if (rc != PAGAN_OK) return rc;
-    const int Lx = left->n_sites - 1, Ly = right->n_sites - 1;
-    RowBand rb;
-    rc = rb.build(Lx, Ly, band);
-    if (rc != PAGAN_OK) return rc;
-    DiagIndex dx;
-    dx.build(Lx, Ly, rb);
-    std::vector<long long> init_at;
-    std::vector<double> init_val;
-    int init_dmin = 0;
-    fb_corner_init(left, right, Lx, Ly, dx, 0.0, init_at, init_val, init_dmin);
-    const FwdLists fl = forward_lists(left), fr = forward_lists(right);
-    FbRoute route;
-    fb_route(left, right, Lx, Ly, dx, band != nullptr, (int)init_at.size(), fl, fr, &route);
-    if (info) for (int k = 0; k < 8; ++k) info[k] = route.info[k];
-    return route.schedule();
-}
 
 int pagan_fb_totals(const pagan_fb *fb, double *log_fwd, double *log_bwd, int64_t *cells) {
     if (!fb) return PAGAN_E_ARG;
@@ -1995,17 +1732,6 @@ int64_t pagan_fb_counts_predict_bytes(int32_t left_sites, int32_t right_sites, i
     const int64_t nb = ((int64_t)left_sites - 1 + FB_CN_ROWS - 1) / FB_CN_ROWS;
     const int64_t segs = ((int64_t)right_sites - 1 + FB_CN_ROWS - 1 + FB_CN_SEG - 1) / FB_CN_SEG;
     return (8 * stride + 12) * nb * segs + 8 * (stride + 3) + (int64_t)sizeof(PgFbJob) + (int64_t)sizeof(PgFbCounts) + 5 * 256;
-}
-
-// What fb_stage's arena takes: F and B (24 B a cell each), the per-diagonal index and plan (20 B a diagonal), the graphs' lists
-// in both directions (sized for four edges a site: 96 B), the score table (up to 211 x 211 doubles) and the record's small
-// pieces; then the pool's allowance of a sixteenth (FbArenaPool::take).  Only the lists are an estimate.
-int64_t pagan_fb_predict_bytes(int32_t left_sites, int32_t right_sites, const pagan_band *band) {
-    const int64_t cells = pagan_dp_count_cells(left_sites, right_sites, band);
-    if (cells < 0) return cells;
-    const int64_t nd = (int64_t)left_sites + right_sites - 3;
-    const int64_t need = 48 * cells + 20 * nd + 96 * ((int64_t)left_sites + right_sites) + (512 << 10) + 8192;
-    return need + need / 16;
 }
 
 // u[s] = (mix(mix(mix(seed) ^ node) ^ s) >> 11) * 2^-53, mix = splitmix64's output function of x + 0x9E3779B97F4A7C15
@@ -2374,11 +2100,11 @@ int pagan_fb_decode_batch(int32_t n, pagan_fb *const *fbs, double gap_weight, ui
     FbCall c;
     FB_DO(c.open(n, fbs));
     // launch order: the fill pairs, then the ring pairs by workgroup size and by whether their score table needs looking at
+    const FbSwitches sw = FbSwitches::read();
     std::vector<int> block(n, 0), order(n), tabfin(n, 1);
     for (int k = 0; k < n; ++k) {
         const pagan_fb *fb = fbs[k];
-        const int mw = fb->dx.max_width;
-        if (fb_decode_route(fb->L, fb->R, fb->Lx, fb->Ly, fb->dx)) block[k] = mw > 512 ? 1024 : (mw > 256 ? 512 : (mw > 128 ? 256 : (mw > 64 ? 128 : 64)));
+        if (fb_decode_route(fb->L, fb->R, fb->Lx, fb->Ly, fb->dx, sw)) block[k] = fb_block_for(fb->dx.max_width);
         for (float v : fb->score) if (!(v > 0.0f) || !(v < HUGE_VALF)) tabfin[k] = 0;
         order[k] = k;
     }
@@ -2409,11 +2135,7 @@ int pagan_fb_decode_batch(int32_t n, pagan_fb *const *fbs, double gap_weight, ui
         R.tab_finite = tabfin[k];
         c.put(o_jobs + (size_t)q * sizeof(PgFbJob), fb->job);
         c.put(o_recs + (size_t)q * sizeof(PgFbDecode), R);
-        if (!block[k]) {
-            const int mw = fb->dx.max_width;
-            fill_block = std::max(fill_block, mw >= 768 ? 1024 : mw >= 384 ? 512 : mw >= 192 ? 256 : (mw >= 96 ? 128 : 64));
-            ++n_fill;
-        }
+        if (!block[k]) { fill_block = std::max(fill_block, fb_block_for(fb->dx.max_width, true)); ++n_fill; }
     }
     const PgFbJob *jobs = c.dev<const PgFbJob>(o_jobs);
     const PgFbDecode *recs = c.dev<const PgFbDecode>(o_recs);
@@ -2493,21 +2215,6 @@ int pagan_fb_decoded_ms(const pagan_fb_decoded *d, double ms[2]) {
     if (!d || !ms) return PAGAN_E_ARG;
     ms[0] = d->ms[0]; ms[1] = d->ms[1];
     return PAGAN_OK;
-}
-
-// Host only: what pagan_fb_decode_batch would decide for this pair under the current environment (it calls the same fb_decode_route).
-int pagan_fb_debug_decode_route(const pagan_graph *left, const pagan_graph *right, const pagan_band *band) {
-    if (!left || !right) return PAGAN_E_ARG;
-    int rc = check_graph(left);
-    if (rc == PAGAN_OK) rc = check_graph(right);
-    if (rc != PAGAN_OK) return rc;
-    const int Lx = left->n_sites - 1, Ly = right->n_sites - 1;
-    RowBand rb;
-    rc = rb.build(Lx, Ly, band);
-    if (rc != PAGAN_OK) return rc;
-    DiagIndex dx;
-    dx.build(Lx, Ly, rb);
-    return fb_decode_route(left, right, Lx, Ly, dx);
 }
 
 // What a decode takes beside the pair's own arena: A with the pool's allowance of a sixteenth (FbArenaPool::take), 12 B a path

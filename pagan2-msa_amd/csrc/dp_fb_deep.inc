@@ -1,5 +1,5 @@
 // dp_fb_deep.inc -- included by dp_fb.hip: the LDS-ring sweeps for GRAPH pairs inside a tunnel (pg_fb_forward_deep /
-// pg_fb_backward_deep).  The host's side -- who takes them (fb_route) and the plan (fb_deep_plan) -- is in dp_fb.hip.
+// pg_fb_backward_deep).  The host's side -- who takes them (fb_route) and the plan (fb_deep_plan) -- is in dp_fb_plan.cpp.
 //
 // Same frame as the ring sweeps of plain sequences (dp_fb.hip, pg_fb_forward_ring): one workgroup a pair, thread x owns the row
 // i = x (mod B) of the current diagonal, a step ends in s_waitcnt lgkmcnt(0) + s_barrier, the scores leave for memory
@@ -22,12 +22,7 @@
 //    host marks the diagonals that hold a far cell (pagan_fb_debug_route counts them); a diagonal without one takes a step that
 //    holds no load from memory and no vmcnt wait.
 
-#define FB_DP_CELLS 4096         // D * B
 #define FB_DP_REFILL 256
-#define FB_DP_W 1352             // sites in a window: <= 1,024 rows of a diagonal + FB_DP_REFILL + the 64 a near edge reaches ahead (backward)
-#define FB_DP_E 1664             // list entries in a window (a pair with more in any FB_DP_W consecutive sites is not eligible)
-#define FB_DP_MINSEG 256         // hysteresis of the segment plan, in diagonals
-#define FB_DP_HALO 64            // diagonals either side that a diagonal's B must hold as well (>= any D - 1)
 
 typedef const __attribute__((address_space(1))) unsigned long long *fb_gcu;
 

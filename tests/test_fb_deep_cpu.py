@@ -1,6 +1,6 @@
 """The deep-ring forward/backward sweeps (dp_fb_deep.inc: pg_fb_forward_deep / pg_fb_backward_deep), what needs no GPU:
 
-  * the routing: pagan_fb_debug_route is the function pagan_fb_run decides with (fb_route in dp_fb.hip), so what it answers here
+  * the routing: pagan_fb_debug_route is the function pagan_fb_run decides with (fb_route in dp_fb_plan.cpp), so what it answers here
     is what the product does -- plain pairs keep the ring sweeps, graph pairs of 4,096 cell diagonals or more inside a tunnel take
     the deep ring, PAGAN_FB_DEEP=0 gives them back to the block schedule, short pairs stay on the one-workgroup kernels, and one
     edge that reaches further back than any ring does not disqualify a pair (it marks a few diagonals far);

@@ -240,6 +240,7 @@ def test_a_batch_mixes_deep_ring_pairs_with_the_other_schedules(pg, oracle, monk
         fb.close()
     assert [s[2] for s in single] == want_sched
     fbs = pgm.full_probability_batch(cases)
+    assert [fb.schedule for fb in fbs] == [pgm.fb_route(c[0], c[1], c[3])[0] for c in cases]     # the plan's code, same environment
     for k in (0, second, n_deep, n_deep + 1, n_deep + 3):                  # deep, deep of the other size, ring, tiled, small
         lf, lb, _, _ = oracle.fb(*cases[k][:3], band=cases[k][3], matrices=False)
         print("pair %d (schedule %d): log_fwd %.12g (oracle %.12g) log_bwd %.12g (oracle %.12g)" % (k, fbs[k].schedule, fbs[k].log_fwd, lf, fbs[k].log_bwd, lb))

@@ -59,7 +59,7 @@ def with_end_edges(g, sources, seed):
 
 
 def n_corner_inits(left, right, band):
-    """the distinct in-band cells initialise_array_corner_bwd assigns, as fb_corner_init (dp_fb.hip) counts them"""
+    """the distinct in-band cells initialise_array_corner_bwd assigns, as fb_corner_init (dp_fb_plan.cpp) counts them"""
     Lx, Ly = left.n_sites - 1, right.n_sites - 1
     inside = lambda i, j: 0 <= i < Lx and 0 <= j < Ly and (band is None or max(band.upper[i], 0) <= j <= min(band.lower[i], Ly - 1))
     le = [int(p) for p in left.bwd_src[left.bwd_off[Lx]:left.bwd_off[Lx + 1]]]
