@@ -416,6 +416,54 @@ int64_t pagan_guide_upgma(int32_t n, const char *const *names, const double *dis
  * that if it is more; pagan_guide_info.device_bytes is what a call did allocate).  PAGAN_E_ARG beyond the limits above.    */
 int64_t pagan_guide_predict_bytes(int32_t n, int64_t total_len);
 
+/* ---- guide tree from an alignment: row pair counts on the device, the same distance, the same UPGMA -----------------
+ * (csrc/dp_alndist.hip, csrc/host_guide.cpp; DESIGN.md "Guide tree from the alignment").  The step back from a first
+ * alignment to a tree: the reference takes it with external programs (--bppdist-tree, --raxml-tree).
+ *
+ * Input: n rows of the same length L (a ragged set: PAGAN_E_ARG; L = 0 is allowed).  data_type 0, 1, 2, 3 is resolved as the
+ * guide's cleaning resolves it, over the rows with their gap characters dropped; a codon alignment (3) is read as DNA over its
+ * nucleotide characters (the walk's codon rows hold three characters a column).
+ * Letters: a character is upper-cased and a DNA U counts as T.  It is a letter if it is a core letter -- ACGT, or the 20 amino
+ * acids in the order ARNDCQEGHILKMFPSTWYV -- and its code is its position in that list.  Everything else is no letter: '-',
+ * '.', N, X, ambiguity codes, anything.  Unlike the sequence cleaner nothing is dropped: a column keeps its place.
+ * Counts: both(x, y) = the columns where row x and row y each hold a letter; match(x, y) = those of them where the two codes are
+ * equal; both(x, x) = match(x, x) = the letters of row x.  Integers, exact whatever the order of summation.
+ * Distance: d(x, y) = pagan_guide_distance_of(match, both, 1, data_type) for x != y (p = 1 - match / both with that function's
+ * clamps and formulas; both = 0 gives the clamp's distance, as "nothing shared" does for k-mers), 0 on the diagonal.
+ * Tree: pagan_guide_upgma over that matrix.
+ *
+ * Limits (PAGAN_E_ARG before anything is allocated): 2 <= n <= PAGAN_GUIDE_MAX_SEQS, L < 2^31 (a count is a uint32 on the
+ * device).  Device, errors: as for the guide tree above -- the caller's current device, left current; PAGAN_E_NODEVICE without
+ * one (there is no host path); PAGAN_E_NOMEM / PAGAN_E_INTERNAL for a HIP error.                                              */
+#define PAGAN_ALN_TILE         64      /* rows a side of the tile of pairs a workgroup owns                               */
+#define PAGAN_ALN_SPLIT_WORDS  8       /* words (of 64 columns) of the granule a tile's columns are split in              */
+typedef struct pagan_aln_info {
+    int32_t data_type;           /* 1 DNA, 2 protein, 3 codon: what 0 was resolved to                            */
+    int32_t planes;              /* bit planes a row is packed in: valid + 2 (DNA, codon) or + 5 (protein) code bits */
+    int32_t tile;                /* PAGAN_ALN_TILE                                                               */
+    int32_t col_splits;          /* workgroups that share the words of one tile (1: no partial sums, no fold)    */
+    int64_t columns;             /* L                                                                            */
+    int64_t words;               /* ceil(L / 64)                                                                 */
+    int64_t pairs;               /* n (n - 1) / 2                                                                */
+    int64_t device_bytes;        /* what the call allocated on the device                                        */
+    double  pack_ms, pairs_ms;   /* device time of the stages (events around their launches; pairs_ms includes the fold; no
+                                    stage waits for the host)                                                    */
+    double  upgma_ms;            /* host time of the tree builder (pagan_aln_tree, pagan_msa_alignment_tree), 0 otherwise */
+} pagan_aln_info;
+/* both, match, dist: [n * n], both triangles and the diagonal filled.  Any of the three may be NULL. */
+int     pagan_aln_distances(int32_t n, const char *const *rows, int32_t data_type, int64_t *both, int64_t *match, double *dist,
+                            pagan_aln_info *info);
+/* The distances, then pagan_guide_upgma.  Returns what pagan_guide_tree returns, under the same contract. */
+int64_t pagan_aln_tree(int32_t n, const char *const *names, const char *const *rows, int32_t data_type, char *newick_out,
+                       int64_t cap, pagan_aln_info *info);
+/* Host only.  Device bytes pagan_aln_distances allocates for n rows of `columns` columns: exact for the call's own buffers of a
+ * protein alignment (6 planes); a DNA or codon call packs 3 planes and takes less (pagan_aln_info.device_bytes is what a call
+ * did allocate, never more than this).  PAGAN_E_ARG beyond the limits above.                                              */
+int64_t pagan_aln_predict_bytes(int32_t n, int64_t columns);
+/* pagan_aln_tree over the leaf rows of a finished walk, under the walk's names and data type.  PAGAN_E_ARG before the rows
+ * exist (a walk not yet aligned / finished).                                                                              */
+int64_t pagan_msa_alignment_tree(const pagan_msa *m, char *newick_out, int64_t cap, pagan_aln_info *info);
+
 #ifdef __cplusplus
 }
 #endif

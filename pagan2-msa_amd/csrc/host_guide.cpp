@@ -1,5 +1,6 @@
 // host_guide.cpp -- the host side of the guide tree from sequences alone (include/pagan_host.h, "guide tree"): the cleaning
-// the walk applies to its input, the default k, the distance from the integers the device counted, and UPGMA.
+// the walk applies to its input, the default k, the distance from the integers the device counted, and UPGMA -- and of the
+// guide tree from an alignment (csrc/dp_alndist.hip): the rows' checks, the letter table, the split rule and the buffer layout.
 //
 // UPGMA keeps, for every active cluster, the partner of smallest distance over its whole row (ties: the partner of lowest id).
 // The pair a step merges is the best (distance, lower id, higher id) over these row candidates: the merged pair (a, b), a < b,
@@ -78,6 +79,71 @@ int guide_check_names(int32_t n, const char *const *names) {
     return PAGAN_OK;
 }
 
+int aln_check_rows(int32_t n, const char *const *rows, int32_t data_type, int64_t *columns, int *resolved_type) {
+    if (n < 2 || n > PAGAN_GUIDE_MAX_SEQS || !rows || data_type < 0 || data_type > 3) return PAGAN_E_ARG;
+    if (!rows[0]) return PAGAN_E_ARG;
+    const size_t L = std::strlen(rows[0]);
+    if (L >= ((size_t)1 << 31)) return PAGAN_E_ARG;
+    for (int k = 1; k < n; ++k)
+        if (!rows[k] || std::strlen(rows[k]) != L) return PAGAN_E_ARG;
+    *columns = (int64_t)L;
+    if (data_type != 0) { *resolved_type = data_type; return PAGAN_OK; }
+    std::vector<std::string> s(n);                                     // guide_clean's first step: upper case, no gaps, no line ends
+    for (int k = 0; k < n; ++k) {
+        s[k].reserve(L);
+        for (const char *p = rows[k]; *p; ++p) {
+            const char c = (char)std::toupper((unsigned char)*p);
+            if (c != '-' && c != '\r' && c != '\n') s[k].push_back(c);
+        }
+    }
+    const int type = ModelFactory::guess_type(s);
+    *resolved_type = type == kDna ? 1 : type == kProtein ? 2 : 3;
+    return PAGAN_OK;
+}
+
+void aln_letter_table(int data_type, unsigned char table[256]) {
+    std::memset(table, kGuideNoLetter, 256);
+    const bool protein = data_type == 2;
+    const char *core = protein ? ModelFactory::protein_alphabet() : "ACGT";
+    for (int c = 0; core[c]; ++c) {
+        table[(unsigned char)core[c]] = (unsigned char)c;
+        table[(unsigned char)std::tolower((unsigned char)core[c])] = (unsigned char)c;
+    }
+    if (!protein) table[(unsigned char)'U'] = table[(unsigned char)'u'] = table[(unsigned char)'T'];
+}
+
+int aln_col_splits(int64_t tiles, int64_t words) {
+    // a workgroup is four waves: 1,024 of them are four waves on every SIMD of the chip's 256 compute units.  Fewer tiles than
+    // that (32 x 150,000 columns is one tile) share their words in whole granules, no split left empty.
+    const int64_t target = 1024, granules = (words + PAGAN_ALN_SPLIT_WORDS - 1) / PAGAN_ALN_SPLIT_WORDS;
+    if (tiles >= target || granules <= 1) return 1;
+    const int64_t want = std::max<int64_t>(1, std::min(granules, target / tiles)), per = (granules + want - 1) / want;
+    return (int)((granules + per - 1) / per);                          // (<= want: splits x tiles <= target)
+}
+
+AlnLayout::AlnLayout(int64_t n, int64_t columns, int planes_) {
+    auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    rows_pad = (n + PAGAN_ALN_TILE - 1) / PAGAN_ALN_TILE * PAGAN_ALN_TILE;
+    const int64_t T = rows_pad / PAGAN_ALN_TILE;
+    tiles = T * (T + 1) / 2;
+    words = (columns + 63) / 64;
+    words_pad = (words + PAGAN_ALN_SPLIT_WORDS - 1) / PAGAN_ALN_SPLIT_WORDS * PAGAN_ALN_SPLIT_WORDS;
+    planes = planes_;
+    splits = aln_col_splits(tiles, words);
+    const size_t tile_bytes = 2 * (size_t)PAGAN_ALN_TILE * PAGAN_ALN_TILE * sizeof(uint32_t);      // both and match
+    size_t at = 0;
+    auto take = [&](size_t b) { const size_t p = at; at += up256(b); return p; };
+    bytes = take((size_t)n * (size_t)columns);
+    table = take(256);
+    packed = take((size_t)words_pad * (size_t)planes * (size_t)rows_pad * sizeof(uint64_t));
+    // slices of one tile's counts: split s of tile t writes slice s * tiles + t, and the fold adds them into slice t.  Room for
+    // every S the split rule can choose at this size (S x tiles <= 1,024, S <= granules), so that the size grows with n and L
+    const int64_t granules = words_pad / PAGAN_ALN_SPLIT_WORDS;
+    slices = tiles >= 1024 || granules <= 1 ? tiles : std::min<int64_t>(1024, granules * tiles);
+    out = take((size_t)slices * tile_bytes);
+    total = at;
+}
+
 namespace {
 
 struct Upgma {
@@ -130,6 +196,11 @@ double pagan_guide_distance_of(int64_t shared, int64_t m, int32_t k, int32_t dat
     }
     if (p > 0.7) p = 0.7;
     return -0.75 * std::log(1.0 - p / 0.75);
+}
+
+int64_t pagan_aln_predict_bytes(int32_t n, int64_t columns) {
+    if (n < 2 || n > PAGAN_GUIDE_MAX_SEQS || columns < 0 || columns >= ((int64_t)1 << 31)) return PAGAN_E_ARG;
+    return (int64_t)AlnLayout(n, columns, 6).total;
 }
 
 int64_t pagan_guide_upgma(int32_t n, const char *const *names, const double *dist, char *newick_out, int64_t cap) {

@@ -1405,6 +1405,15 @@ int pagan_msa_alignment_row(const pagan_msa *m, int32_t leaf, char *buf) {
     return PAGAN_OK;
 }
 
+// The guide tree made from this walk's own alignment (csrc/dp_alndist.hip): the leaf rows, the walk's names and data type.
+int64_t pagan_msa_alignment_tree(const pagan_msa *m, char *newick_out, int64_t cap, pagan_aln_info *info) {
+    if (!m || !m->aligned || (cap > 0 && !newick_out)) return PAGAN_E_ARG;
+    if (const int rc = ensure_rows(const_cast<pagan_msa *>(m))) return rc;
+    std::vector<const char *> names(m->n_leaves), rows(m->n_leaves);
+    for (int k = 0; k < m->n_leaves; ++k) { names[k] = m->names[k].c_str(); rows[k] = m->rows[k].c_str(); }
+    return pagan_aln_tree(m->n_leaves, names.data(), rows.data(), pagan_msa_data_type(m), newick_out, cap, info);
+}
+
 // Fasta_reader::write_fasta (src/utils/fasta_reader.cpp:596-629) over Node::get_alignment's leaf rows
 // (src/main/node.cpp:537-575): one entry per leaf in guide-tree order (left to right, as get_leaf_nodes
 // collects them), `>name`, the aligned row cut into lines of chars_by_line characters (60 by default).

@@ -61,8 +61,16 @@ class CGuideInfo(C.Structure):
                 ("upgma_ms", C.c_double)]
 
 
+class CAlnInfo(C.Structure):
+    _fields_ = [("data_type", C.c_int32), ("planes", C.c_int32), ("tile", C.c_int32), ("col_splits", C.c_int32),
+                ("columns", C.c_int64), ("words", C.c_int64), ("pairs", C.c_int64), ("device_bytes", C.c_int64),
+                ("pack_ms", C.c_double), ("pairs_ms", C.c_double), ("upgma_ms", C.c_double)]
+
+
 GUIDE_MAX_SEQS = 65536
 GUIDE_PAIR_CHUNK = 64
+ALN_TILE = 64
+ALN_SPLIT_WORDS = 8
 
 _declared = False
 
@@ -244,6 +252,14 @@ def _lib():
         L.pagan_guide_upgma.restype = C.c_int64
         L.pagan_guide_predict_bytes.argtypes = [C.c_int32, C.c_int64]
         L.pagan_guide_predict_bytes.restype = C.c_int64
+        L.pagan_aln_distances.argtypes = [C.c_int32, cpp, C.c_int32, i64p, i64p, f64p, C.POINTER(CAlnInfo)]
+        L.pagan_aln_distances.restype = C.c_int
+        L.pagan_aln_tree.argtypes = [C.c_int32, cpp, cpp, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(CAlnInfo)]
+        L.pagan_aln_tree.restype = C.c_int64
+        L.pagan_aln_predict_bytes.argtypes = [C.c_int32, C.c_int64]
+        L.pagan_aln_predict_bytes.restype = C.c_int64
+        L.pagan_msa_alignment_tree.argtypes = [vp, C.c_char_p, C.c_int64, C.POINTER(CAlnInfo)]
+        L.pagan_msa_alignment_tree.restype = C.c_int64
         _declared = True
     return L
 
@@ -268,7 +284,8 @@ HOST_EXPORTED = ["pagan_assign_units", "pagan_msa_default_opts", "pagan_msa_crea
                  "pagan_msa_set_sampler", "pagan_msa_set_decoder", "pagan_msa_node_decode",
                  "pagan_msa_set_counts", "pagan_msa_node_counts", "pagan_msa_set_indel_model", "pagan_fit_indel",
                  "pagan_guide_distances", "pagan_guide_tree", "pagan_guide_kmer_length", "pagan_guide_distance_of",
-                 "pagan_guide_upgma", "pagan_guide_predict_bytes"]
+                 "pagan_guide_upgma", "pagan_guide_predict_bytes",
+                 "pagan_aln_distances", "pagan_aln_tree", "pagan_aln_predict_bytes", "pagan_msa_alignment_tree"]
 
 
 def _ip(a):
@@ -668,6 +685,87 @@ def guide_upgma(names, dist):
                         "pagan_guide_upgma", names)
 
 
+def _aln_info(ci):
+    return {name: getattr(ci, name) for name, _ in CAlnInfo._fields_}
+
+
+def aln_predict_bytes(n, columns):
+    """pagan_aln_predict_bytes (host only): device bytes aln_distances allocates at most for n rows of `columns` columns."""
+    return _guide_check(_lib().pagan_aln_predict_bytes(int(n), int(columns)), "pagan_aln_predict_bytes")
+
+
+def aln_distances(rows, data_type=0):
+    """pagan_aln_distances: (both [n, n] int64, match [n, n] int64, dist [n, n] float64, info dict) -- for every pair of rows of
+    an alignment the columns where both hold a letter and those of them where the letters agree, counted on the current device,
+    and the distances made of them (include/pagan_host.h)."""
+    n = len(rows)
+    both = np.zeros((n, n), np.int64)
+    match = np.zeros((n, n), np.int64)
+    dist = np.zeros((n, n), np.float64)
+    ci = CAlnInfo()
+    i64p, f64p = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+    _guide_check(_lib().pagan_aln_distances(n, _c_strings(rows), int(data_type), both.ctypes.data_as(i64p), match.ctypes.data_as(i64p),
+                                            dist.ctypes.data_as(f64p), C.byref(ci)), "pagan_aln_distances")
+    return both, match, dist, _aln_info(ci)
+
+
+def aln_tree(names, rows, data_type=0, with_info=False):
+    """pagan_aln_tree: the rooted binary UPGMA tree over aln_distances' matrix as a Newick string (with_info: and the info dict),
+    ready for Msa."""
+    n = len(names)
+    if len(rows) != n:
+        raise ValueError("names and rows differ in number")
+    na, ra = _c_strings(names), _c_strings(rows)
+    ci = CAlnInfo()
+    L = _lib()
+    newick = _newick_call(lambda buf, cap: L.pagan_aln_tree(n, na, ra, int(data_type), buf, cap, C.byref(ci)), "pagan_aln_tree", names)
+    return (newick, _aln_info(ci)) if with_info else newick
+
+
+def differing_clades(newick_a, newick_b):
+    """The clades (leaf sets under the internal nodes) of tree a that tree b does not have."""
+    from . import synth
+
+    def clades(newick):
+        out = set()
+
+        def walk(t):
+            if t[0] == "leaf":
+                return frozenset([t[1]])
+            s = walk(t[1]) | walk(t[2])
+            out.add(s)
+            return s
+        walk(synth.parse_newick(newick))
+        return out
+    return len(clades(newick_a) - clades(newick_b))
+
+
+def align_refined(names, seqs, rounds=1, newick=None, **msa_kwargs):
+    """Align, read the guide tree off the alignment, align again on it: walks once exactly as Msa(names, seqs, newick,
+    **msa_kwargs).align() does, then up to `rounds` times takes T = msa.alignment_tree() and walks again on T, stopping when
+    T is the tree just walked (the walk is deterministic: a fixpoint).  Returns the last Msa (the earlier ones are closed) with
+    .history: one dict per walk -- newick, alignment_length, score (the sum of the node scores) and changed_clades (the clades
+    of its tree the previous walk's tree does not have; 0 for the first)."""
+    msa = Msa(names, seqs, newick, **msa_kwargs).align()
+    history = []
+
+    def record(m, before):
+        history.append({"newick": m.newick, "alignment_length": len(m.alignment()[0]),
+                        "score": float(sum(m.node_info(k).score for k in range(m.n_internal))),
+                        "changed_clades": 0 if before is None else differing_clades(m.newick, before)})
+    record(msa, None)
+    for _ in range(int(rounds)):
+        tree = msa.alignment_tree()
+        if tree == msa.newick:
+            break
+        before = msa.newick
+        msa.close()
+        msa = Msa(names, seqs, tree, **msa_kwargs).align()
+        record(msa, before)
+    msa.history = history
+    return msa
+
+
 def _job_copy(j):
     """(Graph, Graph, Model, Band|None) copies of a borrowed CJob."""
     left, right = _graph_from_view(j.left.contents), _graph_from_view(j.right.contents)
@@ -781,6 +879,7 @@ class Msa:
                 raise TypeError("unknown option %s" % k)
             setattr(o, k, v)
         self.n = len(names)
+        self.names = list(names)
         self._h = C.c_void_p()
         if newick is None:
             newick = guide_tree(names, seqs, data_type=o.data_type)
@@ -1019,6 +1118,14 @@ class Msa:
             self._L.pagan_msa_alignment_row(self._h, k, buf)
             rows.append(buf.raw[:n].decode())
         return rows
+
+    def alignment_tree(self, with_info=False):
+        """pagan_msa_alignment_tree: the guide tree made from this walk's own alignment -- aln_tree over the leaf rows under the
+        walk's names and data type (with_info: and the info dict).  PaganError(PAGAN_E_ARG) before the rows exist."""
+        ci = CAlnInfo()
+        newick = _newick_call(lambda buf, cap: self._L.pagan_msa_alignment_tree(self._h, buf, cap, C.byref(ci)),
+                              "pagan_msa_alignment_tree", self.names)
+        return (newick, _aln_info(ci)) if with_info else newick
 
     def alignment_all(self):
         """Rows of every node: leaves 0..n-1, then the internal nodes (ancestors) in alignment order."""
