@@ -20,11 +20,13 @@
 #include <type_traits>
 #include <vector>
 
+#include "dp_hip.h"
 #include "host_anchors.h"
 #include "host_graph.h"
 #include "dp_plan.h"
 
 using namespace pgplan;
+using namespace pgdev;
 
 template <int BLOCK> __global__ void pg_fill_wavefront(const PgDevJob *jobs, const int *which, unsigned flags);
 template <bool TAB_LDS> __global__ void pg_fill_ring(const PgDevJob *jobs, const int *which, unsigned flags);
@@ -48,17 +50,7 @@ extern "C" void pagan_fb_internal_release_cache();             // dp_fb.hip: the
 
 namespace {
 
-#define HIP_TRY(expr)                                                                            \
-    do {                                                                                         \
-        hipError_t e__ = (expr);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            if (std::getenv("PAGAN_DP_VERBOSE"))                                                 \
-                std::fprintf(stderr, "pagan_dp: %s failed: %s\n", #expr, hipGetErrorString(e__)); \
-            return e__ == hipErrorOutOfMemory ? PAGAN_E_NOMEM : PAGAN_E_NODEVICE;                \
-        }                                                                                        \
-    } while (0)
-
-inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+#define HIP_TRY(expr) PG_HIP_CODE(expr, "pagan_dp", PAGAN_E_NODEVICE)
 
 struct Arena {
     char *dev = nullptr;
@@ -68,55 +60,11 @@ struct Arena {
 
 // Device arenas are reused by the next batch on the same device: hipFree of a few GB costs 10-30 ms, and a level
 // of a tree walk is followed by the next.  At most two idle arenas per device; pagan_dp_release_cache() frees them.
-struct ArenaPool {
-    struct Slot { char *p; size_t cap; int device; };
-    std::mutex m;
-    std::vector<Slot> idle;
-    char *take(int device, size_t n, size_t *cap) {
-        std::lock_guard<std::mutex> g(m);
-        int best = -1;
-        for (size_t k = 0; k < idle.size(); ++k)
-            if (idle[k].device == device && idle[k].cap >= n && (best < 0 || idle[k].cap < idle[best].cap)) best = (int)k;
-        if (best < 0) return nullptr;
-        char *p = idle[best].p;
-        *cap = idle[best].cap;
-        idle.erase(idle.begin() + best);
-        return p;
-    }
-    void give(int device, char *p, size_t cap) {
-        std::vector<char *> drop;
-        {
-            std::lock_guard<std::mutex> g(m);
-            idle.push_back({p, cap, device});
-            for (;;) {
-                int count = 0, smallest = -1;
-                for (size_t k = 0; k < idle.size(); ++k)
-                    if (idle[k].device == device) { ++count; if (smallest < 0 || idle[k].cap < idle[smallest].cap) smallest = (int)k; }
-                if (count <= 2) break;
-                drop.push_back(idle[smallest].p);
-                idle.erase(idle.begin() + smallest);
-            }
-        }
-        for (char *q : drop) (void)hipFree(q);
-    }
-    // frees the idle arenas of one device (-1: all)
-    void clear(int device) {
-        std::vector<char *> drop;
-        {
-            std::lock_guard<std::mutex> g(m);
-            for (size_t k = 0; k < idle.size();)
-                if (device < 0 || idle[k].device == device) { drop.push_back(idle[k].p); idle.erase(idle.begin() + k); } else ++k;
-        }
-        for (char *q : drop) (void)hipFree(q);
-    }
-    size_t idle_bytes(int device) {
-        std::lock_guard<std::mutex> g(m);
-        size_t n = 0;
-        for (const Slot &s : idle) if (s.device == device) n += s.cap;
-        return n;
-    }
-};
-ArenaPool arena_pool;
+// Any idle arena that is large enough is taken; a miss allocates what the batch uses, and take_arena does the retry itself.
+const SlabPolicy kArenaPolicy = {
+    /* slack_mul, slack_add */ 0, 0, /* grow_div */ 0, /* max_idle */ 0, /* max_idle_per_device */ 2, /* max_idle_bytes */ 0,
+    /* evict_smallest */ true, /* retry_drained */ false};
+SlabPool arena_pool(kArenaPolicy);
 
 // Streams and events of a batch, reused by the next batch on the same device (at most four idle sets per device).
 struct GpuObjs {
@@ -132,34 +80,8 @@ struct GpuObjs {
         if (ev_join) (void)hipEventDestroy(ev_join);
     }
 };
-struct GpuObjPool {
-    std::mutex m;
-    std::vector<std::pair<int, GpuObjs>> idle;
-    bool take(int device, GpuObjs *o) {
-        std::lock_guard<std::mutex> g(m);
-        for (size_t k = 0; k < idle.size(); ++k)
-            if (idle[k].first == device) { *o = idle[k].second; idle.erase(idle.begin() + k); return true; }
-        return false;
-    }
-    void give(int device, const GpuObjs &o) {
-        GpuObjs drop;
-        bool dropping = false;
-        {
-            std::lock_guard<std::mutex> g(m);
-            int have = 0;
-            for (auto &e : idle) have += e.first == device;
-            if (have >= 4) { drop = o; dropping = true; }
-            else idle.emplace_back(device, o);
-        }
-        if (dropping) drop.destroy();
-    }
-    void release() {
-        std::vector<std::pair<int, GpuObjs>> all;
-        { std::lock_guard<std::mutex> g(m); all.swap(idle); }
-        for (auto &e : all) { (void)hipSetDevice(e.first); e.second.destroy(); }
-    }
-};
-GpuObjPool gpu_pool;
+IdlePerDevice<GpuObjs> gpu_pool;
+void destroy_objs(std::vector<std::pair<int, GpuObjs>> &drop) { for (auto &e : drop) { DeviceScope on(e.first); e.second.destroy(); } }
 
 } // namespace
 
@@ -236,8 +158,8 @@ struct Carver {
     std::vector<size_t> *guards = nullptr;       // (canary mode) offsets of the guard words, in carving order
     template <class T> T *take(size_t count) {
         size_t off = cur;
-        cur = align_up(cur + sizeof(T) * (count ? count : 1));
-        if (guards) { guards->push_back(cur); cur = align_up(cur + PG_CANARY_BYTES); }
+        cur = up256(cur + sizeof(T) * (count ? count : 1));
+        if (guards) { guards->push_back(cur); cur = up256(cur + PG_CANARY_BYTES); }
         return base ? reinterpret_cast<T *>(base + off) : reinterpret_cast<T *>(off);
     }
 };
@@ -604,17 +526,12 @@ BatchRegions carve_batch(Carver &c, pagan_batch *b, const std::vector<pagan_job>
 }
 
 int take_arena(pagan_batch *b) {
-    b->arena.dev = arena_pool.take(b->device, b->arena.size, &b->arena.cap);
+    b->arena.dev = slab_alloc(arena_pool, b->device, b->arena.size, &b->arena.cap);
     if (!b->arena.dev) {
-        b->arena.cap = b->arena.size;
-        if (hipMalloc((void **)&b->arena.dev, b->arena.size) != hipSuccess) {
-            (void)hipGetLastError();
-            b->arena.dev = nullptr;
-            arena_pool.clear(b->device);                 // the idle arenas may be what is in the way -- and the other pools' (parent
-            pagan::parent_release_cache();               // builder slabs, forward/backward arenas: round 4 advisor)
-            pagan_fb_internal_release_cache();
-            HIP_TRY(hipMalloc((void **)&b->arena.dev, b->arena.size));
-        }
+        drain_slabs(arena_pool, b->device);              // the idle arenas may be what is in the way -- and the other pools' (parent
+        pagan::parent_release_cache();                   // builder slabs, forward/backward arenas: round 4 advisor)
+        pagan_fb_internal_release_cache();
+        HIP_TRY(hipMalloc((void **)&b->arena.dev, b->arena.size));
     }
     if (!b->guards.empty()) {
         // (the follow words are zeroed in one sweep per run, guards and all: those regions go unguarded)
@@ -1128,11 +1045,13 @@ void pagan_batch_destroy(pagan_batch *b) {
     if (b->o.stream) {
         (void)hipStreamSynchronize(b->o.stream);
         if (b->o.stream2) (void)hipStreamSynchronize(b->o.stream2);
-        if (b->o.ev_join) gpu_pool.give(b->device, b->o);       // (the set is whole: ev_join is the last one made)
-        else b->o.destroy();
+        std::vector<std::pair<int, GpuObjs>> drop;
+        if (b->o.ev_join) gpu_pool.give(b->device, b->o, 4, &drop);     // (the set is whole: ev_join is the last one made)
+        else drop.emplace_back(b->device, b->o);
+        destroy_objs(drop);
         b->o = GpuObjs();
     }
-    if (b->arena.dev) arena_pool.give(b->device, b->arena.dev, b->arena.cap);
+    give_slab(arena_pool, b->device, b->arena.dev, b->arena.cap);
     if (b->d_guards) { (void)hipFree(b->d_guards); (void)hipFree(b->d_canary); b->d_guards = nullptr; b->d_canary = nullptr; }
     // What is left is host memory only (plans, band indices, compaction maps: megabytes per alignment, milliseconds of
     // unmapping per level of a tree walk): freed by a background thread, off the caller's path.
@@ -1208,8 +1127,10 @@ void pagan_dp_release_cache(void) {
     pagan::anchors_release_cache();
     pagan::parent_release_cache();
     pagan_fb_internal_release_cache();
-    arena_pool.clear(-1);
-    gpu_pool.release();
+    drain_slabs(arena_pool, -1);
+    std::vector<std::pair<int, GpuObjs>> objs;
+    gpu_pool.drain(&objs);
+    destroy_objs(objs);
     std::lock_guard<std::mutex> g(stage_pool.m);
     for (auto &s : stage_pool.idle) std::free(s.first);
     stage_pool.idle.clear();

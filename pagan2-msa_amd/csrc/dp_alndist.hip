@@ -28,9 +28,12 @@
 #include <vector>
 
 #include "../../include/pagan_host.h"
+#include "dp_hip.h"
 #include "host_guide.h"
 
 namespace pagan {
+
+using namespace pgdev;
 
 namespace {
 
@@ -133,18 +136,13 @@ __global__ __launch_bounds__(256) void pad_fold(uint32_t *__restrict__ out, uint
     out[i] = sum;
 }
 
-struct Device {                     // released on every exit path
-    char *mem = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    ~Device() {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (st) (void)hipStreamDestroy(st);
-        if (mem) (void)hipFree(mem);
-    }
+struct Device {                     // released on every exit path (the stream has drained before the buffer is freed: dp_hip.h)
+    DevBuf mem;
+    Stream st;
+    Event ev[3];
 };
 
-#define HIPA(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { if (std::getenv("PAGAN_DP_VERBOSE")) std::fprintf(stderr, "pagan aln: %s -> %s\n", #x, hipGetErrorString(e_)); return e_ == hipErrorOutOfMemory ? PAGAN_E_NOMEM : PAGAN_E_INTERNAL; } } while (0)
+#define HIPA(x) PG_HIP_CODE(x, "pagan aln", PAGAN_E_INTERNAL)
 
 // the tiles' counts [tiles][both | match][y][x] from the device
 int run_device(int n, const char *const *rows, int64_t columns, int planes, int data_type, std::vector<uint32_t> *counts, pagan_aln_info *info) {
@@ -160,13 +158,13 @@ int run_device(int n, const char *const *rows, int64_t columns, int planes, int 
     unsigned char table[256];
     aln_letter_table(data_type, table);
     Device D;
-    HIPA(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
-    for (hipEvent_t &e : D.ev) HIPA(hipEventCreate(&e));
+    HIPA(D.st.create(hipStreamNonBlocking));
+    for (Event &e : D.ev) HIPA(e.create());
     hipStream_t st = D.st;
-    HIPA(hipMalloc((void **)&D.mem, L.total));
-    unsigned char *d_bytes = (unsigned char *)(D.mem + L.bytes), *d_table = (unsigned char *)(D.mem + L.table);
-    uint64_t *packed = (uint64_t *)(D.mem + L.packed);
-    uint32_t *out = (uint32_t *)(D.mem + L.out);
+    HIPA(D.mem.alloc(L.total));
+    unsigned char *d_bytes = (unsigned char *)(D.mem.h + L.bytes), *d_table = (unsigned char *)(D.mem.h + L.table);
+    uint64_t *packed = (uint64_t *)(D.mem.h + L.packed);
+    uint32_t *out = (uint32_t *)(D.mem.h + L.out);
     if (!bytes.empty()) HIPA(hipMemcpyAsync(d_bytes, bytes.data(), bytes.size(), hipMemcpyHostToDevice, st));
     HIPA(hipMemcpyAsync(d_table, table, 256, hipMemcpyHostToDevice, st));
     const uint32_t rows_pad = (uint32_t)L.rows_pad, words_pad = (uint32_t)L.words_pad, tiles = (uint32_t)L.tiles, splits = (uint32_t)L.splits;

@@ -32,13 +32,16 @@
 #include <mutex>
 #include <vector>
 
+#include "dp_hip.h"
 #include "host_anchors.h"
 
 namespace pagan {
 
+using namespace pgdev;
+
 namespace {
 
-#define HIPA(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { if (std::getenv("PAGAN_DP_VERBOSE")) std::fprintf(stderr, "pagan anchors: %s -> %s\n", #x, hipGetErrorString(e_)); return false; } } while (0)
+#define HIPA(x) PG_HIP_BOOL(x, "pagan anchors")
 
 __global__ void pa_symbols(const char *a, int len1, const char *b, int len2, int *rk0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, n = len1 + len2 + 2;
@@ -116,25 +119,12 @@ struct Scratch {
     char *mem = nullptr;
     hipStream_t stream = nullptr;
 };
-struct ScratchPool {
-    std::mutex m;
-    std::vector<Scratch> idle;
-    Scratch take(int device) {
-        std::lock_guard<std::mutex> g(m);
-        for (size_t k = 0; k < idle.size(); ++k)
-            if (idle[k].device == device) { Scratch s = idle[k]; idle.erase(idle.begin() + k); return s; }
-        Scratch s; s.device = device; return s;
-    }
-    void give(const Scratch &s) { std::lock_guard<std::mutex> g(m); idle.push_back(s); }
-};
-ScratchPool scratch_pool;
+IdlePerDevice<Scratch> scratch_pool;
 struct ScratchLease {
     Scratch s;
-    explicit ScratchLease(int device) : s(scratch_pool.take(device)) {}
-    ~ScratchLease() { scratch_pool.give(s); }
+    explicit ScratchLease(int device) { if (!scratch_pool.take(device, &s)) s.device = device; }
+    ~ScratchLease() { std::vector<std::pair<int, Scratch>> none; scratch_pool.give(s.device, s, 0, &none); }
 };
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 } // namespace
 
@@ -142,13 +132,14 @@ inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 // prefix_hits() builds before it sorts by length.  false: no device / a HIP error (the caller takes the host's finder).
 // (pagan_dp_release_cache: the finders' idle scratch and streams go as well)
 void anchors_release_cache() {
-    std::vector<Scratch> all;
-    { std::lock_guard<std::mutex> g(scratch_pool.m); all.swap(scratch_pool.idle); }
-    for (Scratch &s : all) {
-        (void)hipSetDevice(s.device);
-        if (s.mem) (void)hipFree(s.mem);
-        if (s.stream) (void)hipStreamDestroy(s.stream);
+    std::vector<std::pair<int, Scratch>> all;
+    scratch_pool.drain(&all);
+    std::vector<Slab> mem;
+    for (auto &e : all) {
+        if (e.second.mem) mem.push_back({e.first, e.second.mem, e.second.cap});
+        if (e.second.stream) { DeviceScope on(e.first); (void)hipStreamDestroy(e.second.stream); }
     }
+    free_slabs(mem);
 }
 
 bool prefix_hits_device(const std::string &a, const std::string &b, int min_length, std::vector<Hit> *hits, int device) {
@@ -174,21 +165,20 @@ bool prefix_hits_device(const std::string &a, const std::string &b, int min_leng
         HIPA(hipMalloc((void **)&S.mem, need));
         S.cap = need;
     }
-    char *m = S.mem;
-    auto take = [&](size_t bytes) { char *p = m; m += up256(bytes); return p; };
-    char *d_a = take(len1 + 1), *d_b = take(len2 + 1);
+    Carve c{S.mem};
+    char *d_a = c.take<char>(len1 + 1), *d_b = c.take<char>(len2 + 1);
     // key and key2 are carved as ONE block: once the rounds are over it holds the emitted records (12 bytes per hit, and up to
     // n - 3 hits -- identical strings with min_length 1 come close -- which is more than `key` alone holds)
     const size_t key_stride = up256(8 * (size_t)n), out_cap = 2 * key_stride / (3 * sizeof(int));
-    char *keys = take(2 * key_stride);
+    char *keys = c.take<char>(2 * key_stride);
     unsigned long long *key = (unsigned long long *)keys, *key2 = (unsigned long long *)(keys + key_stride);
-    int *idx = (int *)take(4 * (size_t)n), *sa = (int *)take(4 * (size_t)n), *flag = (int *)take(4 * (size_t)n), *fscan = (int *)take(4 * (size_t)n);
-    int *lcp = (int *)take(4 * (size_t)n), *sel = (int *)take(4 * (size_t)n);
+    int *idx = c.take<int>(n), *sa = c.take<int>(n), *flag = c.take<int>(n), *fscan = c.take<int>(n);
+    int *lcp = c.take<int>(n), *sel = c.take<int>(n);
     int *rk[max_rounds + 1];
-    for (int t = 0; t <= max_rounds - 1; ++t) rk[t] = (int *)take(4 * (size_t)n);
-    unsigned char *hit = (unsigned char *)take(n);
-    int *d_count = (int *)take(256);
-    void *d_tmp = take(tmp);
+    for (int t = 0; t <= max_rounds - 1; ++t) rk[t] = c.take<int>(n);
+    unsigned char *hit = c.take<unsigned char>(n);
+    int *d_count = c.take<int>(64);
+    void *d_tmp = c.take<char>(tmp);
     if (len1) HIPA(hipMemcpyAsync(d_a, a.data(), len1, hipMemcpyHostToDevice, st));
     if (len2) HIPA(hipMemcpyAsync(d_b, b.data(), len2, hipMemcpyHostToDevice, st));
     const int B = 256, G = (n + B - 1) / B;

@@ -44,19 +44,14 @@
 #include "../../include/pagan_dp.h"
 #include "dp_band.h"
 #include "dp_fb_plan.h"
+#include "dp_hip.h"
 
 using namespace fbplan;
+using namespace pgdev;
 
 namespace {
 
-#define FB_TRY(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) {                                                                              \
-            if (std::getenv("PAGAN_DP_VERBOSE")) std::fprintf(stderr, "pagan_fb: %s: %s\n", #expr, hipGetErrorString(e_)); \
-            return e_ == hipErrorOutOfMemory ? PAGAN_E_NOMEM : PAGAN_E_NODEVICE;                            \
-        }                                                                                                    \
-    } while (0)
+#define FB_TRY(expr) PG_HIP_CODE(expr, "pagan_fb", PAGAN_E_NODEVICE)
 
 // a call that answers with a PAGAN_* code of its own
 #define FB_DO(call) do { const int rc_ = (call); if (rc_ != PAGAN_OK) return rc_; } while (0)
@@ -916,52 +911,16 @@ int pagan_internal_replay(const pagan_graph *L, const pagan_graph *R, int64_t ce
 // Arenas of finished handles are kept for the next one on the same device (a pair's two matrices are hundreds of MB:
 // allocating and freeing them -- a device-wide synchronisation -- per pair was half of a pair's wall-clock); at most 32 (a batch of a tree level's pairs returns that many at once; eight until round 5)
 // idle ones per process, pagan_fb_release_cache frees them.
+// Idle arenas are bounded by count AND by bytes (a 10 k x 10 k pair's two matrices are 4.8 GB: eight of those idle would
+// sit on 38 GB that the Viterbi batches of the same process may need).  A failed allocation frees the idle arenas, which may be
+// what is in the way, and tries once more.
 namespace {
-struct FbArenaPool {
-    std::mutex m;
-    struct Slab { int device; char *p; size_t cap; };
-    std::vector<Slab> idle;
-    char *take(int device, size_t need, size_t *cap) {
-        {
-            std::lock_guard<std::mutex> g(m);
-            int best = -1;
-            for (size_t k = 0; k < idle.size(); ++k)
-                if (idle[k].device == device && idle[k].cap >= need && (best < 0 || idle[k].cap < idle[best].cap)) best = (int)k;
-            if (best >= 0 && idle[best].cap <= 2 * need + (64u << 20)) { Slab s_ = idle[best]; idle.erase(idle.begin() + best); *cap = s_.cap; return s_.p; }
-        }
-        char *p = nullptr;
-        *cap = need + need / 16;
-        if (hipMalloc((void **)&p, *cap) != hipSuccess) {
-            (void)hipGetLastError();
-            clear();                                           // (idle arenas may be what is in the way)
-            if (hipMalloc((void **)&p, *cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        }
-        return p;
-    }
-    // idle arenas are bounded by count AND by bytes (a 10 k x 10 k pair's two matrices are 4.8 GB: eight of those idle would
-    // sit on 38 GB that the Viterbi batches of the same process may need); the calling thread stays on its device
-    static constexpr size_t kMaxIdleBytes = (size_t)8 << 30;
-    void drop_front() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        (void)hipSetDevice(idle.front().device); (void)hipFree(idle.front().p); idle.erase(idle.begin());
-        if (cur >= 0) (void)hipSetDevice(cur);
-    }
-    void give(int device, char *p, size_t cap) {
-        std::lock_guard<std::mutex> g(m);
-        idle.push_back({device, p, cap});
-        size_t total = 0;
-        for (auto &s_ : idle) total += s_.cap;
-        while (idle.size() > 32 || (total > kMaxIdleBytes && idle.size() > 1)) { total -= idle.front().cap; drop_front(); }
-    }
-    void clear() {
-        std::lock_guard<std::mutex> g(m);
-        while (!idle.empty()) drop_front();
-    }
-};
-FbArenaPool fb_arena_pool;
+const SlabPolicy kFbArenaPolicy = {
+    /* slack_mul, slack_add */ 2, (size_t)64 << 20, /* grow_div */ 16, /* max_idle */ 32, /* max_idle_per_device */ 0,
+    /* max_idle_bytes */ (size_t)8 << 30, /* evict_smallest */ false, /* retry_drained */ true};
+SlabPool fb_arena_pool(kFbArenaPolicy);
 } // namespace
-extern "C" void pagan_fb_internal_release_cache() { fb_arena_pool.clear(); }
+extern "C" void pagan_fb_internal_release_cache() { drain_slabs(fb_arena_pool, -1); }
 
 struct pagan_fb {
     int device = 0;
@@ -988,52 +947,6 @@ struct pagan_fb {
 };
 
 namespace {
-// The calling thread on `device` (negative: the one it is on) for the length of a call, back on the device it came with afterwards.
-struct FbDeviceScope {
-    int back = -1, device; bool ok;
-    explicit FbDeviceScope(int want) : device(want) {
-        ok = hipGetDevice(&back) == hipSuccess;
-        if (ok && device < 0) device = back;
-        ok = ok && hipSetDevice(device) == hipSuccess;
-    }
-    ~FbDeviceScope() { if (back >= 0) (void)hipSetDevice(back); }
-};
-
-// Owners of what a call makes on the device: a stream, an event, an allocation.  Move-only; each frees in its destructor, on the
-// device it was made on, so a return from the middle of a function (FB_TRY) leaks nothing.  A stream is SYNCHRONISED before it is
-// destroyed: on a failure path its kernels may still be writing a pair's arena, and the arena must not reach fb_arena_pool (whose
-// next take would hand it out) before they are done -- so whatever destroys a pagan_fb does so after the streams' owners are gone.
-// On a success path the code has synchronised already and the destructor's wait is a no-op.
-template <class T>
-struct FbOwned {
-    T h = nullptr; int device = 0;
-    FbOwned() = default;
-    FbOwned(FbOwned &&o) noexcept : h(o.h), device(o.device) { o.h = nullptr; }
-    FbOwned(const FbOwned &) = delete;
-    FbOwned &operator=(const FbOwned &) = delete;
-    ~FbOwned() {
-        if (!h) return;
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (cur != device) (void)hipSetDevice(device);
-        drop(h);
-        if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
-    }
-    operator T() const { return h; }
-    static void drop(hipStream_t s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-    static void drop(hipEvent_t e) { (void)hipEventDestroy(e); }
-    static void drop(char *p) { (void)hipFree(p); }
-};
-struct FbStream : FbOwned<hipStream_t> {
-    int create() { FB_TRY(hipGetDevice(&device)); FB_TRY(hipStreamCreate(&h)); return PAGAN_OK; }
-};
-struct FbEvent : FbOwned<hipEvent_t> {
-    int create(bool timing = true) { FB_TRY(hipGetDevice(&device)); FB_TRY(hipEventCreateWithFlags(&h, timing ? hipEventDefault : hipEventDisableTiming)); return PAGAN_OK; }
-};
-struct FbDevBuf : FbOwned<char *> {
-    int alloc(size_t bytes) { FB_TRY(hipGetDevice(&device)); FB_TRY(hipMalloc((void **)&h, bytes)); return PAGAN_OK; }
-};
-
 // The arena's arrays, each named once: add() reserves the array's range (rounded up to 256 bytes) and remembers where its bytes
 // come from and which pointer of the job record is to point at it; bind() fills the staging buffer and sets the pointers once
 // the arena's base is known.
@@ -1052,8 +965,6 @@ struct FbLayout {
     }
 };
 
-static size_t fb_round256(size_t b) { return (b + 255) / 256 * 256; }
-
 // One call that reads finished passes of one device: the thread on that device for the call's length, one device buffer laid
 // out by take() -- first what goes UP (job records, launch records, small inputs), then what comes DOWN with the call (results,
 // summaries), then what only the DEVICE sees (partial sums, traces, pack buffers), every piece rounded up to 256 bytes --, the
@@ -1061,10 +972,10 @@ static size_t fb_round256(size_t b) { return (b + 255) / 256 * 256; }
 // spans, ms(k) once download() has waited for them.  The buffer is shared so that the handles a call makes can keep it.
 struct FbCall {
     enum Region { UP, DOWN, DEVICE };
-    std::optional<FbDeviceScope> on_device;
-    std::shared_ptr<FbDevBuf> buf = std::make_shared<FbDevBuf>();
+    std::optional<DeviceScope> on_device;
+    std::shared_ptr<DevBuf> buf = std::make_shared<DevBuf>();
     std::vector<char> host;
-    std::vector<FbEvent> ev;                 // a span's two events
+    std::vector<Event> ev;                 // a span's two events
     size_t cur = 0, end_of[3] = {0, 0, 0};
     int open(int32_t n, pagan_fb *const *fbs) {
         for (int k = 0; k < n; ++k) if (!fbs[k] || fbs[k]->device != fbs[0]->device) return PAGAN_E_ARG;
@@ -1073,16 +984,16 @@ struct FbCall {
     }
     size_t take(Region r, size_t bytes) {
         const size_t at = cur;
-        cur = fb_round256(cur + bytes);
+        cur = up256(cur + bytes);
         for (int q = r; q < 3; ++q) end_of[q] = cur;
         return at;
     }
-    int alloc() { host.assign(end_of[DOWN], 0); return buf->alloc(cur); }
+    int alloc() { host.assign(end_of[DOWN], 0); FB_TRY(buf->alloc(cur)); return PAGAN_OK; }
     template <class T> T *dev(size_t off) const { return (T *)(buf->h + off); }
     template <class T> void put(size_t off, const T &rec) { std::memcpy(host.data() + off, &rec, sizeof(T)); }
     int upload() { FB_TRY(hipMemcpy(buf->h, host.data(), end_of[UP], hipMemcpyHostToDevice)); return PAGAN_OK; }
     int begin() {
-        for (int q = 0; q < 2; ++q) { ev.emplace_back(); FB_DO(ev.back().create()); }
+        for (int q = 0; q < 2; ++q) { ev.emplace_back(); FB_TRY(ev.back().create()); }
         FB_TRY(hipEventRecord(ev[ev.size() - 2], nullptr));
         return PAGAN_OK;
     }
@@ -1162,7 +1073,7 @@ static int fb_stage(FbPlan &plan, const pagan_graph *left, const pagan_graph *ri
     const size_t in_bytes = lay.cur;
     lay.add(nullptr, 24 * (size_t)cells, &J.F); lay.add(nullptr, 24 * (size_t)cells, &J.B);
     const double th1 = fb_now();
-    fb->arena = fb_arena_pool.take(fb->device, lay.cur, &fb->arena_cap);
+    fb->arena = slab_alloc(fb_arena_pool, fb->device, lay.cur, &fb->arena_cap);
     if (!fb->arena) return PAGAN_E_NOMEM;
     std::vector<char> stage(in_bytes, 0);
     lay.bind(fb->arena, stage.data());
@@ -1250,10 +1161,10 @@ struct FbSpan {
 };
 // what a chunk's launches run on (the streams last: they are synchronised and destroyed before anything else goes)
 struct FbChunkRes {
-    std::vector<FbEvent> events;
-    std::vector<FbStream> streams;
-    int stream(hipStream_t *s) { streams.emplace_back(); const int rc = streams.back().create(); *s = streams.back(); return rc; }
-    int event(bool timing, hipEvent_t *e) { events.emplace_back(); const int rc = events.back().create(timing); *e = events.back(); return rc; }
+    std::vector<Event> events;
+    std::vector<Stream> streams;
+    int stream(hipStream_t *s) { streams.emplace_back(); FB_TRY(streams.back().create()); *s = streams.back(); return PAGAN_OK; }
+    int event(bool timing, hipEvent_t *e) { events.emplace_back(); FB_TRY(events.back().create(timing)); *e = events.back(); return PAGAN_OK; }
 };
 static int fb_launch_span(FbChunkRes &res, const std::vector<FbGroup> &groups, FbSpan &S, bool bwd_first) {
     for (int dir = 0; dir < 2; ++dir) FB_DO(res.stream(&S.lane[dir]));
@@ -1343,11 +1254,11 @@ static int fb_run_chunk(int chunk, const pagan_graph *const *left, const pagan_g
         }
     }
     // Owners, in the order they must outlive each other: the records, the slot lease, the events, the streams.
-    FbDevBuf d_jobs;
+    DevBuf d_jobs;
     FbSlotLease lease{&fb_slots_of[device & 63], 0};
     FbChunkRes res;
     if (!jobs.empty()) {
-        FB_DO(d_jobs.alloc(jobs.size() * sizeof(PgFbJob)));
+        FB_TRY(d_jobs.alloc(jobs.size() * sizeof(PgFbJob)));
         FB_TRY(hipMemcpy(d_jobs, jobs.data(), jobs.size() * sizeof(PgFbJob), hipMemcpyHostToDevice));
         const PgFbJob *at = (const PgFbJob *)d_jobs.h;
         for (FbGroup &G : groups) if (!G.jobs) { G.jobs = at; at += G.ks.size(); }
@@ -1367,7 +1278,7 @@ static int fb_run_chunk(int chunk, const pagan_graph *const *left, const pagan_g
     }
     FB_TRY(hipGetLastError());
     const double th4 = fb_now();
-    for (const FbStream &s : res.streams) FB_TRY(hipStreamSynchronize(s));
+    for (const Stream &s : res.streams) FB_TRY(hipStreamSynchronize(s));
     const double th5 = fb_now();
     // A span's two times go to its first pair, 0 to its others: a sum over the batch is the launches'.  (A one-workgroup pair is
     // timed when it is the call's only pair.)
@@ -1406,7 +1317,7 @@ int pagan_fb_run_batch(int32_t n, const pagan_graph *const *left, const pagan_gr
     if (n == 0) return PAGAN_OK;
     // the device, resolved once: the calling thread is put on it before any allocation, stream or launch (a caller may pass a
     // device that is not its current one), the staging threads are handed it, and the caller's device is restored on the way out
-    FbDeviceScope on_device(opts ? opts->device : -1);
+    DeviceScope on_device(opts ? opts->device : -1);
     if (!on_device.ok) return PAGAN_E_NODEVICE;
     pagan_opts staged_opts;
     staged_opts.flags = opts ? opts->flags : 0u;
@@ -1453,7 +1364,7 @@ int pagan_fb_totals(const pagan_fb *fb, double *log_fwd, double *log_bwd, int64_
 // dst [Lx][Ly][3] row-major, state order X, Y, M; outside the tunnel -inf (logs) / 0 (posterior).
 int pagan_fb_dump(pagan_fb *fb, int32_t which, double *dst) {
     if (!fb || !dst || which < 0 || which > 2) return PAGAN_E_ARG;
-    FbDeviceScope on_device(fb->device);
+    DeviceScope on_device(fb->device);
     if (!on_device.ok) return PAGAN_E_NODEVICE;
     const size_t n = 3 * (size_t)fb->dx.cells;
     std::vector<double> a(n), bb;
@@ -1760,7 +1671,7 @@ int pagan_sample_uniforms_path(uint64_t seed, int32_t node, int32_t path, int32_
 // 3 * (Lx + Ly) ints): the cells of the path end -> start as (i, j, state).
 int pagan_fb_sample_path(pagan_fb *fb, const double *u, int32_t n_u, pagan_result *out, int32_t *visited, int32_t *n_visited) {
     if (!fb || !u || !out) return PAGAN_E_ARG;
-    FbDeviceScope on_device(fb->device);
+    DeviceScope on_device(fb->device);
     if (!on_device.ok) return PAGAN_E_NODEVICE;
     if (fb->hF.empty()) {
         fb->hF.resize(3 * (size_t)fb->dx.cells);
@@ -1858,7 +1769,7 @@ struct FbPaths {
     const pagan_graph *L = nullptr, *R = nullptr;       // borrowed from the pagan_fb: must outlive the handle for result()
     long long cells = 0;
     double log_fwd = 0;
-    std::shared_ptr<FbDevBuf> buf;
+    std::shared_ptr<DevBuf> buf;
     const int *d_trace = nullptr;                       // [group][step][lane of the group][3]; null: PAGAN_SAMPLE_NO_TRACES
     int *d_pack = nullptr;                              // [max_steps][3]: one path out of a group of several (n_paths > 1)
     std::mutex pack_mu;
@@ -1885,7 +1796,7 @@ struct FbPaths {
         trace->assign(3 * ((size_t)n + 1), 0);
         *n_steps = n;
         if (n == 0) return PAGAN_OK;
-        FbDeviceScope on_device(device);
+        DeviceScope on_device(device);
         if (!on_device.ok) return PAGAN_E_NODEVICE;
         const int g = path / 64, lane = path % 64, width = std::min(64, n_paths - 64 * g);
         const int *group = d_trace + 3 * (64ll * g * max_steps);
@@ -1931,8 +1842,8 @@ struct FsSizes { size_t summary, trace, pack; };
 static FsSizes fs_sizes(int Lx, int Ly, int n_paths, uint32_t flags) {
     const size_t steps = (size_t)Lx + Ly;
     const bool traces = !(flags & PAGAN_SAMPLE_NO_TRACES);
-    return {fb_round256(4 * (size_t)FB_SUMMARY_INTS * n_paths), traces ? fb_round256(12 * (size_t)n_paths * steps) : 0,
-            traces && n_paths > 1 ? fb_round256(12 * steps) : 0};
+    return {up256(4 * (size_t)FB_SUMMARY_INTS * n_paths), traces ? up256(12 * (size_t)n_paths * steps) : 0,
+            traces && n_paths > 1 ? up256(12 * steps) : 0};
 }
 } // namespace
 
@@ -2015,7 +1926,7 @@ int pagan_fb_samples_visited(pagan_fb_samples *s, int32_t path, int32_t *visited
 // n_visited [n_paths]
 int pagan_fb_samples_visited_all(pagan_fb_samples *s, int32_t *visited, int32_t *n_visited) {
     if (!s || !s->d_trace || !visited) return PAGAN_E_ARG;
-    FbDeviceScope on_device(s->device);
+    DeviceScope on_device(s->device);
     if (!on_device.ok) return PAGAN_E_NODEVICE;
     const size_t ms = (size_t)s->max_steps;
     std::vector<int32_t> raw(3 * (size_t)s->n_paths * ms);
@@ -2059,7 +1970,7 @@ void pagan_fb_samples_destroy(pagan_fb_samples *s) { delete s; }
 
 void pagan_fb_destroy(pagan_fb *fb) {
     if (!fb) return;
-    if (fb->arena) fb_arena_pool.give(fb->device, fb->arena, fb->arena_cap);
+    give_slab(fb_arena_pool, fb->device, fb->arena, fb->arena_cap);
     delete fb;
 }
 
@@ -2075,14 +1986,14 @@ struct pagan_fb_decoded : FbPaths {
     size_t arena_cap = 0;
     float ms[2] = {0, 0};                               // fill, trace (HIP events), at the batch's first pair
     int schedule = 0;                                   // 0 pg_fb_decode_fill, 1 pg_fb_ring_decode
-    ~pagan_fb_decoded() { if (arena) fb_arena_pool.give(device, arena, arena_cap); }
+    ~pagan_fb_decoded() { give_slab(fb_arena_pool, device, arena, arena_cap); }
 };
 
 namespace {
 // bytes a pair's decode takes: the matrix A (an arena of the pool's), and of the call's allocation the summary and the trace
 struct FdSizes { size_t matrix, summary, trace; };
 static FdSizes fd_sizes(long long cells, int Lx, int Ly) {
-    return {24 * (size_t)cells, fb_round256(4 * FB_SUMMARY_INTS), fb_round256(12 * ((size_t)Lx + Ly))};
+    return {24 * (size_t)cells, up256(4 * FB_SUMMARY_INTS), up256(12 * ((size_t)Lx + Ly))};
 }
 // waits for the default stream when a call leaves, by whichever return: a handle's matrix must not reach fb_arena_pool (whose next
 // take would hand it out) while a kernel may still be writing it
@@ -2125,7 +2036,7 @@ int pagan_fb_decode_batch(int32_t n, pagan_fb *const *fbs, double gap_weight, ui
         pagan_fb_decoded *d = hs[k].get();
         d->bind(fb, 1, flags, c);
         d->schedule = block[k] ? 1 : 0;
-        d->arena = fb_arena_pool.take(d->device, fd_sizes(fb->dx.cells, fb->Lx, fb->Ly).matrix, &d->arena_cap);
+        d->arena = slab_alloc(fb_arena_pool, d->device, fd_sizes(fb->dx.cells, fb->Lx, fb->Ly).matrix, &d->arena_cap);
         if (!d->arena) return PAGAN_E_NOMEM;
         if (flags & PAGAN_DECODE_KEEP_MATRIX) d->dx = fb->dx;
         d->d_trace = c.dev<const int>(o_trace[k]);
@@ -2162,7 +2073,7 @@ int pagan_fb_decode_batch(int32_t n, pagan_fb *const *fbs, double gap_weight, ui
         pagan_fb_decoded *d = hs[k].get();
         d->keep_summary(c, o_sum[k]);
         if (k == 0) { d->ms[0] = c.ms(0); d->ms[1] = c.ms(1); }
-        if (!(flags & PAGAN_DECODE_KEEP_MATRIX)) { fb_arena_pool.give(d->device, d->arena, d->arena_cap); d->arena = nullptr; }
+        if (!(flags & PAGAN_DECODE_KEEP_MATRIX)) { give_slab(fb_arena_pool, d->device, d->arena, d->arena_cap); d->arena = nullptr; }
     }
     for (int k = 0; k < n; ++k) out[k] = hs[k].release();
     return PAGAN_OK;
@@ -2198,7 +2109,7 @@ int pagan_fb_decoded_result(pagan_fb_decoded *d, pagan_result *out) {
 // dst [Lx][Ly][3] row-major, state order X, Y, M; -inf outside the band
 int pagan_fb_decoded_dump(pagan_fb_decoded *d, double *dst) {
     if (!d || !dst || !d->arena || !(d->flags & PAGAN_DECODE_KEEP_MATRIX)) return PAGAN_E_ARG;
-    FbDeviceScope on_device(d->device);
+    DeviceScope on_device(d->device);
     if (!on_device.ok) return PAGAN_E_NODEVICE;
     std::vector<double> a(3 * (size_t)d->cells);
     FB_TRY(hipMemcpy(a.data(), d->arena, 8 * a.size(), hipMemcpyDeviceToHost));

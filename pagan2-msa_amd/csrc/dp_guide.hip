@@ -31,9 +31,12 @@
 #include <vector>
 
 #include "../../include/pagan_host.h"
+#include "dp_hip.h"
 #include "host_guide.h"
 
 namespace pagan {
+
+using namespace pgdev;
 
 namespace {
 
@@ -184,23 +187,20 @@ __global__ __launch_bounds__(1024) void pgd_pairs(const uint64_t *codes, const u
     }
 }
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// the device buffers of one call, carved from one allocation
+// the device buffers of one call, carved from one allocation (offsets: an array of no bytes takes none)
 struct Layout {
     size_t letters, off, kmers, list_off, keys_in, keys_out, seg, head, pos, run_start, counts, pairs, tmp, total;
     Layout(int64_t n, int64_t T, size_t tmp_bytes) {
-        size_t at = 0;
-        auto take = [&](size_t bytes) { const size_t p = at; at += up256(bytes); return p; };
-        letters = take((size_t)T);
-        off = take(4 * (size_t)(n + 1)); kmers = take(4 * (size_t)n); list_off = take(4 * (size_t)(n + 1));
-        keys_in = take(8 * (size_t)T);               // after the sort: the lists' codes
-        keys_out = take(8 * (size_t)T);
-        seg = take(4 * (size_t)T); head = take(4 * (size_t)(T + 1)); pos = take(4 * (size_t)(T + 1));
-        run_start = take(4 * (size_t)T); counts = take(4 * (size_t)T);
-        pairs = take(4 * (size_t)(n * (n - 1) / 2));
-        tmp = take(tmp_bytes);
-        total = at;
+        Carve c{nullptr};
+        letters = c.skip((size_t)T);
+        off = c.skip(4 * (size_t)(n + 1)); kmers = c.skip(4 * (size_t)n); list_off = c.skip(4 * (size_t)(n + 1));
+        keys_in = c.skip(8 * (size_t)T);               // after the sort: the lists' codes
+        keys_out = c.skip(8 * (size_t)T);
+        seg = c.skip(4 * (size_t)T); head = c.skip(4 * (size_t)(T + 1)); pos = c.skip(4 * (size_t)(T + 1));
+        run_start = c.skip(4 * (size_t)T); counts = c.skip(4 * (size_t)T);
+        pairs = c.skip(4 * (size_t)(n * (n - 1) / 2));
+        tmp = c.skip(tmp_bytes);
+        total = c.cur;
     }
 };
 
@@ -208,18 +208,13 @@ struct Layout {
 // scan's block prefixes); run_device takes what they do ask for if that is more
 size_t tmp_bound(int64_t n, int64_t T) { return up256(8 * (size_t)T) + up256(4 * (size_t)T / 64) + 64 * (size_t)n + (1u << 20); }
 
-struct Device {                     // released on every exit path
-    char *mem = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Device() {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (st) (void)hipStreamDestroy(st);
-        if (mem) (void)hipFree(mem);
-    }
+struct Device {                     // released on every exit path (the stream has drained before the buffer is freed: dp_hip.h)
+    DevBuf mem;
+    Stream st;
+    Event ev[5];
 };
 
-#define HIPG(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { if (std::getenv("PAGAN_DP_VERBOSE")) std::fprintf(stderr, "pagan guide: %s -> %s\n", #x, hipGetErrorString(e_)); return e_ == hipErrorOutOfMemory ? PAGAN_E_NOMEM : PAGAN_E_INTERNAL; } } while (0)
+#define HIPG(x) PG_HIP_CODE(x, "pagan guide", PAGAN_E_INTERNAL)
 
 int waves_per_pair(int64_t pairs) {
     // enough waves to fill the chip's 8,192 wave slots when the pairs alone do not (32 x 100 kb: 496 pairs)
@@ -240,8 +235,8 @@ int run_device(const GuideInput &in, int n, int k, std::vector<uint32_t> *pair_s
     info->waves_per_pair = waves_per_pair(P);
     if (T == 0) return PAGAN_OK;
     Device D;
-    HIPG(hipStreamCreateWithFlags(&D.st, hipStreamNonBlocking));
-    for (hipEvent_t &e : D.ev) HIPG(hipEventCreate(&e));
+    HIPG(D.st.create(hipStreamNonBlocking));
+    for (Event &e : D.ev) HIPG(e.create());
     hipStream_t st = D.st;
     const unsigned end_bit = (unsigned)(in.bits * k + 1);
     size_t tmp_sort = 0, tmp_scan = 0;
@@ -249,7 +244,7 @@ int run_device(const GuideInput &in, int n, int k, std::vector<uint32_t> *pair_s
                                             (const uint32_t *)nullptr, (const uint32_t *)nullptr, 0u, end_bit, st));
     HIPG(rocprim::exclusive_scan(nullptr, tmp_scan, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)T + 1, rocprim::plus<uint32_t>(), st));
     const Layout L(n, T, std::max(tmp_bound(n, T), std::max(tmp_sort, tmp_scan)));
-    HIPG(hipMalloc((void **)&D.mem, L.total));
+    HIPG(D.mem.alloc(L.total));
     info->device_bytes = (int64_t)L.total;
     char *m = D.mem;
     unsigned char *letters = (unsigned char *)(m + L.letters);

@@ -39,9 +39,12 @@
 #include <mutex>
 #include <vector>
 
+#include "dp_hip.h"
 #include "host_graph.h"
 
 namespace pagan {
+
+using namespace pgdev;
 
 namespace {
 
@@ -382,56 +385,14 @@ __global__ __launch_bounds__(256) void pp_final_lists(PPArgs A) {
     }
 }
 
-#define PPHIP(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return false; } } while (0)
+#define PPHIP(x) PG_HIP_BOOL(x, "pagan parent")
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// device memory of finished builds, kept for the next one (a level of a walk is followed by the next)
-struct MemPool {
-    std::mutex m;
-    struct Slab { int device; char *p; size_t cap; };
-    std::vector<Slab> idle;
-    char *take(int device, size_t need, size_t *cap) {
-        {
-            std::lock_guard<std::mutex> g(m);
-            int best = -1;
-            for (size_t k = 0; k < idle.size(); ++k)
-                if (idle[k].device == device && idle[k].cap >= need && (best < 0 || idle[k].cap < idle[best].cap)) best = (int)k;
-            if (best >= 0 && idle[best].cap <= 4 * need + (1u << 20)) {
-                Slab s = idle[best]; idle.erase(idle.begin() + best); *cap = s.cap; return s.p;
-            }
-        }
-        char *p = nullptr;
-        *cap = need + need / 8;
-        if (hipMalloc((void **)&p, *cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        return p;
-    }
-    void give(int device, char *p, size_t cap) {
-        if (!p) return;
-        std::lock_guard<std::mutex> g(m);
-        if (idle.size() >= 48) {                                               // (bounded: the oldest goes)
-            int cur = -1;
-            (void)hipGetDevice(&cur);                                          // (the calling thread stays on the device it was on)
-            (void)hipSetDevice(idle.front().device); (void)hipFree(idle.front().p); idle.erase(idle.begin());
-            if (cur >= 0) (void)hipSetDevice(cur);
-        }
-        idle.push_back({device, p, cap});
-    }
-    void clear() {
-        std::lock_guard<std::mutex> g(m);
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        for (auto &s : idle) { (void)hipSetDevice(s.device); (void)hipFree(s.p); }
-        idle.clear();
-        if (cur >= 0) (void)hipSetDevice(cur);
-    }
-};
-MemPool pp_pool;
-
-struct Carve {
-    char *base; size_t cur = 0;
-    template <class T> T *take(size_t n) { T *p = base ? (T *)(base + cur) : nullptr; cur += up256(sizeof(T) * (n ? n : 1)); return p; }
-};
+// device memory of finished builds, kept for the next one (a level of a walk is followed by the next); bounded: the oldest goes.
+// No memory: no retry, the caller takes the host builder.
+const SlabPolicy kParentPolicy = {
+    /* slack_mul, slack_add */ 4, (size_t)1 << 20, /* grow_div */ 8, /* max_idle */ 48, /* max_idle_per_device */ 0,
+    /* max_idle_bytes */ 0, /* evict_smallest */ false, /* retry_drained */ false};
+SlabPool pp_pool(kParentPolicy);
 
 } // namespace
 
@@ -443,7 +404,7 @@ struct DevGraph {
     float *dist_since_used = nullptr; uint8_t *ambiguous = nullptr;
     int32_t *e_start = nullptr, *e_end = nullptr; float *e_w = nullptr, *e_logw = nullptr; int32_t *e_cnt = nullptr, *e_cas = nullptr; float *e_dist = nullptr; uint8_t *e_used = nullptr;
     int32_t *bwd_off = nullptr, *bwd_eid = nullptr, *bwd_src = nullptr; float *bwd_logw = nullptr; int32_t *fwd_off = nullptr, *fwd_eid = nullptr;
-    ~DevGraph() { if (mem) pp_pool.give(device, mem, cap); }
+    ~DevGraph() { give_slab(pp_pool, device, mem, cap); }
     void carve(int n, int e_cap) {
         Carve c{mem};
         lay(c, n, e_cap);
@@ -459,7 +420,7 @@ struct DevGraph {
     }
 };
 
-void parent_release_cache() { pp_pool.clear(); }
+void parent_release_cache() { drain_slabs(pp_pool, -1); }
 
 // The states of a graph changed on the host after it was built (--mostcommon: Node::fix_ambiguous_states, node.cpp:1610-1690,
 // rewrites the states of a node and of the ambiguous sites below it): its copy on the device -- which the build one level up
@@ -468,12 +429,9 @@ bool parent_update_states(SeqGraph &g) {
     DevGraph *d = static_cast<DevGraph *>(g.dev.get());
     if (!d) return true;
     if (d->n_sites != g.n_sites()) return false;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    bool ok = hipSetDevice(d->device) == hipSuccess &&
-              hipMemcpy(d->state, g.state.data(), sizeof(int32_t) * (size_t)d->n_sites, hipMemcpyHostToDevice) == hipSuccess;
+    DeviceScope on(d->device);
+    const bool ok = on.ok && hipMemcpy(d->state, g.state.data(), sizeof(int32_t) * (size_t)d->n_sites, hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) (void)hipGetLastError();
-    if (cur >= 0) (void)hipSetDevice(cur);
     return ok;
 }
 
@@ -486,7 +444,7 @@ bool resident(SeqGraph &g, int device, hipStream_t st, DevGraph **out) {
     std::shared_ptr<DevGraph> nd(new DevGraph());
     nd->device = device; nd->n_sites = g.n_sites(); nd->n_edges = g.n_edges();
     const int n = g.n_sites(), ne = std::max(g.n_edges(), 1);
-    nd->mem = pp_pool.take(device, DevGraph::bytes(n, ne), &nd->cap);
+    nd->mem = slab_alloc(pp_pool, device, DevGraph::bytes(n, ne), &nd->cap);
     if (!nd->mem) return false;
     nd->carve(n, ne);
     auto up = [&](void *dst, const void *src, size_t bytes) { return bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess; };
@@ -511,21 +469,15 @@ PPChild child_view(const DevGraph &d) {
     return c;
 }
 
-struct StreamPool {
-    std::mutex m;
-    std::vector<std::pair<int, hipStream_t>> idle;
-    hipStream_t take(int device) {
-        {
-            std::lock_guard<std::mutex> g(m);
-            for (size_t k = 0; k < idle.size(); ++k) if (idle[k].first == device) { hipStream_t s = idle[k].second; idle.erase(idle.begin() + k); return s; }
-        }
-        hipStream_t s = nullptr;
-        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        return s;
+// a build's stream, kept for the next build on the device (unbounded: one per build in flight)
+IdlePerDevice<hipStream_t> pp_streams;
+struct StreamLease {
+    int device; hipStream_t s = nullptr;
+    explicit StreamLease(int d) : device(d) {
+        if (!pp_streams.take(device, &s) && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); s = nullptr; }
     }
-    void give(int device, hipStream_t s) { if (s) { std::lock_guard<std::mutex> g(m); idle.emplace_back(device, s); } }
+    ~StreamLease() { std::vector<std::pair<int, hipStream_t>> none; if (s) pp_streams.give(device, s, 0, &none); }
 };
-StreamPool pp_streams;
 
 } // namespace
 
@@ -541,9 +493,9 @@ bool make_parent_device(SeqGraph &left, SeqGraph &right, const pagan_result &res
     else PPHIP(hipSetDevice(device));
     for (int k = 0; k < res.n_left_used; ++k) left.e_used[res.left_used[k]] = 1;
     for (int k = 0; k < res.n_right_used; ++k) right.e_used[res.right_used[k]] = 1;
-    hipStream_t st = pp_streams.take(device);
+    StreamLease lease(device);
+    hipStream_t st = lease.s;
     if (!st) return false;
-    struct Lease { int d; hipStream_t s; ~Lease() { pp_streams.give(d, s); } } lease{device, st};
     DevGraph *dl = nullptr, *dr = nullptr;
     const bool l_was = left.dev && static_cast<DevGraph *>(left.dev.get())->device == device;
     const bool r_was = right.dev && static_cast<DevGraph *>(right.dev.get())->device == device;
@@ -555,7 +507,7 @@ bool make_parent_device(SeqGraph &left, SeqGraph &right, const pagan_result &res
     const int e_cap = nbL + nbR + 2 * n;
     std::shared_ptr<DevGraph> pd(new DevGraph());
     pd->device = device; pd->n_sites = n;
-    pd->mem = pp_pool.take(device, DevGraph::bytes(n, e_cap), &pd->cap);
+    pd->mem = slab_alloc(pp_pool, device, DevGraph::bytes(n, e_cap), &pd->cap);
     if (!pd->mem) return false;
     pd->carve(n, e_cap);
 
@@ -582,9 +534,9 @@ bool make_parent_device(SeqGraph &left, SeqGraph &right, const pagan_result &res
         return c.cur;
     };
     const size_t sneed = lay(nullptr);
-    smem = pp_pool.take(device, sneed, &scap);
+    smem = slab_alloc(pp_pool, device, sneed, &scap);
     if (!smem) return false;
-    struct Scratch { int d; char *p; size_t c; ~Scratch() { pp_pool.give(d, p, c); } } scratch{device, smem, scap};
+    struct Scratch { int d; char *p; size_t c; ~Scratch() { give_slab(pp_pool, d, p, c); } } scratch{device, smem, scap};
     lay(smem);
     // Whatever way this function is left (a failed launch or copy returns early), nothing goes back to the pools -- the scratch
     // slab, the parent's slab, the stream -- while kernels or copies queued on the stream may still touch it: this object is the

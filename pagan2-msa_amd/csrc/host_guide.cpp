@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/pagan_host.h"
+#include "dp_pool.h"
 #include "host_guide.h"
 #include "host_model.h"
 
@@ -122,7 +123,6 @@ int aln_col_splits(int64_t tiles, int64_t words) {
 }
 
 AlnLayout::AlnLayout(int64_t n, int64_t columns, int planes_) {
-    auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
     rows_pad = (n + PAGAN_ALN_TILE - 1) / PAGAN_ALN_TILE * PAGAN_ALN_TILE;
     const int64_t T = rows_pad / PAGAN_ALN_TILE;
     tiles = T * (T + 1) / 2;
@@ -131,17 +131,16 @@ AlnLayout::AlnLayout(int64_t n, int64_t columns, int planes_) {
     planes = planes_;
     splits = aln_col_splits(tiles, words);
     const size_t tile_bytes = 2 * (size_t)PAGAN_ALN_TILE * PAGAN_ALN_TILE * sizeof(uint32_t);      // both and match
-    size_t at = 0;
-    auto take = [&](size_t b) { const size_t p = at; at += up256(b); return p; };
-    bytes = take((size_t)n * (size_t)columns);
-    table = take(256);
-    packed = take((size_t)words_pad * (size_t)planes * (size_t)rows_pad * sizeof(uint64_t));
+    pgdev::Carve c{nullptr};                                           // (offsets: an array of no bytes takes none)
+    bytes = c.skip((size_t)n * (size_t)columns);
+    table = c.skip(256);
+    packed = c.skip((size_t)words_pad * (size_t)planes * (size_t)rows_pad * sizeof(uint64_t));
     // slices of one tile's counts: split s of tile t writes slice s * tiles + t, and the fold adds them into slice t.  Room for
     // every S the split rule can choose at this size (S x tiles <= 1,024, S <= granules), so that the size grows with n and L
     const int64_t granules = words_pad / PAGAN_ALN_SPLIT_WORDS;
     slices = tiles >= 1024 || granules <= 1 ? tiles : std::min<int64_t>(1024, granules * tiles);
-    out = take((size_t)slices * tile_bytes);
-    total = at;
+    out = c.skip((size_t)slices * tile_bytes);
+    total = c.cur;
 }
 
 namespace {

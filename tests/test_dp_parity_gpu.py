@@ -225,3 +225,40 @@ def test_idle_arenas_are_kept_for_the_next_batch_and_can_be_released(pg, oracle)
     assert L.pagan_dp_cached_device_bytes(0) == held
     L.pagan_dp_release_cache()
     assert L.pagan_dp_cached_device_bytes(0) == 0
+
+
+def _current_device():
+    """hipGetDevice of the calling thread, asked of the HIP runtime the library itself is linked against"""
+    import ctypes
+    with open("/proc/self/maps") as f:
+        paths = {line.split()[-1] for line in f if "libamdhip64" in line}
+    assert len(paths) == 1, paths
+    device = ctypes.c_int(-1)
+    assert ctypes.CDLL(paths.pop()).hipGetDevice(ctypes.byref(device)) == 0
+    return device.value
+
+
+def test_releasing_the_cache_leaves_the_caller_on_its_device(pg, oracle):
+    """an idle arena, streams and events and a prefix finder's scratch on device 1, released by a thread that is on device 0"""
+    from pagan2_msa_amd import host
+    L = pg.lib()
+    if L.pagan_dp_device_count() < 2:
+        pytest.skip("one device")
+    left, right, seqs = pair_of_leaves(300, 5, sub=0.1, indel_start=0.03)
+    model = synth.jc_like_dna_model(0.1)
+    want = oracle.dp_align(left, right, model)
+    L.pagan_dp_release_cache()
+    try:
+        assert L.pagan_dp_select_device(1) == 0 and _current_device() == 1
+        assert_same(pg.align(left, right, model), want, "device 1")
+        assert L.pagan_dp_cached_device_bytes(1) > 0
+        assert np.array_equal(host.prefix_hits_raw(seqs[0], seqs[1], 12, device=True), host.prefix_hits_raw(seqs[0], seqs[1], 12))
+        assert L.pagan_dp_select_device(0) == 0 and _current_device() == 0
+        L.pagan_dp_release_cache()
+        assert _current_device() == 0
+        assert L.pagan_dp_cached_device_bytes(1) == 0
+        assert_same(pg.align(left, right, model), want, "device 0")
+        assert L.pagan_dp_cached_device_bytes(0) > 0 and L.pagan_dp_cached_device_bytes(1) == 0
+    finally:
+        L.pagan_dp_select_device(0)
+        L.pagan_dp_release_cache()

@@ -96,10 +96,15 @@ def test_integration_md_lists_the_switch_table():
     assert len(literals) == 12 and "getenv" in read and "getenv" not in src.replace(read, "")
     parsed = {v for v in literals if v.startswith("PAGAN_FB_")}
     assert literals - parsed == {"PAGAN_DP_VERBOSE"} and parsed == set(cases.FB_VARIABLES)
-    for name in ("dp_fb.hip", "dp_fb_deep.inc", "dp_fb_post.inc", "dp_fb_counts.inc", "dp_fb_sample.inc", "dp_fb_decode.inc"):
+    # (FB_TRY's error branch is dp_hip.h's hip_code: the one getenv on a HIP error path, and it reads PAGAN_DP_VERBOSE)
+    fb_files = sorted(f for f in os.listdir(CSRC) if re.fullmatch(r"dp_fb_.*\.inc", f))
+    assert {"dp_fb_deep.inc", "dp_fb_post.inc", "dp_fb_counts.inc", "dp_fb_sample.inc", "dp_fb_decode.inc"} <= set(fb_files)
+    for name in ["dp_fb.hip", "dp_pool.h"] + fb_files:
         with open(os.path.join(CSRC, name)) as f:
-            text = f.read()
-        assert text.count("getenv") == (1 if name == "dp_fb.hip" else 0), name      # FB_TRY's error branch
+            assert f.read().count("getenv") == 0, name
+    with open(os.path.join(CSRC, "dp_hip.h")) as f:
+        text = f.read()
+    assert text.count("getenv") == 1 and re.findall(r"getenv\(([^)]*)\)", text) == ['"PAGAN_DP_VERBOSE"']
     with open(os.path.join(ROOT, "INTEGRATION.md")) as f:
         doc = f.read()
     doc = doc[doc.index("The forward/backward side's `PAGAN_FB_*` switches"):doc.index("A process that runs many forward/backward sweeps")]
