@@ -464,6 +464,100 @@ int64_t pagan_aln_predict_bytes(int32_t n, int64_t columns);
  * exist (a walk not yet aligned / finished).                                                                              */
 int64_t pagan_msa_alignment_tree(const pagan_msa *m, char *newick_out, int64_t cap, pagan_aln_info *info);
 
+/* ---- ancestral states by marginal likelihood: pruning up the tree, the outside pass down, on the device --------------
+ * (csrc/dp_anc.hip, csrc/host_anc.cpp; DESIGN.md "Ancestral states").  The reference leaves this to the external program
+ * bppancestor (src/utils/bppancestors.cpp:98-317) and overlays its states on the ancestors' rows.
+ *
+ * Model: the walk's substitution model over its core states -- data_type 1 DNA (S = 4, ACGT), 2 protein (S = 20, WAG,
+ * ARNDCQEGHILKMFPSTWYV), 3 codon (S = 61, the empirical codon model, the sense codons in pagan_codon_alphabet's order).
+ * P(t)[i][j] = max(0, sum_k U[i,k] exp(t root[k]) V[k,j]) with k outermost in fp64, the sum the alignment model takes; it is not
+ * renormalised; t = 0 gives the exact identity.  U, V, root are the eigen solution of the model's rate matrix made a proper one:
+ * the reference's matrices (float products for DNA, a table of decimal literals for codons) are reversible under pi and have zero
+ * row sums only to the digits they carry, which a log-odds table does not mind and a likelihood does (rows of P off 1 by up to
+ * 6.6e-5); so the exchange flows pi_i q_ij are averaged with their mirror images and the diagonal is set to minus the row's sum
+ * before pagan_eigen_qrev's solver runs (pagan_anc_rate_matrix returns that matrix).  Rows of P then sum to 1, and pi_i P_ij = pi_j P_ji, to a few 1e-15.  The alignment
+ * model itself (pagan_dna_model and the others) is unchanged.
+ * Tree: n leaves 0 .. n-1, internal node n + k (k = 0 .. n-2) with children left[k], right[k], both ids < n + k (the walk's ids:
+ * children before parents, the root is 2n - 2); every node but the root is a child exactly once; branch[2n-1] is the length
+ * above each node, finite and >= 0, the root's entry ignored.  Anything else: PAGAN_E_TREE.
+ * Leaf encoding: n rows of equal length (pagan_aln_distances' checks and its resolution of data_type 0).  A character is
+ * upper-cased and a DNA U counts as T.  DNA: the 15 IUPAC letters ACGTRYMKWSBDHVN are state sets (R = AG, Y = CT, M = AC, K = GT,
+ * W = AT, S = CG, B = CGT, D = AGT, H = ACT, V = ACG, N = ACGT); anything else ('-', '.', '?', other letters) is missing data, the
+ * all-ones vector.  Protein: the 20 letters are states; everything else is missing, X, B, Z and U included.  Codon: a column is
+ * three characters (a row length that is no multiple of 3: PAGAN_E_ARG); a triplet pagan_codon_states reads as one of the 61
+ * sense codons is that state; anything else is missing -- NNN, "---", stop codons, partial gaps.
+ * Computation: up, L_v[s] = a[s] b[s], a[s] = sum_t P_left[s][t] L_left[t] with t ascending (b likewise); a leaf's L is the
+ * indicator of its state set; a child none of whose leaves holds data in the column contributes the exact factor 1.  After every
+ * node with data below it the vector is multiplied by 2^-e, e the binary exponent of its largest entry (ldexp: exact), and e is added to the column's
+ * int32.  Root: col_lik = sum_s pi[s] L_root[s], s ascending (the exact 1 for a column without any data).  Down, O_root = pi; for child c of v with sibling b,
+ * W[s] = O_v[s] m_b[s] (m_b the sibling's message a or b above), O_c[t] = sum_s W[s] P_c[s][t] with s ascending, rescaled the
+ * same way.  Posterior of v: q[s] = L_v[s] O_v[s] divided by sum_s q[s] (s ascending; all zero where that sum is zero).  Tie rule
+ * of `best`: the first maximum in state order (a later state replaces it only when strictly larger).  Every sum has a fixed
+ * order and no contraction: the outputs are bit-identical from run to run and for every chunk size.
+ * The device works on chunks of columns (pagan_anc_info.chunk_cols, a multiple of 64), so its footprint is bounded by the chunk,
+ * not by the alignment; PAGAN_ANC_CHUNK_COLS in the environment forces the chunk size.  Device, errors: as for the guide trees
+ * above -- the caller's current device, left current; PAGAN_E_NODEVICE without one (there is no host path).                    */
+#define PAGAN_ANC_MAX_STATES 61
+typedef struct pagan_anc_info {
+    int32_t data_type;           /* 1 DNA, 2 protein, 3 codon: what 0 was resolved to                            */
+    int32_t states;              /* S                                                                            */
+    int32_t chunks;              /* column chunks the call ran                                                   */
+    int32_t matrices;            /* distinct branch lengths = transition matrices uploaded                       */
+    int64_t columns;             /* L (codons: row length / 3)                                                   */
+    int64_t chunk_cols;          /* columns of a chunk                                                           */
+    int64_t device_bytes;        /* what the call allocated on the device                                        */
+    double  encode_ms, up_ms, down_ms;   /* device time of the stages, summed over the chunks (events around the launches) */
+} pagan_anc_info;
+/* Host only.  P [S * S] row-major and pi [S] (either may be NULL) of data_type 1 / 2 / 3 for branch length t; base_freq (DNA
+ * only, NULL: 0.25 each) as pagan_dna_model takes it, kappa and rho at the walk's defaults.  Returns S, or PAGAN_E_ARG (another
+ * data_type, t negative or not finite), PAGAN_E_INTERNAL where the eigen solver fails.                                       */
+int     pagan_anc_pmatrix(int32_t data_type, const float *base_freq, double t, double *P, double *pi);
+/* Host only.  The rate matrix pagan_anc_pmatrix exponentiates, Q [S * S] row-major, and pi [S] (either may be NULL): from the
+ * model's rates q (pagan_dna_model's HKY matrix as the reference builds it, in float arithmetic; the WAG table; the empirical
+ * codon table) r_ij = (pi_i q_ij + pi_j q_ji) / 2 / pi_i for i != j and r_ii = -(sum of the row's other entries, in column
+ * order).  Returns S, or PAGAN_E_ARG.                                                                                      */
+int     pagan_anc_rate_matrix(int32_t data_type, const float *base_freq, double *Q, double *pi);
+/* Host only.  The leaf codes of one row by the tables the device encodes with: codes [strlen(row)] (codons: / 3; a length that
+ * is no multiple of 3: PAGAN_E_ARG).  DNA: the state set as bits (1 A, 2 C, 4 G, 8 T), 0 for missing data; protein, codon: the
+ * state, 255 for missing data.  codes may be NULL.  Returns the number of columns.                                            */
+int64_t pagan_anc_encode_row(int32_t data_type, const char *row, uint8_t *codes);
+/* Host only.  PAGAN_OK or PAGAN_E_TREE (PAGAN_E_ARG: n < 2 or a null array) by the tree rules above. */
+int     pagan_anc_check_tree(int32_t n_leaves, const int32_t *left, const int32_t *right, const double *branch);
+/* Host only.  Device bytes of a pagan_anc_reconstruct call over n_leaves rows of `columns` columns in chunks of chunk_cols
+ * (<= 0: what the call itself would take, PAGAN_ANC_CHUNK_COLS included): exact for the call's own buffers when every branch
+ * length is distinct and every internal node's posterior is asked for; a call with fewer of either takes less
+ * (pagan_anc_info.device_bytes is what a call did allocate, never more than this).  PAGAN_E_ARG beyond the limits.        */
+int64_t pagan_anc_predict_bytes(int32_t n_leaves, int64_t columns, int32_t data_type, int64_t chunk_cols);
+/* rows: n_leaves rows of L characters (codons: 3 L).  flags: 0 (reserved).  post_nodes [n_post]: ids n .. 2n-2 of the internal
+ * nodes whose full posterior vectors are wanted.  Outputs, any may be NULL:
+ *   col_lik [L], col_exp [L]   the column's likelihood as the device left it: col_lik * 2^col_exp
+ *   col_loglik [L]             log(col_lik) + col_exp * ln 2, taken on the host
+ *   loglik                     col_loglik[0] + col_loglik[1] + ..., left to right in fp64: exactly that sum
+ *   best, best_p [(n-1) * L]   row k: internal node n + k's state of largest posterior in each column, and that posterior
+ *   has_data [(2n-1) * L]      bytes: 1 where any leaf below the node holds a non-missing character in the column
+ *   post [n_post * L * S]      the posterior vectors of the listed nodes                                                      */
+int     pagan_anc_reconstruct(int32_t n_leaves, const int32_t *left, const int32_t *right, const double *branch,
+                              const char *const *rows, int32_t data_type, const float *base_freq, uint32_t flags,
+                              int32_t n_post, const int32_t *post_nodes, double *col_lik, int32_t *col_exp, double *col_loglik,
+                              double *loglik, uint8_t *best, float *best_p, uint8_t *has_data, double *post, pagan_anc_info *info);
+/* The reconstruction over a finished walk: its leaf rows, its tree and the branch lengths it ALIGNED under -- the corrected,
+ * truncated lengths (Node::set_distance_to_parent: <= 0 becomes 0.001, anything above truncate_branches is cut to it), not the
+ * input tree's -- and for DNA its empirical base frequencies.  The result is kept in the handle for the three readers below.
+ * col_loglik (alignment_length, codons / 3, doubles) and info may be NULL.  PAGAN_E_ARG before the rows exist.
+ * ancestral_row: pagan_msa_alignment_row's row with every non-gap character of an internal node replaced by the letter of `best`
+ *   (codons: the three characters of the codon) -- the reference's overlay, bppancestors.cpp:242-254: gaps stay gaps, PAGAN's indel
+ *   pattern is kept; leaves come back unchanged.  The reference's copy of the root's characters from its nearer child
+ *   (:273-314, bppancestor works on an unrooted tree) is NOT restated: this pass is rooted and the root has its own posterior.
+ * ancestral_support: the posterior of the shown state per column (codons: per triplet), -1 at gaps; leaves: PAGAN_E_ARG.
+ * write_fasta_ancestral: pagan_msa_write_fasta_nodes(.., 1)'s file with the overlaid rows.
+ * All three return PAGAN_E_ARG before pagan_msa_ancestral has run.                                                          */
+int     pagan_msa_ancestral(pagan_msa *m, uint32_t flags, double *loglik, double *col_loglik, pagan_anc_info *info);
+int     pagan_msa_ancestral_row(const pagan_msa *m, int32_t node, char *buf);
+int     pagan_msa_ancestral_support(const pagan_msa *m, int32_t node, float *buf);
+int     pagan_msa_write_fasta_ancestral(const pagan_msa *m, const char *path, int32_t chars_by_line);
+/* Borrowed views (valid until the next pagan_msa_ancestral or pagan_msa_destroy) of the kept best [(n-1) * L] and best_p. */
+int     pagan_msa_ancestral_best(const pagan_msa *m, const uint8_t **best, const float **best_p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,212 @@
+// host_anc.cpp -- the host-only part of the ancestral reconstruction (include/pagan_host.h, "ancestral states by marginal
+// likelihood"; DESIGN.md "Ancestral states"): the transition matrices, the leaf tables, the tree check, the chunk size and the
+// device layout.  Nothing here needs a device; csrc/dp_anc.hip runs the passes.
+#include "host_anc.h"
+
+#include <algorithm>
+#include <cctype>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+#include "../../include/pagan_host.h"
+#include "dp_pool.h"
+#include "host_guide.h"
+
+namespace pagan {
+
+int anc_states(int data_type) { return data_type == 1 ? 4 : data_type == 2 ? 20 : data_type == 3 ? 61 : 0; }
+
+// The factory's eigen solution again, of the model's rate matrix made a proper one.  The reference's matrices are not: the DNA
+// rates are float products and the codon rates a table of decimal literals, so detailed balance under pi and the zero row sums
+// hold only to the digits those carry, and P(t) of the alignment model has row sums off 1 by up to 1.2e-8 (DNA) and 6.6e-5
+// (codons).  That is harmless in a log-odds score table and wrong in a likelihood.  From the model's Q: r_ij =
+// (pi_i q_ij + pi_j q_ji) / 2 / pi_i for i != j (each exchange flow averaged with its mirror image), r_ii = -(r_i0 + r_i1 + ...)
+// in column order, and eigen_qrev solves that; mf->Q becomes r.  P itself is never renormalised.  False: the solver failed.
+static bool anc_proper_rates(ModelFactory *mf) {
+    const int n = mf->char_as;
+    const std::vector<double> &Q = mf->Q;
+    std::vector<double> R((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i) {
+        double off = 0.0;
+        for (int j = 0; j < n; ++j) {
+            if (j == i) continue;
+            R[(size_t)i * n + j] = 0.5 * (mf->pi[i] * Q[(size_t)i * n + j] + mf->pi[j] * Q[(size_t)j * n + i]) / mf->pi[i];
+            off += R[(size_t)i * n + j];
+        }
+        R[(size_t)i * n + i] = -off;
+    }
+    mf->Q = R;
+    return eigen_qrev(R.data(), mf->pi.data(), n, mf->root.data(), mf->U.data(), mf->V.data()) == 0;
+}
+
+int anc_factory(int data_type, const float *base_freq, ModelFactory *mf) {
+    struct Made { ModelFactory f; bool ok; };
+    if (data_type == 1) {
+        const float flat[4] = {0.25f, 0.25f, 0.25f, 0.25f};
+        mf->init_dna(base_freq ? base_freq : flat);
+        return anc_proper_rates(mf) ? PAGAN_OK : PAGAN_E_INTERNAL;
+    }
+    static const Made protein = [] { Made m; m.f.init_protein(); m.ok = anc_proper_rates(&m.f); return m; }();
+    static const Made codon = [] { Made m; m.f.init_codon(); m.ok = anc_proper_rates(&m.f); return m; }();
+    const Made &made = data_type == 2 ? protein : codon;
+    *mf = made.f;
+    return made.ok ? PAGAN_OK : PAGAN_E_INTERNAL;
+}
+
+void anc_pmatrix(const ModelFactory &mf, double t, double *P) {
+    const int n = mf.char_as;
+    if (t == 0) {
+        for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) P[(size_t)i * n + j] = i == j ? 1.0 : 0.0;
+        return;
+    }
+    std::fill(P, P + (size_t)n * n, 0.0);
+    for (int k = 0; k < n; ++k) {                                  // ModelFactory::alignment_model's sum, k outermost, over anc_factory's solution
+        const double e1 = std::exp(t * mf.root[k]);
+        for (int i = 0; i < n; ++i) {
+            const double e2 = mf.U[(size_t)i * n + k] * e1;
+            for (int j = 0; j < n; ++j) P[(size_t)i * n + j] += e2 * mf.V[(size_t)k * n + j];
+        }
+    }
+    for (size_t k = 0; k < (size_t)n * n; ++k) P[k] = std::max(0.0, P[k]);
+}
+
+void anc_leaf_tables(int data_type, unsigned char table[256], unsigned char triplet[64]) {
+    std::memset(table, data_type == 1 ? 0 : kAncMissing, 256);
+    std::memset(triplet, kAncMissing, 64);
+    auto both_cases = [&](char c, unsigned char v) { table[(unsigned char)c] = table[(unsigned char)std::tolower(c)] = v; };
+    if (data_type == 1) {
+        // dna_full_alphabet()'s letters as the sets alignment_model lists for them
+        static const unsigned char bits[15] = {1, 2, 4, 8, 1 | 4, 2 | 8, 1 | 2, 4 | 8, 1 | 8, 2 | 4, 2 | 4 | 8, 1 | 4 | 8, 1 | 2 | 8, 1 | 2 | 4, 15};
+        const char *a = ModelFactory::dna_full_alphabet();
+        for (int k = 0; k < 15; ++k) both_cases(a[k], bits[k]);
+        both_cases('U', 8);
+    } else if (data_type == 2) {
+        const char *a = ModelFactory::protein_alphabet();
+        for (int k = 0; k < 20; ++k) both_cases(a[k], (unsigned char)k);
+    } else {
+        const char base[4] = {'A', 'C', 'G', 'T'};
+        for (int k = 0; k < 4; ++k) both_cases(base[k], (unsigned char)k);
+        both_cases('U', 3);
+        const char *names = ModelFactory::codon_alphabet();
+        for (int k = 0; k < 61; ++k)
+            triplet[table[(unsigned char)names[3 * k]] * 16 + table[(unsigned char)names[3 * k + 1]] * 4 + table[(unsigned char)names[3 * k + 2]]] = (unsigned char)k;
+    }
+}
+
+int anc_check_tree(int32_t n, const int32_t *left, const int32_t *right, const double *branch) {
+    if (n < 2 || !left || !right || !branch) return PAGAN_E_ARG;
+    std::vector<char> used((size_t)2 * n - 1, 0);
+    for (int k = 0; k < n - 1; ++k)
+        for (const int32_t c : {left[k], right[k]}) {
+            if (c < 0 || c >= n + k || used[c]) return PAGAN_E_TREE;
+            used[c] = 1;
+        }
+    for (int v = 0; v < 2 * n - 2; ++v) {
+        if (!used[v]) return PAGAN_E_TREE;
+        if (!std::isfinite(branch[v]) || branch[v] < 0) return PAGAN_E_TREE;
+    }
+    return PAGAN_OK;
+}
+
+AncSwitches AncSwitches::read() {
+    AncSwitches s;
+    if (const char *e = std::getenv("PAGAN_ANC_CHUNK_COLS")) s.chunk_cols = std::max(0ll, std::atoll(e));
+    return s;
+}
+
+int64_t anc_chunk_cols(int32_t n, int64_t columns, int S, int64_t want, const AncSwitches &sw) {
+    const int64_t all = std::max<int64_t>(64, (columns + 63) / 64 * 64);
+    if (want <= 0) want = sw.chunk_cols;
+    if (want <= 0) want = std::max<int64_t>(64, kAncBudgetBytes / (2 * (int64_t)(n - 1) * S * (int64_t)sizeof(double)) / 64 * 64);
+    want = want > all ? all : (want + 63) / 64 * 64;               // (compared first: no overflow in the rounding)
+    return want;
+}
+
+AncLayout::AncLayout(int64_t n, int S, int chars_per_col, int64_t C, int64_t matrices, int64_t n_post) {
+    pgdev::Carve c{nullptr};
+    const size_t in = (size_t)(n - 1), cols = (size_t)C;
+    raw = c.skip((size_t)n * cols * chars_per_col);
+    table = c.skip(256 + 64);
+    codes = c.skip((size_t)n * cols);
+    has = c.skip((size_t)(2 * n - 1) * cols);
+    part = c.skip(in * S * cols * sizeof(double));
+    outs = c.skip(in * S * cols * sizeof(double));
+    P = c.skip((size_t)matrices * S * S * sizeof(double));
+    PT = c.skip((size_t)matrices * S * S * sizeof(double));
+    pi = c.skip((size_t)S * sizeof(double));
+    nodes = c.skip(5 * in * sizeof(int32_t));
+    col_lik = c.skip(cols * sizeof(double));
+    col_exp = c.skip(cols * sizeof(int32_t));
+    best = c.skip(in * cols);
+    best_p = c.skip(in * cols * sizeof(float));
+    post = c.skip((size_t)n_post * S * cols * sizeof(double));
+    total = c.cur;
+}
+
+} // namespace pagan
+
+using namespace pagan;
+
+extern "C" {
+
+int pagan_anc_pmatrix(int32_t data_type, const float *base_freq, double t, double *P, double *pi) {
+    const int S = anc_states(data_type);
+    if (!S || !std::isfinite(t) || t < 0) return PAGAN_E_ARG;
+    try {
+        ModelFactory mf;
+        if (anc_factory(data_type, base_freq, &mf) != PAGAN_OK) return PAGAN_E_INTERNAL;
+        if (P) anc_pmatrix(mf, t, P);
+        if (pi) std::copy(mf.pi.begin(), mf.pi.begin() + S, pi);
+        return S;
+    } catch (const std::bad_alloc &) {
+        return PAGAN_E_NOMEM;
+    }
+}
+
+int pagan_anc_rate_matrix(int32_t data_type, const float *base_freq, double *Q, double *pi) {
+    const int S = anc_states(data_type);
+    if (!S) return PAGAN_E_ARG;
+    try {
+        ModelFactory mf;
+        if (anc_factory(data_type, base_freq, &mf) != PAGAN_OK) return PAGAN_E_INTERNAL;
+        if (Q) std::copy(mf.Q.begin(), mf.Q.end(), Q);
+        if (pi) std::copy(mf.pi.begin(), mf.pi.begin() + S, pi);
+        return S;
+    } catch (const std::bad_alloc &) {
+        return PAGAN_E_NOMEM;
+    }
+}
+
+int64_t pagan_anc_encode_row(int32_t data_type, const char *row, uint8_t *codes) {
+    if (!anc_states(data_type) || !row) return PAGAN_E_ARG;
+    const size_t chars = std::strlen(row), w = data_type == 3 ? 3 : 1;
+    if (chars % w) return PAGAN_E_ARG;
+    unsigned char table[256], triplet[64];
+    anc_leaf_tables(data_type, table, triplet);
+    for (size_t c = 0; c < chars / w && codes; ++c) {
+        const unsigned char *p = (const unsigned char *)row + c * w;
+        if (data_type != 3) { codes[c] = table[p[0]]; continue; }
+        const unsigned a = table[p[0]], b = table[p[1]], d = table[p[2]];               // (pa_encode's steps)
+        codes[c] = a < 4 && b < 4 && d < 4 ? triplet[a * 16 + b * 4 + d] : kAncMissing;
+    }
+    return (int64_t)(chars / w);
+}
+
+int pagan_anc_check_tree(int32_t n_leaves, const int32_t *left, const int32_t *right, const double *branch) {
+    try {
+        return anc_check_tree(n_leaves, left, right, branch);
+    } catch (const std::bad_alloc &) {
+        return PAGAN_E_NOMEM;
+    }
+}
+
+int64_t pagan_anc_predict_bytes(int32_t n_leaves, int64_t columns, int32_t data_type, int64_t chunk_cols) {
+    const int S = anc_states(data_type);
+    if (!S || n_leaves < 2 || n_leaves > PAGAN_GUIDE_MAX_SEQS || columns < 0 || columns >= (1ll << 31)) return PAGAN_E_ARG;
+    const int64_t C = anc_chunk_cols(n_leaves, columns, S, chunk_cols, AncSwitches::read());
+    return (int64_t)AncLayout(n_leaves, S, data_type == 3 ? 3 : 1, C, 2 * (int64_t)n_leaves - 2, n_leaves - 1).total;
+}
+
+} // extern "C"

@@ -253,6 +253,7 @@ void ModelFactory::init_dna(const float bf[4], float kappa, float rho) {
     q(3, 0) = beta * bf[0]; q(3, 1) = alfaY * bf[1] / piY + beta * bf[1]; q(3, 2) = beta * bf[2];          // :1434-1444
     q(3, 3) = 0 - q(3, 0) - q(3, 1) - q(3, 2);
     U.assign(16, 0.0); V.assign(16, 0.0); root.assign(4, 0.0);
+    this->Q.assign(Q, Q + 16);
     eigen_qrev(Q, pi.data(), 4, root.data(), U.data(), V.data());
     // parsimony table, model_factory.cpp:147-227 (the DNA most-common table is the same table, :218-224)
     const int bits[15] = {1, 2, 4, 8, 1 | 4, 2 | 8, 1 | 2, 4 | 8, 1 | 8, 2 | 4, 2 | 4 | 8, 1 | 4 | 8, 1 | 2 | 8, 1 | 2 | 4, 15};
@@ -323,6 +324,7 @@ void ModelFactory::init_protein() {
     mostcommon.assign(400, 0);
     for (int i = 0; i < 20; ++i) for (int j = 0; j < 20; ++j) mostcommon[i + j * 20] = kWagPi[i] > kWagPi[j] ? i : j;
     U.assign(400, 0.0); V.assign(400, 0.0); root.assign(20, 0.0);
+    Q.assign(kWagQ, kWagQ + 400);
     eigen_qrev(kWagQ, pi.data(), 20, root.data(), U.data(), V.data());
 }
 
@@ -453,6 +455,7 @@ void ModelFactory::init_codon() {
     mostcommon.assign(61 * 61, 0);
     for (int i = 0; i < 61; ++i) for (int j = 0; j < 61; ++j) mostcommon[i + j * 61] = kCodonPi[i] > kCodonPi[j] ? i : j;
     U.assign(61 * 61, 0.0); V.assign(61 * 61, 0.0); root.assign(61, 0.0);
+    Q.assign(kCodonQ, kCodonQ + 61 * 61);
     eigen_qrev(kCodonQ, pi.data(), 61, root.data(), U.data(), V.data());
 }
 

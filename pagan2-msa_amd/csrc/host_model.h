@@ -49,6 +49,7 @@ struct ModelFactory {
     std::string ancestral_alphabet;                       // Model_factory::ancestral_character_alphabet, one char per state
     float ins_rate = 0.01f, del_rate = 0.01f, ext_prob = 0.8f, end_ext_prob = 0.95f;
     std::vector<double> pi, U, V, root;
+    std::vector<double> Q;                                // the rate matrix the eigen solution was made of, row-major [char_as * char_as]
     std::vector<int32_t> parsimony;                       // [i + j*S]
     std::vector<int32_t> mostcommon;                      // [i + j*mc_dim] (--mostcommon)
     int mc_dim = 0;

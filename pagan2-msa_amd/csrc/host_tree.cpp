@@ -176,6 +176,10 @@ struct pagan_msa {
     std::atomic<int> lazy_err{0};        // first error of a deferred parent build (an imported result that does not fit the child graphs)
     bool rows_built = false;             // m->rows are valid (pagan_msa_finish builds them at once, pagan_msa_finish_lazy on first use)
     std::mutex lazy_mu;                  // deferred builds started from the accessors
+    // pagan_msa_ancestral's result: row k is internal node n + k's state of largest posterior per column, and that posterior
+    bool anc_done = false;
+    std::vector<uint8_t> anc_best;
+    std::vector<float> anc_best_p;
     ~pagan_msa() { for (auto &w : work) if (w.has_res) pagan_result_free(&w.res); }
 };
 
@@ -1423,9 +1427,7 @@ int pagan_msa_write_fasta(const pagan_msa *m, const char *path, int32_t chars_by
 
 // ... with include_internal (--output-ancestors): every node in Node::get_all_nodes order -- left subtree, the node,
 // right subtree (node.h:277-290) -- internal nodes named #k# in alignment order (node.h:479-495).
-int pagan_msa_write_fasta_nodes(const pagan_msa *m, const char *path, int32_t chars_by_line, int32_t include_internal) {
-    if (!m || !m->aligned || !path) return PAGAN_E_ARG;
-    if (const int rc = ensure_rows(const_cast<pagan_msa *>(m))) return rc;
+static int write_fasta_rows(const pagan_msa *m, const std::vector<std::string> &rows, const char *path, int32_t chars_by_line, int32_t include_internal) {
     const size_t width = chars_by_line > 0 ? (size_t)chars_by_line : 60;
     std::FILE *f = std::fopen(path, "w");
     if (!f) return PAGAN_E_ARG;
@@ -1447,10 +1449,100 @@ int pagan_msa_write_fasta_nodes(const pagan_msa *m, const char *path, int32_t ch
     for (int leaf : order) {
         if (leaf < m->n_leaves) std::fprintf(f, ">%s\n", m->names[leaf].c_str());
         else std::fprintf(f, ">#%d#\n", leaf - m->n_leaves + 1);
-        const std::string &row = m->rows[leaf];
+        const std::string &row = rows[leaf];
         for (size_t at = 0; at < row.size(); at += width) std::fprintf(f, "%.*s\n", (int)std::min(width, row.size() - at), row.c_str() + at);
     }
     return std::fclose(f) == 0 ? PAGAN_OK : PAGAN_E_ARG;
+}
+
+int pagan_msa_write_fasta_nodes(const pagan_msa *m, const char *path, int32_t chars_by_line, int32_t include_internal) {
+    if (!m || !m->aligned || !path) return PAGAN_E_ARG;
+    if (const int rc = ensure_rows(const_cast<pagan_msa *>(m))) return rc;
+    return write_fasta_rows(m, m->rows, path, chars_by_line, include_internal);
+}
+
+// ---- ancestral states by marginal likelihood (csrc/dp_anc.hip) over the finished walk -----------------------------------
+// The walk's tree in its public ids (children before parents, the root 2n - 2) under the branch lengths it aligned with:
+// tree[].dist after corrected_branch.
+int pagan_msa_ancestral(pagan_msa *m, uint32_t flags, double *loglik, double *col_loglik, pagan_anc_info *info) {
+    if (!m || !m->aligned) return PAGAN_E_ARG;
+    if (const int rc = ensure_rows(m)) return rc;
+    try {
+        const int n = m->n_leaves;
+        std::vector<int32_t> left(n - 1), right(n - 1);
+        std::vector<double> branch((size_t)2 * n - 1, 0.0);
+        std::vector<const char *> rows(n);
+        for (int k = 0; k < n - 1; ++k) {
+            const TreeNode &t = m->tree[m->tree_of_id[n + k]];
+            left[k] = m->id_of_tree[t.left]; right[k] = m->id_of_tree[t.right];
+        }
+        for (int id = 0; id < 2 * n - 1; ++id) branch[id] = m->tree[m->tree_of_id[id]].dist;
+        for (int k = 0; k < n; ++k) rows[k] = m->rows[k].c_str();
+        float bf[4] = {0.25f, 0.25f, 0.25f, 0.25f};
+        if (m->mf.type == kDna) for (int k = 0; k < 4; ++k) bf[k] = (float)m->mf.pi[k];     // (the floats init_dna took)
+        const size_t L = m->rows[0].size() / (m->mf.type == kCodon ? 3 : 1);
+        std::vector<uint8_t> best((size_t)(n - 1) * L);
+        std::vector<float> best_p((size_t)(n - 1) * L);
+        m->anc_done = false;
+        const int rc = pagan_anc_reconstruct(n, left.data(), right.data(), branch.data(), rows.data(), pagan_msa_data_type(m), bf, flags, 0, nullptr,
+                                             nullptr, nullptr, col_loglik, loglik, best.data(), best_p.data(), nullptr, nullptr, info);
+        if (rc != PAGAN_OK) return rc;
+        m->anc_best.swap(best); m->anc_best_p.swap(best_p);
+        m->anc_done = true;
+        return PAGAN_OK;
+    } catch (const std::bad_alloc &) {
+        return PAGAN_E_NOMEM;
+    }
+}
+
+// The overlay of bppancestors.cpp:242-254: every character of an ancestor's row that is no gap becomes the state of largest
+// posterior; the root keeps its own (no copy from a child as at :273-314: the pass is rooted).
+static std::string ancestral_row_of(const pagan_msa *m, int node) {
+    std::string row = m->rows[node];
+    const int n = m->n_leaves;
+    if (node < n) return row;
+    const int w = m->mf.type == kCodon ? 3 : 1;
+    const size_t L = row.size() / w;
+    const char *letters = m->mf.type == kCodon ? ModelFactory::codon_alphabet() : m->mf.type == kProtein ? ModelFactory::protein_alphabet() : ModelFactory::dna_full_alphabet();
+    const uint8_t *best = m->anc_best.data() + (size_t)(node - n) * L;
+    for (size_t c = 0; c < L; ++c)
+        if (row[c * w] != '-') for (int j = 0; j < w; ++j) row[c * w + j] = letters[(size_t)best[c] * w + j];
+    return row;
+}
+
+int pagan_msa_ancestral_row(const pagan_msa *m, int32_t node, char *buf) {
+    if (!m || !m->aligned || !m->anc_done || !buf || node < 0 || node >= (int)m->rows.size()) return PAGAN_E_ARG;
+    const std::string row = ancestral_row_of(m, node);
+    std::memcpy(buf, row.c_str(), row.size() + 1);
+    return PAGAN_OK;
+}
+
+int pagan_msa_ancestral_support(const pagan_msa *m, int32_t node, float *buf) {
+    if (!m || !m->aligned || !m->anc_done || !buf || node < m->n_leaves || node >= (int)m->rows.size()) return PAGAN_E_ARG;
+    const int w = m->mf.type == kCodon ? 3 : 1;
+    const std::string &row = m->rows[node];
+    const size_t L = row.size() / w;
+    const float *p = m->anc_best_p.data() + (size_t)(node - m->n_leaves) * L;
+    for (size_t c = 0; c < L; ++c) buf[c] = row[c * w] != '-' ? p[c] : -1.0f;
+    return PAGAN_OK;
+}
+
+int pagan_msa_write_fasta_ancestral(const pagan_msa *m, const char *path, int32_t chars_by_line) {
+    if (!m || !m->aligned || !m->anc_done || !path) return PAGAN_E_ARG;
+    try {
+        std::vector<std::string> rows(m->rows.size());
+        for (size_t id = 0; id < rows.size(); ++id) rows[id] = ancestral_row_of(m, (int)id);
+        return write_fasta_rows(m, rows, path, chars_by_line, 1);
+    } catch (const std::bad_alloc &) {
+        return PAGAN_E_NOMEM;
+    }
+}
+
+int pagan_msa_ancestral_best(const pagan_msa *m, const uint8_t **best, const float **best_p) {
+    if (!m || !m->anc_done) return PAGAN_E_ARG;
+    if (best) *best = m->anc_best.data();
+    if (best_p) *best_p = m->anc_best_p.data();
+    return PAGAN_OK;
 }
 
 void *pagan_msa_node_graph(const pagan_msa *m, int32_t node) {

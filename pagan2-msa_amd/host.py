@@ -67,6 +67,12 @@ class CAlnInfo(C.Structure):
                 ("pack_ms", C.c_double), ("pairs_ms", C.c_double), ("upgma_ms", C.c_double)]
 
 
+class CAncInfo(C.Structure):
+    _fields_ = [("data_type", C.c_int32), ("states", C.c_int32), ("chunks", C.c_int32), ("matrices", C.c_int32),
+                ("columns", C.c_int64), ("chunk_cols", C.c_int64), ("device_bytes", C.c_int64),
+                ("encode_ms", C.c_double), ("up_ms", C.c_double), ("down_ms", C.c_double)]
+
+
 GUIDE_MAX_SEQS = 65536
 GUIDE_PAIR_CHUNK = 64
 ALN_TILE = 64
@@ -260,6 +266,30 @@ def _lib():
         L.pagan_aln_predict_bytes.restype = C.c_int64
         L.pagan_msa_alignment_tree.argtypes = [vp, C.c_char_p, C.c_int64, C.POINTER(CAlnInfo)]
         L.pagan_msa_alignment_tree.restype = C.c_int64
+        u8p = C.POINTER(C.c_uint8)
+        L.pagan_anc_pmatrix.argtypes = [C.c_int32, _f32p, C.c_double, f64p, f64p]
+        L.pagan_anc_pmatrix.restype = C.c_int
+        L.pagan_anc_rate_matrix.argtypes = [C.c_int32, _f32p, f64p, f64p]
+        L.pagan_anc_rate_matrix.restype = C.c_int
+        L.pagan_anc_encode_row.argtypes = [C.c_int32, C.c_char_p, u8p]
+        L.pagan_anc_encode_row.restype = C.c_int64
+        L.pagan_anc_check_tree.argtypes = [C.c_int32, _i32p, _i32p, f64p]
+        L.pagan_anc_check_tree.restype = C.c_int
+        L.pagan_anc_predict_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int64]
+        L.pagan_anc_predict_bytes.restype = C.c_int64
+        L.pagan_anc_reconstruct.argtypes = [C.c_int32, _i32p, _i32p, f64p, cpp, C.c_int32, _f32p, C.c_uint32, C.c_int32, _i32p,
+                                            f64p, _i32p, f64p, f64p, u8p, _f32p, u8p, f64p, C.POINTER(CAncInfo)]
+        L.pagan_anc_reconstruct.restype = C.c_int
+        L.pagan_msa_ancestral.argtypes = [vp, C.c_uint32, f64p, f64p, C.POINTER(CAncInfo)]
+        L.pagan_msa_ancestral.restype = C.c_int
+        L.pagan_msa_ancestral_row.argtypes = [vp, C.c_int32, C.c_char_p]
+        L.pagan_msa_ancestral_row.restype = C.c_int
+        L.pagan_msa_ancestral_support.argtypes = [vp, C.c_int32, _f32p]
+        L.pagan_msa_ancestral_support.restype = C.c_int
+        L.pagan_msa_write_fasta_ancestral.argtypes = [vp, C.c_char_p, C.c_int32]
+        L.pagan_msa_write_fasta_ancestral.restype = C.c_int
+        L.pagan_msa_ancestral_best.argtypes = [vp, C.POINTER(u8p), C.POINTER(_f32p)]
+        L.pagan_msa_ancestral_best.restype = C.c_int
         _declared = True
     return L
 
@@ -285,7 +315,10 @@ HOST_EXPORTED = ["pagan_assign_units", "pagan_msa_default_opts", "pagan_msa_crea
                  "pagan_msa_set_counts", "pagan_msa_node_counts", "pagan_msa_set_indel_model", "pagan_fit_indel",
                  "pagan_guide_distances", "pagan_guide_tree", "pagan_guide_kmer_length", "pagan_guide_distance_of",
                  "pagan_guide_upgma", "pagan_guide_predict_bytes",
-                 "pagan_aln_distances", "pagan_aln_tree", "pagan_aln_predict_bytes", "pagan_msa_alignment_tree"]
+                 "pagan_aln_distances", "pagan_aln_tree", "pagan_aln_predict_bytes", "pagan_msa_alignment_tree",
+                 "pagan_anc_pmatrix", "pagan_anc_rate_matrix", "pagan_anc_encode_row", "pagan_anc_check_tree", "pagan_anc_predict_bytes", "pagan_anc_reconstruct",
+                 "pagan_msa_ancestral", "pagan_msa_ancestral_row", "pagan_msa_ancestral_support",
+                 "pagan_msa_write_fasta_ancestral", "pagan_msa_ancestral_best"]
 
 
 def _ip(a):
@@ -722,6 +755,126 @@ def aln_tree(names, rows, data_type=0, with_info=False):
     return (newick, _aln_info(ci)) if with_info else newick
 
 
+ANC_STATES = {1: 4, 2: 20, 3: 61}
+
+
+def _anc_info(ci):
+    return {name: getattr(ci, name) for name, _ in CAncInfo._fields_}
+
+
+def _base_freq(base_freq):
+    if base_freq is None:
+        return None, None
+    bf = np.ascontiguousarray(base_freq, np.float32)
+    if bf.shape != (4,):
+        raise ValueError("base_freq must hold four frequencies")
+    return bf, _fp(bf)
+
+
+def anc_pmatrix(data_type, t, base_freq=None):
+    """pagan_anc_pmatrix (host only): (P [S, S], pi [S]) of the walk's substitution model over its core states (S = 4 / 20 / 61
+    for data_type 1 / 2 / 3) for branch length t; base_freq (DNA only) as dna_model takes it."""
+    S = ANC_STATES.get(int(data_type), 1)
+    P, pi = np.zeros((S, S), np.float64), np.zeros(S, np.float64)
+    f64p = C.POINTER(C.c_double)
+    _keep, bfp = _base_freq(base_freq)
+    _guide_check(_lib().pagan_anc_pmatrix(int(data_type), bfp, float(t), P.ctypes.data_as(f64p), pi.ctypes.data_as(f64p)), "pagan_anc_pmatrix")
+    return P, pi
+
+
+def anc_rate_matrix(data_type, base_freq=None):
+    """pagan_anc_rate_matrix (host only): (Q [S, S], pi [S]) -- the rate matrix anc_pmatrix exponentiates, the model's made proper."""
+    S = ANC_STATES.get(int(data_type), 1)
+    Q, pi = np.zeros((S, S), np.float64), np.zeros(S, np.float64)
+    f64p = C.POINTER(C.c_double)
+    _keep, bfp = _base_freq(base_freq)
+    _guide_check(_lib().pagan_anc_rate_matrix(int(data_type), bfp, Q.ctypes.data_as(f64p), pi.ctypes.data_as(f64p)), "pagan_anc_rate_matrix")
+    return Q, pi
+
+
+def anc_encode_row(data_type, row):
+    """pagan_anc_encode_row (host only): the row's leaf codes (uint8) by the tables the device encodes with -- DNA the state set as
+    bits (0: missing data), protein and codon the state (255: missing data)."""
+    raw = row.encode() if isinstance(row, str) else bytes(row)
+    codes = np.zeros(max(len(raw), 1), np.uint8)
+    n = _guide_check(_lib().pagan_anc_encode_row(int(data_type), raw, codes.ctypes.data_as(C.POINTER(C.c_uint8))), "pagan_anc_encode_row")
+    return codes[:n].copy()
+
+
+def anc_check_tree(left, right, branch):
+    """pagan_anc_check_tree (host only): raises PaganError(PAGAN_E_TREE) for a tree the reconstruction would refuse."""
+    le, ri = np.ascontiguousarray(left, np.int32), np.ascontiguousarray(right, np.int32)
+    br = np.ascontiguousarray(branch, np.float64)
+    n = len(le) + 1
+    if len(ri) != n - 1 or len(br) != 2 * n - 1:
+        raise ValueError("left, right hold n - 1 entries and branch 2 n - 1")
+    _guide_check(_lib().pagan_anc_check_tree(n, _ip(le), _ip(ri), br.ctypes.data_as(C.POINTER(C.c_double))), "pagan_anc_check_tree")
+
+
+def anc_predict_bytes(n_leaves, columns, data_type, chunk_cols=0):
+    """pagan_anc_predict_bytes (host only): device bytes anc_reconstruct allocates at most."""
+    return _guide_check(_lib().pagan_anc_predict_bytes(int(n_leaves), int(columns), int(data_type), int(chunk_cols)), "pagan_anc_predict_bytes")
+
+
+def anc_reconstruct(left, right, branch, rows, data_type=0, base_freq=None, post_nodes=()):
+    """pagan_anc_reconstruct: marginal ancestral states of an alignment on its tree, on the current device.  left, right [n - 1]:
+    the children of internal node n + k; branch [2 n - 1]: the length above every node.  Returns a dict: col_lik, col_exp,
+    col_loglik [L]; loglik; best (uint8), best_p (float32) [n - 1, L]; has_data (uint8) [2 n - 1, L]; post [len(post_nodes), L, S];
+    info (include/pagan_host.h)."""
+    le, ri = np.ascontiguousarray(left, np.int32), np.ascontiguousarray(right, np.int32)
+    br = np.ascontiguousarray(branch, np.float64)
+    n = len(rows)
+    if len(le) != n - 1 or len(ri) != n - 1 or len(br) != 2 * n - 1:
+        raise ValueError("left, right hold n - 1 entries and branch 2 n - 1")
+    pn = np.ascontiguousarray(post_nodes, np.int32)
+    chars = len(rows[0]) if n else 0
+    f64p, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+    _keep, bfp = _base_freq(base_freq)
+    ci = CAncInfo()
+    # the columns are known only once the data type is resolved: size for one character a column, cut afterwards
+    col_lik, col_exp, col_loglik = np.zeros(chars, np.float64), np.zeros(chars, np.int32), np.zeros(chars, np.float64)
+    loglik = C.c_double(0.0)
+    best, best_p = np.zeros((n - 1) * chars, np.uint8), np.zeros((n - 1) * chars, np.float32)
+    has = np.zeros((2 * n - 1) * chars, np.uint8)
+    post = np.zeros(len(pn) * chars * ANC_STATES[3], np.float64)
+    _guide_check(_lib().pagan_anc_reconstruct(n, _ip(le), _ip(ri), br.ctypes.data_as(f64p), _c_strings(rows), int(data_type), bfp, 0,
+                                              len(pn), _ip(pn), col_lik.ctypes.data_as(f64p), _ip(col_exp), col_loglik.ctypes.data_as(f64p),
+                                              C.byref(loglik), best.ctypes.data_as(u8p), _fp(best_p), has.ctypes.data_as(u8p),
+                                              post.ctypes.data_as(f64p), C.byref(ci)), "pagan_anc_reconstruct")
+    L, S = int(ci.columns), int(ci.states)
+    return {"col_lik": col_lik[:L].copy(), "col_exp": col_exp[:L].copy(), "col_loglik": col_loglik[:L].copy(), "loglik": loglik.value,
+            "best": best[:(n - 1) * L].reshape(n - 1, L).copy(), "best_p": best_p[:(n - 1) * L].reshape(n - 1, L).copy(),
+            "has_data": has[:(2 * n - 1) * L].reshape(2 * n - 1, L).copy(), "post": post[:len(pn) * L * S].reshape(len(pn), L, S).copy(),
+            "info": _anc_info(ci)}
+
+
+class Ancestral:
+    """What Msa.ancestral() leaves: loglik, col_loglik [L], best / best_p [n - 1, L], info, and the overlaid rows."""
+
+    def __init__(self, msa, loglik, col_loglik, best, best_p, info):
+        self._msa, self.loglik, self.col_loglik, self.best, self.best_p, self.info = msa, loglik, col_loglik, best, best_p, info
+
+    def row(self, node):
+        """pagan_msa_ancestral_row: the node's row with every non-gap character of an ancestor replaced by its most probable state."""
+        m = self._msa
+        n = m._L.pagan_msa_alignment_length(m._h)
+        buf = C.create_string_buffer(n + 1)
+        m._fb_check(m._L.pagan_msa_ancestral_row(m._h, node, buf), "pagan_msa_ancestral_row")
+        return buf.raw[:n].decode()
+
+    def support(self, node):
+        """pagan_msa_ancestral_support: the posterior of the shown state per column (float32), -1 at gaps."""
+        m = self._msa
+        buf = np.zeros(int(self.info["columns"]), np.float32)
+        m._fb_check(m._L.pagan_msa_ancestral_support(m._h, node, _fp(buf)), "pagan_msa_ancestral_support")
+        return buf
+
+    def write_fasta(self, path, chars_by_line=60):
+        """pagan_msa_write_fasta_ancestral: write_fasta(include_internal=True)'s file with the overlaid rows."""
+        m = self._msa
+        m._fb_check(m._L.pagan_msa_write_fasta_ancestral(m._h, str(path).encode(), chars_by_line), "pagan_msa_write_fasta_ancestral")
+
+
 def differing_clades(newick_a, newick_b):
     """The clades (leaf sets under the internal nodes) of tree a that tree b does not have."""
     from . import synth
@@ -1126,6 +1279,24 @@ class Msa:
         newick = _newick_call(lambda buf, cap: self._L.pagan_msa_alignment_tree(self._h, buf, cap, C.byref(ci)),
                               "pagan_msa_alignment_tree", self.names)
         return (newick, _aln_info(ci)) if with_info else newick
+
+    def ancestral(self):
+        """pagan_msa_ancestral: marginal ancestral states of the finished walk on the current device -- its leaf rows, its tree,
+        the branch lengths it aligned under.  Returns an Ancestral; PaganError(PAGAN_E_ARG) before the rows exist."""
+        n = self._L.pagan_msa_alignment_length(self._h)
+        col = np.zeros(max(n, 0), np.float64)
+        loglik, ci = C.c_double(0.0), CAncInfo()
+        self._fb_check(self._L.pagan_msa_ancestral(self._h, 0, C.byref(loglik), col.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ci)),
+                       "pagan_msa_ancestral")
+        L = int(ci.columns)
+        bp, pp = C.POINTER(C.c_uint8)(), _f32p()
+        self._fb_check(self._L.pagan_msa_ancestral_best(self._h, C.byref(bp), C.byref(pp)), "pagan_msa_ancestral_best")
+        shape = (self.n - 1, L)
+        if L:
+            best, best_p = np.ctypeslib.as_array(bp, shape=shape).copy(), np.ctypeslib.as_array(pp, shape=shape).copy()
+        else:
+            best, best_p = np.zeros(shape, np.uint8), np.zeros(shape, np.float32)
+        return Ancestral(self, loglik.value, col[:L].copy(), best, best_p, _anc_info(ci))
 
     def alignment_all(self):
         """Rows of every node: leaves 0..n-1, then the internal nodes (ancestors) in alignment order."""

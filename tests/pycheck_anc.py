@@ -1,0 +1,318 @@
+"""A second, independent reading of the ancestral reconstruction (include/pagan_host.h, "ancestral states by marginal
+likelihood") in plain Python.  It takes the transition matrices P(t) and the stationary frequencies pi from host.anc_pmatrix
+and nothing else from the library; the leaf encoding is restated here from the header's text.
+
+Two readings, both in `decimal` at 50 digits (a double converts to a Decimal exactly):
+  by_definition   for S = 4 and a handful of leaves: every assignment of states to the internal nodes is enumerated; the sum of
+                  the path products is the column's likelihood, the sums restricted to one node's state are its marginals.
+  pruning         Felsenstein pruning up the tree and the outside pass down, for any number of leaves and states.
+Both keep the header's rule for missing data: a child none of whose leaves holds data contributes the exact factor 1 (not the
+row sum of P, which is 1 only up to rounding), and a column without any data has likelihood 1.
+
+The shapes the CPU and the GPU tests share are made here (case()), with their readings cached, so that a reading is computed
+once in a test run."""
+import functools
+from decimal import Decimal, getcontext
+
+import numpy as np
+
+from pagan2_msa_amd import host
+
+getcontext().prec = 50
+D0, D1 = Decimal(0), Decimal(1)
+
+DNA_SETS = {"A": (0,), "C": (1,), "G": (2,), "T": (3,), "R": (0, 2), "Y": (1, 3), "M": (0, 1), "K": (2, 3), "W": (0, 3), "S": (1, 2),
+            "B": (1, 2, 3), "D": (0, 2, 3), "H": (0, 1, 3), "V": (0, 1, 2), "N": (0, 1, 2, 3)}
+PROTEIN = "ARNDCQEGHILKMFPSTWYV"
+CODONS = [a + b + c for a in "ACGT" for b in "ACGT" for c in "ACGT" if a + b + c not in ("TAA", "TAG", "TGA")]
+STATES = {1: 4, 2: 20, 3: 61}
+LETTERS = {1: "ACGT", 2: PROTEIN}
+
+
+def leaf_sets(row, data_type):
+    """Per column the tuple of states the leaf's character stands for, or None for missing data."""
+    row = row.upper()
+    if data_type == 1:
+        return [DNA_SETS.get("T" if c == "U" else c) for c in row]
+    if data_type == 2:
+        return [(PROTEIN.index(c),) if c in PROTEIN else None for c in row]
+    assert len(row) % 3 == 0
+    trip = [row[i:i + 3].replace("U", "T") for i in range(0, len(row), 3)]
+    return [(CODONS.index(t),) if t in CODONS else None for t in trip]
+
+
+def state_text(state, data_type):
+    return CODONS[state] if data_type == 3 else LETTERS[data_type][state]
+
+
+def height(left, right):
+    """The nodes on the longest path from the root to a leaf, both ends counted."""
+    n = len(left) + 1
+    h = [1] * (2 * n - 1)
+    for k in range(n - 1):
+        h[n + k] = 1 + max(h[left[k]], h[right[k]])
+    return h[2 * n - 2]
+
+
+def tolerance(left, right, S):
+    """8 h (S + 3) 2^-53: every sum is over non-negative terms, so the relative error of a column's likelihood is at most the
+    number of roundings on its deepest chain times 2^-53."""
+    return 8 * height(left, right) * (S + 3) * 2.0 ** -53
+
+
+def _model(branch, data_type, base_freq):
+    """({length: P as an object array of Decimals}, pi as Decimals)."""
+    mats, pi = {}, None
+    for t in set(float(b) for b in branch[:-1]):
+        P, p = host.anc_pmatrix(data_type, t, base_freq)
+        mats[t] = np.array([[Decimal(float(x)) for x in r] for r in P], dtype=object)
+        pi = [Decimal(float(x)) for x in p]
+    return mats, pi
+
+
+def _has_data(left, right, sets):
+    n, L = len(sets), len(sets[0])
+    has = np.zeros((2 * n - 1, L), np.uint8)
+    for k in range(n):
+        has[k] = [s is not None for s in sets[k]]
+    for k in range(n - 1):
+        has[n + k] = has[left[k]] | has[right[k]]
+    return has
+
+
+def _normalise(q):
+    """q over its sum in state order; zeros where the sum is zero."""
+    total = D0
+    for x in q:
+        total += x
+    return [x / total if total > 0 else D0 for x in q]
+
+
+def by_definition(left, right, branch, rows, base_freq):
+    """DNA only.  {"lik": [L] Decimal, "post": [n - 1][L][4] Decimal, "has_data": uint8 [2 n - 1, L]}."""
+    n, S = len(rows), 4
+    mats, pi = _model(branch, 1, base_freq)
+    sets = [leaf_sets(r, 1) for r in rows]
+    L = len(sets[0])
+    has = _has_data(left, right, sets)
+    parent = {}
+    for k in range(n - 1):
+        parent[left[k]] = parent[right[k]] = n + k
+    root = 2 * n - 2
+
+    def total_over(col, nodes, pinned=None):
+        """The sum over all assignments to `nodes` (internal ids; a node not listed and everything below it count 1) of the path
+        products; pinned = (node, state) keeps one of them fixed."""
+        nodes = sorted(nodes)
+        if root not in nodes:
+            return D1
+        out = D0
+        for code in range(S ** len(nodes)):
+            st, c = {}, code
+            for v in nodes:
+                st[v], c = c % S, c // S
+            if pinned and st[pinned[0]] != pinned[1]:
+                continue
+            p = pi[st[root]]
+            for v in nodes:
+                for ch in (left[v - n], right[v - n]):
+                    P = mats[float(branch[ch])]
+                    if ch < n:
+                        if sets[ch][col] is not None:
+                            f = D0
+                            for t in sets[ch][col]:
+                                f += P[st[v]][t]
+                            p *= f
+                    elif ch in st:
+                        p *= P[st[v]][st[ch]]
+            out += p
+        return out
+
+    lik, post = [], [[None] * L for _ in range(n - 1)]
+    for col in range(L):
+        with_data = [n + k for k in range(n - 1) if has[n + k, col]]
+        lik.append(total_over(col, with_data))
+        for k in range(n - 1):
+            v, nodes = n + k, set(with_data)
+            while True:
+                nodes.add(v)
+                if v == root:
+                    break
+                v = parent[v]
+            post[k][col] = _normalise([total_over(col, nodes, (n + k, s)) for s in range(S)])
+    return {"lik": lik, "post": post, "has_data": has}
+
+
+def pruning(left, right, branch, rows, data_type, base_freq=None, down=True):
+    """Any tree, any data type.  The same dict as by_definition (post is None with down=False)."""
+    n, S = len(rows), STATES[data_type]
+    mats, pi = _model(branch, data_type, base_freq)
+    sets = [leaf_sets(r, data_type) for r in rows]
+    L = len(sets[0])
+    has = _has_data(left, right, sets)
+
+    def leaf_vector(k):
+        v = np.full((S, L), D0, dtype=object)
+        for col, s in enumerate(sets[k]):
+            for t in (s if s is not None else range(S)):
+                v[t, col] = D1
+        return v
+
+    part = {k: leaf_vector(k) for k in range(n)}
+
+    def message(child):
+        """[S, L]: sum_t P[s][t] L_child[t], 1 in the columns where the child has no data."""
+        m = mats[float(branch[child])].dot(part[child])
+        for col in range(L):
+            if not has[child, col]:
+                m[:, col] = D1
+        return m
+
+    for k in range(n - 1):
+        part[n + k] = message(left[k]) * message(right[k])
+    root = 2 * n - 2
+    lik = []
+    for col in range(L):
+        total = D0
+        for s in range(S):
+            total += pi[s] * part[root][s, col]
+        lik.append(total if has[root, col] else D1)
+    if not down:
+        return {"lik": lik, "post": None, "has_data": has}
+    outs = {root: np.array([[pi[s]] * L for s in range(S)], dtype=object)}
+    post = [None] * (n - 1)
+    for k in range(n - 2, -1, -1):
+        v = n + k
+        q = part[v] * outs[v]
+        post[k] = [_normalise(list(q[:, col])) for col in range(L)]
+        for c, b in ((left[k], right[k]), (right[k], left[k])):
+            if c >= n:
+                W = outs[v] * message(b)
+                outs[c] = mats[float(branch[c])].T.dot(W)
+    return {"lik": lik, "post": post, "has_data": has}
+
+
+def best_of(post_col):
+    """(state, posterior): the first maximum in state order."""
+    s = 0
+    for t in range(1, len(post_col)):
+        if post_col[t] > post_col[s]:
+            s = t
+    return s, post_col[s]
+
+
+def decided(post_col, tol):
+    """The largest and the second-largest posterior differ by more than 4 tol: `best` is compared in this column."""
+    top = sorted(post_col, reverse=True)
+    return top[0] - top[1] > Decimal(4 * tol)
+
+
+# ---- trees and rows ---------------------------------------------------------------------------------------------------
+
+def random_tree(n, rng, lo=0.02, hi=0.6):
+    """(left, right, branch): a random rooted binary tree in the walk's ids, unequal branch lengths."""
+    live, left, right = list(range(n)), [], []
+    for k in range(n - 1):
+        a, b = sorted(rng.choice(len(live), 2, replace=False))
+        x, y = live[a], live[b]
+        live = [v for v in live if v not in (x, y)] + [n + k]
+        left.append(x)
+        right.append(y)
+    branch = [float(t) for t in rng.uniform(lo, hi, 2 * n - 1)]
+    branch[-1] = 0.0
+    return left, right, branch
+
+
+def caterpillar(n, t):
+    """((((0, 1), 2), 3), ...): internal node n + k joins n + k - 1 and leaf k + 1."""
+    left = [0] + [n + k - 1 for k in range(1, n - 1)]
+    right = [k + 1 for k in range(n - 1)]
+    return left, right, [t] * (2 * n - 2) + [0.0]
+
+
+def balanced4(t):
+    return [0, 2, 4], [1, 3, 5], list(t) + [0.0]
+
+
+def random_rows(n, L, data_type, seed, share=0.15):
+    """n rows of L columns: core letters, and `share` characters that are gaps, ambiguity codes or missing data.  Column 1
+    (where there is one) is all gaps and column 2 holds a single letter."""
+    rng = np.random.default_rng(seed)
+    if data_type == 3:
+        core, other = CODONS, ["---", "NNN", "TAA", "A-C", "AC-", "TGA"]
+    elif data_type == 2:
+        core, other = list(PROTEIN), list("-X.BZU")
+    else:
+        core, other = list("ACGT"), list("--.?RYMKWSBDHVNu")
+    rows = []
+    for r in range(n):
+        cells = [other[rng.integers(len(other))] if rng.random() < share else core[rng.integers(len(core))] for _ in range(L)]
+        rows.append(cells)
+    for r in range(n):                                   # a tenth of the cells in lower case: a character is upper-cased first
+        rows[r] = [c.lower() if rng.random() < 0.1 else c for c in rows[r]]
+    gap = "---" if data_type == 3 else "-"
+    if L > 1:
+        for r in range(n):
+            rows[r][1] = gap
+    if L > 2:
+        for r in range(n):
+            rows[r][2] = gap
+        rows[n // 2][2] = core[1]
+    return ["".join(c) for c in rows]
+
+
+BASE_FREQ = (0.1, 0.2, 0.3, 0.4)
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """A named shape the CPU and the GPU tests share: dict(left, right, branch, rows, data_type, base_freq, reading)."""
+    kind, _, arg = name.partition(":")
+    bf = BASE_FREQ
+    if kind == "edge":                                   # n = 5 against the reading by definition
+        L = int(arg)
+        left, right, branch = random_tree(5, np.random.default_rng(500 + L))
+        rows, t = random_rows(5, L, 1, 600 + L), 1
+        reading = by_definition(left, right, branch, rows, bf)
+    elif kind == "zero":                                 # zero-length branches (identity matrices), at most one under a node
+        left, right, branch = balanced4([0.0, 0.3, 0.11, 0.0, 0.0, 0.27])
+        rows, t = random_rows(4, 70, 1, 41), 1
+        reading = pruning(left, right, branch, rows, 1, bf)
+    elif kind == "impossible":                           # two leaves at length 0 under one parent with different letters
+        left, right, branch = balanced4([0.0, 0.0, 0.1, 0.2, 0.3, 0.4])
+        rows, t = ["ACA", "AGC", "ATT", "AAG"], 1
+        reading = pruning(left, right, branch, rows, 1, bf)
+    elif kind == "long":
+        left, right, branch = balanced4([0.05, 50.0, 0.11, 0.07, 0.21, 0.13])
+        rows, t = random_rows(4, 70, 1, 43), 1
+        reading = pruning(left, right, branch, rows, 1, bf)
+    elif kind == "caterpillar":
+        left, right, branch = caterpillar(600, 0.2)
+        rows, t = random_rows(600, 70, 1, 44, share=0.1), 1
+        reading = pruning(left, right, branch, rows, 1, bf, down=False)
+    elif kind == "chunks":
+        left, right, branch = random_tree(6, np.random.default_rng(45))
+        rows, t, reading = random_rows(6, 200, 1, 46), 1, None
+    elif kind == "protein":
+        left, right, branch = random_tree(6, np.random.default_rng(47))
+        rows, t, bf = random_rows(6, 65, 2, 48), 2, None
+        reading = pruning(left, right, branch, rows, 2)
+    elif kind == "codon":
+        left, right, branch = random_tree(4, np.random.default_rng(49))
+        rows, t, bf = random_rows(4, 65, 3, 50), 3, None
+        reading = pruning(left, right, branch, rows, 3)
+    else:
+        raise KeyError(name)
+    return {"left": left, "right": right, "branch": branch, "rows": rows, "data_type": t, "base_freq": bf, "reading": reading}
+
+
+EDGE_COLUMNS = (1, 63, 64, 65, 130)
+POSTERIOR_CASES = ["edge:%d" % L for L in EDGE_COLUMNS] + ["zero", "long", "protein", "codon"]
+
+
+def undecided_share(c):
+    """The share of (node, column) pairs whose `best` the tie condition leaves out."""
+    tol = tolerance(c["left"], c["right"], STATES[c["data_type"]])
+    post = c["reading"]["post"]
+    cells = [decided(col, tol) for node in post for col in node]
+    return 1.0 - sum(cells) / len(cells)
