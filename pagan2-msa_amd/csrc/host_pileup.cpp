@@ -24,6 +24,7 @@
 #include "../../include/pagan_host.h"
 #include "host_anchors.h"
 #include "host_graph.h"
+#include "host_job.h"
 #include "host_model.h"
 
 using namespace pagan;
@@ -35,14 +36,9 @@ struct Step {
     bool accepted = false;
     float overlap = -1, identity = -1;
     int aligned = 0, matched = 0, read_length = 0;
-    pagan_result res;
-    bool has_res = false;
+    NodeJob job;                             // job.res is held once the step's alignment has run
     std::shared_ptr<SeqGraph> left;          // the root the read was aligned against
     std::shared_ptr<SeqGraph> node;          // the temporary node's graph (the new root if accepted)
-    std::vector<int32_t> upper, lower;
-    pagan_graph gl, gr;
-    pagan_band pb;
-    bool banded = false;
 };
 
 } // namespace
@@ -62,7 +58,6 @@ struct pagan_pileup {
     pagan_batch_fn backend = nullptr;
     void *backend_user = nullptr;
     std::vector<std::string> rows;
-    ~pagan_pileup() { for (Step &s : steps) if (s.has_res) pagan_result_free(&s.res); }
 };
 
 extern "C" {
@@ -132,30 +127,34 @@ int pagan_pileup_align(pagan_pileup *p) {
         st.read = i;
         st.left = p->root;
         SeqGraph &gl = *p->root, &gr = *p->leaf[i];
-        st.gl = gl.view(); st.gr = gr.view();
+        NodeJob &j = st.job;
+        j.gl = gl.view(); j.gr = gr.view();
         if (p->opts.use_anchors) {
             AnchorSettings as;
             as.offset = p->opts.anchors_offset; as.prefix_hit_length = p->opts.prefix_hit_length; as.hit_trim = p->opts.hit_trim;
             const std::string &alpha = p->mf.ancestral_alphabet;
             define_tunnel(sequence_string(gl, false, alpha), sequence_string(gr, false, alpha), sequence_string(gl, true, alpha),
-                          sequence_string(gr, true, alpha), as, &st.upper, &st.lower);
-            st.pb.n = (int32_t)st.upper.size(); st.pb.upper = st.upper.data(); st.pb.lower = st.lower.data();
-            st.banded = true;
+                          sequence_string(gr, true, alpha), as, &j.upper, &j.lower);
+            j.set_band();
         }
-        pagan_job jb;
-        jb.left = &st.gl; jb.right = &st.gr; jb.model = &p->pm; jb.band = st.banded ? &st.pb : nullptr;
-        int rc = p->backend ? p->backend(1, &jb, &po, &st.res, p->backend_user) : pagan_dp_align_batch(1, &jb, &po, &st.res);
-        if (rc == PAGAN_OK && st.banded && st.res.status == PAGAN_DP_UNREACHABLE) {       // viterbi_alignment.cpp:298-317
-            pagan_result_free(&st.res);
-            st.banded = false; jb.band = nullptr;
-            rc = p->backend ? p->backend(1, &jb, &po, &st.res, p->backend_user) : pagan_dp_align_batch(1, &jb, &po, &st.res);
-        }
+        // after an error return nothing in raw is valid (the library released it): adopted after PAGAN_OK only
+        pagan_result raw;
+        pagan_job jb = j.job(&p->pm);
+        int rc = call_aligner(p->backend, p->backend_user, 1, &jb, &po, &raw);
         if (rc != PAGAN_OK) return rc;
-        st.has_res = true;
-        if (st.res.status != PAGAN_DP_REACHED) continue;                                  // nothing to score: the read is dropped
+        j.res.adopt(raw);
+        if (j.banded && raw.status == PAGAN_DP_UNREACHABLE) {                             // viterbi_alignment.cpp:298-317
+            j.res.reset();
+            j.banded = false; jb = j.job(&p->pm);
+            rc = call_aligner(p->backend, p->backend_user, 1, &jb, &po, &raw);
+            if (rc != PAGAN_OK) return rc;
+            j.res.adopt(raw);
+        }
+        const pagan_result &res = j.res.get();
+        if (res.status != PAGAN_DP_REACHED) continue;                                     // nothing to score: the read is dropped
         // make_parent marks the root's edges the path used (backtrack_new_path's side effect).  The reference never clears
         // Edge::used, so the marks of a rejected attempt stay on the root and count as "used" in later attempts: kept.
-        st.node = std::make_shared<SeqGraph>(make_parent(gl, gr, st.res, lbl, rbl, p->mf.parsimony.data(), p->mf.S, p->mf.char_as, bs));
+        st.node = std::make_shared<SeqGraph>(make_parent(gl, gr, res, lbl, rbl, p->mf.parsimony.data(), p->mf.S, p->mf.char_as, bs));
         // read_alignment_scores (reads_aligner.cpp:3405-3465), columns 1 .. sites-1: the stop column counts as a column
         // both have (has_site_at_alignment_column is true for a node asked about itself, node.h:1107-1113), with state -1
         const SeqGraph &g = *st.node;
@@ -221,21 +220,21 @@ int pagan_pileup_step_info(const pagan_pileup *p, int32_t k, pagan_pileup_step *
     std::memset(o, 0, sizeof(*o));
     o->read = s.read; o->accepted = s.accepted ? 1 : 0; o->overlap = s.overlap; o->identity = s.identity;
     o->aligned = s.aligned; o->matched = s.matched; o->read_length = s.read_length;
-    o->left_sites = s.gl.n_sites; o->right_sites = s.gr.n_sites;
-    if (s.has_res) { o->status = s.res.status; o->score = s.res.score; o->cells = s.res.cells; o->n_cols = s.res.n_cols; }
+    o->left_sites = s.job.gl.n_sites; o->right_sites = s.job.gr.n_sites;
+    const pagan_result &res = s.job.res.get();
+    if (s.job.res.held()) { o->status = res.status; o->score = res.score; o->cells = res.cells; o->n_cols = res.n_cols; }
     return PAGAN_OK;
 }
 
 int pagan_pileup_step_job(const pagan_pileup *p, int32_t k, pagan_job *o) {
     if (!p || !o || k < 0 || k >= (int)p->steps.size()) return PAGAN_E_ARG;
-    const Step &s = p->steps[k];
-    o->left = &s.gl; o->right = &s.gr; o->model = &p->pm; o->band = s.banded ? &s.pb : nullptr;
+    *o = p->steps[k].job.job(&p->pm);
     return PAGAN_OK;
 }
 
 int pagan_pileup_step_result(const pagan_pileup *p, int32_t k, pagan_result *o) {
-    if (!p || !o || k < 0 || k >= (int)p->steps.size() || !p->steps[k].has_res) return PAGAN_E_ARG;
-    *o = p->steps[k].res;
+    if (!p || !o || k < 0 || k >= (int)p->steps.size() || !p->steps[k].job.res.held()) return PAGAN_E_ARG;
+    *o = p->steps[k].job.res.get();
     return PAGAN_OK;
 }
 

@@ -1,4 +1,6 @@
-// host_tree.cpp -- guide-tree walk and the C ABI of include/pagan_host.h.
+// host_tree.cpp -- the guide-tree walk of include/pagan_host.h: the tree, the nodes' jobs, their forward/backward pass, the two
+// schedulers, results across processes, the per-node accessors.  (host_rows.cpp: what reads the finished alignment;
+// host_capi.cpp: the entries that take no pagan_msa; host_msa.h: the state they share.)
 //
 // Counterpart of Node::start_openmp_alignment / align_sequences_this_node
 // (src/main/node.cpp:52-285): nodes whose two children carry a sequence graph are "ready"
@@ -9,51 +11,16 @@
 // between devices (parents are built on the host), hence no collective.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <cmath>
 #include <cstdio>
-#include <cstring>
-#include <map>
-#include <memory>
 #include <sched.h>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
 
-#include "../../include/pagan_host.h"
-#include "host_anchors.h"
-#include "host_graph.h"
-#include "host_model.h"
+#include "host_msa.h"
 
 using namespace pagan;
 
-struct pagan_hgraph { SeqGraph g; };
-
 namespace {
-
-double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-template <class F> void parallel_for(int n, int threads, F f) {
-    if (threads <= 1 || n <= 1) { for (int i = 0; i < n; ++i) f(i); return; }
-    std::atomic<int> next(0);
-    std::vector<std::thread> pool;
-    const int t = std::min(threads, n);
-    for (int k = 0; k < t; ++k) pool.emplace_back([&] { for (int i; (i = next.fetch_add(1)) < n;) f(i); });
-    for (auto &th : pool) th.join();
-}
-
-struct TreeNode {
-    int left = -1, right = -1, parent = -1;
-    double dist = 0;             // distance to parent after correction
-    std::string name;
-    int leaf_index = -1;         // input sequence index for leaves
-};
 
 // Node::set_distance_to_parent, src/main/node.h:122-159 (defaults: no --scale-branches,
 // no --real-branches, --truncate-branches 0.2 always active).
@@ -110,81 +77,6 @@ struct Newick {
     }
 };
 
-struct NodeWork {                // everything one internal node's alignment consumed / produced
-    int node = -1, level = 0;
-    std::shared_ptr<EvolModel> model;
-    std::vector<int32_t> upper, lower;
-    std::vector<TunnelBlock> blocks;     // empty tunnel blocks, ascending by size (anchor_mode 1; --force-gap takes the last)
-    int n_hits = 0, n_forced = 0;
-    int imp_l = 0, imp_r = 0;    // sites of the children of a node whose result was imported (pagan_msa_import_result)
-    pagan_graph gl, gr;
-    pagan_model pm;
-    pagan_band pb;
-    bool banded = false;
-    pagan_result res;
-    bool has_res = false;        // res is valid (aligned here, or imported from the rank that aligned it)
-    bool has_job = false;        // gl/gr/pm/pb are valid: this process prepared and aligned the node
-    int  device = -1;            // device the alignment ran on (-1: another rank)
-    bool parent_pending = false; // imported: the result is stored, the parent graph is built when somebody needs it (ensure_graph)
-    // the forward/backward pass of the node (full_probability / sample_path), on the band the node finally used
-    bool has_fb = false;
-    double log_fwd = 0, log_bwd = 0, fb_sweep_ms = 0, fb_post_ms = 0;
-    std::vector<double> support;         // [res.n_cols] posterior of every column's own cell, -1 at skip columns
-    bool has_marg = false;               // full_probability == 2: the site marginals (pagan_fb_site_marginals' eight arrays)
-    std::vector<double> mg_d[6];         // pX, pM_left, best_p_left [Lx]; pY, pM_right, best_p_right [Ly]
-    std::vector<int32_t> mg_i[2];        // best_j [Lx], best_i [Ly]
-    // posterior decoding (pagan_msa_set_decoder): the node's result is the replay of its maximum expected accuracy path
-    bool has_dec = false;
-    double dec_objective = 0, dec_steps = 0, dec_ms = 0;   // dec_ms: the sub-batch's fill + trace, booked at its first node
-    // expected counts (pagan_msa_set_counts): pagan_fb_expected_counts' trans[12] and, for DNA, emit[S * S]
-    bool has_counts = false;
-    double trans[12] = {0};
-    std::vector<double> emit;
-};
-
-} // namespace
-
-struct pagan_msa {
-    pagan_msa_opts opts;
-    std::vector<std::string> names, seqs;
-    std::vector<TreeNode> tree;          // as parsed
-    int root = -1;
-    std::vector<int> id_of_tree;         // tree index -> public node id
-    std::vector<int> tree_of_id;         // public id -> tree index
-    std::vector<std::unique_ptr<pagan_hgraph>> graph;    // by public node id
-    std::vector<NodeWork> work;          // by internal order k (public id = n_leaves + k)
-    ModelFactory mf;
-    pagan_msa_timing tm;
-    bool aligned = false;
-    int n_leaves = 0;
-    std::vector<std::string> rows;
-    // walk state (pagan_msa_ready / align_nodes / import_result)
-    std::vector<char> done;              // by public node id
-    int remaining = 0, rounds = 0;
-    std::map<double, std::shared_ptr<EvolModel>> model_cache;    // one table per distinct distance
-    std::mutex mu;                       // model cache, timing sums
-    std::vector<int32_t> state_table;    // parent state of a matched column: parsimony table, or with --mostcommon the
-                                         // most-common table where it is defined (basic_alignment.cpp:146-149)
-    pagan_batch_fn backend = nullptr;    // test seam (pagan_msa_set_batch_backend); null = pagan_dp_align_batch
-    void *backend_user = nullptr;
-    int sample_on_device = 0;            // pagan_msa_set_sampler: sample_path's paths come from pg_fb_sample (1) or the host's walk (0)
-    int decode_on = 0;                   // pagan_msa_set_decoder: the nodes' results are their posteriors' maximum expected accuracy paths
-    double decode_gap = 0.5;             // ... with this gap weight
-    bool indel_set = false;              // pagan_msa_set_indel_model replaced a rate of the data type's defaults
-    int counts_on = 0;                   // pagan_msa_set_counts: every forward/backward pass also leaves the node's expected counts
-    std::atomic<int> parents_built{0};   // parent graphs this process has built (pagan_msa_parents_built)
-    std::atomic<int> lazy_err{0};        // first error of a deferred parent build (an imported result that does not fit the child graphs)
-    bool rows_built = false;             // m->rows are valid (pagan_msa_finish builds them at once, pagan_msa_finish_lazy on first use)
-    std::mutex lazy_mu;                  // deferred builds started from the accessors
-    // pagan_msa_ancestral's result: row k is internal node n + k's state of largest posterior per column, and that posterior
-    bool anc_done = false;
-    std::vector<uint8_t> anc_best;
-    std::vector<float> anc_best_p;
-    ~pagan_msa() { for (auto &w : work) if (w.has_res) pagan_result_free(&w.res); }
-};
-
-namespace {
-
 int device_budget(const pagan_msa *m, int dev, int64_t *bytes) {
     const pagan_msa_opts &o = m->opts;
     if (o.device_mem_budget > 0) { *bytes = o.device_mem_budget; return PAGAN_OK; }
@@ -211,25 +103,21 @@ int align_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, double *f
         int64_t used = 0;
         while (at < ks.size()) {
             NodeWork &w = m->work[ks[at]];
-            const int64_t need = pagan_dp_predict_bytes(w.gl.n_sites, w.gr.n_sites, w.banded ? &w.pb : nullptr);
+            const int64_t need = pagan_dp_predict_bytes(w.job.gl.n_sites, w.job.gr.n_sites, w.job.band());
             if (need < 0) return (int)need;
             if (need > budget) return PAGAN_E_MEMCAP;
             if (!jobs.empty() && used + need > budget) break;
             used += need;
-            pagan_job jb; jb.left = &w.gl; jb.right = &w.gr; jb.model = &w.pm; jb.band = w.banded ? &w.pb : nullptr;
-            jobs.push_back(jb); which.push_back(ks[at]); ++at;
+            jobs.push_back(w.job.job(&w.pm)); which.push_back(ks[at]); ++at;
         }
         std::vector<pagan_result> res(jobs.size());
-        rc = m->backend ? m->backend((int32_t)jobs.size(), jobs.data(), &po, res.data(), m->backend_user)
-                        : pagan_dp_align_batch((int32_t)jobs.size(), jobs.data(), &po, res.data());
-        if (rc != PAGAN_OK) return rc;            // nothing in res[] is valid then (the library released it)
-        for (size_t k = 0; k < jobs.size(); ++k) { m->work[which[k]].res = res[k]; m->work[which[k]].has_res = true; }
+        rc = call_aligner(m->backend, m->backend_user, (int32_t)jobs.size(), jobs.data(), &po, res.data());
+        if (rc != PAGAN_OK) return rc;            // nothing in res[] is valid then (the library released it): adopted after PAGAN_OK only
+        for (size_t k = 0; k < jobs.size(); ++k) m->work[which[k]].job.res.adopt(res[k]);
         if (!res.empty()) { *fill_ms += res[0].fill_ms; *trace_ms += res[0].trace_ms; }
     }
     return PAGAN_OK;
 }
-
-int host_threads_of(const pagan_msa *m);
 
 // The compute_full_score pass of the nodes `ks` on device `dev` (viterbi_alignment.cpp:329-371), behind their Viterbi batch:
 // pagan_fb_run_batch in sub-batches that fit the memory budget by pagan_fb_predict_bytes, the model's probability-space view
@@ -278,16 +166,16 @@ struct FbSub {
 int fb_cut(const pagan_msa *m, const FbMode &md, const std::vector<int> &ks, size_t *at, int64_t budget, std::vector<int> *which) {
     int64_t used = 0;
     for (; *at < ks.size(); ++*at) {
-        const NodeWork &w = m->work[ks[*at]];
-        const pagan_band *band = w.banded ? &w.pb : nullptr;
-        int64_t need = pagan_fb_predict_bytes(w.gl.n_sites, w.gr.n_sites, band);
+        const NodeJob &j = m->work[ks[*at]].job;
+        const pagan_band *band = j.band();
+        int64_t need = pagan_fb_predict_bytes(j.gl.n_sites, j.gr.n_sites, band);
         if (need < 0) return (int)need;
         if (md.decode) {
-            const int64_t more = pagan_fb_decode_predict_bytes(w.gl.n_sites, w.gr.n_sites, band);
+            const int64_t more = pagan_fb_decode_predict_bytes(j.gl.n_sites, j.gr.n_sites, band);
             if (more < 0) return (int)more;
             need += more;
-        } else if (md.device_sampler) need += pagan_fb_sample_predict_bytes(w.gl.n_sites, w.gr.n_sites, 1, 0);    // (the path's trace)
-        if (md.counts) need += pagan_fb_counts_predict_bytes(w.gl.n_sites, w.gr.n_sites, m->mf.S);
+        } else if (md.device_sampler) need += pagan_fb_sample_predict_bytes(j.gl.n_sites, j.gr.n_sites, 1, 0);    // (the path's trace)
+        if (md.counts) need += pagan_fb_counts_predict_bytes(j.gl.n_sites, j.gr.n_sites, m->mf.S);
         if (need > budget) return PAGAN_E_MEMCAP;
         if (!which->empty() && used + need > budget) break;
         used += need;
@@ -307,7 +195,7 @@ int fb_sweeps(pagan_msa *m, FbSub &sb, int dev) {
     for (int q = 0; q < n; ++q) {
         NodeWork &w = m->work[sb.which[q]];
         mp[q] = w.model->prob_view();
-        gl[q] = &w.gl; gr[q] = &w.gr; mpp[q] = &mp[q]; bd[q] = w.banded ? &w.pb : nullptr;
+        gl[q] = &w.job.gl; gr[q] = &w.job.gr; mpp[q] = &mp[q]; bd[q] = w.job.band();
     }
     return pagan_fb_run_batch(n, gl.data(), gr.data(), mpp.data(), bd.data(), &po, sb.fbs.data());
 }
@@ -340,27 +228,29 @@ int fb_node(pagan_msa *m, const FbMode &md, FbSub &sb, int q) {
     w.fb_sweep_ms = ms[0] + ms[1]; w.fb_post_ms = 0;
     w.has_marg = false; w.support.clear(); w.has_dec = false;
     if (r == PAGAN_OK && md.path) {
-        if (w.has_res) { pagan_result_free(&w.res); w.has_res = false; }
-        if (!(w.log_fwd > -HUGE_VAL) && w.banded) { sb.again[q] = 1; return PAGAN_OK; }
+        w.job.res.reset();                                                   // (a banded first attempt's, when this is the retry)
+        if (!(w.log_fwd > -HUGE_VAL) && w.job.banded) { sb.again[q] = 1; return PAGAN_OK; }
+        pagan_result raw;
         if (sb.dec[q]) {
             int32_t steps = 0;
             r = pagan_fb_decoded_summary(sb.dec[q], nullptr, &w.dec_objective, &steps, nullptr, nullptr);
-            if (r == PAGAN_OK) r = pagan_fb_decoded_result(sb.dec[q], &w.res);
+            if (r == PAGAN_OK) r = pagan_fb_decoded_result(sb.dec[q], &raw);
             w.dec_steps = steps; w.dec_ms = q == 0 ? sb.dec_ms : 0.0;
             w.has_dec = r == PAGAN_OK;
         } else if (sb.smp[q]) {
-            r = pagan_fb_samples_result(sb.smp[q], 0, &w.res);
+            r = pagan_fb_samples_result(sb.smp[q], 0, &raw);
         } else {
-            const int n_u = w.gl.n_sites + w.gr.n_sites - 1;                 // Lx + Ly + 1
+            const int n_u = w.job.gl.n_sites + w.job.gr.n_sites - 1;         // Lx + Ly + 1
             std::vector<double> u((size_t)n_u);
             r = pagan_sample_uniforms(m->opts.sample_seed, w.node, n_u, u.data());
-            if (r == PAGAN_OK) r = pagan_fb_sample_path(sb.fbs[q], u.data(), n_u, &w.res, nullptr, nullptr);
+            if (r == PAGAN_OK) r = pagan_fb_sample_path(sb.fbs[q], u.data(), n_u, &raw, nullptr, nullptr);
         }
-        w.has_res = r == PAGAN_OK;
+        if (r == PAGAN_OK) w.job.res.adopt(raw);
     }
-    if (r == PAGAN_OK && w.res.status == PAGAN_DP_REACHED) {
-        w.support.assign((size_t)w.res.n_cols, 0.0);
-        r = pagan_fb_path_support(sb.fbs[q], w.res.cols, w.res.n_cols, w.support.data());
+    const pagan_result &res = w.job.res.get();
+    if (r == PAGAN_OK && res.status == PAGAN_DP_REACHED) {
+        w.support.assign((size_t)res.n_cols, 0.0);
+        r = pagan_fb_path_support(sb.fbs[q], res.cols, res.n_cols, w.support.data());
     }
     return r;
 }
@@ -375,7 +265,7 @@ int fb_readers(pagan_msa *m, const FbMode &md, const FbSub &sb, int rc, std::vec
         std::vector<int32_t *> pi[2];
         for (int q = 0; q < n; ++q) {
             NodeWork &w = m->work[sb.which[q]];
-            const size_t Lx = (size_t)w.gl.n_sites - 1, Ly = (size_t)w.gr.n_sites - 1;
+            const size_t Lx = (size_t)w.job.gl.n_sites - 1, Ly = (size_t)w.job.gr.n_sites - 1;
             for (int a = 0; a < 6; ++a) { w.mg_d[a].assign(a < 3 ? Lx : Ly, 0.0); pd[a].push_back(sb.again[q] ? nullptr : w.mg_d[a].data()); }
             for (int a = 0; a < 2; ++a) { w.mg_i[a].assign(a < 1 ? Lx : Ly, 0); pi[a].push_back(sb.again[q] ? nullptr : w.mg_i[a].data()); }
             w.has_marg = !sb.again[q];
@@ -435,118 +325,9 @@ int fb_on_device(pagan_msa *m, const std::vector<int> &ks, int dev, int threads,
     return rc;
 }
 
-void build_rows(pagan_msa *m) {
-    const int n = m->n_leaves;
-    const int root_id = m->id_of_tree[m->root];
-    const int width = m->graph[root_id]->g.n_sites() - 2;
-    // a node's column map: site -> column of the alignment (-1: none).  Storage that the host's threads touch first (round 5:
-    // the maps' 27 MB and the rows' 8 MB of a 32 x 100 kb walk, allocated and filled by one thread, were most of this function's time)
-    std::vector<std::unique_ptr<int32_t[]>> col(m->graph.size());
-    col[root_id].reset(new int32_t[width + 2]);
-    for (int s = 0; s < width + 2; ++s) col[root_id][s] = s - 1;
-    const int w = m->mf.type == kCodon ? 3 : 1;                 // characters per column ("---" gaps for codons)
-    m->rows.assign(m->graph.size(), std::string());
-    const std::string &anc = m->mf.type == kCodon ? m->mf.codon_names : m->mf.ancestral_alphabet;
-    // A node's columns follow from its parent's: the tree is walked by DEPTH, the nodes of one depth side by side on the
-    // host's threads (round 5: one thread walking all 2n - 1 nodes was 25 ms of a 0.7 s walk of 32 x 100 kb).
-    std::vector<std::vector<int>> by_depth;
-    {
-        std::vector<std::pair<int, int>> stack{{m->root, 0}};      // (tree index, depth)
-        while (!stack.empty()) {
-            const auto [t, depth] = stack.back();
-            stack.pop_back();
-            if ((int)by_depth.size() <= depth) by_depth.resize(depth + 1);
-            by_depth[depth].push_back(m->id_of_tree[t]);
-            const TreeNode &tn = m->tree[t];
-            if (tn.left >= 0) { stack.push_back({tn.left, depth + 1}); stack.push_back({tn.right, depth + 1}); }
-        }
-    }
-    const int threads = host_threads_of(m);
-    parallel_for((int)m->rows.size(), threads, [&](int id) { m->rows[id].assign((size_t)width * w, '-'); });
-    for (const std::vector<int> &ids : by_depth) {
-        // the upper depths hold 1, 2, 4 nodes of 10^5 sites each: a node's sites in `parts` ranges (every site writes its own
-        // column of its own row and its own entries of the children's column maps)
-        const int parts = std::max(1, std::min(threads, (2 * threads) / std::max(1, (int)ids.size())));
-        std::vector<int> kids;
-        for (int id : ids)
-            if (id >= n) {
-                const TreeNode &t = m->tree[m->tree_of_id[id]];
-                for (int kid : {m->id_of_tree[t.left], m->id_of_tree[t.right]}) {
-                    if (kid < n) continue;                     // (a leaf has no map: its parent writes the leaf's row, below)
-                    col[kid].reset(new int32_t[m->graph[kid]->g.n_sites()]);
-                    kids.push_back(kid);
-                }
-            }
-        parallel_for((int)kids.size() * parts, threads, [&](int task) {
-            const int kid = kids[task / parts], part = task % parts, ns = m->graph[kid]->g.n_sites();
-            std::fill(col[kid].get() + (long long)ns * part / parts, col[kid].get() + (long long)ns * (part + 1) / parts, -1);
-        });
-        parallel_for((int)ids.size() * parts, threads, [&](int task) {
-            const int id = ids[task / parts], part = task % parts;
-            const SeqGraph &g = m->graph[id]->g;
-            std::string &row = m->rows[id];
-            const int32_t *mine = col[id].get();
-            const int n_in = g.n_sites() - 2;                      // sites 1 .. n_in
-            const int s_first = 1 + (int)((long long)n_in * part / parts), s_last = 1 + (int)((long long)n_in * (part + 1) / parts);
-            if (id < n) {                                          // a leaf: its residues at its columns (only a tree of one leaf comes here)
-                if (!mine) return;
-                for (int s = s_first; s < s_last; ++s)
-                    for (int c = 0; c < w; ++c) row[(size_t)mine[s] * w + c] = g.symbols[(size_t)(s - 1) * w + c];
-                return;
-            }
-            const TreeNode &t = m->tree[m->tree_of_id[id]];
-            const int lid = m->id_of_tree[t.left], rid = m->id_of_tree[t.right];
-            int32_t *cl = col[lid].get(), *cr = col[rid].get();
-            // a child that is a leaf has no map of its own (half of a tree's nodes, and of the maps' pages): its residues go to
-            // its row from here, site c of the leaf at this site's column
-            const SeqGraph *gl = lid < n ? &m->graph[lid]->g : nullptr, *gr = rid < n ? &m->graph[rid]->g : nullptr;
-            std::string *rl = lid < n ? &m->rows[lid] : nullptr, *rr = rid < n ? &m->rows[rid] : nullptr;
-            for (int s = s_first; s < s_last; ++s) {
-                const int a = g.child_l[s], b = g.child_r[s];
-                if (a >= 0) {
-                    if (gl) { for (int c = 0; c < w; ++c) (*rl)[(size_t)mine[s] * w + c] = gl->symbols[(size_t)(a - 1) * w + c]; }
-                    else cl[a] = mine[s];
-                }
-                if (b >= 0) {
-                    if (gr) { for (int c = 0; c < w; ++c) (*rr)[(size_t)mine[s] * w + c] = gr->symbols[(size_t)(b - 1) * w + c]; }
-                    else cr[b] = mine[s];
-                }
-                // the ancestor's own row (get_alignment_column_at with include_internal_nodes, node.cpp:808-818): its
-                // state's character, a gap where the site is skipped or was deleted
-                const int ps = g.path_state[s];
-                if (!(ps == PAGAN_XSKIPPED || ps == PAGAN_YSKIPPED || g.site_type[s] == kNonReal) && g.state[s] >= 0)
-                    for (int c = 0; c < w; ++c) row[(size_t)mine[s] * w + c] = anc[(size_t)g.state[s] * w + c];
-            }
-        });
-        for (int id : ids) col[id].reset();
-    }
-}
-
-const ModelFactory &codon_factory() {             // the empirical model's eigen solution and 1892 x 1892 tables: made once
-    static ModelFactory mf;
-    static std::once_flag once;
-    std::call_once(once, [] { mf.init_codon(); });
-    return mf;
-}
-
 } // namespace
 
 extern "C" {
-
-// Work-queue assignment shared by the in-process multi-device walk and the one-process-per-GPU
-// bench: units sorted by cost (largest first, stable), each to the currently least-loaded worker.
-void pagan_assign_units(int32_t n, const int64_t *cost, int32_t n_workers, int32_t *owner) {
-    if (n <= 0 || n_workers <= 0) return;
-    std::vector<int> order(n);
-    for (int k = 0; k < n; ++k) order[k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-    std::vector<int64_t> load(n_workers, 0);
-    for (int k : order) {
-        int best = 0;
-        for (int d = 1; d < n_workers; ++d) if (load[d] < load[best]) best = d;
-        owner[k] = best; load[best] += cost[k];
-    }
-}
 
 void pagan_msa_default_opts(pagan_msa_opts *o) {
     std::memset(o, 0, sizeof(*o));
@@ -570,15 +351,10 @@ int pagan_msa_create(int32_t n_seqs, const char *const *names, const char *const
     }
     // per-leaf work (cleaning the residues here, the leaf graphs below) runs on a few threads: 32 x 100 kb
     // leaves are 0.2 s of the tree's 1.3 s otherwise
-    auto over_leaves = [&](auto f) {
-        const int hw = (int)std::thread::hardware_concurrency();
-        int nt = std::max(1, std::min({(int)n_seqs, hw > 0 ? hw : 1, 8}));      // allocation-heavy: oversubscribed, it is slower than serial
-        if (const char *e = std::getenv("PAGAN_HOST_THREADS")) nt = std::max(1, std::min(nt, std::atoi(e)));
-        std::atomic<int> next{0};
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nt; ++t) pool.emplace_back([&] { for (int k = next++; k < n_seqs; k = next++) f(k); });
-        for (auto &th : pool) th.join();
-    };
+    const HostSwitches sw = HostSwitches::read();
+    int nt = std::min(8, host_threads_of(m.get()));                 // allocation-heavy: oversubscribed, it is slower than serial
+    if (sw.host_threads_cap > 0) nt = std::min(nt, sw.host_threads_cap);
+    auto over_leaves = [&](auto f) { parallel_for(n_seqs, nt, f); };
     // fasta_reader.cpp:138-160: upper case, no gaps, no line ends
     over_leaves([&](int k) {
         std::string s;
@@ -692,18 +468,21 @@ int default_host_threads() {
     }();
     return cached;
 }
-int host_threads_of(const pagan_msa *m) {
+
+} // namespace
+
+int pagan::host_threads_of(const pagan_msa *m) {
     const int threads = m->opts.host_threads > 0 ? m->opts.host_threads : default_host_threads();
     return threads < 1 ? 1 : threads;
 }
+
+namespace {
 
 bool node_ready(const pagan_msa *m, int id) {
     if (m->done[id]) return false;
     const TreeNode &t = m->tree[m->tree_of_id[id]];
     return m->done[m->id_of_tree[t.left]] && m->done[m->id_of_tree[t.right]];
 }
-
-int ensure_graph(pagan_msa *m, int id);
 
 // What align_sequences_this_node does before the aligner is called (node.cpp:70-152): the model for
 // dist = d_left + d_right (serialised in the reference too: omp critical, node.cpp:415-416), the
@@ -728,8 +507,9 @@ void prepare_node(pagan_msa *m, int id, int round) {
         if (rc != PAGAN_OK) { int zero = 0; m->lazy_err.compare_exchange_strong(zero, rc); return; }
     }
     const SeqGraph &gl = m->graph[m->id_of_tree[t.left]]->g, &gr = m->graph[m->id_of_tree[t.right]]->g;
-    w.gl = gl.view(); w.gr = gr.view(); w.pm = w.model->view();
-    w.banded = false;
+    NodeJob &j = w.job;
+    j.gl = gl.view(); j.gr = gr.view(); w.pm = w.model->view();
+    j.banded = false;
     if (m->opts.use_anchors) {
         AnchorSettings as;
         as.offset = m->opts.anchors_offset; as.prefix_hit_length = m->opts.prefix_hit_length; as.hit_trim = m->opts.hit_trim;
@@ -746,14 +526,13 @@ void prepare_node(pagan_msa *m, int id, int round) {
             std::vector<Hit> hits;
             prefix_hits(str(gl, false), str(gr, false), as.prefix_hit_length, &hits);
             drop_bad_hits(&hits, (unsigned)m->opts.overlap_total, (unsigned)m->opts.overlap_partly);
-            w.upper.clear(); w.lower.clear(); w.blocks.clear();
-            hits_to_band_overlapping(hits, str(gl, true), str(gr, true), as.offset, &w.upper, &w.lower, &w.blocks);
+            j.upper.clear(); j.lower.clear(); w.blocks.clear();
+            hits_to_band_overlapping(hits, str(gl, true), str(gr, true), as.offset, &j.upper, &j.lower, &w.blocks);
             w.n_hits = (int)hits.size();
         } else {
-            w.n_hits = define_tunnel(str(gl, false), str(gr, false), str(gl, true), str(gr, true), as, &w.upper, &w.lower);
+            w.n_hits = define_tunnel(str(gl, false), str(gr, false), str(gl, true), str(gr, true), as, &j.upper, &j.lower);
         }
-        w.pb.n = (int32_t)w.upper.size(); w.pb.upper = w.upper.data(); w.pb.lower = w.lower.data();
-        w.banded = true;
+        j.set_band();
     }
     w.has_job = true;
 }
@@ -803,9 +582,10 @@ void fix_ambiguous_states(pagan_msa *m, int id) {
 std::atomic<long long> parents_on_device{0};                     // (diagnostic: pagan_parents_device_calls)
 
 // add_ancestral_sequence(va.get_simple_sequence()) (node.cpp:166): the parent graph from the path.
-int build_parent(pagan_msa *m, int id, int unit_nodes) {
+int build_parent(pagan_msa *m, int id, int unit_nodes, const HostSwitches &sw) {
     NodeWork &w = m->work[id - m->n_leaves];
-    if (!w.has_res || w.res.status != PAGAN_DP_REACHED) return PAGAN_E_INTERNAL;
+    const pagan_result &res = w.job.res.get();
+    if (!w.job.res.held() || res.status != PAGAN_DP_REACHED) return PAGAN_E_INTERNAL;
     BuildSettings bs;
     if (m->opts.keep_all_edges) bs.reads_mode();
     if (m->opts.dp_flags & PAGAN_OPT_NO_REDUCED_TERMINAL_PEN) bs.reduced_terminal = false;
@@ -819,14 +599,13 @@ int build_parent(pagan_msa *m, int id, int unit_nodes) {
     // build one level up reads its children's states from, takes the node's over (the graphs below have no device copy left).
     bool on_device = false;
     if (!m->backend && w.device >= 0) {
-        const char *e = std::getenv("PAGAN_PARENTS");
-        const bool force_host = e && std::strcmp(e, "host") == 0, force_dev = e && std::strcmp(e, "device") == 0;
+        const bool force_host = sw.parents == HostSwitches::PARENTS_HOST, force_dev = sw.parents == HostSwitches::PARENTS_DEVICE;
         // (a wide level's parents are built side by side on the host's threads, and as many uploads of leaf-sized children
         //  at once cost more than they save: measured on 32 x 100 kb, 16 nodes 17 ms on the device against 7 on 16 threads,
         //  one node 3 ms against 8-15; so the device takes the levels of at most four long nodes)
-        if (!force_host && (force_dev || (w.res.n_cols >= 20000 && unit_nodes <= 4))) {
+        if (!force_host && (force_dev || (res.n_cols >= 20000 && unit_nodes <= 4))) {
             SeqGraph g;
-            if (make_parent_device(gl, gr, w.res, (float)m->tree[t.left].dist, (float)m->tree[t.right].dist, m->state_table.data(),
+            if (make_parent_device(gl, gr, res, (float)m->tree[t.left].dist, (float)m->tree[t.right].dist, m->state_table.data(),
                                    m->mf.S, m->mf.char_as, bs, w.device, &g)) {
                 m->graph[id]->g = std::move(g);
                 on_device = true;
@@ -835,7 +614,7 @@ int build_parent(pagan_msa *m, int id, int unit_nodes) {
         }
     }
     if (!on_device)
-        m->graph[id]->g = make_parent(gl, gr, w.res, (float)m->tree[t.left].dist, (float)m->tree[t.right].dist,
+        m->graph[id]->g = make_parent(gl, gr, res, (float)m->tree[t.left].dist, (float)m->tree[t.right].dist,
                                       m->state_table.data(), m->mf.S, m->mf.char_as, bs);
     // (grandchildren's device copies are no longer needed: their parents are built)
     gl.dev.reset(); gr.dev.reset();
@@ -853,15 +632,17 @@ int build_parent(pagan_msa *m, int id, int unit_nodes) {
 // basic_alignment.cpp:61-179: skipped and later deleted columns stay as sites).
 int sites_of(const pagan_msa *m, int id) {
     if (m->graph[id]) return m->graph[id]->g.n_sites();
-    return m->work[id - m->n_leaves].res.n_cols + 2;
+    return m->work[id - m->n_leaves].job.res.get().n_cols + 2;
 }
+
+} // namespace
 
 // The graph of node `id`, built now if it is an imported node's that nobody has needed so far -- together with whatever is
 // pending below it, children first (iteratively: a caterpillar tree is as deep as it has leaves).  Rank mode (one process
 // per GPU): a rank builds the parents of the nodes it aligns and of the imported nodes BELOW the nodes it claims; the rest
 // only if it is asked for the rows (node.cpp:196-223, 273-345: a thread builds the ancestor of the node it aligned).
 // Ready nodes have disjoint subtrees, so the units of a round may call this side by side.
-int ensure_graph(pagan_msa *m, int id) {
+int pagan::ensure_graph(pagan_msa *m, int id) {
     if (m->graph[id]) return PAGAN_OK;
     std::vector<int> stack{id};
     while (!stack.empty()) {
@@ -879,8 +660,8 @@ int ensure_graph(pagan_msa *m, int id) {
         // what pagan_msa_import_result could not check without the child graphs: a column names a child site (1 .. n_sites - 2)
         // or none (-1) -- which of the two follows from its path state --, a used edge is an edge of the child
         const SeqGraph &gl = m->graph[lid]->g, &gr = m->graph[rid]->g;
-        const pagan_result &r = w.res;
-        bool good = w.has_res;
+        const pagan_result &r = w.job.res.get();
+        bool good = w.job.res.held();
         for (int k = 0; good && k < r.n_cols; ++k) {
             const pagan_col &c = r.cols[k];
             const bool hl = c.path_state == PAGAN_MATCHED || c.path_state == PAGAN_XGAPPED || c.path_state == PAGAN_XSKIPPED;
@@ -892,7 +673,7 @@ int ensure_graph(pagan_msa *m, int id) {
         for (int k = 0; good && k < r.n_right_used; ++k) if (r.right_used[k] < 0 || r.right_used[k] >= gr.n_edges()) good = false;
         if (!good) return PAGAN_E_ARG;
         const double t0 = now_s();
-        const int rc = build_parent(m, cur, 1 << 20);                          // (imported: w.device is -1, the host builder)
+        const int rc = build_parent(m, cur, 1 << 20, HostSwitches{0, HostSwitches::PARENTS_HOST, false});   // (imported: w.device is -1, the host builder)
         {
             std::lock_guard<std::mutex> g(m->mu);
             m->tm.build_s += now_s() - t0;
@@ -903,11 +684,13 @@ int ensure_graph(pagan_msa *m, int id) {
     return PAGAN_OK;
 }
 
+namespace {
+
 // One unit of the work queue: the nodes `ids` (all ready) prepared, aligned on device `dev`, their parents
 // built.  Runs on the calling thread (+ the host thread pool); several of these run side by side on
 // different devices.  "anchored alignment failed: trying again" (viterbi_alignment.cpp:298-317): a node
 // whose end corner is unreachable inside its tunnel is re-aligned over the full matrix.
-int run_unit(pagan_msa *m, const std::vector<int> &ids, int dev, int round, int threads) {
+int run_unit(pagan_msa *m, const std::vector<int> &ids, int dev, int round, int threads, const HostSwitches &sw) {
     const int n = m->n_leaves;
     double t0 = now_s();
     parallel_for((int)ids.size(), threads, [&](int r) { set_anchor_device(dev); prepare_node(m, ids[r], round); });
@@ -924,9 +707,10 @@ int run_unit(pagan_msa *m, const std::vector<int> &ids, int dev, int round, int 
         if (rc != PAGAN_OK) return rc;
         for (int id : ids) {
             NodeWork &w = m->work[id - n];
-            if (!w.banded) continue;
-            while (pagan_dp_predict_bytes(w.gl.n_sites, w.gr.n_sites, &w.pb) > budget) {
-                if (!force_gap(&w.upper, &w.lower, &w.blocks, m->opts.force_gap_threshold, m->opts.anchors_offset, m->opts.force_gap_wide != 0))
+            NodeJob &j = w.job;
+            if (!j.banded) continue;
+            while (pagan_dp_predict_bytes(j.gl.n_sites, j.gr.n_sites, &j.pb) > budget) {
+                if (!force_gap(&j.upper, &j.lower, &w.blocks, m->opts.force_gap_threshold, m->opts.anchors_offset, m->opts.force_gap_wide != 0))
                     return PAGAN_E_MEMCAP;
                 ++w.n_forced;
             }
@@ -934,7 +718,7 @@ int run_unit(pagan_msa *m, const std::vector<int> &ids, int dev, int round, int 
     }
     for (size_t r = 0; r < ids.size(); ++r) {
         NodeWork &w = m->work[ids[r] - n];
-        cost[r] = pagan_dp_count_cells(w.gl.n_sites, w.gr.n_sites, w.banded ? &w.pb : nullptr);
+        cost[r] = pagan_dp_count_cells(w.job.gl.n_sites, w.job.gr.n_sites, w.job.band());
         if (cost[r] < 0) return (int)cost[r];
         w.device = dev;
     }
@@ -949,9 +733,9 @@ int run_unit(pagan_msa *m, const std::vector<int> &ids, int dev, int round, int 
         rc = align_on_device(m, ks, dev, &fill_ms, &trace_ms);
         if (rc != PAGAN_OK) return rc;
         std::vector<int> retry;
-        for (int k : ks) if (m->work[k].banded && m->work[k].res.status == PAGAN_DP_UNREACHABLE) retry.push_back(k);
+        for (int k : ks) if (m->work[k].job.banded && m->work[k].job.res.get().status == PAGAN_DP_UNREACHABLE) retry.push_back(k);
         if (!retry.empty()) {
-            for (int k : retry) { m->work[k].banded = false; pagan_result_free(&m->work[k].res); m->work[k].has_res = false; }
+            for (int k : retry) { m->work[k].job.banded = false; m->work[k].job.res.reset(); }
             rc = align_on_device(m, retry, dev, &fill_ms, &trace_ms);
             if (rc != PAGAN_OK) return rc;
         }
@@ -962,18 +746,18 @@ int run_unit(pagan_msa *m, const std::vector<int> &ids, int dev, int round, int 
         rc = fb_on_device(m, ks, dev, threads, &retry);
         if (rc != PAGAN_OK) return rc;
         if (!retry.empty()) {
-            for (int k : retry) m->work[k].banded = false;
+            for (int k : retry) m->work[k].job.banded = false;
             rc = fb_on_device(m, retry, dev, threads, &none);
             if (rc != PAGAN_OK) return rc;
         }
-        for (int k : ks) if (!m->work[k].has_res) return PAGAN_E_INTERNAL;
+        for (int k : ks) if (!m->work[k].job.res.held()) return PAGAN_E_INTERNAL;
     }
     const double t_dp = now_s() - t0;
     t0 = now_s();
     std::atomic<int> bad(0);
-    parallel_for((int)ids.size(), threads, [&](int r) { if (build_parent(m, ids[r], (int)ids.size()) != PAGAN_OK) bad = 1; });
+    parallel_for((int)ids.size(), threads, [&](int r) { if (build_parent(m, ids[r], (int)ids.size(), sw) != PAGAN_OK) bad = 1; });
     const double t_build = now_s() - t0;
-    if (std::getenv("PAGAN_DP_VERBOSE"))
+    if (sw.verbose)
         std::fprintf(stderr, "pagan_msa: unit of %d node(s) on device %d: prepare (model, children, anchors, tunnel) %.1f ms, DP (plan, batch, kernels, fetch) %.1f ms, parents %.1f ms\n",
                      (int)ids.size(), dev, 1e3 * t_prep, 1e3 * t_dp, 1e3 * t_build);
     {
@@ -1006,6 +790,33 @@ bool indel_model_fits(const pagan_msa *m) {
     return true;
 }
 
+// What both schedulers refuse before anything runs, in this order
+int walk_mode_check(const pagan_msa *m) {
+    const bool pass = m->opts.full_probability || m->opts.sample_path || m->decode_on;
+    if (m->decode_on && m->opts.sample_path) return PAGAN_E_ARG;        // (a node has one path: the decoded one or a sampled one)
+    if (m->counts_on && !pass) return PAGAN_E_ARG;                      // (no pass to take the counts from)
+    if (!indel_model_fits(m)) return PAGAN_E_ARG;
+    if (m->backend && pass) return PAGAN_E_NODEVICE;                    // (the seam has no forward/backward pass: never skipped silently)
+    return PAGAN_OK;
+}
+
+// the devices of the walk: opts' first_device / n_devices, or (n_devices <= 0) the caller's current device alone
+int resolve_devices(const pagan_msa *m, int *first, int *n) {
+    *n = m->opts.n_devices; *first = m->opts.first_device;
+    if (*n <= 0) { *n = 1; if (!m->backend && hipGetDevice(first) != hipSuccess) return PAGAN_E_NODEVICE; }
+    return PAGAN_OK;
+}
+
+// Internal node k where it has all of `what` (kAny: where it exists), else NULL: the per-node accessors' PAGAN_E_ARG
+enum : unsigned { kAny = 0, kRes = 1, kJob = 2, kFb = 4, kMarg = 8, kDec = 16, kCounts = 32 };
+const NodeWork *node_with(const pagan_msa *m, int32_t k, unsigned what) {
+    if (!m || k < 0 || k >= m->n_leaves - 1) return nullptr;
+    const NodeWork &w = m->work[k];
+    const unsigned has = (w.job.res.held() ? kRes : 0) | (w.has_job ? kJob : 0) | (w.has_fb ? kFb : 0) | (w.has_marg ? kMarg : 0) |
+                         (w.has_dec ? kDec : 0) | (w.has_counts ? kCounts : 0);
+    return (what & ~has) ? nullptr : &w;
+}
+
 } // namespace
 
 extern "C" {
@@ -1032,17 +843,14 @@ int64_t pagan_msa_node_cost(const pagan_msa *m, int32_t id) {
 // device that finishes early picks up what is ready without waiting for the others.
 int pagan_msa_align_nodes(pagan_msa *m, int32_t n_ids, const int32_t *ids) {
     if (!m || m->aligned || n_ids < 0 || (n_ids > 0 && !ids)) return PAGAN_E_ARG;
-    if (m->decode_on && m->opts.sample_path) return PAGAN_E_ARG;        // (a node has one path: the decoded one or a sampled one)
-    if (m->counts_on && !(m->opts.full_probability || m->opts.sample_path || m->decode_on)) return PAGAN_E_ARG;   // (no pass to take the counts from)
-    if (!indel_model_fits(m)) return PAGAN_E_ARG;
-    if (m->backend && (m->opts.full_probability || m->opts.sample_path || m->decode_on)) return PAGAN_E_NODEVICE;   // (the seam has no forward/backward pass: never skipped silently)
+    if (const int rc = walk_mode_check(m)) return rc;
     for (int k = 0; k < n_ids; ++k)
         if (ids[k] < m->n_leaves || ids[k] >= 2 * m->n_leaves - 1 || !node_ready(m, ids[k])) return PAGAN_E_ARG;
     if (n_ids == 0) return PAGAN_OK;
     const double t_start = now_s();
-    int ndev = m->opts.n_devices;
-    int first_dev = m->opts.first_device;
-    if (ndev <= 0) { ndev = 1; if (!m->backend && hipGetDevice(&first_dev) != hipSuccess) return PAGAN_E_NODEVICE; }
+    int ndev = 0, first_dev = 0;
+    if (const int rc = resolve_devices(m, &first_dev, &ndev)) return rc;
+    const HostSwitches sw = HostSwitches::read();
     const int threads = host_threads_of(m);
     std::vector<int64_t> cost(n_ids);
     for (int k = 0; k < n_ids; ++k) cost[k] = node_cost_estimate(m, ids[k]);
@@ -1054,12 +862,12 @@ int pagan_msa_align_nodes(pagan_msa *m, int32_t n_ids, const int32_t *ids) {
     std::vector<int> rcs(workers, PAGAN_OK);
     const int round = m->rounds++;
     if (workers == 1) {
-        rcs[0] = run_unit(m, share[0], first_dev, round, threads);
+        rcs[0] = run_unit(m, share[0], first_dev, round, threads, sw);
     } else {
         std::vector<std::thread> feeders;
         const int per = std::max(1, threads / workers);
         for (int d = 0; d < workers; ++d)
-            feeders.emplace_back([&, d] { rcs[d] = run_unit(m, share[d], first_dev + d, round, per); });
+            feeders.emplace_back([&, d] { rcs[d] = run_unit(m, share[d], first_dev + d, round, per, sw); });
         for (auto &th : feeders) th.join();
     }
     for (int rc : rcs) if (rc != PAGAN_OK) return rc;
@@ -1068,27 +876,10 @@ int pagan_msa_align_nodes(pagan_msa *m, int32_t n_ids, const int32_t *ids) {
     return PAGAN_OK;
 }
 
-// The rows of the alignment need every node's graph (an ancestor's row is read off its sites; the leaves' columns follow
-// the child maps down from the root): parents still pending (imported nodes, rank mode) are built first.
-static int ensure_rows(pagan_msa *m) {
-    std::lock_guard<std::mutex> g(m->lazy_mu);
-    if (m->rows_built) return PAGAN_OK;
-    const double t0 = now_s();
-    const int rc = ensure_graph(m, m->id_of_tree[m->root]);
-    if (rc != PAGAN_OK) return rc;
-    const double t1 = now_s();
-    build_rows(m);
-    m->tm.total_s += now_s() - t0;
-    if (std::getenv("PAGAN_DP_VERBOSE"))
-        std::fprintf(stderr, "pagan_msa: finish: pending parents %.1f ms, rows %.1f ms\n", 1e3 * (t1 - t0), 1e3 * (now_s() - t1));
-    m->rows_built = true;
-    return PAGAN_OK;
-}
-
 int pagan_msa_finish(pagan_msa *m) {
     if (!m || m->aligned || m->remaining != 0) return PAGAN_E_ARG;
     m->aligned = true;
-    return ensure_rows(m);
+    return ensure_rows(m, HostSwitches::read());
 }
 
 // Rank mode: the walk is over, but this process may never be asked for the rows -- the graphs of the nodes other ranks
@@ -1104,13 +895,10 @@ int pagan_msa_parents_built(const pagan_msa *m) { return m ? m->parents_built.lo
 
 int pagan_msa_align(pagan_msa *m) {
     if (!m || m->aligned) return PAGAN_E_ARG;
-    if (m->decode_on && m->opts.sample_path) return PAGAN_E_ARG;
-    if (m->counts_on && !(m->opts.full_probability || m->opts.sample_path || m->decode_on)) return PAGAN_E_ARG;   // (no pass to take the counts from)
-    if (!indel_model_fits(m)) return PAGAN_E_ARG;
-    if (m->backend && (m->opts.full_probability || m->opts.sample_path || m->decode_on)) return PAGAN_E_NODEVICE;
-    int ndev = m->opts.n_devices;
-    int first_dev = m->opts.first_device;
-    if (ndev <= 0) { ndev = 1; if (!m->backend && hipGetDevice(&first_dev) != hipSuccess) return PAGAN_E_NODEVICE; }
+    if (const int rc = walk_mode_check(m)) return rc;
+    int ndev = 0, first_dev = 0;
+    if (const int rc = resolve_devices(m, &first_dev, &ndev)) return rc;
+    const HostSwitches sw = HostSwitches::read();
     const int threads = host_threads_of(m);
     if (ndev == 1) {
         // one device: every round takes all ready nodes as one batch (the guide tree's levels)
@@ -1153,7 +941,7 @@ int pagan_msa_align(pagan_msa *m) {
                 const int d = idle[w];
                 busy[d] = 1; ++in_flight;
                 running[d] = std::thread([&, d, mine, round] {
-                    const int rc = run_unit(m, mine, first_dev + d, round, per);
+                    const int rc = run_unit(m, mine, first_dev + d, round, per, sw);
                     std::lock_guard<std::mutex> g(qm);
                     if (rc != PAGAN_OK && err == PAGAN_OK) err = rc;
                     if (rc == PAGAN_OK) for (int id : mine) { m->done[id] = 1; --m->remaining; }
@@ -1181,10 +969,9 @@ int pagan_msa_align(pagan_msa *m) {
 static const int32_t kResultMagic = 0x50475232;   // "PGR2"
 
 int64_t pagan_msa_export_result(const pagan_msa *m, int32_t id, void *buf, int64_t cap) {
-    if (!m || id < m->n_leaves || id >= 2 * m->n_leaves - 1) return PAGAN_E_ARG;
-    const NodeWork &w = m->work[id - m->n_leaves];
-    if (!w.has_res) return PAGAN_E_ARG;
-    const pagan_result &r = w.res;
+    const NodeWork *w = m ? node_with(m, id - m->n_leaves, kRes) : nullptr;
+    if (!w) return PAGAN_E_ARG;
+    const pagan_result &r = w->job.res.get();
     bool packed = true;
     {
         int l = 1, rr = 1;
@@ -1228,18 +1015,19 @@ int pagan_msa_import_result(pagan_msa *m, const void *buf, int64_t bytes) {
     const int64_t need = 12 * 4 + 16 + (packed ? (int64_t)n_cols : 12 * (int64_t)n_cols) + 4 * ((int64_t)nl + nr);
     if (bytes < need) return PAGAN_E_ARG;
     NodeWork &w = m->work[id - m->n_leaves];
-    if (w.has_res) { pagan_result_free(&w.res); w.has_res = false; }
-    pagan_result &r = w.res;
-    std::memset(&r, 0, sizeof(r));
+    w.job.res.reset();
+    pagan_result r{};
     r.status = head[2]; r.end_matrix = head[3]; r.end_x = head[4]; r.end_y = head[5]; r.end_x_edge = head[6]; r.end_y_edge = head[7];
     r.n_cols = n_cols; r.n_left_used = nl; r.n_right_used = nr;
     std::memcpy(&r.cells, p, 8); p += 8;
     std::memcpy(&r.score, p, 8); p += 8;
-    // pagan_result_free releases these with free()
+    // the owner releases these with free(), on every return from here on (it reaches the node only when the payload is good)
     r.cols = (pagan_col *)std::malloc(sizeof(pagan_col) * (size_t)std::max(n_cols, 1));
     r.left_used = (int32_t *)std::malloc(4 * (size_t)std::max(nl, 1));
     r.right_used = (int32_t *)std::malloc(4 * (size_t)std::max(nr, 1));
-    if (!r.cols || !r.left_used || !r.right_used) { std::free(r.cols); std::free(r.left_used); std::free(r.right_used); return PAGAN_E_NOMEM; }
+    OwnedResult in;
+    in.adopt(r);
+    if (!r.cols || !r.left_used || !r.right_used) return PAGAN_E_NOMEM;
     if (packed) {
         int l = 1, rr = 1;
         for (int k = 0; k < n_cols; ++k) {
@@ -1266,8 +1054,9 @@ int pagan_msa_import_result(pagan_msa *m, const void *buf, int64_t bytes) {
         if (hl ? c.left < 1 : c.left != -1) good = false;
         if (hr ? c.right < 1 : c.right != -1) good = false;
     }
-    if (!good) { pagan_result_free(&r); std::memset(&r, 0, sizeof(r)); return PAGAN_E_ARG; }
-    w.has_res = true; w.has_job = false; w.device = -1; w.node = id; w.level = m->rounds;
+    if (!good) return PAGAN_E_ARG;
+    w.job.res = std::move(in);
+    w.has_job = false; w.device = -1; w.node = id; w.level = m->rounds;
     w.has_fb = false; w.has_marg = false;                          // (support is not part of the exchange format)
     w.imp_l = sites_of(m, m->id_of_tree[t.left]); w.imp_r = sites_of(m, m->id_of_tree[t.right]);   // (no job was prepared here: node_info reports the children's sizes from these)
     if (r.status != PAGAN_DP_REACHED) return PAGAN_E_INTERNAL;       // (the owner retries an unreachable corner itself: it never posts one)
@@ -1279,113 +1068,87 @@ int pagan_msa_import_result(pagan_msa *m, const void *buf, int64_t bytes) {
 int pagan_msa_n_internal(const pagan_msa *m) { return m ? m->n_leaves - 1 : 0; }
 
 int pagan_msa_node_info(const pagan_msa *m, int32_t k, pagan_node_info *o) {
-    if (!m || !o || k < 0 || k >= m->n_leaves - 1) return PAGAN_E_ARG;
-    const NodeWork &w = m->work[k];
+    const NodeWork *wp = node_with(m, k, kAny);
+    if (!wp || !o) return PAGAN_E_ARG;
+    const NodeWork &w = *wp;
+    const pagan_result &res = w.job.res.get();
     const int id = m->n_leaves + k;
     const TreeNode &t = m->tree[m->tree_of_id[id]];
     std::memset(o, 0, sizeof(*o));
     o->node = id; o->left = m->id_of_tree[t.left]; o->right = m->id_of_tree[t.right];
     o->level = w.level; o->n_hits = w.n_hits; o->n_forced_gaps = w.n_forced;
     o->dist = m->tree[t.left].dist + m->tree[t.right].dist;
-    if (w.has_res) {
-        o->left_sites = w.has_job ? w.gl.n_sites : w.imp_l; o->right_sites = w.has_job ? w.gr.n_sites : w.imp_r;
-        o->cells = w.res.cells; o->score = w.res.score; o->status = w.res.status;
+    if (w.job.res.held()) {
+        o->left_sites = w.has_job ? w.job.gl.n_sites : w.imp_l; o->right_sites = w.has_job ? w.job.gr.n_sites : w.imp_r;
+        o->cells = res.cells; o->score = res.score; o->status = res.status;
     }
     if (m->graph[id]) o->sites = m->graph[id]->g.n_sites();
     return PAGAN_OK;
 }
 
 int pagan_msa_node_job(const pagan_msa *m, int32_t k, pagan_job *o) {
-    if (!m || !o || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_res || !m->work[k].has_job) return PAGAN_E_ARG;
-    const NodeWork &w = m->work[k];
-    o->left = &w.gl; o->right = &w.gr; o->model = &w.pm; o->band = w.banded ? &w.pb : nullptr;
+    const NodeWork *w = node_with(m, k, kRes | kJob);
+    if (!w || !o) return PAGAN_E_ARG;
+    *o = w->job.job(&w->pm);
     return PAGAN_OK;
 }
 
 int pagan_msa_node_result(const pagan_msa *m, int32_t k, pagan_result *o) {
-    if (!m || !o || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_res) return PAGAN_E_ARG;
-    *o = m->work[k].res;
+    const NodeWork *w = node_with(m, k, kRes);
+    if (!w || !o) return PAGAN_E_ARG;
+    *o = w->job.res.get();                                          // (a borrowed shallow copy: the node keeps the arrays)
     return PAGAN_OK;
 }
 
 // ---- what the forward/backward pass left at a node (full_probability / sample_path); PAGAN_E_ARG for a node this process
 // did not align
 int pagan_msa_node_fb(const pagan_msa *m, int32_t k, double out[4]) {
-    if (!m || !out || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_fb) return PAGAN_E_ARG;
-    const NodeWork &w = m->work[k];
-    out[0] = w.log_fwd; out[1] = w.log_bwd; out[2] = w.fb_sweep_ms; out[3] = w.fb_post_ms;
+    const NodeWork *w = node_with(m, k, kFb);
+    if (!w || !out) return PAGAN_E_ARG;
+    out[0] = w->log_fwd; out[1] = w->log_bwd; out[2] = w->fb_sweep_ms; out[3] = w->fb_post_ms;
     return PAGAN_OK;
 }
 
 // ... and the posterior decoding (pagan_msa_set_decoder)
 int pagan_msa_node_decode(const pagan_msa *m, int32_t k, double out[3]) {
-    if (!m || !out || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_dec) return PAGAN_E_ARG;
-    const NodeWork &w = m->work[k];
-    out[0] = w.dec_objective; out[1] = w.dec_steps; out[2] = w.dec_ms;
+    const NodeWork *w = node_with(m, k, kDec);
+    if (!w || !out) return PAGAN_E_ARG;
+    out[0] = w->dec_objective; out[1] = w->dec_steps; out[2] = w->dec_ms;
     return PAGAN_OK;
 }
 
 // ... and the expected counts (pagan_msa_set_counts): trans[12], emit[S * S] (DNA; NULL: not wanted)
 int pagan_msa_node_counts(const pagan_msa *m, int32_t k, double *trans, double *emit) {
-    if (!m || !trans || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_fb || !m->work[k].has_counts) return PAGAN_E_ARG;
-    const NodeWork &w = m->work[k];
-    if (emit && w.emit.empty()) return PAGAN_E_ARG;                 // (protein and codon tables: not provided)
-    std::memcpy(trans, w.trans, sizeof(w.trans));
-    if (emit) std::memcpy(emit, w.emit.data(), 8 * w.emit.size());
+    const NodeWork *w = node_with(m, k, kFb | kCounts);
+    if (!w || !trans) return PAGAN_E_ARG;
+    if (emit && w->emit.empty()) return PAGAN_E_ARG;                // (protein and codon tables: not provided)
+    std::memcpy(trans, w->trans, sizeof(w->trans));
+    if (emit) std::memcpy(emit, w->emit.data(), 8 * w->emit.size());
     return PAGAN_OK;
 }
 
 int pagan_msa_node_support(const pagan_msa *m, int32_t k, double *support) {
-    if (!m || !support || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_fb) return PAGAN_E_ARG;
-    const NodeWork &w = m->work[k];
-    if (!w.support.empty()) std::memcpy(support, w.support.data(), 8 * w.support.size());
+    const NodeWork *w = node_with(m, k, kFb);
+    if (!w || !support) return PAGAN_E_ARG;
+    if (!w->support.empty()) std::memcpy(support, w->support.data(), 8 * w->support.size());
     return PAGAN_OK;
 }
 
 int pagan_msa_node_marginals(const pagan_msa *m, int32_t k, double *pX, double *pM_left, int32_t *best_j, double *best_p_left,
                              double *pY, double *pM_right, int32_t *best_i, double *best_p_right) {
-    if (!m || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_fb || !m->work[k].has_marg) return PAGAN_E_ARG;
-    const NodeWork &w = m->work[k];
+    const NodeWork *w = node_with(m, k, kFb | kMarg);
+    if (!w) return PAGAN_E_ARG;
     double *const d[6] = {pX, pM_left, best_p_left, pY, pM_right, best_p_right};
     int32_t *const i[2] = {best_j, best_i};
-    for (int a = 0; a < 6; ++a) if (d[a] && !w.mg_d[a].empty()) std::memcpy(d[a], w.mg_d[a].data(), 8 * w.mg_d[a].size());
-    for (int a = 0; a < 2; ++a) if (i[a] && !w.mg_i[a].empty()) std::memcpy(i[a], w.mg_i[a].data(), 4 * w.mg_i[a].size());
+    for (int a = 0; a < 6; ++a) if (d[a] && !w->mg_d[a].empty()) std::memcpy(d[a], w->mg_d[a].data(), 8 * w->mg_d[a].size());
+    for (int a = 0; a < 2; ++a) if (i[a] && !w->mg_i[a].empty()) std::memcpy(i[a], w->mg_i[a].data(), 4 * w->mg_i[a].size());
     return PAGAN_OK;
 }
 
 int pagan_msa_node_model_prob(const pagan_msa *m, int32_t k, pagan_model_prob *out) {
-    if (!m || !out || k < 0 || k >= m->n_leaves - 1 || !m->work[k].has_job || !m->work[k].model) return PAGAN_E_ARG;
-    *out = m->work[k].model->prob_view();
-    return PAGAN_OK;
-}
-
-// A node's column support on the columns of the final alignment: the node's sites are followed up the tree, parent by parent,
-// to the root's sites, which are the alignment's columns (as build_rows follows them down).
-int pagan_msa_support_row(const pagan_msa *m, int32_t node, float *buf) {
-    if (!m || !m->aligned || !buf) return PAGAN_E_ARG;
-    if (node < m->n_leaves || node >= 2 * m->n_leaves - 1 || !m->work[node - m->n_leaves].has_fb) return PAGAN_E_ARG;
-    if (const int rc = ensure_rows(const_cast<pagan_msa *>(m))) return rc;
-    const NodeWork &w = m->work[node - m->n_leaves];
-    const int width = (int)m->rows[0].size() / (m->mf.type == kCodon ? 3 : 1);
-    for (int c = 0; c < width; ++c) buf[c] = -1.0f;
-    const int ns = m->graph[node]->g.n_sites();
-    if (ns != w.res.n_cols + 2 || (int)w.support.size() != w.res.n_cols) return PAGAN_E_INTERNAL;
-    std::vector<int32_t> at(ns);                                   // site of `node` -> site of the ancestor reached so far
-    for (int s = 0; s < ns; ++s) at[s] = s;
-    for (int t = m->tree_of_id[node]; m->tree[t].parent >= 0; t = m->tree[t].parent) {
-        const int pt = m->tree[t].parent;
-        const SeqGraph &pg = m->graph[m->id_of_tree[pt]]->g;
-        const std::vector<int32_t> &child = m->tree[pt].left == t ? pg.child_l : pg.child_r;
-        std::vector<int32_t> up((size_t)m->graph[m->id_of_tree[t]]->g.n_sites(), -1);
-        for (int s = 1; s < pg.n_sites() - 1; ++s) if (child[s] >= 0) up[child[s]] = s;
-        for (int s = 1; s < ns - 1; ++s) if (at[s] >= 0) at[s] = up[at[s]];
-    }
-    for (int k = 0; k < w.res.n_cols; ++k) {
-        const int ps = w.res.cols[k].path_state;
-        if (ps != PAGAN_MATCHED && ps != PAGAN_XGAPPED && ps != PAGAN_YGAPPED) continue;
-        const int c = at[k + 1] - 1;                               // (the root's site s is column s - 1)
-        if (c >= 0 && c < width) buf[c] = (float)w.support[k];
-    }
+    const NodeWork *w = node_with(m, k, kJob);
+    if (!w || !out || !w->model) return PAGAN_E_ARG;
+    *out = w->model->prob_view();
     return PAGAN_OK;
 }
 
@@ -1395,388 +1158,9 @@ int pagan_msa_timing_get(const pagan_msa *m, pagan_msa_timing *o) {
     return PAGAN_OK;
 }
 
-int pagan_msa_alignment_length(const pagan_msa *m) {
-    if (!m || !m->aligned) return PAGAN_E_ARG;
-    if (const int rc = ensure_rows(const_cast<pagan_msa *>(m))) return rc;       // (pagan_msa_finish_lazy: built on first use)
-    return (int)m->rows[0].size();
-}
-
-int pagan_msa_alignment_row(const pagan_msa *m, int32_t leaf, char *buf) {
-    if (!m || !m->aligned || !buf) return PAGAN_E_ARG;
-    if (const int rc = ensure_rows(const_cast<pagan_msa *>(m))) return rc;
-    if (leaf < 0 || leaf >= (int)m->rows.size()) return PAGAN_E_ARG;
-    std::memcpy(buf, m->rows[leaf].c_str(), m->rows[leaf].size() + 1);
-    return PAGAN_OK;
-}
-
-// The guide tree made from this walk's own alignment (csrc/dp_alndist.hip): the leaf rows, the walk's names and data type.
-int64_t pagan_msa_alignment_tree(const pagan_msa *m, char *newick_out, int64_t cap, pagan_aln_info *info) {
-    if (!m || !m->aligned || (cap > 0 && !newick_out)) return PAGAN_E_ARG;
-    if (const int rc = ensure_rows(const_cast<pagan_msa *>(m))) return rc;
-    std::vector<const char *> names(m->n_leaves), rows(m->n_leaves);
-    for (int k = 0; k < m->n_leaves; ++k) { names[k] = m->names[k].c_str(); rows[k] = m->rows[k].c_str(); }
-    return pagan_aln_tree(m->n_leaves, names.data(), rows.data(), pagan_msa_data_type(m), newick_out, cap, info);
-}
-
-// Fasta_reader::write_fasta (src/utils/fasta_reader.cpp:596-629) over Node::get_alignment's leaf rows
-// (src/main/node.cpp:537-575): one entry per leaf in guide-tree order (left to right, as get_leaf_nodes
-// collects them), `>name`, the aligned row cut into lines of chars_by_line characters (60 by default).
-int pagan_msa_write_fasta(const pagan_msa *m, const char *path, int32_t chars_by_line) {
-    return pagan_msa_write_fasta_nodes(m, path, chars_by_line, 0);
-}
-
-// ... with include_internal (--output-ancestors): every node in Node::get_all_nodes order -- left subtree, the node,
-// right subtree (node.h:277-290) -- internal nodes named #k# in alignment order (node.h:479-495).
-static int write_fasta_rows(const pagan_msa *m, const std::vector<std::string> &rows, const char *path, int32_t chars_by_line, int32_t include_internal) {
-    const size_t width = chars_by_line > 0 ? (size_t)chars_by_line : 60;
-    std::FILE *f = std::fopen(path, "w");
-    if (!f) return PAGAN_E_ARG;
-    std::vector<int> order;
-    {
-        // in-order walk without recursion: (tree index, children done?)
-        std::vector<std::pair<int, bool>> stack{{m->root, false}};
-        while (!stack.empty()) {
-            const auto [t, visited] = stack.back();
-            stack.pop_back();
-            const TreeNode &n = m->tree[t];
-            if (n.left < 0) { order.push_back(m->id_of_tree[t]); continue; }
-            if (visited) { if (include_internal) order.push_back(m->id_of_tree[t]); continue; }
-            stack.push_back({n.right, false});
-            stack.push_back({t, true});
-            stack.push_back({n.left, false});
-        }
-    }
-    for (int leaf : order) {
-        if (leaf < m->n_leaves) std::fprintf(f, ">%s\n", m->names[leaf].c_str());
-        else std::fprintf(f, ">#%d#\n", leaf - m->n_leaves + 1);
-        const std::string &row = rows[leaf];
-        for (size_t at = 0; at < row.size(); at += width) std::fprintf(f, "%.*s\n", (int)std::min(width, row.size() - at), row.c_str() + at);
-    }
-    return std::fclose(f) == 0 ? PAGAN_OK : PAGAN_E_ARG;
-}
-
-int pagan_msa_write_fasta_nodes(const pagan_msa *m, const char *path, int32_t chars_by_line, int32_t include_internal) {
-    if (!m || !m->aligned || !path) return PAGAN_E_ARG;
-    if (const int rc = ensure_rows(const_cast<pagan_msa *>(m))) return rc;
-    return write_fasta_rows(m, m->rows, path, chars_by_line, include_internal);
-}
-
-// ---- ancestral states by marginal likelihood (csrc/dp_anc.hip) over the finished walk -----------------------------------
-// The walk's tree in its public ids (children before parents, the root 2n - 2) under the branch lengths it aligned with:
-// tree[].dist after corrected_branch.
-int pagan_msa_ancestral(pagan_msa *m, uint32_t flags, double *loglik, double *col_loglik, pagan_anc_info *info) {
-    if (!m || !m->aligned) return PAGAN_E_ARG;
-    if (const int rc = ensure_rows(m)) return rc;
-    try {
-        const int n = m->n_leaves;
-        std::vector<int32_t> left(n - 1), right(n - 1);
-        std::vector<double> branch((size_t)2 * n - 1, 0.0);
-        std::vector<const char *> rows(n);
-        for (int k = 0; k < n - 1; ++k) {
-            const TreeNode &t = m->tree[m->tree_of_id[n + k]];
-            left[k] = m->id_of_tree[t.left]; right[k] = m->id_of_tree[t.right];
-        }
-        for (int id = 0; id < 2 * n - 1; ++id) branch[id] = m->tree[m->tree_of_id[id]].dist;
-        for (int k = 0; k < n; ++k) rows[k] = m->rows[k].c_str();
-        float bf[4] = {0.25f, 0.25f, 0.25f, 0.25f};
-        if (m->mf.type == kDna) for (int k = 0; k < 4; ++k) bf[k] = (float)m->mf.pi[k];     // (the floats init_dna took)
-        const size_t L = m->rows[0].size() / (m->mf.type == kCodon ? 3 : 1);
-        std::vector<uint8_t> best((size_t)(n - 1) * L);
-        std::vector<float> best_p((size_t)(n - 1) * L);
-        m->anc_done = false;
-        const int rc = pagan_anc_reconstruct(n, left.data(), right.data(), branch.data(), rows.data(), pagan_msa_data_type(m), bf, flags, 0, nullptr,
-                                             nullptr, nullptr, col_loglik, loglik, best.data(), best_p.data(), nullptr, nullptr, info);
-        if (rc != PAGAN_OK) return rc;
-        m->anc_best.swap(best); m->anc_best_p.swap(best_p);
-        m->anc_done = true;
-        return PAGAN_OK;
-    } catch (const std::bad_alloc &) {
-        return PAGAN_E_NOMEM;
-    }
-}
-
-// The overlay of bppancestors.cpp:242-254: every character of an ancestor's row that is no gap becomes the state of largest
-// posterior; the root keeps its own (no copy from a child as at :273-314: the pass is rooted).
-static std::string ancestral_row_of(const pagan_msa *m, int node) {
-    std::string row = m->rows[node];
-    const int n = m->n_leaves;
-    if (node < n) return row;
-    const int w = m->mf.type == kCodon ? 3 : 1;
-    const size_t L = row.size() / w;
-    const char *letters = m->mf.type == kCodon ? ModelFactory::codon_alphabet() : m->mf.type == kProtein ? ModelFactory::protein_alphabet() : ModelFactory::dna_full_alphabet();
-    const uint8_t *best = m->anc_best.data() + (size_t)(node - n) * L;
-    for (size_t c = 0; c < L; ++c)
-        if (row[c * w] != '-') for (int j = 0; j < w; ++j) row[c * w + j] = letters[(size_t)best[c] * w + j];
-    return row;
-}
-
-int pagan_msa_ancestral_row(const pagan_msa *m, int32_t node, char *buf) {
-    if (!m || !m->aligned || !m->anc_done || !buf || node < 0 || node >= (int)m->rows.size()) return PAGAN_E_ARG;
-    const std::string row = ancestral_row_of(m, node);
-    std::memcpy(buf, row.c_str(), row.size() + 1);
-    return PAGAN_OK;
-}
-
-int pagan_msa_ancestral_support(const pagan_msa *m, int32_t node, float *buf) {
-    if (!m || !m->aligned || !m->anc_done || !buf || node < m->n_leaves || node >= (int)m->rows.size()) return PAGAN_E_ARG;
-    const int w = m->mf.type == kCodon ? 3 : 1;
-    const std::string &row = m->rows[node];
-    const size_t L = row.size() / w;
-    const float *p = m->anc_best_p.data() + (size_t)(node - m->n_leaves) * L;
-    for (size_t c = 0; c < L; ++c) buf[c] = row[c * w] != '-' ? p[c] : -1.0f;
-    return PAGAN_OK;
-}
-
-int pagan_msa_write_fasta_ancestral(const pagan_msa *m, const char *path, int32_t chars_by_line) {
-    if (!m || !m->aligned || !m->anc_done || !path) return PAGAN_E_ARG;
-    try {
-        std::vector<std::string> rows(m->rows.size());
-        for (size_t id = 0; id < rows.size(); ++id) rows[id] = ancestral_row_of(m, (int)id);
-        return write_fasta_rows(m, rows, path, chars_by_line, 1);
-    } catch (const std::bad_alloc &) {
-        return PAGAN_E_NOMEM;
-    }
-}
-
-int pagan_msa_ancestral_best(const pagan_msa *m, const uint8_t **best, const float **best_p) {
-    if (!m || !m->anc_done) return PAGAN_E_ARG;
-    if (best) *best = m->anc_best.data();
-    if (best_p) *best_p = m->anc_best_p.data();
-    return PAGAN_OK;
-}
-
-void *pagan_msa_node_graph(const pagan_msa *m, int32_t node) {
-    if (!m || node < 0 || node >= (int)m->graph.size()) return nullptr;
-    if (!m->graph[node] && m->done[node]) {                        // (an imported node's graph: built when somebody asks for it)
-        pagan_msa *mm = const_cast<pagan_msa *>(m);
-        std::lock_guard<std::mutex> g(mm->lazy_mu);
-        if (ensure_graph(mm, node) != PAGAN_OK) return nullptr;
-    }
-    return m->graph[node].get();
-}
-
 void pagan_msa_destroy(pagan_msa *m) { delete m; }
 
-// ---- host graphs on their own -------------------------------------------------------------
-pagan_hgraph *pagan_hgraph_leaf(const char *residues, const char *alphabet, int32_t flags) {
-    pagan_hgraph *h = new pagan_hgraph();
-    h->g = make_leaf(residues, alphabet, flags);
-    return h;
-}
-
-pagan_hgraph *pagan_hgraph_leaf_codon(const char *nucleotides) {
-    if (!nucleotides) return nullptr;
-    pagan_hgraph *h = new pagan_hgraph();
-    std::string symbols;
-    const std::vector<int32_t> states = ModelFactory::codon_states(nucleotides, &symbols);
-    h->g = make_leaf_states(states, std::move(symbols), 3, 0);
-    return h;
-}
-
-pagan_hgraph *pagan_hgraph_parent(pagan_hgraph *l, pagan_hgraph *r, const pagan_result *res, float lbl, float rbl,
-                                  const int32_t *parsimony, int32_t S, int32_t char_as, int32_t flags) {
-    BuildSettings bs;
-    if (flags & 1) bs.reads_mode();
-    if (flags & 2) bs.reduced_terminal = false;
-    pagan_hgraph *h = new pagan_hgraph();
-    h->g = make_parent(l->g, r->g, *res, lbl, rbl, parsimony, S, char_as, bs);
-    return h;
-}
-
-// The same graph built on the current device (dp_parent.hip).  NULL without a device or on a HIP error -- never a host-built
-// graph in its place.  info (may be NULL): runs of skipped sites, fixpoint rounds of the boundary pass, deleted sites, edge
-// weights outside the log table, log weights the host had to put right.
-pagan_hgraph *pagan_hgraph_parent_device(pagan_hgraph *l, pagan_hgraph *r, const pagan_result *res, float lbl, float rbl,
-                                         const int32_t *parsimony, int32_t S, int32_t char_as, int32_t flags, int32_t *info) {
-    BuildSettings bs;
-    if (flags & 1) bs.reads_mode();
-    if (flags & 2) bs.reduced_terminal = false;
-    pagan_hgraph *h = new pagan_hgraph();
-    ParentBuildInfo pi;
-    if (!make_parent_device(l->g, r->g, *res, lbl, rbl, parsimony, S, char_as, bs, -1, &h->g, &pi)) { delete h; return nullptr; }
-    if (info) { info[0] = pi.runs; info[1] = pi.rounds; info[2] = pi.deleted_sites; info[3] = pi.weights_outside_table; info[4] = pi.log_weights_patched; }
-    return h;
-}
 long long pagan_parents_device_calls(void) { return parents_on_device.load(); }
-
-void pagan_hgraph_view(const pagan_hgraph *g, pagan_graph *out) { *out = g->g.view(); }
-
-void pagan_hgraph_attrs(const pagan_hgraph *h, int32_t *sa, float *sd, int32_t *ea, float *ef) {
-    const SeqGraph &g = h->g;
-    std::vector<char> linked(g.n_edges(), 0);
-    for (int e : g.fwd_eid) linked[e] = 1;
-    for (int s = 0; s < g.n_sites(); ++s) {
-        int32_t *a = sa + 8 * s;
-        a[0] = g.state[s]; a[1] = g.site_type[s]; a[2] = g.path_state[s]; a[3] = g.child_l[s]; a[4] = g.child_r[s];
-        a[5] = g.count_since_used[s]; a[6] = g.ambiguous[s]; a[7] = g.fwd_off[s + 1] - g.fwd_off[s];
-        sd[s] = g.dist_since_used[s];
-    }
-    for (int e = 0; e < g.n_edges(); ++e) {
-        int32_t *a = ea + 6 * e;
-        a[0] = g.e_start[e]; a[1] = g.e_end[e]; a[2] = g.e_used[e]; a[3] = g.e_count_since_used[e];
-        a[4] = g.e_count_as_skipped[e]; a[5] = linked[e];
-        ef[3 * e] = g.e_w[e]; ef[3 * e + 1] = g.e_logw[e]; ef[3 * e + 2] = g.e_dist_since_used[e];
-    }
-}
-
-void pagan_hgraph_fwd(const pagan_hgraph *h, int32_t *fwd_off, int32_t *fwd_eid) {
-    std::memcpy(fwd_off, h->g.fwd_off.data(), sizeof(int32_t) * h->g.fwd_off.size());
-    if (!h->g.fwd_eid.empty()) std::memcpy(fwd_eid, h->g.fwd_eid.data(), sizeof(int32_t) * h->g.fwd_eid.size());
-}
-
-int pagan_hgraph_string(const pagan_hgraph *h, int32_t with_gaps, const char *alphabet, char *out) {
-    const std::string s = sequence_string(h->g, with_gaps != 0, alphabet);
-    std::memcpy(out, s.c_str(), s.size() + 1);
-    return (int)s.size();
-}
-
-void pagan_hgraph_free(pagan_hgraph *g) { delete g; }
-
-int pagan_define_tunnel(const char *s1, const char *s2, const char *g1, const char *g2, int32_t prefix_hit_length,
-                        int32_t hit_trim, int32_t offset, int32_t *upper, int32_t *lower) {
-    AnchorSettings as;
-    as.prefix_hit_length = prefix_hit_length; as.hit_trim = hit_trim; as.offset = offset;
-    std::vector<int32_t> up, lo;
-    const int n = define_tunnel(s1, s2, g1, g2, as, &up, &lo);
-    std::memcpy(upper, up.data(), sizeof(int32_t) * up.size());
-    std::memcpy(lower, lo.data(), sizeof(int32_t) * lo.size());
-    return n;
-}
-
-int pagan_prefix_hits(const char *s1, const char *s2, int32_t min_length, int32_t *hits, int32_t cap) {
-    if (!s1 || !s2) return PAGAN_E_ARG;
-    std::vector<Hit> v;
-    prefix_hits(s1, s2, min_length, &v);
-    for (size_t k = 0; k < v.size() && (int)k < cap; ++k) { hits[4 * k] = v[k].s1; hits[4 * k + 1] = v[k].s2; hits[4 * k + 2] = v[k].len; hits[4 * k + 3] = v[k].score; }
-    return (int)v.size();
-}
-
-int pagan_prefix_hits_raw(const char *s1, const char *s2, int32_t min_length, int32_t where, int32_t *hits, int32_t cap) {
-    if (!s1 || !s2 || min_length < 1 || cap < 0 || (cap > 0 && !hits) || (where != 0 && where != 1)) return PAGAN_E_ARG;
-    std::vector<Hit> v;
-    if (where == 0) prefix_hits_raw_host(s1, s2, min_length, &v);
-    else if (!prefix_hits_device(s1, s2, min_length, &v, anchor_device())) return PAGAN_E_NODEVICE;
-    for (size_t k = 0; k < v.size() && (int)k < cap; ++k) { hits[3 * k] = v[k].s1; hits[3 * k + 1] = v[k].s2; hits[3 * k + 2] = v[k].len; }
-    return (int)v.size();
-}
-
-long long pagan_anchors_device_calls(void) { return device_finder_calls.load(); }
-
-int pagan_drop_bad_hits(int32_t *hits, int32_t n, int32_t thr_total, int32_t thr_partly) {
-    if (n < 0 || (n > 0 && !hits)) return PAGAN_E_ARG;
-    std::vector<Hit> v(n);
-    for (int k = 0; k < n; ++k) v[k] = Hit{hits[4 * k], hits[4 * k + 1], hits[4 * k + 2], hits[4 * k + 3]};
-    drop_bad_hits(&v, (unsigned)thr_total, (unsigned)thr_partly);
-    for (size_t k = 0; k < v.size(); ++k) { hits[4 * k] = v[k].s1; hits[4 * k + 1] = v[k].s2; hits[4 * k + 2] = v[k].len; hits[4 * k + 3] = v[k].score; }
-    return (int)v.size();
-}
-
-int pagan_define_tunnel_overlapping(const int32_t *hits, int32_t n, const char *g1, const char *g2, int32_t width,
-                                    int32_t *upper, int32_t *lower, int32_t *blocks, int32_t cap) {
-    if (n < 0 || (n > 0 && !hits) || !g1 || !g2 || !upper || !lower) return PAGAN_E_ARG;
-    std::vector<Hit> v(n);
-    for (int k = 0; k < n; ++k) v[k] = Hit{hits[4 * k], hits[4 * k + 1], hits[4 * k + 2], hits[4 * k + 3]};
-    std::vector<int32_t> up, lo;
-    std::vector<TunnelBlock> eb;
-    hits_to_band_overlapping(v, g1, g2, width, &up, &lo, &eb);
-    std::memcpy(upper, up.data(), sizeof(int32_t) * up.size());
-    std::memcpy(lower, lo.data(), sizeof(int32_t) * lo.size());
-    for (size_t k = 0; k < eb.size() && (int)k < cap; ++k) { blocks[4 * k] = eb[k].sx; blocks[4 * k + 1] = eb[k].sy; blocks[4 * k + 2] = eb[k].ex; blocks[4 * k + 3] = eb[k].ey; }
-    return (int)eb.size();
-}
-
-int pagan_force_gap(int32_t *upper, int32_t *lower, int32_t n, const int32_t *blocks, int32_t n_blocks, int32_t threshold,
-                    int32_t width, int32_t wide) {
-    if (!upper || !lower || n < 1 || n_blocks < 0 || (n_blocks > 0 && !blocks)) return PAGAN_E_ARG;
-    std::vector<int32_t> up(upper, upper + n), lo(lower, lower + n);
-    std::vector<TunnelBlock> eb(n_blocks);
-    for (int k = 0; k < n_blocks; ++k) { eb[k].sx = blocks[4 * k]; eb[k].sy = blocks[4 * k + 1]; eb[k].ex = blocks[4 * k + 2]; eb[k].ey = blocks[4 * k + 3]; }
-    const bool done = force_gap(&up, &lo, &eb, threshold, width, wide != 0);
-    std::memcpy(upper, up.data(), sizeof(int32_t) * n);
-    std::memcpy(lower, lo.data(), sizeof(int32_t) * n);
-    return done ? 1 : 0;
-}
-
-int pagan_dna_model(const float bf[4], double distance, float *table, float *params, int32_t *parsimony) {
-    if (!bf || !table || !params) return PAGAN_E_ARG;
-    ModelFactory mf;
-    mf.init_dna(bf);
-    const EvolModel em = mf.alignment_model(distance);
-    std::memcpy(table, em.log_score.data(), sizeof(float) * 225);
-    params[0] = em.log_gap_open; params[1] = em.log_gap_ext; params[2] = em.log_gap_end_ext; params[3] = em.log_non_gap;
-    if (parsimony) std::memcpy(parsimony, mf.parsimony.data(), sizeof(int32_t) * 225);
-    return PAGAN_OK;
-}
-
-int pagan_protein_model(double distance, float *table, float *params, int32_t *parsimony) {
-    if (!table || !params) return PAGAN_E_ARG;
-    static ModelFactory mf;                       // the WAG eigen solution does not depend on the input
-    static std::once_flag once;
-    std::call_once(once, [] { mf.init_protein(); });
-    const EvolModel em = mf.alignment_model(distance);
-    std::memcpy(table, em.log_score.data(), sizeof(float) * em.log_score.size());
-    params[0] = em.log_gap_open; params[1] = em.log_gap_ext; params[2] = em.log_gap_end_ext; params[3] = em.log_non_gap;
-    if (parsimony) std::memcpy(parsimony, mf.parsimony.data(), sizeof(int32_t) * mf.parsimony.size());
-    return PAGAN_OK;
-}
-
-int pagan_codon_model(double distance, float *table, float *params, int32_t *parsimony) {
-    if (!table || !params) return PAGAN_E_ARG;
-    const ModelFactory &mf = codon_factory();
-    const EvolModel em = mf.alignment_model(distance);
-    std::memcpy(table, em.log_score.data(), sizeof(float) * em.log_score.size());
-    params[0] = em.log_gap_open; params[1] = em.log_gap_ext; params[2] = em.log_gap_end_ext; params[3] = em.log_non_gap;
-    if (parsimony) std::memcpy(parsimony, mf.parsimony.data(), sizeof(int32_t) * mf.parsimony.size());
-    return PAGAN_OK;
-}
-
-int pagan_codon_alphabet(char *names, int32_t *mostcommon) {
-    const ModelFactory &mf = codon_factory();
-    if (names) std::memcpy(names, mf.codon_names.c_str(), mf.codon_names.size() + 1);
-    if (mostcommon) std::memcpy(mostcommon, mf.mostcommon.data(), sizeof(int32_t) * mf.mostcommon.size());
-    return mf.S;
-}
-
-int pagan_codon_translate(const char *codons, char *out) {
-    if (!codons || !out) return PAGAN_E_ARG;
-    const std::string p = ModelFactory::translate_codons(codons);
-    std::memcpy(out, p.c_str(), p.size() + 1);
-    return (int)p.size();
-}
-
-int pagan_codon_states(const char *nucleotides, int32_t *states) {
-    if (!nucleotides || !states) return PAGAN_E_ARG;
-    const std::vector<int32_t> st = ModelFactory::codon_states(nucleotides);
-    if (!st.empty()) std::memcpy(states, st.data(), sizeof(int32_t) * st.size());
-    return (int)st.size();
-}
-
-// Probability-space view of the same model (Evol_model::score / gap_open / gap_ext / non_gap): score [a + b*S],
-// params[3] = gap_open, gap_ext, non_gap.  data_type 1: DNA (base_freq needed), 2: protein, 3: codon.
-int pagan_model_prob_table(int32_t data_type, const float *base_freq, double distance, float *score, float *params) {
-    if (!score || !params || (data_type != 2 && data_type != 3 && !base_freq)) return PAGAN_E_ARG;
-    ModelFactory own;
-    if (data_type == 2) own.init_protein(); else if (data_type != 3) own.init_dna(base_freq);
-    const ModelFactory &mf = data_type == 3 ? codon_factory() : own;
-    const EvolModel em = mf.alignment_model(distance);
-    std::memcpy(score, em.score.data(), sizeof(float) * em.score.size());
-    params[0] = em.gap_open; params[1] = em.gap_ext; params[2] = em.non_gap;
-    return PAGAN_OK;
-}
-
-int pagan_model_alphabets(int32_t data_type, char *leaf_alphabet, char *ancestral_alphabet) {
-    ModelFactory mf;
-    if (data_type == 2) mf.init_protein();
-    else { const float bf[4] = {0.25f, 0.25f, 0.25f, 0.25f}; mf.init_dna(bf); }
-    if (leaf_alphabet) std::memcpy(leaf_alphabet, mf.leaf_alphabet.c_str(), mf.leaf_alphabet.size() + 1);
-    if (ancestral_alphabet) std::memcpy(ancestral_alphabet, mf.ancestral_alphabet.c_str(), mf.ancestral_alphabet.size() + 1);
-    return mf.S;
-}
-
-int pagan_eigen_qrev(const double *Q, const double *pi, int32_t n, double *root, double *U, double *V) {
-    if (!Q || !pi || n < 1 || !root || !U || !V) return PAGAN_E_ARG;
-    return eigen_qrev(Q, pi, n, root, U, V);
-}
 
 int pagan_msa_set_batch_backend(pagan_msa *m, pagan_batch_fn fn, void *user) {
     if (!m) return PAGAN_E_ARG;
@@ -1818,49 +1202,9 @@ int pagan_msa_set_indel_model(pagan_msa *m, double ins_rate, double del_rate, do
     return PAGAN_OK;
 }
 
-// A moment / pseudo-likelihood estimate of the indel model from the nodes' expected counts (include/pagan_host.h).
-int pagan_fit_indel(int32_t n, const double *dist, const double *trans, double *indel_rate, double *gap_ext) {
-    if (n < 0 || (n > 0 && (!dist || !trans)) || !indel_rate || !gap_ext) return PAGAN_E_ARG;
-    double stay = 0, leave = 0, d_max = 0;
-    std::vector<double> O(n), Sm(n);
-    bool any_open = false, any = false;
-    for (int k = 0; k < n; ++k) {
-        const double *t = trans + 12 * (size_t)k;
-        for (int q = 0; q < 12; ++q) if (!(t[q] >= 0.0) || !(t[q] < HUGE_VAL)) return PAGAN_E_ARG;
-        if (!(dist[k] >= 0.0) || !(dist[k] < HUGE_VAL)) return PAGAN_E_ARG;
-        stay += t[0] + t[4];                                        // n_XX + n_YY
-        leave += t[1] + t[3] + t[2] + t[5] + t[9] + t[10];          // n_XY + n_YX + n_XM + n_YM + n_Xend + n_Yend
-        O[k] = t[6] + t[7]; Sm[k] = t[8] + t[11];                   // n_MX + n_MY; n_MM + n_Mend
-        if (dist[k] > 0 && O[k] + Sm[k] > 0) { any = true; any_open = any_open || O[k] > 0; d_max = std::max(d_max, dist[k]); }
-    }
-    *gap_ext = stay + leave > 0 ? stay / (stay + leave) : 0.0;
-    *indel_rate = 0.0;
-    if (!any || !any_open) return PAGAN_OK;                         // (no transition out of a match seen, or no gap opened: rate 0)
-    // g(r) = sum_k d_k [ O_k (1 - t_k) / (2 t_k) - S_k (1 - t_k) / (1 - 2 t_k) ], t_k = 1 - exp(-0.5 r d_k): the derivative of the
-    // objective by r; it falls from +inf at r = 0 and reaches -inf where 1 - 2 t_k = 0 at the longest distance (r d_max = 2 ln 2),
-    // unless no node with d = d_max has S > 0, when the root may lie at the bound itself
-    auto g = [&](double r) {
-        double s = 0;
-        for (int k = 0; k < n; ++k) {
-            if (!(dist[k] > 0) || !(O[k] + Sm[k] > 0)) continue;
-            const double e = std::exp(-0.5 * r * dist[k]), tk = 1.0 - e;
-            s += dist[k] * (O[k] * e / (2 * tk) - Sm[k] * e / (1.0 - 2 * tk));
-        }
-        return s;
-    };
-    double lo = 0.0, hi = 2.0 * std::log(2.0) / d_max;
-    for (int it = 0; it < 200 && hi - lo > 1e-13 * hi; ++it) {
-        const double mid = 0.5 * (lo + hi);
-        const double v = g(mid);
-        if (v > 0) lo = mid; else hi = mid;                         // (NaN at the bound itself -- inf - inf -- counts as beyond the root)
-    }
-    *indel_rate = 0.25 * (lo + hi);                                 // r / 2
-    return PAGAN_OK;
-}
-
 int pagan_msa_node_device(const pagan_msa *m, int32_t k) {
-    if (!m || k < 0 || k >= m->n_leaves - 1) return PAGAN_E_ARG;
-    return m->work[k].device;
+    const NodeWork *w = node_with(m, k, kAny);
+    return w ? w->device : PAGAN_E_ARG;
 }
 
 int pagan_msa_data_type(const pagan_msa *m) { return m ? (m->mf.type == kCodon ? 3 : m->mf.type == kProtein ? 2 : 1) : PAGAN_E_ARG; }

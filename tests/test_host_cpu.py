@@ -1,5 +1,7 @@
 """CPU tests of the host-side pieces (graph builder, anchors, model) against the oracle's
 restatement.  No GPU: the alignment paths fed to the builders come from the oracle DP."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -151,3 +153,112 @@ def test_dna_model_against_numpy(pg):
         assert model.log_score[14, 14] == model.log_score[:4, :4].max()
         assert model.log_score[4, 0] == max(model.log_score[0, 0], model.log_score[2, 0])   # R vs A
     assert np.array_equal(pars, __import__("oracle").dna_parsimony())
+
+
+# ---- the walk's entry points under the oracle's DP behind the batch seam: what one entry check, one switch read and one guard for
+# the per-node accessors must leave as it was
+
+def _seam(oracle):
+    L = oracle.lib()
+
+    def fn(n, jobs, opts, out, user):
+        for k in range(n):
+            j = jobs[k]
+            rc = L.oracle_dp_align(j.left, j.right, j.model, j.band if j.band else None, opts, C.byref(out[k]))
+            if rc != 0:
+                return rc
+        return 0
+    return fn
+
+
+def _seam_walk(oracle, names, seqs, nwk, **opts):
+    msa = host.Msa(names, seqs, nwk, **opts)
+    msa.set_batch_backend(_seam(oracle))
+    return msa
+
+
+@pytest.mark.parametrize("opts, code", [
+    (dict(posterior_decode=1, sample_path=1), abi.PAGAN_E_ARG),          # a decoder together with sample_path
+    (dict(expected_counts=1), abi.PAGAN_E_ARG),                          # counts without a pass
+    (dict(indel_model=(8.0, 8.0, -1, -1)), abi.PAGAN_E_ARG),             # no room for a match at the root's distance
+    (dict(full_probability=1), abi.PAGAN_E_NODEVICE),                    # the seam has no forward/backward pass
+])
+def test_refusals_are_the_same_through_align_and_align_nodes(oracle, pg, opts, code):
+    names, seqs, nwk = synth.evolve_balanced(4, 60, branch=0.05, sub=0.05, indel_start=0.01, mean_len=3, seed=31)
+    H = host._lib()
+    msa = _seam_walk(oracle, names, seqs, nwk, use_anchors=0, **opts)
+    ids = np.array(msa.ready(), np.int32)
+    assert len(ids) == 2
+    assert H.pagan_msa_align(msa._h) == code
+    assert H.pagan_msa_align_nodes(msa._h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32))) == code
+    assert H.pagan_msa_align_nodes(msa._h, 0, None) == code              # (before the list of nodes is looked at)
+    assert msa.remaining == 3 and msa.ready() == list(ids)               # nothing ran
+
+
+def test_host_threads_switch_changes_no_output(oracle, pg, tmp_path, monkeypatch):
+    names, seqs, nwk = synth.evolve_caterpillar(6, 150, seed=17)
+
+    def outputs(tag):
+        msa = _seam_walk(oracle, names, seqs, nwk, use_anchors=1).align()
+        path = str(tmp_path / (tag + ".fas"))
+        msa.write_fasta(path, include_internal=True)
+        with open(path, "rb") as f:
+            fasta = f.read()
+        return msa.alignment_all(), [msa.export_result(msa.n + k).tobytes() for k in range(msa.n_internal)], fasta
+
+    monkeypatch.delenv("PAGAN_HOST_THREADS", raising=False)
+    unset = outputs("unset")
+    monkeypatch.setenv("PAGAN_HOST_THREADS", "1")
+    one = outputs("one")
+    assert len(unset[0]) == 11 and len(unset[1]) == 5 and unset[2].count(b">") == 11
+    assert one == unset
+
+
+def test_node_accessors_on_the_edges(oracle, pg):
+    """Every pagan_msa_node_* entry: PAGAN_E_ARG below and above the internal nodes and for a node not aligned yet, success once it
+    is.  Two keep what they always returned for a node that exists but is not aligned: node_info is PAGAN_OK with an empty
+    result part, node_device is -1.  The five readers of a forward/backward pass stay PAGAN_E_ARG behind the seam, which has no
+    pass (their success is the GPU suite's: tests/test_msa_fb_gpu.py, test_fb_decode_gpu.py, test_fb_counts_gpu.py)."""
+    names, seqs, nwk = synth.evolve_balanced(4, 60, branch=0.05, sub=0.05, indel_start=0.01, mean_len=3, seed=31)
+    H = host._lib()
+    msa = _seam_walk(oracle, names, seqs, nwk, use_anchors=1)
+    h = msa._h
+    d = (C.c_double * 64)()
+    i = (C.c_int32 * 64)()
+    f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    dp, ip = C.cast(d, f64p), C.cast(i, i32p)
+    info, job, res, prob = host.CNodeInfo(), abi.CJob(), abi.CResult(), abi.CModelProb()
+    plain = {"info": lambda k: H.pagan_msa_node_info(h, k, C.byref(info)),
+             "job": lambda k: H.pagan_msa_node_job(h, k, C.byref(job)),
+             "result": lambda k: H.pagan_msa_node_result(h, k, C.byref(res)),
+             "model_prob": lambda k: H.pagan_msa_node_model_prob(h, k, C.byref(prob)),
+             "device": lambda k: H.pagan_msa_node_device(h, k)}
+    of_a_pass = {"fb": lambda k: H.pagan_msa_node_fb(h, k, dp),
+                 "decode": lambda k: H.pagan_msa_node_decode(h, k, dp),
+                 "counts": lambda k: H.pagan_msa_node_counts(h, k, dp, None),
+                 "support": lambda k: H.pagan_msa_node_support(h, k, dp),
+                 "marginals": lambda k: H.pagan_msa_node_marginals(h, k, dp, dp, ip, dp, dp, dp, ip, dp)}
+    n_internal = msa.n_internal
+    assert n_internal == 3
+    for name, call in list(plain.items()) + list(of_a_pass.items()):
+        for k in (-1, n_internal):
+            assert call(k) == abi.PAGAN_E_ARG, (name, k)
+    first = msa.ready()[0] - msa.n                                   # not aligned yet
+    for name, call in list(plain.items()) + list(of_a_pass.items()):
+        if name == "info":
+            assert call(first) == abi.PAGAN_OK and info.node == msa.n + first and info.cells == 0 and info.left_sites == 0
+        else:
+            assert call(first) == abi.PAGAN_E_ARG, name              # (node_device: -1 is also "no device")
+    msa.align_nodes([msa.n + first])
+    assert plain["info"](first) == abi.PAGAN_OK and info.cells > 0 and info.left_sites > 2
+    assert plain["job"](first) == abi.PAGAN_OK and job.left.contents.n_sites == info.left_sites and bool(job.band)
+    assert plain["result"](first) == abi.PAGAN_OK and res.n_cols > 0 and res.cells == info.cells
+    assert plain["model_prob"](first) == abi.PAGAN_OK and prob.n_states == 15
+    assert plain["device"](first) >= 0
+    for name, call in of_a_pass.items():
+        assert call(first) == abi.PAGAN_E_ARG, name
+    # null outputs are refused as before, on an aligned node too
+    assert H.pagan_msa_node_info(h, first, None) == abi.PAGAN_E_ARG and H.pagan_msa_node_job(h, first, None) == abi.PAGAN_E_ARG
+    assert H.pagan_msa_node_result(h, first, None) == abi.PAGAN_E_ARG and H.pagan_msa_node_model_prob(h, first, None) == abi.PAGAN_E_ARG
+    other = [k for k in range(n_internal) if k != first and msa.n + k in msa.ready()][0]
+    assert plain["result"](other) == abi.PAGAN_E_ARG                 # its sibling is still to come
