@@ -492,7 +492,8 @@ int64_t pagan_msa_alignment_tree(const pagan_msa *m, char *newick_out, int64_t c
  * int32.  Root: col_lik = sum_s pi[s] L_root[s], s ascending (the exact 1 for a column without any data).  Down, O_root = pi; for child c of v with sibling b,
  * W[s] = O_v[s] m_b[s] (m_b the sibling's message a or b above), O_c[t] = sum_s W[s] P_c[s][t] with s ascending, rescaled the
  * same way.  Posterior of v: q[s] = L_v[s] O_v[s] divided by sum_s q[s] (s ascending; all zero where that sum is zero).  Tie rule
- * of `best`: the first maximum in state order (a later state replaces it only when strictly larger).  Every sum has a fixed
+ * of `best`: the first maximum in state order (a later state replaces it only when strictly larger); in a column that cannot
+ * happen (likelihood 0, every q[s] zero) that is state 0, with best_p 0.  Every sum has a fixed
  * order and no contraction: the outputs are bit-identical from run to run and for every chunk size.
  * The device works on chunks of columns (pagan_anc_info.chunk_cols, a multiple of 64), so its footprint is bounded by the chunk,
  * not by the alignment; PAGAN_ANC_CHUNK_COLS in the environment forces the chunk size.  Device, errors: as for the guide trees

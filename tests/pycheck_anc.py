@@ -234,6 +234,100 @@ def balanced4(t):
     return [0, 2, 4], [1, 3, 5], list(t) + [0.0]
 
 
+def balanced(n, rng, lo=0.02, hi=0.6):
+    """A fully balanced tree of n = 2^k leaves, level by level: (0, 1) is node n, (2, 3) node n + 1, ..., then the pairs of
+    those.  Every internal node above the lowest level has two internal children."""
+    level, left, right = list(range(n)), [], []
+    while len(level) > 1:
+        nxt = []
+        for a, b in zip(level[0::2], level[1::2]):
+            nxt.append(n + len(left))
+            left.append(a)
+            right.append(b)
+        level = nxt
+    branch = [float(t) for t in rng.uniform(lo, hi, 2 * n - 1)]
+    branch[-1] = 0.0
+    return left, right, branch
+
+
+def cherry_spine(m, rng, lengths=(0.05, 0.1, 0.2, 0.3)):
+    """A spine of m cherries, 2 m leaves: cherry i is (leaf 2 i, leaf 2 i + 1); cherry 0 is the spine's lowest node and spine
+    node i = (spine node i - 1, cherry i), so both children of every spine node above it are internal.  Ids in the walk's order:
+    cherry i is node n + 2 i - 1, spine node i is n + 2 i, the root n + 2 (m - 1) = 2 n - 2.  The branch lengths are drawn from
+    `lengths`, so that as many matrices are in play."""
+    n = 2 * m
+    left, right = [0], [1]
+    for i in range(1, m):
+        left.append(2 * i)
+        right.append(2 * i + 1)
+        left.append(n + 2 * i - 2)
+        right.append(n + 2 * i - 1)
+    branch = [float(lengths[j]) for j in rng.integers(len(lengths), size=2 * n - 1)]
+    branch[-1] = 0.0
+    return left, right, branch
+
+
+def depths(left, right):
+    """[n - 1]: the edges between the root and internal node n + k."""
+    n = len(left) + 1
+    d = [0] * (n - 1)
+    for k in range(n - 2, -1, -1):
+        for c in (left[k], right[k]):
+            if c >= n:
+                d[c - n] = d[k] + 1
+    return d
+
+
+def deepest(left, right, count=1):
+    """The ids of the `count` internal nodes farthest from the root, the farthest first (the lower id first among equals)."""
+    n, d = len(left) + 1, depths(left, right)
+    return [n + k for k in sorted(range(n - 1), key=lambda k: (-d[k], k))[:count]]
+
+
+def internal_children(left, right):
+    """[n - 1]: how many of node n + k's two children are internal nodes."""
+    n = len(left) + 1
+    return [(left[k] >= n) + (right[k] >= n) for k in range(n - 1)]
+
+
+def outside_without_rescaling(left, right, branch, rows, data_type, base_freq=None):
+    """What the down pass would hold if it did not rescale, in plain fp64 numpy: the partials of the up pass rescaled by the power
+    of two of their largest entry as the header says, the outside vectors O_c = P_c^T (O_v m_b) left as they come.  Returns
+    ({internal node: [S, L] doubles}, has_data).  Not a reading of anything the device returns: it says how deep a tree has to be
+    before the rescaling of the outside vectors matters at all (tests/test_anc_cpu.py)."""
+    n, S = len(rows), STATES[data_type]
+    mats, pi = {}, None
+    for t in set(float(b) for b in branch[:-1]):
+        mats[t], pi = host.anc_pmatrix(data_type, t, base_freq)
+    sets = [leaf_sets(r, data_type) for r in rows]
+    L = len(sets[0])
+    has = _has_data(left, right, sets)
+    part = {}
+    for k in range(n):
+        v = np.zeros((S, L))
+        for col, s in enumerate(sets[k]):
+            for t in (s or ()):
+                v[t, col] = 1.0
+        part[k] = v
+
+    def message(child):
+        m = mats[float(branch[child])].dot(part[child])
+        m[:, has[child] == 0] = 1.0
+        return m
+
+    for k in range(n - 1):
+        p = message(left[k]) * message(right[k])
+        top = p.max(axis=0)
+        e = np.where((top > 0) & (has[n + k] != 0), np.frexp(top)[1], 0)
+        part[n + k] = np.ldexp(p, -e)
+    outs = {2 * n - 2: np.repeat(np.asarray(pi, np.float64)[:, None], L, axis=1)}
+    for k in range(n - 2, -1, -1):
+        for c, b in ((left[k], right[k]), (right[k], left[k])):
+            if c >= n:
+                outs[c] = mats[float(branch[c])].T.dot(outs[n + k] * message(b))
+    return outs, has
+
+
 def random_rows(n, L, data_type, seed, share=0.15):
     """n rows of L columns: core letters, and `share` characters that are gaps, ambiguity codes or missing data.  Column 1
     (where there is one) is all gaps and column 2 holds a single letter."""
@@ -269,7 +363,24 @@ def case(name):
     """A named shape the CPU and the GPU tests share: dict(left, right, branch, rows, data_type, base_freq, reading)."""
     kind, _, arg = name.partition(":")
     bf = BASE_FREQ
-    if kind == "edge":                                   # n = 5 against the reading by definition
+    if kind in ("zero", "impossible") and arg:           # `zero` and `impossible` on the four-wave kernels, a handful of columns
+        t = {"protein": 2, "codon": 3}[arg]
+        if kind == "zero":
+            left, right, branch = balanced4([0.0, 0.3, 0.11, 0.0, 0.0, 0.27])
+            rows = random_rows(4, 9, t, 62 + t)
+        else:                                            # column 0 can happen, 1 and 2 cannot, 3 (the same letter) and 4 (one missing) can
+            left, right, branch = balanced4([0.0, 0.0, 0.1, 0.2, 0.3, 0.4])
+            cells = [[0, 1, 0, 17, None], [0, 2, 1, 17, 11], [0, 3, 3, 18, 10], [0, 0, 4, 19, 12]]
+            gap = "---" if t == 3 else "-"
+            rows = ["".join(gap if x is None else state_text(3 * x if t == 3 else x, t) for x in r) for r in cells]
+        bf = None
+        reading = pruning(left, right, branch, rows, t)
+    elif kind == "chunks" and arg:                       # three chunks of 64 columns, the last two columns wide, with a reading
+        left, right, branch = random_tree(8, np.random.default_rng(66))
+        t = {"protein": 2}[arg]
+        rows, bf = random_rows(8, 130, t, 67), None
+        reading = pruning(left, right, branch, rows, t)
+    elif kind == "edge":                                 # n = 5 against the reading by definition
         L = int(arg)
         left, right, branch = random_tree(5, np.random.default_rng(500 + L))
         rows, t = random_rows(5, L, 1, 600 + L), 1
@@ -301,13 +412,34 @@ def case(name):
         left, right, branch = random_tree(4, np.random.default_rng(49))
         rows, t, bf = random_rows(4, 65, 3, 50), 3, None
         reading = pruning(left, right, branch, rows, 3)
+    elif kind == "deep" and arg == "cherries":           # the sibling of every internal spine child is internal; deep enough to underflow
+        left, right, branch = cherry_spine(500, np.random.default_rng(51))
+        rows, t = random_rows(1000, 8, 1, 52, share=0.1), 1
+        reading = pruning(left, right, branch, rows, 1, bf)
+    elif kind == "deep":                                 # caterpillars whose outside vectors leave fp64's range without rescaling
+        t = {"dna": 1, "protein": 2, "codon": 3}[arg]
+        n, L = {1: (600, 8), 2: (260, 4), 3: (190, 2)}[t]
+        left, right, branch = caterpillar(n, 0.2)
+        rows, bf = random_rows(n, L, t, 52 + t, share=0.1), bf if t == 1 else None
+        reading = pruning(left, right, branch, rows, t, bf)
+    elif kind == "balanced":                             # half the internal nodes have two internal children
+        t = {"protein": 2, "codon": 3}[arg]
+        n, L = {2: (16, 65), 3: (8, 66)}[t]
+        left, right, branch = balanced(n, np.random.default_rng(56 + t))
+        rows, bf = random_rows(n, L, t, 58 + t), None
+        reading = pruning(left, right, branch, rows, t)
     else:
         raise KeyError(name)
     return {"left": left, "right": right, "branch": branch, "rows": rows, "data_type": t, "base_freq": bf, "reading": reading}
 
 
 EDGE_COLUMNS = (1, 63, 64, 65, 130)
-POSTERIOR_CASES = ["edge:%d" % L for L in EDGE_COLUMNS] + ["zero", "long", "protein", "codon"]
+DEEP_CASES = ["deep:dna", "deep:protein", "deep:codon", "deep:cherries"]
+BALANCED_CASES = ["balanced:protein", "balanced:codon"]
+# every case whose posteriors and `best` are compared cell by cell.  The impossible:* cases are not among them, as `impossible`
+# never was: a column that cannot happen has no posterior to decide, and the tests assert its zeros outright.
+POSTERIOR_CASES = (["edge:%d" % L for L in EDGE_COLUMNS] + ["zero", "long", "protein", "codon"] + DEEP_CASES + BALANCED_CASES
+                   + ["zero:protein", "zero:codon", "chunks:protein"])
 
 
 def undecided_share(c):

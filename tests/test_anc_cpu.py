@@ -68,6 +68,47 @@ def test_every_shared_case_keeps_the_tie_condition():
         assert A.undecided_share(A.case(name)) <= 0.01, name
 
 
+@pytest.mark.parametrize("name", A.DEEP_CASES)
+def test_deep_cases_underflow_without_rescaling(name):
+    """What the deep:* cases are for: with the outside vectors left unscaled (plain fp64, the partials rescaled as the header
+    says), the vector at the deepest internal node lies below the normal range, 2^-1022, in a column that holds data.  A
+    change of seed or size that makes the case shallow fails here, not silently on the device."""
+    c = A.case(name)
+    n = len(c["rows"])
+    host.anc_check_tree(c["left"], c["right"], c["branch"])
+    outs, has = A.outside_without_rescaling(c["left"], c["right"], c["branch"], c["rows"], c["data_type"], c["base_freq"])
+    node = A.deepest(c["left"], c["right"])[0]
+    top = outs[node].max(axis=0)
+    under = [col for col in range(len(top)) if has[2 * n - 2, col] and top[col] < 2.0 ** -1022]
+    assert under, (name, top)
+    assert np.array_equal(has, c["reading"]["has_data"])
+
+
+def test_balanced_and_cherry_cases_have_nodes_with_two_internal_children():
+    for name in A.BALANCED_CASES:
+        c = A.case(name)
+        host.anc_check_tree(c["left"], c["right"], c["branch"])
+        kids = A.internal_children(c["left"], c["right"])
+        assert 3 * kids.count(2) >= len(kids), (name, kids)
+    c = A.case("deep:cherries")
+    host.anc_check_tree(c["left"], c["right"], c["branch"])                       # the walk's ids: children first, the root 2 n - 2
+    n, kids = len(c["rows"]), A.internal_children(c["left"], c["right"])
+    assert kids.count(0) == n // 2 and kids.count(1) == 0 and kids.count(2) == n // 2 - 1     # cherries, and spine nodes over two internal nodes
+    spine, v = 0, 2 * n - 2                                                        # down the spine: the left child, while it has children of its own
+    while kids[v - n] == 2:
+        spine, v = spine + 1, c["left"][v - n]
+    assert spine == n // 2 - 1 and v == n
+    assert len(set(c["branch"][:-1])) >= 3                                         # several matrices in play
+
+
+def test_impossible_cases_on_the_wider_alphabets():
+    for name in ("impossible:protein", "impossible:codon"):
+        c = A.case(name)
+        lik = c["reading"]["lik"]
+        assert [x == 0 for x in lik] == [False, True, True, False, False], name
+        assert all(x == 0 for k in range(3) for col in (1, 2) for x in c["reading"]["post"][k][col])
+
+
 # ---- the transition matrices -------------------------------------------------------------------------------------------
 
 TIMES = (0.05, 0.2, 0.25, 0.7, 0.9, 50.0)

@@ -63,9 +63,23 @@ def codon_walk():
     return names, seqs, balanced_newick(names, [0.05, 0.12, 0.07, 0.15, 0.04, 0.09]), {"use_anchors": 0, "data_type": 3}, 3
 
 
+_walks = {}
+
+
+def walked(kind):
+    """The walk, its ancestral states and their reading, made once a kind."""
+    if kind not in _walks:
+        _walks[kind] = make_walk(kind)
+    return _walks[kind]
+
+
 @pytest.fixture(scope="module", params=["dna", "codon"])
 def walk(request):
-    names, seqs, newick, opts, data_type = dna_walk() if request.param == "dna" else codon_walk()
+    return walked(request.param)
+
+
+def make_walk(kind):
+    names, seqs, newick, opts, data_type = dna_walk() if kind == "dna" else codon_walk()
     msa = host.Msa(names, seqs, newick, **opts).align()
     before = msa.alignment_all()
     anc = msa.ancestral()
@@ -159,6 +173,23 @@ def test_fasta(walk, tmp_path):
     assert all(rows[name] == row for name, row in b)
     anc.write_fasta(tmp_path / "anc7.fas", chars_by_line=7)
     assert entries(tmp_path / "anc7.fas") == b and max(len(x) for x in open(tmp_path / "anc7.fas").read().split("\n")) <= 7
+
+
+def test_chunks_in_the_walk_change_no_byte(monkeypatch):
+    """The DNA walk once more, its ancestral states in chunks of 64 columns: rows, best, best_p and the log likelihoods are the
+    bytes of the walk that ran in one chunk."""
+    one = walked("dna")
+    assert one["anc"].info["chunks"] == 1
+    names, seqs, newick, opts, _ = dna_walk()
+    msa = host.Msa(names, seqs, newick, **opts).align()
+    assert msa.alignment_all() == one["before"]
+    monkeypatch.setenv("PAGAN_ANC_CHUNK_COLS", "64")
+    anc = msa.ancestral()
+    assert anc.info["chunk_cols"] == 64 and anc.info["chunks"] == (anc.info["columns"] + 63) // 64 > 1
+    assert [anc.row(v) for v in range(2 * one["n"] - 1)] == [one["anc"].row(v) for v in range(2 * one["n"] - 1)]
+    for a, b in ((anc.best, one["anc"].best), (anc.best_p, one["anc"].best_p), (anc.col_loglik, one["anc"].col_loglik)):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    assert np.float64(anc.loglik).tobytes() == np.float64(one["anc"].loglik).tobytes()
 
 
 def host_error():
