@@ -13,8 +13,11 @@ There is no CPU fallback: if the library or a HIP device is missing the calls ra
 import ctypes as C
 import os
 
+import numpy as np
+
 from . import abi
 from .abi import Band, Graph, Model, ModelProb, Result  # noqa: F401
+from .abi import _dp, _f64p, _i32p, _i64p, _ip, _u8p, _u32p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PAGAN_DP_LIB: a diagnostic build (tools/build_stamps.sh writes libpagan_dp_stats.so) instead of the product library
@@ -28,13 +31,27 @@ class PaganError(RuntimeError):
         self.code = code
 
 
+def check(rc, what):
+    """The one error path of the C ABI: a negative return value is a PAGAN_E_* code and raises; anything else (PAGAN_OK, a
+    count, a size) is handed back."""
+    if rc < 0:
+        raise PaganError(int(rc), what)
+    return rc
+
+
+def declare(L):
+    """Attach argtypes / restype of every entry point of both headers (abi.PROTOTYPES, host.PROTOTYPES) to the library L."""
+    from . import host           # (host imports PaganError, check and lib from here at its top: not before they exist)
+    return abi.declare(abi.declare(L), host.PROTOTYPES)
+
+
 def lib():
-    """The loaded C-ABI library.  Raises if it has not been built (see build.py)."""
+    """The loaded C-ABI library, every entry point declared.  Raises if it has not been built (see build.py)."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError("libpagan_dp.so is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        _lib = abi.declare(C.CDLL(LIB_PATH))
+        _lib = declare(C.CDLL(LIB_PATH))
     return _lib
 
 
@@ -42,9 +59,27 @@ def device_count():
     return lib().pagan_dp_device_count()
 
 
-def _check(code, what):
-    if code != abi.PAGAN_OK:
-        raise PaganError(code, what)
+class Handle:
+    """Owner of one handle of the library: _h, the entry point that destroys it (_destroy), close() and __del__.  A handle
+    that is borrowed (owned = False) is left alone."""
+    _destroy = None
+    owned = True
+
+    def close(self):
+        if self.owned and self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _band(band):
+    """The band argument of an entry point: NULL for a full matrix."""
+    return C.byref(band.c) if band is not None else None
 
 
 def _jobs_array(jobs):
@@ -65,7 +100,7 @@ def align_batch(jobs, flags=0, device=-1):
     res = (abi.CResult * len(jobs))()
     rc = L.pagan_dp_align_batch(len(jobs), arr, C.byref(opts), res)
     try:
-        _check(rc, "pagan_dp_align_batch")
+        check(rc, "pagan_dp_align_batch")
         return [Result(r) for r in res]
     finally:
         for r in res:
@@ -78,15 +113,15 @@ def align(left, right, model, band=None, flags=0, device=-1):
     opts = abi.COpts(flags, device)
     res = abi.CResult()
     rc = L.pagan_dp_align(C.byref(left.c), C.byref(right.c), C.byref(model.c),
-                          C.byref(band.c) if band is not None else None, C.byref(opts), C.byref(res))
+                          _band(band), C.byref(opts), C.byref(res))
     try:
-        _check(rc, "pagan_dp_align")
+        check(rc, "pagan_dp_align")
         return Result(res)
     finally:
         L.pagan_result_free(C.byref(res))
 
 
-class FullProbability:
+class FullProbability(Handle):
     """Forward/backward matrices of one alignment on the GPU (the reference's compute_full_score pass:
     --full-probability, posteriors, --sample-path), in log space.
 
@@ -99,9 +134,9 @@ class FullProbability:
         fb.expected_counts()            expected transition, end and emission counts (pg_fb_counts)
     """
 
+    _destroy = "pagan_fb_destroy"
+
     def __init__(self, left, right, model_prob, band=None, device=-1, _handle=None):
-        import numpy as np
-        self._np = np
         self._L = lib()
         self.left, self.right, self.model, self.band = left, right, model_prob, band     # keep the arrays alive
         if _handle is not None:                          # (full_probability_batch: the pair ran in a batch's launches)
@@ -109,22 +144,22 @@ class FullProbability:
         else:
             opts = abi.COpts(0, device)
             self._h = C.c_void_p()
-            _check(self._L.pagan_fb_run(C.byref(left.c), C.byref(right.c), C.byref(model_prob.c),
-                                        C.byref(band.c) if band is not None else None, C.byref(opts), C.byref(self._h)),
-                   "pagan_fb_run")
+            check(self._L.pagan_fb_run(C.byref(left.c), C.byref(right.c), C.byref(model_prob.c),
+                                       _band(band), C.byref(opts), C.byref(self._h)),
+                  "pagan_fb_run")
         a, b, c = C.c_double(), C.c_double(), C.c_int64()
-        _check(self._L.pagan_fb_totals(self._h, C.byref(a), C.byref(b), C.byref(c)), "pagan_fb_totals")
+        check(self._L.pagan_fb_totals(self._h, C.byref(a), C.byref(b), C.byref(c)), "pagan_fb_totals")
         self.log_fwd, self.log_bwd, self.cells = a.value, b.value, c.value
         kms = (C.c_double * 2)()
-        _check(self._L.pagan_fb_kernel_ms(self._h, kms), "pagan_fb_kernel_ms")
+        check(self._L.pagan_fb_kernel_ms(self._h, kms), "pagan_fb_kernel_ms")
         self.forward_ms, self.backward_ms = kms[0], kms[1]
         self.groups = self._L.pagan_fb_groups(self._h)       # 1: one-workgroup sweeps; > 1: 64 x 64 blocks, a wave each; 0: LDS-ring sweeps
         self.schedule = self._L.pagan_fb_schedule(self._h)   # 0 one-workgroup kernels, 1 blocks, 2 LDS ring (plain sequences), 3 deep ring (graph pairs in a tunnel)
         self.shape = (left.n_sites - 1, right.n_sites - 1, 3)
 
     def _dump(self, which):
-        out = self._np.zeros(self.shape, self._np.float64)
-        _check(self._L.pagan_fb_dump(self._h, which, out.ctypes.data_as(C.POINTER(C.c_double))), "pagan_fb_dump")
+        out = np.zeros(self.shape, np.float64)
+        check(self._L.pagan_fb_dump(self._h, which, _dp(out)), "pagan_fb_dump")
         return out
 
     def log_forward(self):
@@ -137,18 +172,16 @@ class FullProbability:
         return self._dump(2)
 
     def posterior_cells(self, cells):
-        c = self._np.ascontiguousarray(cells, self._np.int32).reshape(-1, 3)
-        out = self._np.zeros(c.shape[0], self._np.float64)
-        _check(self._L.pagan_fb_posterior_cells(self._h, c.shape[0], c.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                out.ctypes.data_as(C.POINTER(C.c_double))), "pagan_fb_posterior_cells")
+        c = np.ascontiguousarray(cells, np.int32).reshape(-1, 3)
+        out = np.zeros(c.shape[0], np.float64)
+        check(self._L.pagan_fb_posterior_cells(self._h, c.shape[0], _ip(c), _dp(out)), "pagan_fb_posterior_cells")
         return out
 
     def path_support(self, cols):
         """pagan_fb_path_support: the posterior of every column's own cell along a path (Result.cols), -1 at skip columns."""
-        c = self._np.ascontiguousarray(cols, self._np.int32).reshape(-1, 3)
-        out = self._np.zeros(c.shape[0], self._np.float64)
-        _check(self._L.pagan_fb_path_support(self._h, c.ctypes.data_as(C.POINTER(abi.CCol)), c.shape[0],
-                                             out.ctypes.data_as(C.POINTER(C.c_double))), "pagan_fb_path_support")
+        c = np.ascontiguousarray(cols, np.int32).reshape(-1, 3)
+        out = np.zeros(c.shape[0], np.float64)
+        check(self._L.pagan_fb_path_support(self._h, c.ctypes.data_as(abi.colp), c.shape[0], _dp(out)), "pagan_fb_path_support")
         return out
 
     def site_marginals(self, rows=True, columns=True):
@@ -159,19 +192,18 @@ class FullProbability:
     def post_ms(self):
         """Device ms of the handle's last gather, row pass, column pass."""
         ms = (C.c_double * 3)()
-        _check(self._L.pagan_fb_post_ms(self._h, ms), "pagan_fb_post_ms")
+        check(self._L.pagan_fb_post_ms(self._h, ms), "pagan_fb_post_ms")
         return ms[0], ms[1], ms[2]
 
     def sample_path(self, u):
         """(Result, visited cells end -> start as rows (i, j, state))."""
-        uu = self._np.ascontiguousarray(u, self._np.float64)
+        uu = np.ascontiguousarray(u, np.float64)
         res = abi.CResult()
-        vis = self._np.zeros((self.shape[0] + self.shape[1] + 2, 3), self._np.int32)
+        vis = np.zeros((self.shape[0] + self.shape[1] + 2, 3), np.int32)
         n = C.c_int32()
-        rc = self._L.pagan_fb_sample_path(self._h, uu.ctypes.data_as(C.POINTER(C.c_double)), int(uu.shape[0]), C.byref(res),
-                                          vis.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n))
+        rc = self._L.pagan_fb_sample_path(self._h, _dp(uu), int(uu.shape[0]), C.byref(res), _ip(vis), C.byref(n))
         try:
-            _check(rc, "pagan_fb_sample_path")
+            check(rc, "pagan_fb_sample_path")
             return Result(res), vis[:n.value].copy()
         finally:
             self._L.pagan_result_free(C.byref(res))
@@ -194,28 +226,17 @@ class FullProbability:
     def counts_ms(self):
         """Device ms of the handle's last counts pass, booked at the batch's first pair."""
         ms = C.c_double()
-        _check(self._L.pagan_fb_counts_ms(self._h, C.byref(ms)), "pagan_fb_counts_ms")
+        check(self._L.pagan_fb_counts_ms(self._h, C.byref(ms)), "pagan_fb_counts_ms")
         return ms.value
 
-    def close(self):
-        if self._h:
-            self._L.pagan_fb_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SampledPaths:
+class SampledPaths(Handle):
     """pagan_fb_samples: the paths one pg_fb_sample launch drew for a pair -- summaries on the host, traces on the device until
     a path is asked for.  Keeps its FullProbability (and with it the graphs result() reads) alive."""
 
+    _destroy = "pagan_fb_samples_destroy"
+
     def __init__(self, fb, handle, n_paths, traces):
-        import numpy as np
-        self._np = np
         self._L = lib()
         self._fb = fb
         self._h = handle
@@ -223,33 +244,29 @@ class SampledPaths:
         self.traces = bool(traces)
         self.max_steps = fb.shape[0] + fb.shape[1]
         ms = C.c_double()
-        _check(self._L.pagan_fb_samples_ms(self._h, C.byref(ms)), "pagan_fb_samples_ms")
+        check(self._L.pagan_fb_samples_ms(self._h, C.byref(ms)), "pagan_fb_samples_ms")
         self.ms = ms.value               # device ms of pg_fb_sample, booked at the batch's first pair
 
     def summary(self):
         """dict of status, n_steps, n_m, n_x, n_y (int32 [n_paths]) and log_q (float64 [n_paths])."""
-        np = self._np
-        i32p = C.POINTER(C.c_int32)
         out = {k: np.zeros(self.n_paths, np.int32) for k in ("status", "n_steps", "n_m", "n_x", "n_y")}
         out["log_q"] = np.zeros(self.n_paths, np.float64)
-        _check(self._L.pagan_fb_samples_summary(self._h, *[out[k].ctypes.data_as(i32p) for k in ("status", "n_steps", "n_m", "n_x", "n_y")],
-                                                out["log_q"].ctypes.data_as(C.POINTER(C.c_double))), "pagan_fb_samples_summary")
+        check(self._L.pagan_fb_samples_summary(self._h, *[_ip(out[k]) for k in ("status", "n_steps", "n_m", "n_x", "n_y")],
+                                               _dp(out["log_q"])), "pagan_fb_samples_summary")
         return out
 
     def visited(self, p):
         """Path p's cells end -> start as rows (i, j, state): FullProbability.sample_path's second value."""
-        vis = self._np.zeros((self.max_steps + 1, 3), self._np.int32)
+        vis = np.zeros((self.max_steps + 1, 3), np.int32)
         n = C.c_int32()
-        _check(self._L.pagan_fb_samples_visited(self._h, int(p), vis.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)),
-               "pagan_fb_samples_visited")
+        check(self._L.pagan_fb_samples_visited(self._h, int(p), _ip(vis), C.byref(n)), "pagan_fb_samples_visited")
         return vis[:n.value].copy()
 
     def visited_all(self):
         """Every path's cells in one copy of the trace buffer: ([n_paths, Lx + Ly, 3] int32, [n_paths] step counts)."""
-        vis = self._np.zeros((self.n_paths, self.max_steps, 3), self._np.int32)
-        n = self._np.zeros(self.n_paths, self._np.int32)
-        _check(self._L.pagan_fb_samples_visited_all(self._h, vis.ctypes.data_as(C.POINTER(C.c_int32)), n.ctypes.data_as(C.POINTER(C.c_int32))),
-               "pagan_fb_samples_visited_all")
+        vis = np.zeros((self.n_paths, self.max_steps, 3), np.int32)
+        n = np.zeros(self.n_paths, np.int32)
+        check(self._L.pagan_fb_samples_visited_all(self._h, _ip(vis), _ip(n)), "pagan_fb_samples_visited_all")
         return vis, n
 
     def result(self, p):
@@ -257,30 +274,19 @@ class SampledPaths:
         res = abi.CResult()
         rc = self._L.pagan_fb_samples_result(self._h, int(p), C.byref(res))
         try:
-            _check(rc, "pagan_fb_samples_result")
+            check(rc, "pagan_fb_samples_result")
             return Result(res)
         finally:
             self._L.pagan_result_free(C.byref(res))
 
-    def close(self):
-        if self._h:
-            self._L.pagan_fb_samples_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DecodedPath:
+class DecodedPath(Handle):
     """pagan_fb_decoded: the maximum expected accuracy path of one pair -- the summary on the host, the trace (and, with
     keep_matrix, the score matrix) on the device.  Keeps its FullProbability (and with it the graphs result() reads) alive."""
 
+    _destroy = "pagan_fb_decoded_destroy"
+
     def __init__(self, fb, handle, keep_matrix):
-        import numpy as np
-        self._np = np
         self._L = lib()
         self._fb = fb
         self._h = handle
@@ -292,16 +298,16 @@ class DecodedPath:
         """dict of status, objective, n_steps, n_m, n_x, n_y and schedule (0 pg_fb_decode_fill, 1 pg_fb_ring_decode)."""
         status, steps, schedule, obj = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
         counts = (C.c_int32 * 3)()
-        _check(self._L.pagan_fb_decoded_summary(self._h, C.byref(status), C.byref(obj), C.byref(steps), counts, C.byref(schedule)),
-               "pagan_fb_decoded_summary")
+        check(self._L.pagan_fb_decoded_summary(self._h, C.byref(status), C.byref(obj), C.byref(steps), counts, C.byref(schedule)),
+              "pagan_fb_decoded_summary")
         return {"status": status.value, "objective": obj.value, "n_steps": steps.value, "n_m": counts[0], "n_x": counts[1],
                 "n_y": counts[2], "schedule": schedule.value}
 
     def visited(self):
         """The path's cells end -> start as rows (i, j, state): FullProbability.sample_path's second value."""
-        vis = self._np.zeros((self.max_steps + 1, 3), self._np.int32)
+        vis = np.zeros((self.max_steps + 1, 3), np.int32)
         n = C.c_int32()
-        _check(self._L.pagan_fb_decoded_visited(self._h, vis.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)), "pagan_fb_decoded_visited")
+        check(self._L.pagan_fb_decoded_visited(self._h, _ip(vis), C.byref(n)), "pagan_fb_decoded_visited")
         return vis[:n.value].copy()
 
     def result(self):
@@ -309,33 +315,22 @@ class DecodedPath:
         res = abi.CResult()
         rc = self._L.pagan_fb_decoded_result(self._h, C.byref(res))
         try:
-            _check(rc, "pagan_fb_decoded_result")
+            check(rc, "pagan_fb_decoded_result")
             return Result(res)
         finally:
             self._L.pagan_result_free(C.byref(res))
 
     def matrix(self):
         """The score matrix [Lx, Ly, 3] (X, Y, M), -inf outside the band; needs keep_matrix."""
-        out = self._np.zeros(self.shape, self._np.float64)
-        _check(self._L.pagan_fb_decoded_dump(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), "pagan_fb_decoded_dump")
+        out = np.zeros(self.shape, np.float64)
+        check(self._L.pagan_fb_decoded_dump(self._h, _dp(out)), "pagan_fb_decoded_dump")
         return out
 
     def ms(self):
         """Device ms of the fill and of the trace, booked at the batch's first pair."""
         ms = (C.c_double * 2)()
-        _check(self._L.pagan_fb_decoded_ms(self._h, ms), "pagan_fb_decoded_ms")
+        check(self._L.pagan_fb_decoded_ms(self._h, ms), "pagan_fb_decoded_ms")
         return ms[0], ms[1]
-
-    def close(self):
-        if self._h:
-            self._L.pagan_fb_decoded_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def decode_batch(fbs, gap_weight=0.5, keep_matrix=False):
@@ -345,33 +340,30 @@ def decode_batch(fbs, gap_weight=0.5, keep_matrix=False):
     n = len(fbs)
     handles = (C.c_void_p * n)(*[fb._h for fb in fbs])
     outs = (C.c_void_p * n)()
-    _check(L.pagan_fb_decode_batch(n, handles, float(gap_weight), abi.DECODE_KEEP_MATRIX if keep_matrix else 0, outs), "pagan_fb_decode_batch")
+    check(L.pagan_fb_decode_batch(n, handles, float(gap_weight), abi.DECODE_KEEP_MATRIX if keep_matrix else 0, outs), "pagan_fb_decode_batch")
     return [DecodedPath(fb, C.c_void_p(outs[k]), keep_matrix) for k, fb in enumerate(fbs)]
 
 
 def fb_decode_route(left, right, band=None):
     """pagan_fb_debug_decode_route (host only): 1 when the pair's decode would fill on the LDS ring, 0 on pg_fb_decode_fill."""
-    rc = lib().pagan_fb_debug_decode_route(C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None)
-    _check(min(rc, 0), "pagan_fb_debug_decode_route")
-    return rc
+    return check(lib().pagan_fb_debug_decode_route(C.byref(left.c), C.byref(right.c), _band(band)), "pagan_fb_debug_decode_route")
 
 
 def fb_decode_predict_bytes(left_sites, right_sites, band=None):
-    return lib().pagan_fb_decode_predict_bytes(left_sites, right_sites, C.byref(band.c) if band is not None else None)
+    return lib().pagan_fb_decode_predict_bytes(left_sites, right_sites, _band(band))
 
 
 def sample_paths_batch(fbs, seed, nodes, n_paths, traces=True):
     """pagan_fb_sample_paths_batch: n_paths paths for each FullProbability of one device in one launch (node k's key is
     (seed, nodes[k])) -> [SampledPaths, ...]."""
-    import numpy as np
     L = lib()
     n = len(fbs)
     ids = np.ascontiguousarray(nodes, np.int32)
     assert ids.shape == (n,)
     handles = (C.c_void_p * n)(*[fb._h for fb in fbs])
     outs = (C.c_void_p * n)()
-    _check(L.pagan_fb_sample_paths_batch(n, handles, int(seed) & 0xFFFFFFFFFFFFFFFF, ids.ctypes.data_as(C.POINTER(C.c_int32)), int(n_paths),
-                                         0 if traces else abi.SAMPLE_NO_TRACES, outs), "pagan_fb_sample_paths_batch")
+    check(L.pagan_fb_sample_paths_batch(n, handles, int(seed) & 0xFFFFFFFFFFFFFFFF, _ip(ids), int(n_paths),
+                                        0 if traces else abi.SAMPLE_NO_TRACES, outs), "pagan_fb_sample_paths_batch")
     return [SampledPaths(fb, C.c_void_p(outs[k]), n_paths, traces) for k, fb in enumerate(fbs)]
 
 
@@ -382,40 +374,31 @@ def fb_sample_predict_bytes(left_sites, right_sites, n_paths, traces=True):
 def debug_tiles(left, right, band=None):
     """Diagnostic (host only): (tile side, [(tile row, tile column), ...]) the wide-matrix fill kernel would be
     launched over for this job; an empty list when the job cannot be tiled."""
-    import numpy as np
     L = lib()
     cap = ((left.n_sites + 62) // 64 + 1) * ((right.n_sites + 62) // 64 + 1)
     out = np.zeros(2 * cap, np.int32)
     side = C.c_int32()
-    n = L.pagan_dp_debug_tiles(C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None,
-                               out.ctypes.data_as(C.POINTER(C.c_int32)), cap, C.byref(side))
-    _check(min(n, 0), "pagan_dp_debug_tiles")
+    n = check(L.pagan_dp_debug_tiles(C.byref(left.c), C.byref(right.c), _band(band), _ip(out), cap, C.byref(side)), "pagan_dp_debug_tiles")
     return side.value, [tuple(int(v) for v in out[2 * k: 2 * k + 2]) for k in range(min(n, cap))]
 
 
 def debug_tiles_staircase(tiles):
     """Diagnostic (host only): whether a list of (tile row, tile column) pairs is a staircase (include/pagan_dp.h)."""
-    import numpy as np
     a = np.ascontiguousarray(np.array(tiles, np.int32).reshape(-1, 2))
-    rc = lib().pagan_dp_debug_tiles_staircase(a.ctypes.data_as(C.POINTER(C.c_int32)), len(a))
-    _check(min(rc, 0), "pagan_dp_debug_tiles_staircase")
-    return bool(rc)
+    return bool(check(lib().pagan_dp_debug_tiles_staircase(_ip(a), len(a)), "pagan_dp_debug_tiles_staircase"))
 
 
 def debug_compact(left, right, band=None):
     """Diagnostic (host only): the compacted numbering the library aligns graphs with many dead sites in:
     dict with keep_left / keep_right (compacted site -> caller's site), slot_left / slot_right (per kept bwd edge: its position
     in the caller's list of its site), upper / lower (the band over the compacted matrices)."""
-    import numpy as np
     L = lib()
-    p32 = C.POINTER(C.c_int32)
     kl = np.zeros(left.n_sites, np.int32); kr = np.zeros(right.n_sites, np.int32)
     sl = np.zeros(max(int(left.bwd_off[-1]), 1), np.int32); sr = np.zeros(max(int(right.bwd_off[-1]), 1), np.int32)
     up = np.zeros(left.n_sites, np.int32); lo = np.zeros(left.n_sites, np.int32)
     n = np.zeros(4, np.int32)
-    _check(L.pagan_dp_debug_compact(C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None,
-                                    kl.ctypes.data_as(p32), kr.ctypes.data_as(p32), sl.ctypes.data_as(p32), sr.ctypes.data_as(p32),
-                                    up.ctypes.data_as(p32), lo.ctypes.data_as(p32), n.ctypes.data_as(p32)), "pagan_dp_debug_compact")
+    check(L.pagan_dp_debug_compact(C.byref(left.c), C.byref(right.c), _band(band), _ip(kl), _ip(kr), _ip(sl), _ip(sr), _ip(up), _ip(lo),
+                                   _ip(n)), "pagan_dp_debug_compact")
     return {"keep_left": kl[:n[0]].copy(), "keep_right": kr[:n[1]].copy(), "slot_left": sl[:n[2]].copy(), "slot_right": sr[:n[3]].copy(),
             "upper": up[:n[0] - 1].copy(), "lower": lo[:n[0] - 1].copy()}
 
@@ -426,11 +409,8 @@ ROUTES = ("pg_fill_pipe", "pg_fill_pipe (large table)", "pg_fill_tiles_flow", "p
 def debug_route(left, right, model, band=None):
     """Diagnostic (host only): (fill kernel pagan_batch_create would give this job, dead sites taken out first?, cells of
     the widest anti-diagonal)."""
-    import numpy as np
     n = np.zeros(2, np.int32)
-    rc = lib().pagan_dp_debug_route(C.byref(left.c), C.byref(right.c), C.byref(model.c), C.byref(band.c) if band is not None else None,
-                                    n.ctypes.data_as(C.POINTER(C.c_int32)))
-    _check(min(rc, 0), "pagan_dp_debug_route")
+    rc = check(lib().pagan_dp_debug_route(C.byref(left.c), C.byref(right.c), C.byref(model.c), _band(band), _ip(n)), "pagan_dp_debug_route")
     return ROUTES[rc], bool(n[0]), int(n[1])
 
 
@@ -438,17 +418,14 @@ def debug_strips(left, right, band=None, max_sites=0):
     """Diagnostic (host only): the row strips a wide job would be filled as -- [(first row, last row, first diagonal, last
     diagonal + 1, feeder wave, first column staged, desc)] with desc[d - first diagonal] = (first row on d, last row, cell index
     of the first row's score in the job's arrays, class); [] when max_sites refuses the job."""
-    import numpy as np
     Lx, Ly = left.n_sites - 1, right.n_sites - 1
     cap = Lx // 192 + 2
     desc_cap = (cap + 1) * (Ly + 192 + 64) + 64
     strips = np.zeros(6 * cap, np.int32)
     off = np.zeros(cap + 1, np.int64)
     desc = np.zeros(4 * desc_cap, np.int64)
-    n = lib().pagan_dp_debug_strips(C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None, max_sites,
-                                    strips.ctypes.data_as(C.POINTER(C.c_int32)), cap, off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                    desc.ctypes.data_as(C.POINTER(C.c_int64)), desc_cap)
-    _check(min(n, 0), "pagan_dp_debug_strips")
+    n = check(lib().pagan_dp_debug_strips(C.byref(left.c), C.byref(right.c), _band(band), max_sites, _ip(strips), cap,
+                                          off.ctypes.data_as(_i64p), desc.ctypes.data_as(_i64p), desc_cap), "pagan_dp_debug_strips")
     desc = desc.reshape(-1, 4)
     return [tuple(int(v) for v in strips[6 * k: 6 * k + 6]) + (desc[off[k]: off[k + 1]].copy(),) for k in range(n)]
 
@@ -458,11 +435,8 @@ FB_ROUTE_INFO = ("diagonals", "widest", "segments", "min_D", "reach_left", "reac
 
 def fb_route(left, right, band=None):
     """pagan_fb_debug_route (host only): (schedule code FullProbability would take under the current environment, info dict)."""
-    import numpy as np
     info = np.zeros(8, np.int32)
-    rc = lib().pagan_fb_debug_route(C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None,
-                                    info.ctypes.data_as(C.POINTER(C.c_int32)))
-    _check(min(rc, 0), "pagan_fb_debug_route")
+    rc = check(lib().pagan_fb_debug_route(C.byref(left.c), C.byref(right.c), _band(band), _ip(info)), "pagan_fb_debug_route")
     return rc, dict(zip(FB_ROUTE_INFO, (int(v) for v in info)))
 
 
@@ -473,17 +447,15 @@ FB_PLAN_HEAD = ("schedule", "groups", "groups_fwd", "groups_bwd", "block", "nspl
 def fb_plan(left, right, band=None, n_states=4, groups_cap=64, groups_cap_b=64):
     """pagan_fb_debug_plan (host only): everything FullProbability's plan fixes for the pair under the current environment -- a
     dict of the head words (FB_PLAN_HEAD) and the arrays init_at, seg_start, seg_B, dfar."""
-    import numpy as np
     L = lib()
-    p32, p64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-    args = (C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None, n_states, groups_cap, groups_cap_b)
+    args = (C.byref(left.c), C.byref(right.c), _band(band), n_states, groups_cap, groups_cap_b)
     head = np.zeros(16, np.int32)
-    _check(min(L.pagan_fb_debug_plan(*args, head.ctypes.data_as(p32), None, 0, None, None, 0, None, 0), 0), "pagan_fb_debug_plan")
+    check(L.pagan_fb_debug_plan(*args, _ip(head), None, 0, None, None, 0, None, 0), "pagan_fb_debug_plan")
     out = dict(zip(FB_PLAN_HEAD, (int(v) for v in head)))
     n_init, nseg, n_dfar = out["n_init"], out["segments"], out["n_dfar"]
     init_at = np.zeros(n_init, np.int64); seg_start = np.zeros(nseg + 1, np.int32); seg_B = np.zeros(nseg, np.int32); dfar = np.zeros(n_dfar, np.int32)
-    _check(min(L.pagan_fb_debug_plan(*args, head.ctypes.data_as(p32), init_at.ctypes.data_as(p64), n_init, seg_start.ctypes.data_as(p32),
-                                     seg_B.ctypes.data_as(p32), nseg, dfar.ctypes.data_as(p32), n_dfar), 0), "pagan_fb_debug_plan")
+    check(L.pagan_fb_debug_plan(*args, _ip(head), init_at.ctypes.data_as(_i64p), n_init, _ip(seg_start), _ip(seg_B), nseg, _ip(dfar), n_dfar),
+          "pagan_fb_debug_plan")
     out.update(init_at=init_at, seg_start=seg_start[:nseg + 1 if nseg else 0], seg_B=seg_B, dfar=dfar)
     return out
 
@@ -493,14 +465,14 @@ def full_probability_batch(pairs, device=-1):
     run in one launch and their backward sweeps in another (all pairs side by side on the device)."""
     L = lib()
     n = len(pairs)
-    gp, mpp, bp = C.POINTER(abi.CGraph), C.POINTER(abi.CModelProb), C.POINTER(abi.CBand)
+    gp, mpp, bp = abi.gp, abi.mpp, abi.bp
     lefts = (gp * n)(*[C.pointer(p[0].c) for p in pairs])
     rights = (gp * n)(*[C.pointer(p[1].c) for p in pairs])
     models = (mpp * n)(*[C.pointer(p[2].c) for p in pairs])
     bands = (bp * n)(*[(C.pointer(p[3].c) if p[3] is not None else bp()) for p in pairs])
     outs = (C.c_void_p * n)()
     opts = abi.COpts(0, device)
-    _check(L.pagan_fb_run_batch(n, lefts, rights, models, bands, C.byref(opts), outs), "pagan_fb_run_batch")
+    check(L.pagan_fb_run_batch(n, lefts, rights, models, bands, C.byref(opts), outs), "pagan_fb_run_batch")
     return [FullProbability(p[0], p[1], p[2], p[3], device=device, _handle=C.c_void_p(outs[k])) for k, p in enumerate(pairs)]
 
 
@@ -511,42 +483,38 @@ _MARGINALS = (("pX", 0, "f"), ("pM_left", 0, "f"), ("best_j", 0, "i"), ("best_p_
 def site_marginals_batch(fbs, rows=True, columns=True):
     """pagan_fb_site_marginals_batch over FullProbability handles of one device (one launch per pass): a list of dicts as
     FullProbability.site_marginals returns."""
-    import numpy as np
     L = lib()
     n = len(fbs)
-    f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     out = [{} for _ in range(n)]
     args = []
     for name, side, kind in _MARGINALS:
         if not (columns if side else rows):
             args.append(None)
             continue
-        ptrs = ((f64p if kind == "f" else i32p) * n)()
+        ptrs = ((_f64p if kind == "f" else _i32p) * n)()
         for k, fb in enumerate(fbs):
             a = np.zeros(fb.shape[side], np.float64 if kind == "f" else np.int32)
             out[k][name] = a
-            ptrs[k] = a.ctypes.data_as(f64p if kind == "f" else i32p)
+            ptrs[k] = _dp(a) if kind == "f" else _ip(a)
         args.append(ptrs)
     handles = (C.c_void_p * n)(*[fb._h for fb in fbs])
-    _check(L.pagan_fb_site_marginals_batch(n, handles, *args), "pagan_fb_site_marginals_batch")
+    check(L.pagan_fb_site_marginals_batch(n, handles, *args), "pagan_fb_site_marginals_batch")
     return out
 
 
 def expected_counts_batch(fbs, emissions=True):
     """pagan_fb_expected_counts_batch over FullProbability handles of one device (one launch of pg_fb_counts): a list of dicts
     as FullProbability.expected_counts returns.  emissions: one switch for all pairs, or one per pair."""
-    import numpy as np
     L = lib()
     n = len(fbs)
-    f64p = C.POINTER(C.c_double)
     want = [bool(emissions)] * n if isinstance(emissions, (bool, int)) else [bool(e) for e in emissions]
     assert len(want) == n
     trans = [np.zeros(12, np.float64) for _ in fbs]
     emit = [np.zeros(fb.model.n_states ** 2, np.float64) if w else None for fb, w in zip(fbs, want)]
-    tp = (f64p * n)(*[t.ctypes.data_as(f64p) for t in trans])
-    ep = (f64p * n)(*[(e.ctypes.data_as(f64p) if e is not None else f64p()) for e in emit])
+    tp = (_f64p * n)(*[_dp(t) for t in trans])
+    ep = (_f64p * n)(*[(_dp(e) if e is not None else _f64p()) for e in emit])
     handles = (C.c_void_p * n)(*[fb._h for fb in fbs])
-    _check(L.pagan_fb_expected_counts_batch(n, handles, tp, ep), "pagan_fb_expected_counts_batch")
+    check(L.pagan_fb_expected_counts_batch(n, handles, tp, ep), "pagan_fb_expected_counts_batch")
     out = []
     for k, fb in enumerate(fbs):
         S = fb.model.n_states
@@ -561,67 +529,55 @@ def fb_counts_predict_bytes(left_sites, right_sites, n_states):
 
 def path_cells(cols):
     """pagan_path_cells (host only): [n, 3] int32 rows (state, i, j) of the DP cell each column sits on, (-1, -1, -1) at skip columns."""
-    import numpy as np
     c = np.ascontiguousarray(cols, np.int32).reshape(-1, 3)
     out = np.zeros((c.shape[0], 3), np.int32)
-    _check(lib().pagan_path_cells(c.ctypes.data_as(C.POINTER(abi.CCol)), c.shape[0], out.ctypes.data_as(C.POINTER(C.c_int32))),
-           "pagan_path_cells")
+    check(lib().pagan_path_cells(c.ctypes.data_as(abi.colp), c.shape[0], _ip(out)), "pagan_path_cells")
     return out
 
 
 def sample_uniforms(seed, node, n):
     """pagan_sample_uniforms (host only): n numbers in [0, 1), a pure function of (seed, node, index)."""
-    import numpy as np
     u = np.zeros(n, np.float64)
-    _check(lib().pagan_sample_uniforms(int(seed) & 0xFFFFFFFFFFFFFFFF, int(node), int(n), u.ctypes.data_as(C.POINTER(C.c_double))),
-           "pagan_sample_uniforms")
+    check(lib().pagan_sample_uniforms(int(seed) & 0xFFFFFFFFFFFFFFFF, int(node), int(n), _dp(u)), "pagan_sample_uniforms")
     return u
 
 
 def sample_uniforms_path(seed, node, path, n):
     """pagan_sample_uniforms_path (host only): the stream of path `path` of node `node`'s ensemble; path 0 is sample_uniforms."""
-    import numpy as np
     u = np.zeros(n, np.float64)
-    _check(lib().pagan_sample_uniforms_path(int(seed) & 0xFFFFFFFFFFFFFFFF, int(node), int(path), int(n), u.ctypes.data_as(C.POINTER(C.c_double))),
-           "pagan_sample_uniforms_path")
+    check(lib().pagan_sample_uniforms_path(int(seed) & 0xFFFFFFFFFFFFFFFF, int(node), int(path), int(n), _dp(u)),
+          "pagan_sample_uniforms_path")
     return u
 
 
 def fb_predict_bytes(left_sites, right_sites, band=None):
-    return lib().pagan_fb_predict_bytes(left_sites, right_sites, C.byref(band.c) if band is not None else None)
+    return lib().pagan_fb_predict_bytes(left_sites, right_sites, _band(band))
 
 
 def debug_far(left, right, band=None):
     """Diagnostic (host only): the far histories of a banded job -- (n_served, hfL[Lx], hfR[Ly], hbit[nd], classes[nd])."""
-    import numpy as np
     L = lib()
     Lx, Ly = left.n_sites - 1, right.n_sites - 1
     nd = Lx + Ly - 1
     hfl, hfr, hb, cls = np.zeros(Lx, np.uint8), np.zeros(Ly, np.uint8), np.zeros(nd, np.uint8), np.zeros(nd, np.uint8)
-    u8 = C.POINTER(C.c_uint8)
-    n = L.pagan_dp_debug_far(C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None,
-                             hfl.ctypes.data_as(u8), hfr.ctypes.data_as(u8), hb.ctypes.data_as(u8), cls.ctypes.data_as(u8))
-    if n < 0:
-        raise PaganError(n, "pagan_dp_debug_far")
+    n = check(L.pagan_dp_debug_far(C.byref(left.c), C.byref(right.c), _band(band), hfl.ctypes.data_as(_u8p), hfr.ctypes.data_as(_u8p),
+                                   hb.ctypes.data_as(_u8p), cls.ctypes.data_as(_u8p)), "pagan_dp_debug_far")
     return n, hfl, hfr, hb, cls
 
 
 def debug_descriptors(left, right, band=None, n_states=15):
     """Diagnostic (host only): the descriptor words pg_fill_pipe would read for this job under a model of n_states states, as an
     int32 array [diagonals, 8] (include/pagan_dp.h has the layout); [0, 8] for a job the planner does not give to pg_fill_pipe."""
-    import numpy as np
     nd = left.n_sites + right.n_sites - 3
     words = np.zeros((nd, 8), np.int32)
-    n = lib().pagan_dp_debug_descriptors(C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None,
-                                         int(n_states), words.ctypes.data_as(C.POINTER(C.c_int32)), words.size)
-    _check(min(n, 0), "pagan_dp_debug_descriptors")
+    n = check(lib().pagan_dp_debug_descriptors(C.byref(left.c), C.byref(right.c), _band(band), int(n_states), _ip(words), words.size),
+              "pagan_dp_debug_descriptors")
     return words[:n]
 
 
 def debug_plan(left, right, band=None, with_lead=False):
     """Diagnostic (host only): (classes[Lx+Ly-1] uint8, [awake intervals of wave 0..3]) the banded fill kernel
     would be given for this job; with_lead adds the per-diagonal downstream-progress requirement."""
-    import numpy as np
     L = lib()
     nd = left.n_sites + right.n_sites - 3
     cls = np.zeros(nd, np.uint8)
@@ -629,9 +585,8 @@ def debug_plan(left, right, band=None, with_lead=False):
     sched = np.zeros(cap, np.int32)
     n = C.c_int32()
     lead = np.zeros(nd, np.int32)
-    _check(L.pagan_dp_debug_plan(C.byref(left.c), C.byref(right.c), C.byref(band.c) if band is not None else None,
-                                 cls.ctypes.data_as(C.POINTER(C.c_uint8)), nd, sched.ctypes.data_as(C.POINTER(C.c_int32)),
-                                 cap, C.byref(n), lead.ctypes.data_as(C.POINTER(C.c_int32))), "pagan_dp_debug_plan")
+    check(L.pagan_dp_debug_plan(C.byref(left.c), C.byref(right.c), _band(band), cls.ctypes.data_as(_u8p), nd, _ip(sched), cap, C.byref(n),
+                                _ip(lead)), "pagan_dp_debug_plan")
     waves = []
     for w in range(4):
         k = int(sched[w])
@@ -645,8 +600,10 @@ def debug_plan(left, right, band=None, with_lead=False):
     return cls, waves
 
 
-class Batch:
+class Batch(Handle):
     """Jobs uploaded once and kept resident in HBM; run() replays the hot path on them."""
+
+    _destroy = "pagan_batch_destroy"
 
     def __init__(self, jobs, flags=0, device=-1):
         self._L = lib()
@@ -655,28 +612,28 @@ class Batch:
         arr = _jobs_array(self.jobs)
         opts = abi.COpts(flags, device)
         self._h = C.c_void_p()
-        _check(self._L.pagan_batch_create(self.n, arr, C.byref(opts), C.byref(self._h)), "pagan_batch_create")
+        check(self._L.pagan_batch_create(self.n, arr, C.byref(opts), C.byref(self._h)), "pagan_batch_create")
 
     @property
     def cells(self):
         return self._L.pagan_batch_cells(self._h)
 
     def run(self):
-        _check(self._L.pagan_batch_run(self._h), "pagan_batch_run")
+        check(self._L.pagan_batch_run(self._h), "pagan_batch_run")
 
     def sync(self):
-        _check(self._L.pagan_batch_sync(self._h), "pagan_batch_sync")
+        check(self._L.pagan_batch_sync(self._h), "pagan_batch_sync")
 
     def last_ms(self):
         ms = (C.c_double * 2)()
-        _check(self._L.pagan_batch_last_ms(self._h, ms), "pagan_batch_last_ms")
+        check(self._L.pagan_batch_last_ms(self._h, ms), "pagan_batch_last_ms")
         return ms[0], ms[1]
 
     def fetch(self):
         res = (abi.CResult * self.n)()
         rc = self._L.pagan_batch_fetch(self._h, res)
         try:
-            _check(rc, "pagan_batch_fetch")
+            check(rc, "pagan_batch_fetch")
             return [Result(r) for r in res]
         finally:
             for r in res:
@@ -684,30 +641,26 @@ class Batch:
 
     def debug_scores(self, k):
         """Diagnostic: job k's device score array as [cells, 3] float64 (X, Y, M), diagonal-major."""
-        import numpy as np
         out = np.empty((self.cells_of(k), 3), np.float64)
-        _check(self._L.pagan_batch_debug_scores(self._h, k, out.ctypes.data_as(C.POINTER(C.c_double)), out.size),
-               "pagan_batch_debug_scores")
+        check(self._L.pagan_batch_debug_scores(self._h, k, _dp(out), out.size), "pagan_batch_debug_scores")
         return out
 
     def debug_backptrs(self, k):
         """Diagnostic: job k's device back-pointer array as [cells, 3] uint32 (X, Y, M), diagonal-major."""
-        import numpy as np
         out = np.empty((self.cells_of(k), 3), np.uint32)
-        _check(self._L.pagan_batch_debug_backptrs(self._h, k, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size),
-               "pagan_batch_debug_backptrs")
+        check(self._L.pagan_batch_debug_backptrs(self._h, k, out.ctypes.data_as(_u32p), out.size), "pagan_batch_debug_backptrs")
         return out
 
     def debug_followed(self, k):
         """Diagnostic: (chunks of 16 diagonals of job k whose back-pointers were written behind the banded fill by its
         follower workgroups, all chunks of the job); (0, 0) for a job of another kernel."""
         c = (C.c_int32 * 2)()
-        _check(self._L.pagan_batch_debug_followed(self._h, k, c), "pagan_batch_debug_followed")
+        check(self._L.pagan_batch_debug_followed(self._h, k, c), "pagan_batch_debug_followed")
         return int(c[0]), int(c[1])
 
     def debug_poke_bp(self, k, i, j, vit, word):
         """Test hook: after the next run's fill, state `vit` of cell (i, j) of job k gets `word` as its back-pointer (once)."""
-        _check(self._L.pagan_batch_debug_poke_bp(self._h, k, i, j, vit, word), "pagan_batch_debug_poke_bp")
+        check(self._L.pagan_batch_debug_poke_bp(self._h, k, i, j, vit, word), "pagan_batch_debug_poke_bp")
 
     def debug_reruns(self):
         """How often fetch() ran the batch again after a failed path check."""
@@ -715,34 +668,19 @@ class Batch:
 
     def debug_trace(self, k, n_cells):
         """Diagnostic: the first n_cells visited cells of job k's last traceback as [n, 3] int32 rows (i, j, word)."""
-        import numpy as np
         out = np.empty((n_cells, 3), np.int32)
-        _check(self._L.pagan_batch_debug_trace(self._h, k, out.ctypes.data_as(C.c_void_p), out.nbytes), "pagan_batch_debug_trace")
+        check(self._L.pagan_batch_debug_trace(self._h, k, out.ctypes.data_as(C.c_void_p), out.nbytes), "pagan_batch_debug_trace")
         return out
 
     def debug_segments(self, k):
         """Diagnostic: (n_bound, [n_segments, 5] int32 rows (i, j, state, cells, offset), cells of the path, device status)
         of job k's last traceback."""
-        import numpy as np
         info = np.zeros(4, np.int32)
-        i32p = C.POINTER(C.c_int32)
-        _check(self._L.pagan_batch_debug_segments(self._h, k, info.ctypes.data_as(i32p), None, 0), "pagan_batch_debug_segments")
+        check(self._L.pagan_batch_debug_segments(self._h, k, _ip(info), None, 0), "pagan_batch_debug_segments")
         segs = np.zeros((int(info[1]), 5), np.int32)
-        _check(self._L.pagan_batch_debug_segments(self._h, k, info.ctypes.data_as(i32p), segs.ctypes.data_as(i32p), segs.shape[0]),
-               "pagan_batch_debug_segments")
+        check(self._L.pagan_batch_debug_segments(self._h, k, _ip(info), _ip(segs), segs.shape[0]), "pagan_batch_debug_segments")
         return int(info[0]), segs, int(info[2]), int(info[3])
 
     def cells_of(self, k):
         left, right, _, band = self.jobs[k]
-        return self._L.pagan_dp_count_cells(left.n_sites, right.n_sites, C.byref(band.c) if band is not None else None)
-
-    def close(self):
-        if self._h:
-            self._L.pagan_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._L.pagan_dp_count_cells(left.n_sites, right.n_sites, _band(band))

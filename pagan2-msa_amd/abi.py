@@ -19,8 +19,24 @@ DECODE_KEEP_MATRIX = 1
 X_MAT, Y_MAT, M_MAT = 0, 1, 2
 MATCHED, XGAPPED, YGAPPED, XSKIPPED, YSKIPPED = 2, 3, 4, 5, 6
 
-_i32p = C.POINTER(C.c_int32)
-_f32p = C.POINTER(C.c_float)
+# ---- the short names the prototype tables (PROTOTYPES, host.PROTOTYPES) are written in ------
+cint, i32, i64, u8, u32, u64, f32, f64 = C.c_int, C.c_int32, C.c_int64, C.c_uint8, C.c_uint32, C.c_uint64, C.c_float, C.c_double
+vp, cp = C.c_void_p, C.c_char_p                     # vp: a pointer to an opaque handle type as well (pagan_batch * ...)
+vpp, cpp = C.POINTER(vp), C.POINTER(cp)
+_i32p, _i64p, _u8p, _u32p, _f32p, _f64p = (C.POINTER(t) for t in (i32, i64, u8, u32, f32, f64))
+_i32pp, _f64pp = C.POINTER(_i32p), C.POINTER(_f64p)
+
+
+def _ip(a):
+    return a.ctypes.data_as(_i32p)
+
+
+def _fp(a):
+    return a.ctypes.data_as(_f32p)
+
+
+def _dp(a):
+    return a.ctypes.data_as(_f64p)
 
 
 class CGraph(C.Structure):
@@ -59,10 +75,6 @@ class CJob(C.Structure):
                 ("band", C.POINTER(CBand))]
 
 
-def _p(arr, typ):
-    return arr.ctypes.data_as(typ)
-
-
 class Graph:
     """One child Sequence flattened to CSR (pagan_graph)."""
 
@@ -77,8 +89,8 @@ class Graph:
             n_edges = int(self.bwd_eid.max()) + 1 if self.bwd_eid.size else 0
         self.n_edges = int(n_edges)
         assert self.bwd_off.shape[0] == self.n_sites + 1
-        self.c = CGraph(self.n_sites, self.n_edges, _p(self.state, _i32p), _p(self.bwd_off, _i32p),
-                        _p(self.bwd_src, _i32p), _p(self.bwd_logw, _f32p), _p(self.bwd_eid, _i32p))
+        self.c = CGraph(self.n_sites, self.n_edges, _ip(self.state), _ip(self.bwd_off),
+                        _ip(self.bwd_src), _fp(self.bwd_logw), _ip(self.bwd_eid))
 
     @classmethod
     def chain(cls, states):
@@ -102,7 +114,7 @@ class Model:
         self.table = np.ascontiguousarray(t.T.reshape(-1))
         self.log_score = t
         self.params = tuple(np.float32(x) for x in (log_gap_open, log_gap_ext, log_gap_end_ext, log_non_gap))
-        self.c = CModel(self.n_states, _p(self.table, _f32p), *[float(x) for x in self.params])
+        self.c = CModel(self.n_states, _fp(self.table), *[float(x) for x in self.params])
 
 
 class CModelProb(C.Structure):
@@ -120,7 +132,7 @@ class ModelProb:
         self.table = np.ascontiguousarray(t.T.reshape(-1))       # score(a,b) = table[a + b*S]
         self.score = t
         self.gap_open, self.gap_ext, self.non_gap = (float(np.float32(x)) for x in (gap_open, gap_ext, non_gap))
-        self.c = CModelProb(self.n_states, _p(self.table, _f32p), self.gap_open, self.gap_ext, self.non_gap)
+        self.c = CModelProb(self.n_states, _fp(self.table), self.gap_open, self.gap_ext, self.non_gap)
 
 
 class Band:
@@ -128,7 +140,7 @@ class Band:
         self.upper = np.ascontiguousarray(upper, dtype=np.int32)
         self.lower = np.ascontiguousarray(lower, dtype=np.int32)
         assert self.upper.shape == self.lower.shape
-        self.c = CBand(int(self.upper.shape[0]), _p(self.upper, _i32p), _p(self.lower, _i32p))
+        self.c = CBand(int(self.upper.shape[0]), _ip(self.upper), _ip(self.lower))
 
 
 class Result:
@@ -161,178 +173,104 @@ class Result:
                 np.array_equal(self.right_used, other.right_used))
 
 
-def declare(lib):
-    """Attach argtypes/restype for every symbol include/pagan_dp.h declares."""
-    gp, mp, bp, op, rp = (C.POINTER(CGraph), C.POINTER(CModel), C.POINTER(CBand), C.POINTER(COpts),
-                          C.POINTER(CResult))
-    lib.pagan_dp_align.argtypes = [gp, gp, mp, bp, op, rp]
-    lib.pagan_dp_align.restype = C.c_int
-    lib.pagan_dp_align_batch.argtypes = [C.c_int32, C.POINTER(CJob), op, rp]
-    lib.pagan_dp_align_batch.restype = C.c_int
-    lib.pagan_result_free.argtypes = [rp]
-    lib.pagan_result_free.restype = None
-    lib.pagan_dp_predict_bytes.argtypes = [C.c_int32, C.c_int32, bp]
-    lib.pagan_dp_predict_bytes.restype = C.c_int64
-    lib.pagan_dp_count_cells.argtypes = [C.c_int32, C.c_int32, bp]
-    lib.pagan_dp_count_cells.restype = C.c_int64
-    lib.pagan_dp_device_count.argtypes = []
-    lib.pagan_dp_device_count.restype = C.c_int
-    lib.pagan_dp_select_device.argtypes = [C.c_int32]
-    lib.pagan_dp_select_device.restype = C.c_int
-    lib.pagan_batch_create.argtypes = [C.c_int32, C.POINTER(CJob), op, C.POINTER(C.c_void_p)]
-    lib.pagan_batch_create.restype = C.c_int
-    lib.pagan_batch_run.argtypes = [C.c_void_p]
-    lib.pagan_batch_run.restype = C.c_int
-    lib.pagan_batch_sync.argtypes = [C.c_void_p]
-    lib.pagan_batch_sync.restype = C.c_int
-    lib.pagan_batch_fetch.argtypes = [C.c_void_p, rp]
-    lib.pagan_batch_fetch.restype = C.c_int
-    lib.pagan_batch_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    lib.pagan_batch_last_ms.restype = C.c_int
-    lib.pagan_batch_last_ms_detail.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    lib.pagan_batch_last_ms_detail.restype = C.c_int
-    lib.pagan_batch_cells.argtypes = [C.c_void_p]
-    lib.pagan_batch_cells.restype = C.c_int64
-    lib.pagan_batch_destroy.argtypes = [C.c_void_p]
-    lib.pagan_batch_destroy.restype = None
-    lib.pagan_batch_debug_trace.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
-    lib.pagan_batch_debug_trace.restype = C.c_int
-    lib.pagan_batch_debug_segments.argtypes = [C.c_void_p, C.c_int32, _i32p, _i32p, C.c_int64]
-    lib.pagan_batch_debug_segments.restype = C.c_int
-    lib.pagan_dp_debug_plan.argtypes = [gp, gp, bp, C.POINTER(C.c_uint8), C.c_int32, _i32p, C.c_int32, _i32p, _i32p]
-    lib.pagan_dp_debug_plan.restype = C.c_int
-    lib.pagan_dp_debug_far.argtypes = [gp, gp, bp] + [C.POINTER(C.c_uint8)] * 4
-    lib.pagan_dp_debug_far.restype = C.c_int
-    lib.pagan_dp_debug_descriptors.argtypes = [gp, gp, bp, C.c_int32, _i32p, C.c_int64]
-    lib.pagan_dp_debug_descriptors.restype = C.c_int
-    lib.pagan_dp_debug_strips.argtypes = [gp, gp, bp, C.c_int32, _i32p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64]
-    lib.pagan_dp_debug_strips.restype = C.c_int
-    lib.pagan_dp_debug_tiles.argtypes = [gp, gp, bp, _i32p, C.c_int32, _i32p]
-    lib.pagan_dp_debug_tiles.restype = C.c_int
-    lib.pagan_dp_debug_compact.argtypes = [gp, gp, bp, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]
-    lib.pagan_dp_debug_compact.restype = C.c_int
-    lib.pagan_dp_debug_tiles_staircase.argtypes = [_i32p, C.c_int32]
-    lib.pagan_dp_debug_tiles_staircase.restype = C.c_int
-    lib.pagan_dp_debug_route.argtypes = [gp, gp, C.POINTER(CModel), bp, _i32p]
-    lib.pagan_dp_debug_route.restype = C.c_int
-    lib.pagan_batch_debug_scores.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int64]
-    lib.pagan_batch_debug_scores.restype = C.c_int
-    lib.pagan_batch_debug_backptrs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.c_int64]
-    lib.pagan_batch_debug_backptrs.restype = C.c_int
-    lib.pagan_batch_debug_followed.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    lib.pagan_batch_debug_followed.restype = C.c_int
-    lib.pagan_batch_debug_poke_bp.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
-    lib.pagan_batch_debug_poke_bp.restype = C.c_int
-    lib.pagan_batch_debug_reruns.argtypes = [C.c_void_p]
-    lib.pagan_batch_debug_reruns.restype = C.c_int
-    lib.pagan_batch_debug_poison.argtypes = [C.c_void_p]
-    lib.pagan_batch_debug_poison.restype = C.c_int
-    lib.pagan_dp_release_cache.argtypes = []
-    lib.pagan_dp_release_cache.restype = None
-    lib.pagan_dp_cached_device_bytes.argtypes = [C.c_int32]
-    lib.pagan_dp_cached_device_bytes.restype = C.c_int64
-    mpp, f64p = C.POINTER(CModelProb), C.POINTER(C.c_double)
-    lib.pagan_fb_run.argtypes = [gp, gp, mpp, bp, op, C.POINTER(C.c_void_p)]
-    lib.pagan_fb_run.restype = C.c_int
-    lib.pagan_fb_run_batch.argtypes = [C.c_int32, C.POINTER(gp), C.POINTER(gp), C.POINTER(mpp), C.POINTER(bp), op, C.POINTER(C.c_void_p)]
-    lib.pagan_fb_run_batch.restype = C.c_int
-    lib.pagan_fb_totals.argtypes = [C.c_void_p, f64p, f64p, C.POINTER(C.c_int64)]
-    lib.pagan_fb_totals.restype = C.c_int
-    lib.pagan_fb_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    lib.pagan_fb_kernel_ms.restype = C.c_int
-    lib.pagan_fb_groups.argtypes = [C.c_void_p]
-    lib.pagan_fb_groups.restype = C.c_int
-    lib.pagan_fb_schedule.argtypes = [C.c_void_p]
-    lib.pagan_fb_schedule.restype = C.c_int
-    lib.pagan_fb_debug_route.argtypes = [gp, gp, bp, _i32p]
-    lib.pagan_fb_debug_route.restype = C.c_int
-    lib.pagan_fb_debug_plan.argtypes = [gp, gp, bp, C.c_int32, C.c_int32, C.c_int32, _i32p, C.POINTER(C.c_int64), C.c_int32, _i32p, _i32p, C.c_int32, _i32p, C.c_int32]
-    lib.pagan_fb_debug_plan.restype = C.c_int
-    lib.pagan_fb_dump.argtypes = [C.c_void_p, C.c_int32, f64p]
-    lib.pagan_fb_dump.restype = C.c_int
-    lib.pagan_fb_posterior_cells.argtypes = [C.c_void_p, C.c_int32, _i32p, f64p]
-    lib.pagan_fb_posterior_cells.restype = C.c_int
-    lib.pagan_fb_sample_path.argtypes = [C.c_void_p, f64p, C.c_int32, rp, _i32p, _i32p]
-    lib.pagan_fb_sample_path.restype = C.c_int
-    colp, f64pp, i32pp = C.POINTER(CCol), C.POINTER(f64p), C.POINTER(_i32p)
-    lib.pagan_path_cells.argtypes = [colp, C.c_int32, _i32p]
-    lib.pagan_path_cells.restype = C.c_int
-    lib.pagan_fb_path_support.argtypes = [C.c_void_p, colp, C.c_int32, f64p]
-    lib.pagan_fb_path_support.restype = C.c_int
-    lib.pagan_fb_site_marginals.argtypes = [C.c_void_p, f64p, f64p, _i32p, f64p, f64p, f64p, _i32p, f64p]
-    lib.pagan_fb_site_marginals.restype = C.c_int
-    lib.pagan_fb_site_marginals_batch.argtypes = [C.c_int32, C.POINTER(C.c_void_p), f64pp, f64pp, i32pp, f64pp, f64pp, f64pp, i32pp, f64pp]
-    lib.pagan_fb_site_marginals_batch.restype = C.c_int
-    lib.pagan_fb_post_ms.argtypes = [C.c_void_p, f64p]
-    lib.pagan_fb_post_ms.restype = C.c_int
-    lib.pagan_fb_expected_counts.argtypes = [C.c_void_p, f64p, f64p]
-    lib.pagan_fb_expected_counts.restype = C.c_int
-    lib.pagan_fb_expected_counts_batch.argtypes = [C.c_int32, C.POINTER(C.c_void_p), f64pp, f64pp]
-    lib.pagan_fb_expected_counts_batch.restype = C.c_int
-    lib.pagan_fb_counts_ms.argtypes = [C.c_void_p, f64p]
-    lib.pagan_fb_counts_ms.restype = C.c_int
-    lib.pagan_fb_counts_predict_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.pagan_fb_counts_predict_bytes.restype = C.c_int64
-    lib.pagan_fb_predict_bytes.argtypes = [C.c_int32, C.c_int32, bp]
-    lib.pagan_fb_predict_bytes.restype = C.c_int64
-    lib.pagan_sample_uniforms.argtypes = [C.c_uint64, C.c_int32, C.c_int32, f64p]
-    lib.pagan_sample_uniforms.restype = C.c_int
-    lib.pagan_sample_uniforms_path.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, f64p]
-    lib.pagan_sample_uniforms_path.restype = C.c_int
-    lib.pagan_fb_sample_paths_batch.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.c_uint64, _i32p, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.pagan_fb_sample_paths_batch.restype = C.c_int
-    lib.pagan_fb_sample_paths.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.pagan_fb_sample_paths.restype = C.c_int
-    lib.pagan_fb_samples_summary.argtypes = [C.c_void_p, _i32p, _i32p, _i32p, _i32p, _i32p, f64p]
-    lib.pagan_fb_samples_summary.restype = C.c_int
-    lib.pagan_fb_samples_visited.argtypes = [C.c_void_p, C.c_int32, _i32p, _i32p]
-    lib.pagan_fb_samples_visited.restype = C.c_int
-    lib.pagan_fb_samples_visited_all.argtypes = [C.c_void_p, _i32p, _i32p]
-    lib.pagan_fb_samples_visited_all.restype = C.c_int
-    lib.pagan_fb_samples_result.argtypes = [C.c_void_p, C.c_int32, rp]
-    lib.pagan_fb_samples_result.restype = C.c_int
-    lib.pagan_fb_samples_ms.argtypes = [C.c_void_p, f64p]
-    lib.pagan_fb_samples_ms.restype = C.c_int
-    lib.pagan_fb_sample_predict_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
-    lib.pagan_fb_sample_predict_bytes.restype = C.c_int64
-    lib.pagan_fb_samples_destroy.argtypes = [C.c_void_p]
-    lib.pagan_fb_samples_destroy.restype = None
-    lib.pagan_fb_decode_batch.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.c_double, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.pagan_fb_decode_batch.restype = C.c_int
-    lib.pagan_fb_decode.argtypes = [C.c_void_p, C.c_double, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.pagan_fb_decode.restype = C.c_int
-    lib.pagan_fb_decoded_summary.argtypes = [C.c_void_p, _i32p, f64p, _i32p, _i32p, _i32p]
-    lib.pagan_fb_decoded_summary.restype = C.c_int
-    lib.pagan_fb_decoded_visited.argtypes = [C.c_void_p, _i32p, _i32p]
-    lib.pagan_fb_decoded_visited.restype = C.c_int
-    lib.pagan_fb_decoded_result.argtypes = [C.c_void_p, rp]
-    lib.pagan_fb_decoded_result.restype = C.c_int
-    lib.pagan_fb_decoded_dump.argtypes = [C.c_void_p, f64p]
-    lib.pagan_fb_decoded_dump.restype = C.c_int
-    lib.pagan_fb_decoded_ms.argtypes = [C.c_void_p, f64p]
-    lib.pagan_fb_decoded_ms.restype = C.c_int
-    lib.pagan_fb_debug_decode_route.argtypes = [gp, gp, bp]
-    lib.pagan_fb_debug_decode_route.restype = C.c_int
-    lib.pagan_fb_decode_predict_bytes.argtypes = [C.c_int32, C.c_int32, bp]
-    lib.pagan_fb_decode_predict_bytes.restype = C.c_int64
-    lib.pagan_fb_decoded_destroy.argtypes = [C.c_void_p]
-    lib.pagan_fb_decoded_destroy.restype = None
-    lib.pagan_fb_destroy.argtypes = [C.c_void_p]
-    lib.pagan_fb_destroy.restype = None
-    lib.pagan_dp_version.argtypes = []
-    lib.pagan_dp_version.restype = C.c_char_p
+def struct_dict(s):
+    """A struct mirror's fields as a dict (the info and timing structs the library fills)."""
+    return {name: getattr(s, name) for name, _ in s._fields_}
+
+
+# C struct name -> mirror, for every struct include/pagan_dp.h declares with a body (host.STRUCTS: both headers')
+STRUCTS = {"pagan_graph": CGraph, "pagan_model": CModel, "pagan_band": CBand, "pagan_opts": COpts, "pagan_col": CCol,
+           "pagan_result": CResult, "pagan_job": CJob, "pagan_model_prob": CModelProb}
+
+gp, mp, mpp, bp, op, rp, jp, colp = (C.POINTER(t) for t in (CGraph, CModel, CModelProb, CBand, COpts, CResult, CJob, CCol))
+
+# Every entry point of include/pagan_dp.h in the header's order: name -> (restype, (argtypes...)).  A new entry point is one
+# line here; tests/test_abi_cpu.py holds the table against the header's prototypes.
+PROTOTYPES = {
+    "pagan_dp_align": (cint, (gp, gp, mp, bp, op, rp)),
+    "pagan_dp_align_batch": (cint, (i32, jp, op, rp)),
+    "pagan_result_free": (None, (rp,)),
+    "pagan_dp_predict_bytes": (i64, (i32, i32, bp)),
+    "pagan_dp_count_cells": (i64, (i32, i32, bp)),
+    "pagan_dp_device_count": (cint, ()),
+    "pagan_dp_select_device": (cint, (i32,)),
+    "pagan_batch_create": (cint, (i32, jp, op, vpp)),
+    "pagan_batch_run": (cint, (vp,)),
+    "pagan_batch_sync": (cint, (vp,)),
+    "pagan_batch_fetch": (cint, (vp, rp)),
+    "pagan_batch_last_ms": (cint, (vp, _f64p)),
+    "pagan_batch_last_ms_detail": (cint, (vp, _f64p)),
+    "pagan_batch_cells": (i64, (vp,)),
+    "pagan_batch_destroy": (None, (vp,)),
+    "pagan_batch_debug_trace": (cint, (vp, i32, vp, i64)),
+    "pagan_batch_debug_segments": (cint, (vp, i32, _i32p, _i32p, i64)),
+    "pagan_dp_debug_plan": (cint, (gp, gp, bp, _u8p, i32, _i32p, i32, _i32p, _i32p)),
+    "pagan_dp_debug_far": (cint, (gp, gp, bp, _u8p, _u8p, _u8p, _u8p)),
+    "pagan_dp_debug_descriptors": (cint, (gp, gp, bp, i32, _i32p, i64)),
+    "pagan_dp_debug_strips": (cint, (gp, gp, bp, i32, _i32p, i32, _i64p, _i64p, i64)),
+    "pagan_dp_debug_tiles": (cint, (gp, gp, bp, _i32p, i32, _i32p)),
+    "pagan_dp_debug_tiles_staircase": (cint, (_i32p, i32)),
+    "pagan_dp_debug_compact": (cint, (gp, gp, bp, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p)),
+    "pagan_dp_debug_route": (cint, (gp, gp, mp, bp, _i32p)),
+    "pagan_batch_debug_scores": (cint, (vp, i32, _f64p, i64)),
+    "pagan_batch_debug_backptrs": (cint, (vp, i32, _u32p, i64)),
+    "pagan_batch_debug_poison": (cint, (vp,)),
+    "pagan_batch_debug_followed": (cint, (vp, i32, _i32p)),
+    "pagan_batch_debug_poke_bp": (cint, (vp, i32, i32, i32, i32, u32)),
+    "pagan_batch_debug_reruns": (cint, (vp,)),
+    "pagan_dp_release_cache": (None, ()),
+    "pagan_dp_cached_device_bytes": (i64, (i32,)),
+    "pagan_fb_run": (cint, (gp, gp, mpp, bp, op, vpp)),
+    "pagan_fb_run_batch": (cint, (i32, C.POINTER(gp), C.POINTER(gp), C.POINTER(mpp), C.POINTER(bp), op, vpp)),
+    "pagan_fb_totals": (cint, (vp, _f64p, _f64p, _i64p)),
+    "pagan_fb_kernel_ms": (cint, (vp, _f64p)),
+    "pagan_fb_groups": (cint, (vp,)),
+    "pagan_fb_schedule": (cint, (vp,)),
+    "pagan_fb_debug_route": (cint, (gp, gp, bp, _i32p)),
+    "pagan_fb_debug_plan": (cint, (gp, gp, bp, i32, i32, i32, _i32p, _i64p, i32, _i32p, _i32p, i32, _i32p, i32)),
+    "pagan_fb_dump": (cint, (vp, i32, _f64p)),
+    "pagan_fb_posterior_cells": (cint, (vp, i32, _i32p, _f64p)),
+    "pagan_fb_sample_path": (cint, (vp, _f64p, i32, rp, _i32p, _i32p)),
+    "pagan_fb_destroy": (None, (vp,)),
+    "pagan_path_cells": (cint, (colp, i32, _i32p)),
+    "pagan_fb_path_support": (cint, (vp, colp, i32, _f64p)),
+    "pagan_fb_site_marginals": (cint, (vp, _f64p, _f64p, _i32p, _f64p, _f64p, _f64p, _i32p, _f64p)),
+    "pagan_fb_site_marginals_batch": (cint, (i32, vpp, _f64pp, _f64pp, _i32pp, _f64pp, _f64pp, _f64pp, _i32pp, _f64pp)),
+    "pagan_fb_post_ms": (cint, (vp, _f64p)),
+    "pagan_fb_expected_counts": (cint, (vp, _f64p, _f64p)),
+    "pagan_fb_expected_counts_batch": (cint, (i32, vpp, _f64pp, _f64pp)),
+    "pagan_fb_counts_ms": (cint, (vp, _f64p)),
+    "pagan_fb_counts_predict_bytes": (i64, (i32, i32, i32)),
+    "pagan_fb_predict_bytes": (i64, (i32, i32, bp)),
+    "pagan_sample_uniforms": (cint, (u64, i32, i32, _f64p)),
+    "pagan_sample_uniforms_path": (cint, (u64, i32, i32, i32, _f64p)),
+    "pagan_fb_sample_paths_batch": (cint, (i32, vpp, u64, _i32p, i32, u32, vpp)),
+    "pagan_fb_sample_paths": (cint, (vp, u64, i32, i32, u32, vpp)),
+    "pagan_fb_samples_summary": (cint, (vp, _i32p, _i32p, _i32p, _i32p, _i32p, _f64p)),
+    "pagan_fb_samples_visited": (cint, (vp, i32, _i32p, _i32p)),
+    "pagan_fb_samples_visited_all": (cint, (vp, _i32p, _i32p)),
+    "pagan_fb_samples_result": (cint, (vp, i32, rp)),
+    "pagan_fb_samples_ms": (cint, (vp, _f64p)),
+    "pagan_fb_sample_predict_bytes": (i64, (i32, i32, i32, u32)),
+    "pagan_fb_samples_destroy": (None, (vp,)),
+    "pagan_fb_decode_batch": (cint, (i32, vpp, f64, u32, vpp)),
+    "pagan_fb_decode": (cint, (vp, f64, u32, vpp)),
+    "pagan_fb_decoded_summary": (cint, (vp, _i32p, _f64p, _i32p, _i32p, _i32p)),
+    "pagan_fb_decoded_visited": (cint, (vp, _i32p, _i32p)),
+    "pagan_fb_decoded_result": (cint, (vp, rp)),
+    "pagan_fb_decoded_dump": (cint, (vp, _f64p)),
+    "pagan_fb_decoded_ms": (cint, (vp, _f64p)),
+    "pagan_fb_debug_decode_route": (cint, (gp, gp, bp)),
+    "pagan_fb_decode_predict_bytes": (i64, (i32, i32, bp)),
+    "pagan_fb_decoded_destroy": (None, (vp,)),
+    "pagan_dp_version": (cp, ()),
+}
+EXPORTED = list(PROTOTYPES)
+
+
+def declare(lib, table=PROTOTYPES):
+    """Attach the argtypes/restype of every entry point of `table` to the loaded library."""
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = list(argtypes), restype
     return lib
-
-
-EXPORTED = ["pagan_dp_align", "pagan_dp_align_batch", "pagan_result_free", "pagan_dp_predict_bytes",
-            "pagan_dp_count_cells", "pagan_dp_device_count", "pagan_dp_select_device", "pagan_batch_create",
-            "pagan_batch_run", "pagan_batch_sync", "pagan_batch_fetch", "pagan_batch_last_ms",
-            "pagan_batch_cells", "pagan_batch_last_ms_detail", "pagan_batch_destroy", "pagan_batch_debug_trace", "pagan_batch_debug_segments", "pagan_dp_debug_plan", "pagan_dp_debug_far", "pagan_dp_debug_descriptors", "pagan_dp_debug_strips", "pagan_dp_debug_tiles", "pagan_dp_debug_compact", "pagan_dp_debug_tiles_staircase", "pagan_dp_release_cache", "pagan_dp_cached_device_bytes", "pagan_dp_debug_route", "pagan_batch_debug_scores", "pagan_batch_debug_backptrs", "pagan_batch_debug_poison", "pagan_batch_debug_followed", "pagan_batch_debug_poke_bp", "pagan_batch_debug_reruns",
-            "pagan_fb_run", "pagan_fb_run_batch", "pagan_fb_totals", "pagan_fb_kernel_ms", "pagan_fb_groups", "pagan_fb_schedule", "pagan_fb_debug_route", "pagan_fb_debug_plan", "pagan_fb_dump", "pagan_fb_posterior_cells", "pagan_fb_sample_path",
-            "pagan_path_cells", "pagan_fb_path_support", "pagan_fb_site_marginals", "pagan_fb_site_marginals_batch", "pagan_fb_post_ms", "pagan_fb_predict_bytes", "pagan_sample_uniforms",
-            "pagan_sample_uniforms_path", "pagan_fb_sample_paths_batch", "pagan_fb_sample_paths", "pagan_fb_samples_summary", "pagan_fb_samples_visited",
-            "pagan_fb_samples_visited_all", "pagan_fb_samples_result", "pagan_fb_samples_ms", "pagan_fb_sample_predict_bytes", "pagan_fb_samples_destroy",
-            "pagan_fb_decode_batch", "pagan_fb_decode", "pagan_fb_decoded_summary", "pagan_fb_decoded_visited", "pagan_fb_decoded_result",
-            "pagan_fb_decoded_dump", "pagan_fb_decoded_ms", "pagan_fb_debug_decode_route", "pagan_fb_decode_predict_bytes", "pagan_fb_decoded_destroy",
-            "pagan_fb_expected_counts", "pagan_fb_expected_counts_batch", "pagan_fb_counts_ms", "pagan_fb_counts_predict_bytes",
-            "pagan_fb_destroy", "pagan_dp_version"]

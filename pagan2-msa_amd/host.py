@@ -5,14 +5,14 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi
+from . import Handle, PaganError, abi, check, lib  # noqa: F401  (PaganError: what check raises, for callers of this module)
+from . import sample_uniforms, sample_uniforms_path  # noqa: F401  (the numbers the walk samples a node's paths with)
+from .abi import (_dp, _f32p, _f64p, _fp, _i32p, _i64p, _ip, _u8p, cint, cp, cpp, f32, f64, gp, i32, i64, jp, mpp, rp, struct_dict, u32,
+                  vp, vpp)
 
 PAGAN_E_TREE = -20
 PAGAN_E_MEMCAP = -21
 DNA_FULL = "ACGTRYMKWSBDHVN"
-
-_i32p = C.POINTER(C.c_int32)
-_f32p = C.POINTER(C.c_float)
 
 
 class CMsaOpts(C.Structure):
@@ -40,6 +40,7 @@ class CTiming(C.Structure):
 
 # pagan_batch_fn (include/pagan_host.h): the test seam's callback type
 BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_int32, C.POINTER(abi.CJob), C.POINTER(abi.COpts), C.POINTER(abi.CResult), C.c_void_p)
+
 
 class CPileupOpts(C.Structure):
     _fields_ = [("leaf_flags", C.c_int32), ("dp_flags", C.c_uint32), ("query_distance", C.c_float), ("min_overlap", C.c_float),
@@ -78,255 +79,119 @@ GUIDE_PAIR_CHUNK = 64
 ALN_TILE = 64
 ALN_SPLIT_WORDS = 8
 
-_declared = False
+# C struct name -> mirror, for every struct the two headers declare with a body
+STRUCTS = dict(abi.STRUCTS, pagan_msa_opts=CMsaOpts, pagan_node_info=CNodeInfo, pagan_msa_timing=CTiming,
+               pagan_pileup_opts=CPileupOpts, pagan_pileup_step=CPileupStep, pagan_guide_info=CGuideInfo,
+               pagan_aln_info=CAlnInfo, pagan_anc_info=CAncInfo)
+
+# Every entry point of include/pagan_host.h in the header's order: name -> (restype, (argtypes...)).  A new entry point is
+# one line here; tests/test_abi_cpu.py holds the table against the header's prototypes.
+PROTOTYPES = {
+    "pagan_msa_default_opts": (None, (C.POINTER(CMsaOpts),)),
+    "pagan_assign_units": (None, (i32, _i64p, i32, _i32p)),
+    "pagan_msa_create": (cint, (i32, cpp, cpp, cp, C.POINTER(CMsaOpts), vpp)),
+    "pagan_msa_align": (cint, (vp,)),
+    "pagan_msa_ready": (cint, (vp, _i32p, i32)),
+    "pagan_msa_remaining": (cint, (vp,)),
+    "pagan_msa_node_cost": (i64, (vp, i32)),
+    "pagan_msa_align_nodes": (cint, (vp, i32, _i32p)),
+    "pagan_msa_export_result": (i64, (vp, i32, vp, i64)),
+    "pagan_msa_import_result": (cint, (vp, vp, i64)),
+    "pagan_msa_finish": (cint, (vp,)),
+    "pagan_msa_finish_lazy": (cint, (vp,)),
+    "pagan_msa_parents_built": (cint, (vp,)),
+    "pagan_msa_data_type": (cint, (vp,)),
+    "pagan_msa_node_device": (cint, (vp, i32)),
+    "pagan_msa_set_batch_backend": (cint, (vp, BATCH_FN, vp)),
+    "pagan_msa_set_sampler": (cint, (vp, i32)),
+    "pagan_msa_set_decoder": (cint, (vp, i32, f64)),
+    "pagan_msa_set_counts": (cint, (vp, i32)),
+    "pagan_msa_node_counts": (cint, (vp, i32, _f64p, _f64p)),
+    "pagan_msa_set_indel_model": (cint, (vp, f64, f64, f64, f64)),
+    "pagan_fit_indel": (cint, (i32, _f64p, _f64p, _f64p, _f64p)),
+    "pagan_msa_n_internal": (cint, (vp,)),
+    "pagan_msa_node_info": (cint, (vp, i32, C.POINTER(CNodeInfo))),
+    "pagan_msa_node_job": (cint, (vp, i32, jp)),
+    "pagan_msa_node_result": (cint, (vp, i32, rp)),
+    "pagan_msa_node_fb": (cint, (vp, i32, _f64p)),
+    "pagan_msa_node_decode": (cint, (vp, i32, _f64p)),
+    "pagan_msa_node_support": (cint, (vp, i32, _f64p)),
+    "pagan_msa_node_marginals": (cint, (vp, i32, _f64p, _f64p, _i32p, _f64p, _f64p, _f64p, _i32p, _f64p)),
+    "pagan_msa_node_model_prob": (cint, (vp, i32, mpp)),
+    "pagan_msa_support_row": (cint, (vp, i32, _f32p)),
+    "pagan_msa_timing_get": (cint, (vp, C.POINTER(CTiming))),
+    "pagan_msa_alignment_length": (cint, (vp,)),
+    "pagan_msa_alignment_row": (cint, (vp, i32, cp)),
+    "pagan_msa_write_fasta": (cint, (vp, cp, i32)),
+    "pagan_msa_write_fasta_nodes": (cint, (vp, cp, i32, i32)),
+    "pagan_msa_node_graph": (vp, (vp, i32)),
+    "pagan_msa_destroy": (None, (vp,)),
+    "pagan_pileup_default_opts": (None, (C.POINTER(CPileupOpts),)),
+    "pagan_pileup_create": (cint, (i32, cpp, cpp, C.POINTER(CPileupOpts), vpp)),
+    "pagan_pileup_align": (cint, (vp,)),
+    "pagan_pileup_n_steps": (cint, (vp,)),
+    "pagan_pileup_step_info": (cint, (vp, i32, C.POINTER(CPileupStep))),
+    "pagan_pileup_step_job": (cint, (vp, i32, jp)),
+    "pagan_pileup_step_result": (cint, (vp, i32, rp)),
+    "pagan_pileup_alignment_length": (cint, (vp,)),
+    "pagan_pileup_alignment_row": (cint, (vp, i32, cp)),
+    "pagan_pileup_set_batch_backend": (cint, (vp, BATCH_FN, vp)),
+    "pagan_pileup_destroy": (None, (vp,)),
+    "pagan_hgraph_leaf": (vp, (cp, cp, i32)),
+    "pagan_hgraph_leaf_codon": (vp, (cp,)),
+    "pagan_hgraph_parent": (vp, (vp, vp, rp, f32, f32, _i32p, i32, i32, i32)),
+    "pagan_hgraph_parent_device": (vp, (vp, vp, rp, f32, f32, _i32p, i32, i32, i32, _i32p)),
+    "pagan_parents_device_calls": (C.c_longlong, ()),
+    "pagan_hgraph_view": (None, (vp, gp)),
+    "pagan_hgraph_attrs": (None, (vp, _i32p, _f32p, _i32p, _f32p)),
+    "pagan_hgraph_fwd": (None, (vp, _i32p, _i32p)),
+    "pagan_hgraph_string": (cint, (vp, i32, cp, cp)),
+    "pagan_hgraph_free": (None, (vp,)),
+    "pagan_define_tunnel": (cint, (cp, cp, cp, cp, i32, i32, i32, _i32p, _i32p)),
+    "pagan_prefix_hits": (cint, (cp, cp, i32, _i32p, i32)),
+    "pagan_anchors_device_calls": (C.c_longlong, ()),
+    "pagan_prefix_hits_raw": (cint, (cp, cp, i32, i32, _i32p, i32)),
+    "pagan_drop_bad_hits": (cint, (_i32p, i32, i32, i32)),
+    "pagan_define_tunnel_overlapping": (cint, (_i32p, i32, cp, cp, i32, _i32p, _i32p, _i32p, i32)),
+    "pagan_force_gap": (cint, (_i32p, _i32p, i32, _i32p, i32, i32, i32, i32)),
+    "pagan_dna_model": (cint, (_f32p, f64, _f32p, _f32p, _i32p)),
+    "pagan_protein_model": (cint, (f64, _f32p, _f32p, _i32p)),
+    "pagan_codon_model": (cint, (f64, _f32p, _f32p, _i32p)),
+    "pagan_codon_alphabet": (cint, (cp, _i32p)),
+    "pagan_codon_translate": (cint, (cp, cp)),
+    "pagan_codon_states": (cint, (cp, _i32p)),
+    "pagan_model_prob_table": (cint, (i32, _f32p, f64, _f32p, _f32p)),
+    "pagan_model_alphabets": (cint, (i32, cp, cp)),
+    "pagan_eigen_qrev": (cint, (_f64p, _f64p, i32, _f64p, _f64p, _f64p)),
+    "pagan_guide_distances": (cint, (i32, cpp, i32, i32, _i64p, _i64p, _f64p, C.POINTER(CGuideInfo))),
+    "pagan_guide_tree": (i64, (i32, cpp, cpp, i32, i32, cp, i64, C.POINTER(CGuideInfo))),
+    "pagan_guide_kmer_length": (cint, (i32, i64)),
+    "pagan_guide_distance_of": (f64, (i64, i64, i32, i32)),
+    "pagan_guide_upgma": (i64, (i32, cpp, _f64p, cp, i64)),
+    "pagan_guide_predict_bytes": (i64, (i32, i64)),
+    "pagan_aln_distances": (cint, (i32, cpp, i32, _i64p, _i64p, _f64p, C.POINTER(CAlnInfo))),
+    "pagan_aln_tree": (i64, (i32, cpp, cpp, i32, cp, i64, C.POINTER(CAlnInfo))),
+    "pagan_aln_predict_bytes": (i64, (i32, i64)),
+    "pagan_msa_alignment_tree": (i64, (vp, cp, i64, C.POINTER(CAlnInfo))),
+    "pagan_anc_pmatrix": (cint, (i32, _f32p, f64, _f64p, _f64p)),
+    "pagan_anc_rate_matrix": (cint, (i32, _f32p, _f64p, _f64p)),
+    "pagan_anc_encode_row": (i64, (i32, cp, _u8p)),
+    "pagan_anc_check_tree": (cint, (i32, _i32p, _i32p, _f64p)),
+    "pagan_anc_predict_bytes": (i64, (i32, i64, i32, i64)),
+    "pagan_anc_reconstruct": (cint, (i32, _i32p, _i32p, _f64p, cpp, i32, _f32p, u32, i32, _i32p, _f64p, _i32p, _f64p, _f64p, _u8p,
+                                     _f32p, _u8p, _f64p, C.POINTER(CAncInfo))),
+    "pagan_msa_ancestral": (cint, (vp, u32, _f64p, _f64p, C.POINTER(CAncInfo))),
+    "pagan_msa_ancestral_row": (cint, (vp, i32, cp)),
+    "pagan_msa_ancestral_support": (cint, (vp, i32, _f32p)),
+    "pagan_msa_write_fasta_ancestral": (cint, (vp, cp, i32)),
+    "pagan_msa_ancestral_best": (cint, (vp, C.POINTER(_u8p), C.POINTER(_f32p))),
+}
+HOST_EXPORTED = list(PROTOTYPES)
 
 
 def _lib():
-    from . import lib
-    L = lib()
-    global _declared
-    if not _declared:
-        vp = C.c_void_p
-        L.pagan_msa_default_opts.argtypes = [C.POINTER(CMsaOpts)]
-        L.pagan_msa_default_opts.restype = None
-        L.pagan_msa_create.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_char_p,
-                                       C.POINTER(CMsaOpts), C.POINTER(vp)]
-        L.pagan_msa_create.restype = C.c_int
-        L.pagan_msa_align.argtypes = [vp]
-        L.pagan_msa_align.restype = C.c_int
-        L.pagan_msa_n_internal.argtypes = [vp]
-        L.pagan_msa_n_internal.restype = C.c_int
-        L.pagan_msa_node_info.argtypes = [vp, C.c_int32, C.POINTER(CNodeInfo)]
-        L.pagan_msa_node_info.restype = C.c_int
-        L.pagan_msa_node_job.argtypes = [vp, C.c_int32, C.POINTER(abi.CJob)]
-        L.pagan_msa_node_job.restype = C.c_int
-        L.pagan_msa_node_result.argtypes = [vp, C.c_int32, C.POINTER(abi.CResult)]
-        L.pagan_msa_node_result.restype = C.c_int
-        L.pagan_msa_timing_get.argtypes = [vp, C.POINTER(CTiming)]
-        L.pagan_msa_timing_get.restype = C.c_int
-        L.pagan_msa_alignment_length.argtypes = [vp]
-        L.pagan_msa_alignment_length.restype = C.c_int
-        L.pagan_msa_alignment_row.argtypes = [vp, C.c_int32, C.c_char_p]
-        L.pagan_msa_alignment_row.restype = C.c_int
-        L.pagan_msa_write_fasta.argtypes = [vp, C.c_char_p, C.c_int32]
-        L.pagan_msa_write_fasta.restype = C.c_int
-        L.pagan_msa_write_fasta_nodes.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32]
-        L.pagan_msa_write_fasta_nodes.restype = C.c_int
-        L.pagan_msa_node_graph.argtypes = [vp, C.c_int32]
-        L.pagan_msa_node_graph.restype = vp
-        L.pagan_msa_destroy.argtypes = [vp]
-        L.pagan_msa_destroy.restype = None
-        L.pagan_hgraph_leaf.argtypes = [C.c_char_p, C.c_char_p, C.c_int32]
-        L.pagan_hgraph_leaf.restype = vp
-        L.pagan_hgraph_parent.argtypes = [vp, vp, C.POINTER(abi.CResult), C.c_float, C.c_float, _i32p, C.c_int32,
-                                          C.c_int32, C.c_int32]
-        L.pagan_hgraph_parent.restype = vp
-        L.pagan_hgraph_parent_device.argtypes = [vp, vp, C.POINTER(abi.CResult), C.c_float, C.c_float, _i32p, C.c_int32,
-                                                 C.c_int32, C.c_int32, _i32p]
-        L.pagan_hgraph_parent_device.restype = vp
-        L.pagan_parents_device_calls.argtypes = []
-        L.pagan_parents_device_calls.restype = C.c_longlong
-        L.pagan_hgraph_view.argtypes = [vp, C.POINTER(abi.CGraph)]
-        L.pagan_hgraph_view.restype = None
-        L.pagan_hgraph_attrs.argtypes = [vp, _i32p, _f32p, _i32p, _f32p]
-        L.pagan_hgraph_attrs.restype = None
-        L.pagan_hgraph_fwd.argtypes = [vp, _i32p, _i32p]
-        L.pagan_hgraph_fwd.restype = None
-        L.pagan_hgraph_string.argtypes = [vp, C.c_int32, C.c_char_p, C.c_char_p]
-        L.pagan_hgraph_string.restype = C.c_int
-        L.pagan_hgraph_free.argtypes = [vp]
-        L.pagan_hgraph_free.restype = None
-        L.pagan_define_tunnel.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32,
-                                          C.c_int32, _i32p, _i32p]
-        L.pagan_define_tunnel.restype = C.c_int
-        L.pagan_assign_units.argtypes = [C.c_int32, C.POINTER(C.c_int64), C.c_int32, _i32p]
-        L.pagan_assign_units.restype = None
-        L.pagan_prefix_hits.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, _i32p, C.c_int32]
-        L.pagan_prefix_hits.restype = C.c_int
-        L.pagan_prefix_hits_raw.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, _i32p, C.c_int32]
-        L.pagan_prefix_hits_raw.restype = C.c_int
-        L.pagan_anchors_device_calls.argtypes = []
-        L.pagan_anchors_device_calls.restype = C.c_longlong
-        L.pagan_drop_bad_hits.argtypes = [_i32p, C.c_int32, C.c_int32, C.c_int32]
-        L.pagan_drop_bad_hits.restype = C.c_int
-        L.pagan_define_tunnel_overlapping.argtypes = [_i32p, C.c_int32, C.c_char_p, C.c_char_p, C.c_int32, _i32p, _i32p,
-                                                      _i32p, C.c_int32]
-        L.pagan_define_tunnel_overlapping.restype = C.c_int
-        L.pagan_force_gap.argtypes = [_i32p, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-        L.pagan_force_gap.restype = C.c_int
-        L.pagan_dna_model.argtypes = [_f32p, C.c_double, _f32p, _f32p, _i32p]
-        L.pagan_dna_model.restype = C.c_int
-        L.pagan_protein_model.argtypes = [C.c_double, _f32p, _f32p, _i32p]
-        L.pagan_protein_model.restype = C.c_int
-        L.pagan_codon_model.argtypes = [C.c_double, _f32p, _f32p, _i32p]
-        L.pagan_codon_model.restype = C.c_int
-        L.pagan_codon_alphabet.argtypes = [C.c_char_p, _i32p]
-        L.pagan_codon_alphabet.restype = C.c_int
-        L.pagan_codon_translate.argtypes = [C.c_char_p, C.c_char_p]
-        L.pagan_codon_translate.restype = C.c_int
-        L.pagan_codon_states.argtypes = [C.c_char_p, _i32p]
-        L.pagan_codon_states.restype = C.c_int
-        L.pagan_hgraph_leaf_codon.argtypes = [C.c_char_p]
-        L.pagan_hgraph_leaf_codon.restype = vp
-        L.pagan_model_prob_table.argtypes = [C.c_int32, _f32p, C.c_double, _f32p, _f32p]
-        L.pagan_model_prob_table.restype = C.c_int
-        L.pagan_model_alphabets.argtypes = [C.c_int32, C.c_char_p, C.c_char_p]
-        L.pagan_model_alphabets.restype = C.c_int
-        f64p = C.POINTER(C.c_double)
-        L.pagan_eigen_qrev.argtypes = [f64p, f64p, C.c_int32, f64p, f64p, f64p]
-        L.pagan_eigen_qrev.restype = C.c_int
-        L.pagan_msa_ready.argtypes = [vp, _i32p, C.c_int32]
-        L.pagan_msa_ready.restype = C.c_int
-        L.pagan_msa_remaining.argtypes = [vp]
-        L.pagan_msa_remaining.restype = C.c_int
-        L.pagan_msa_node_cost.argtypes = [vp, C.c_int32]
-        L.pagan_msa_node_cost.restype = C.c_int64
-        L.pagan_msa_align_nodes.argtypes = [vp, C.c_int32, _i32p]
-        L.pagan_msa_align_nodes.restype = C.c_int
-        L.pagan_msa_export_result.argtypes = [vp, C.c_int32, C.c_void_p, C.c_int64]
-        L.pagan_msa_export_result.restype = C.c_int64
-        L.pagan_msa_import_result.argtypes = [vp, C.c_void_p, C.c_int64]
-        L.pagan_msa_import_result.restype = C.c_int
-        L.pagan_msa_finish.argtypes = [vp]
-        L.pagan_msa_finish.restype = C.c_int
-        L.pagan_msa_finish_lazy.argtypes = [vp]
-        L.pagan_msa_finish_lazy.restype = C.c_int
-        L.pagan_msa_parents_built.argtypes = [vp]
-        L.pagan_msa_parents_built.restype = C.c_int
-        L.pagan_msa_data_type.argtypes = [vp]
-        L.pagan_msa_data_type.restype = C.c_int
-        L.pagan_msa_node_device.argtypes = [vp, C.c_int32]
-        L.pagan_msa_node_device.restype = C.c_int
-        L.pagan_msa_set_batch_backend.argtypes = [vp, BATCH_FN, C.c_void_p]
-        L.pagan_msa_set_batch_backend.restype = C.c_int
-        L.pagan_msa_set_sampler.argtypes = [vp, C.c_int32]
-        L.pagan_msa_set_sampler.restype = C.c_int
-        L.pagan_msa_set_decoder.argtypes = [vp, C.c_int32, C.c_double]
-        L.pagan_msa_set_decoder.restype = C.c_int
-        L.pagan_msa_node_decode.argtypes = [vp, C.c_int32, f64p]
-        L.pagan_msa_node_decode.restype = C.c_int
-        L.pagan_pileup_default_opts.argtypes = [C.POINTER(CPileupOpts)]
-        L.pagan_pileup_default_opts.restype = None
-        L.pagan_pileup_create.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(CPileupOpts), C.POINTER(vp)]
-        L.pagan_pileup_create.restype = C.c_int
-        L.pagan_pileup_align.argtypes = [vp]
-        L.pagan_pileup_align.restype = C.c_int
-        L.pagan_pileup_n_steps.argtypes = [vp]
-        L.pagan_pileup_n_steps.restype = C.c_int
-        L.pagan_pileup_step_info.argtypes = [vp, C.c_int32, C.POINTER(CPileupStep)]
-        L.pagan_pileup_step_info.restype = C.c_int
-        L.pagan_pileup_step_job.argtypes = [vp, C.c_int32, C.POINTER(abi.CJob)]
-        L.pagan_pileup_step_job.restype = C.c_int
-        L.pagan_pileup_step_result.argtypes = [vp, C.c_int32, C.POINTER(abi.CResult)]
-        L.pagan_pileup_step_result.restype = C.c_int
-        L.pagan_pileup_alignment_length.argtypes = [vp]
-        L.pagan_pileup_alignment_length.restype = C.c_int
-        L.pagan_pileup_alignment_row.argtypes = [vp, C.c_int32, C.c_char_p]
-        L.pagan_pileup_alignment_row.restype = C.c_int
-        L.pagan_pileup_set_batch_backend.argtypes = [vp, BATCH_FN, C.c_void_p]
-        L.pagan_pileup_set_batch_backend.restype = C.c_int
-        L.pagan_pileup_destroy.argtypes = [vp]
-        L.pagan_pileup_destroy.restype = None
-        L.pagan_msa_node_fb.argtypes = [vp, C.c_int32, f64p]
-        L.pagan_msa_node_fb.restype = C.c_int
-        L.pagan_msa_node_support.argtypes = [vp, C.c_int32, f64p]
-        L.pagan_msa_node_support.restype = C.c_int
-        L.pagan_msa_node_marginals.argtypes = [vp, C.c_int32, f64p, f64p, _i32p, f64p, f64p, f64p, _i32p, f64p]
-        L.pagan_msa_node_marginals.restype = C.c_int
-        L.pagan_msa_node_model_prob.argtypes = [vp, C.c_int32, C.POINTER(abi.CModelProb)]
-        L.pagan_msa_node_model_prob.restype = C.c_int
-        L.pagan_msa_support_row.argtypes = [vp, C.c_int32, _f32p]
-        L.pagan_msa_support_row.restype = C.c_int
-        L.pagan_msa_set_counts.argtypes = [vp, C.c_int32]
-        L.pagan_msa_set_counts.restype = C.c_int
-        L.pagan_msa_node_counts.argtypes = [vp, C.c_int32, f64p, f64p]
-        L.pagan_msa_node_counts.restype = C.c_int
-        L.pagan_msa_set_indel_model.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double]
-        L.pagan_msa_set_indel_model.restype = C.c_int
-        L.pagan_fit_indel.argtypes = [C.c_int32, f64p, f64p, f64p, f64p]
-        L.pagan_fit_indel.restype = C.c_int
-        i64p, cpp = C.POINTER(C.c_int64), C.POINTER(C.c_char_p)
-        L.pagan_guide_distances.argtypes = [C.c_int32, cpp, C.c_int32, C.c_int32, i64p, i64p, f64p, C.POINTER(CGuideInfo)]
-        L.pagan_guide_distances.restype = C.c_int
-        L.pagan_guide_tree.argtypes = [C.c_int32, cpp, cpp, C.c_int32, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(CGuideInfo)]
-        L.pagan_guide_tree.restype = C.c_int64
-        L.pagan_guide_kmer_length.argtypes = [C.c_int32, C.c_int64]
-        L.pagan_guide_kmer_length.restype = C.c_int
-        L.pagan_guide_distance_of.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32]
-        L.pagan_guide_distance_of.restype = C.c_double
-        L.pagan_guide_upgma.argtypes = [C.c_int32, cpp, f64p, C.c_char_p, C.c_int64]
-        L.pagan_guide_upgma.restype = C.c_int64
-        L.pagan_guide_predict_bytes.argtypes = [C.c_int32, C.c_int64]
-        L.pagan_guide_predict_bytes.restype = C.c_int64
-        L.pagan_aln_distances.argtypes = [C.c_int32, cpp, C.c_int32, i64p, i64p, f64p, C.POINTER(CAlnInfo)]
-        L.pagan_aln_distances.restype = C.c_int
-        L.pagan_aln_tree.argtypes = [C.c_int32, cpp, cpp, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(CAlnInfo)]
-        L.pagan_aln_tree.restype = C.c_int64
-        L.pagan_aln_predict_bytes.argtypes = [C.c_int32, C.c_int64]
-        L.pagan_aln_predict_bytes.restype = C.c_int64
-        L.pagan_msa_alignment_tree.argtypes = [vp, C.c_char_p, C.c_int64, C.POINTER(CAlnInfo)]
-        L.pagan_msa_alignment_tree.restype = C.c_int64
-        u8p = C.POINTER(C.c_uint8)
-        L.pagan_anc_pmatrix.argtypes = [C.c_int32, _f32p, C.c_double, f64p, f64p]
-        L.pagan_anc_pmatrix.restype = C.c_int
-        L.pagan_anc_rate_matrix.argtypes = [C.c_int32, _f32p, f64p, f64p]
-        L.pagan_anc_rate_matrix.restype = C.c_int
-        L.pagan_anc_encode_row.argtypes = [C.c_int32, C.c_char_p, u8p]
-        L.pagan_anc_encode_row.restype = C.c_int64
-        L.pagan_anc_check_tree.argtypes = [C.c_int32, _i32p, _i32p, f64p]
-        L.pagan_anc_check_tree.restype = C.c_int
-        L.pagan_anc_predict_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int64]
-        L.pagan_anc_predict_bytes.restype = C.c_int64
-        L.pagan_anc_reconstruct.argtypes = [C.c_int32, _i32p, _i32p, f64p, cpp, C.c_int32, _f32p, C.c_uint32, C.c_int32, _i32p,
-                                            f64p, _i32p, f64p, f64p, u8p, _f32p, u8p, f64p, C.POINTER(CAncInfo)]
-        L.pagan_anc_reconstruct.restype = C.c_int
-        L.pagan_msa_ancestral.argtypes = [vp, C.c_uint32, f64p, f64p, C.POINTER(CAncInfo)]
-        L.pagan_msa_ancestral.restype = C.c_int
-        L.pagan_msa_ancestral_row.argtypes = [vp, C.c_int32, C.c_char_p]
-        L.pagan_msa_ancestral_row.restype = C.c_int
-        L.pagan_msa_ancestral_support.argtypes = [vp, C.c_int32, _f32p]
-        L.pagan_msa_ancestral_support.restype = C.c_int
-        L.pagan_msa_write_fasta_ancestral.argtypes = [vp, C.c_char_p, C.c_int32]
-        L.pagan_msa_write_fasta_ancestral.restype = C.c_int
-        L.pagan_msa_ancestral_best.argtypes = [vp, C.POINTER(u8p), C.POINTER(_f32p)]
-        L.pagan_msa_ancestral_best.restype = C.c_int
-        _declared = True
-    return L
-
-
-HOST_EXPORTED = ["pagan_assign_units", "pagan_msa_default_opts", "pagan_msa_create", "pagan_msa_align", "pagan_msa_n_internal",
-                 "pagan_msa_node_info", "pagan_msa_node_job", "pagan_msa_node_result", "pagan_msa_timing_get",
-                 "pagan_msa_alignment_length", "pagan_msa_alignment_row", "pagan_msa_write_fasta", "pagan_msa_write_fasta_nodes",
-                 "pagan_msa_node_graph", "pagan_msa_finish_lazy", "pagan_msa_parents_built",
-                 "pagan_msa_destroy", "pagan_hgraph_leaf", "pagan_hgraph_parent", "pagan_hgraph_parent_device", "pagan_parents_device_calls", "pagan_hgraph_view",
-                 "pagan_hgraph_attrs", "pagan_hgraph_fwd", "pagan_hgraph_string", "pagan_hgraph_free",
-                 "pagan_define_tunnel", "pagan_prefix_hits", "pagan_prefix_hits_raw", "pagan_anchors_device_calls", "pagan_drop_bad_hits", "pagan_define_tunnel_overlapping",
-                 "pagan_force_gap", "pagan_dna_model", "pagan_protein_model", "pagan_model_prob_table", "pagan_model_alphabets",
-                 "pagan_codon_model", "pagan_codon_alphabet", "pagan_codon_states", "pagan_codon_translate", "pagan_hgraph_leaf_codon",
-                 "pagan_eigen_qrev", "pagan_msa_ready", "pagan_msa_remaining", "pagan_msa_node_cost",
-                 "pagan_msa_align_nodes", "pagan_msa_export_result", "pagan_msa_import_result", "pagan_msa_finish",
-                 "pagan_msa_data_type", "pagan_msa_node_device", "pagan_msa_set_batch_backend",
-                 "pagan_pileup_default_opts", "pagan_pileup_create", "pagan_pileup_align", "pagan_pileup_n_steps",
-                 "pagan_pileup_step_info", "pagan_pileup_step_job", "pagan_pileup_step_result",
-                 "pagan_pileup_alignment_length", "pagan_pileup_alignment_row", "pagan_pileup_set_batch_backend",
-                 "pagan_pileup_destroy",
-                 "pagan_msa_node_fb", "pagan_msa_node_support", "pagan_msa_node_marginals", "pagan_msa_node_model_prob", "pagan_msa_support_row",
-                 "pagan_msa_set_sampler", "pagan_msa_set_decoder", "pagan_msa_node_decode",
-                 "pagan_msa_set_counts", "pagan_msa_node_counts", "pagan_msa_set_indel_model", "pagan_fit_indel",
-                 "pagan_guide_distances", "pagan_guide_tree", "pagan_guide_kmer_length", "pagan_guide_distance_of",
-                 "pagan_guide_upgma", "pagan_guide_predict_bytes",
-                 "pagan_aln_distances", "pagan_aln_tree", "pagan_aln_predict_bytes", "pagan_msa_alignment_tree",
-                 "pagan_anc_pmatrix", "pagan_anc_rate_matrix", "pagan_anc_encode_row", "pagan_anc_check_tree", "pagan_anc_predict_bytes", "pagan_anc_reconstruct",
-                 "pagan_msa_ancestral", "pagan_msa_ancestral_row", "pagan_msa_ancestral_support",
-                 "pagan_msa_write_fasta_ancestral", "pagan_msa_ancestral_best"]
-
-
-def _ip(a):
-    return a.ctypes.data_as(_i32p)
-
-
-def _fp(a):
-    return a.ctypes.data_as(_f32p)
+    """The loaded library: every entry point of both headers is declared from the moment lib() loads it."""
+    return lib()
 
 
 def _graph_from_view(v):
@@ -343,11 +208,23 @@ def _graph_from_view(v):
     return abi.Graph(np.ctypeslib.as_array(v.state, shape=(ns,)).copy(), off, src, lw, eid, n_edges=v.n_edges)
 
 
-class HGraph:
-    """Host sequence graph (leaf or parent).  `owned=False` for graphs borrowed from an Msa."""
+def _result_view(result):
+    """(a pagan_result over an abi.Result's columns and used edges, the arrays it points into)."""
+    keep = [np.ascontiguousarray(a, np.int32) for a in (result.cols, result.left_used, result.right_used)]
+    r = abi.CResult()
+    r.n_cols, r.cols = int(keep[0].shape[0]), C.cast(_ip(keep[0]), abi.colp)
+    r.n_left_used, r.left_used = int(keep[1].shape[0]), _ip(keep[1])
+    r.n_right_used, r.right_used = int(keep[2].shape[0]), _ip(keep[2])
+    return r, keep
+
+
+class HGraph(Handle):
+    """Host sequence graph (leaf or parent).  `owned=False` for graphs borrowed from an Msa, which `keep` keeps alive."""
+    _destroy = "pagan_hgraph_free"
+    h = property(lambda self: self._h)
 
     def __init__(self, handle, owned=True, keep=None):
-        self.h, self.owned, self._keep = handle, owned, keep
+        self._h, self.owned, self._keep = handle, owned, keep
 
     @classmethod
     def leaf(cls, seq, alphabet=DNA_FULL, flags=0):
@@ -361,14 +238,7 @@ class HGraph:
     @classmethod
     def parent(cls, left, right, result, lbl, rbl, parsimony, char_as, flags=0):
         """result: abi.Result (columns + used edges) of aligning left and right."""
-        r = abi.CResult()
-        cols = np.ascontiguousarray(result.cols, np.int32)
-        lu = np.ascontiguousarray(result.left_used, np.int32)
-        ru = np.ascontiguousarray(result.right_used, np.int32)
-        r.n_cols = int(cols.shape[0])
-        r.cols = C.cast(_ip(cols), C.POINTER(abi.CCol))
-        r.n_left_used, r.left_used = int(lu.shape[0]), _ip(lu)
-        r.n_right_used, r.right_used = int(ru.shape[0]), _ip(ru)
+        r, _keep = _result_view(result)
         pars = np.ascontiguousarray(parsimony, np.int32)
         S = int(round(pars.size ** 0.5))
         return cls(_lib().pagan_hgraph_parent(left.h, right.h, C.byref(r), lbl, rbl, _ip(pars), S, char_as, flags))
@@ -378,14 +248,7 @@ class HGraph:
         """The same parent built on the current HIP device (csrc/dp_parent.hip).  Raises without a device: there is no
         host graph in its place.  The returned graph carries `.build_info` = (runs of skipped sites, rounds of the boundary
         pass, deleted sites, weights outside the log table, log weights corrected by the host)."""
-        r = abi.CResult()
-        cols = np.ascontiguousarray(result.cols, np.int32)
-        lu = np.ascontiguousarray(result.left_used, np.int32)
-        ru = np.ascontiguousarray(result.right_used, np.int32)
-        r.n_cols = int(cols.shape[0])
-        r.cols = C.cast(_ip(cols), C.POINTER(abi.CCol))
-        r.n_left_used, r.left_used = int(lu.shape[0]), _ip(lu)
-        r.n_right_used, r.right_used = int(ru.shape[0]), _ip(ru)
+        r, _keep = _result_view(result)
         pars = np.ascontiguousarray(parsimony, np.int32)
         S = int(round(pars.size ** 0.5))
         info = np.zeros(8, np.int32)
@@ -395,11 +258,6 @@ class HGraph:
         g = cls(h)
         g.build_info = tuple(int(x) for x in info[:5])
         return g
-
-    def __del__(self):
-        if getattr(self, "owned", False) and self.h:
-            _lib().pagan_hgraph_free(self.h)
-            self.h = None
 
     def flatten(self):
         v = abi.CGraph()
@@ -440,7 +298,7 @@ def assign_units(costs, n_workers):
     """owner[k] for every unit: largest first, least-loaded worker (pagan_assign_units)."""
     c = np.ascontiguousarray(costs, np.int64)
     owner = np.zeros(c.shape[0], np.int32)
-    _lib().pagan_assign_units(int(c.shape[0]), c.ctypes.data_as(C.POINTER(C.c_int64)), int(n_workers), _ip(owner))
+    _lib().pagan_assign_units(int(c.shape[0]), c.ctypes.data_as(_i64p), int(n_workers), _ip(owner))
     return owner
 
 
@@ -495,10 +353,8 @@ def define_tunnel_overlapping(hits, g1, g2, width=15):
     lo = np.zeros(len(g1) + 1, np.int32)
     cap = len(g1) + 2
     blocks = np.zeros((cap, 4), np.int32)
-    n = _lib().pagan_define_tunnel_overlapping(_ip(h), int(h.shape[0]), g1.encode(), g2.encode(), width, _ip(up), _ip(lo),
-                                               _ip(blocks), cap)
-    if n < 0:
-        raise RuntimeError("pagan_define_tunnel_overlapping failed: %d" % n)
+    n = check(_lib().pagan_define_tunnel_overlapping(_ip(h), int(h.shape[0]), g1.encode(), g2.encode(), width, _ip(up), _ip(lo),
+                                                     _ip(blocks), cap), "pagan_define_tunnel_overlapping")
     return abi.Band(up, lo), blocks[:n].copy()
 
 
@@ -516,9 +372,7 @@ def dna_model(base_freq, dist):
     table = np.zeros(225, np.float32)
     params = np.zeros(4, np.float32)
     pars = np.zeros(225, np.int32)
-    rc = _lib().pagan_dna_model(_fp(bf), float(dist), _fp(table), _fp(params), _ip(pars))
-    if rc != 0:
-        raise RuntimeError("pagan_dna_model failed: %d" % rc)
+    check(_lib().pagan_dna_model(_fp(bf), float(dist), _fp(table), _fp(params), _ip(pars)), "pagan_dna_model")
     return abi.Model(table.reshape(15, 15).T, *params), pars
 
 
@@ -527,9 +381,7 @@ def protein_model(dist):
     table = np.zeros(211 * 211, np.float32)
     params = np.zeros(4, np.float32)
     pars = np.zeros(211 * 211, np.int32)
-    rc = _lib().pagan_protein_model(float(dist), _fp(table), _fp(params), _ip(pars))
-    if rc != 0:
-        raise RuntimeError("pagan_protein_model failed: %d" % rc)
+    check(_lib().pagan_protein_model(float(dist), _fp(table), _fp(params), _ip(pars)), "pagan_protein_model")
     return abi.Model(table.reshape(211, 211).T, *params), pars
 
 
@@ -542,9 +394,7 @@ def codon_model(dist):
     table = np.zeros(S * S, np.float32)
     params = np.zeros(4, np.float32)
     pars = np.zeros(S * S, np.int32)
-    rc = _lib().pagan_codon_model(float(dist), _fp(table), _fp(params), _ip(pars))
-    if rc != 0:
-        raise RuntimeError("pagan_codon_model failed: %d" % rc)
+    check(_lib().pagan_codon_model(float(dist), _fp(table), _fp(params), _ip(pars)), "pagan_codon_model")
     return abi.Model(table.reshape(S, S).T, *params), pars
 
 
@@ -559,17 +409,13 @@ def codon_alphabet():
 def codon_translate(codon_string):
     """One amino-acid letter per triplet (Codon_translation::gapped_DNA_to_protein)."""
     buf = C.create_string_buffer(len(codon_string) // 3 + 2)
-    n = _lib().pagan_codon_translate(codon_string.encode(), buf)
-    if n < 0:
-        raise RuntimeError("pagan_codon_translate failed: %d" % n)
+    n = check(_lib().pagan_codon_translate(codon_string.encode(), buf), "pagan_codon_translate")
     return buf.raw[:n].decode()
 
 
 def codon_states(nucleotides):
     out = np.zeros(len(nucleotides) // 3 + 2, np.int32)
-    n = _lib().pagan_codon_states(nucleotides.encode(), _ip(out))
-    if n < 0:
-        raise RuntimeError("pagan_codon_states failed: %d" % n)
+    n = check(_lib().pagan_codon_states(nucleotides.encode(), _ip(out)), "pagan_codon_states")
     return out[:n].copy()
 
 
@@ -579,9 +425,7 @@ def model_prob(data_type, dist, base_freq=None):
     score = np.zeros(S * S, np.float32)
     params = np.zeros(3, np.float32)
     bf = np.ascontiguousarray(base_freq if base_freq is not None else [0.25] * 4, np.float32)
-    rc = _lib().pagan_model_prob_table(int(data_type), _fp(bf), float(dist), _fp(score), _fp(params))
-    if rc != 0:
-        raise RuntimeError("pagan_model_prob_table failed: %d" % rc)
+    check(_lib().pagan_model_prob_table(int(data_type), _fp(bf), float(dist), _fp(score), _fp(params)), "pagan_model_prob_table")
     return abi.ModelProb(score.reshape(S, S).T, *params)
 
 
@@ -594,25 +438,9 @@ def fit_indel(dists, trans):
             if isinstance(t, dict) else np.asarray(t, np.float64).reshape(12) for t in trans]
     t = np.ascontiguousarray(np.array(rows, np.float64).reshape(-1, 12))
     assert t.shape[0] == d.shape[0]
-    f64p = C.POINTER(C.c_double)
     rate, ext = C.c_double(), C.c_double()
-    rc = _lib().pagan_fit_indel(int(d.shape[0]), d.ctypes.data_as(f64p), t.ctypes.data_as(f64p), C.byref(rate), C.byref(ext))
-    if rc != 0:
-        from . import PaganError
-        raise PaganError(rc, "pagan_fit_indel")
+    check(_lib().pagan_fit_indel(int(d.shape[0]), _dp(d), _dp(t), C.byref(rate), C.byref(ext)), "pagan_fit_indel")
     return rate.value, ext.value
-
-
-def sample_uniforms(seed, node, n):
-    """pagan_sample_uniforms: the numbers the walk samples node `node`'s path with under sample_seed=seed."""
-    from . import sample_uniforms as f
-    return f(seed, node, n)
-
-
-def sample_uniforms_path(seed, node, path, n):
-    """pagan_sample_uniforms_path: the numbers path `path` of node `node`'s ensemble is sampled with (path 0: sample_uniforms)."""
-    from . import sample_uniforms_path as f
-    return f(seed, node, path, n)
 
 
 def alphabets(data_type):
@@ -628,32 +456,17 @@ def eigen_qrev(Q, pi):
     pi = np.ascontiguousarray(pi, np.float64)
     n = pi.shape[0]
     root, U, V = np.zeros(n), np.zeros((n, n)), np.zeros((n, n))
-    dp = C.POINTER(C.c_double)
-    rc = _lib().pagan_eigen_qrev(Q.ctypes.data_as(dp), pi.ctypes.data_as(dp), n, root.ctypes.data_as(dp),
-                                 U.ctypes.data_as(dp), V.ctypes.data_as(dp))
-    if rc != 0:
-        raise RuntimeError("pagan_eigen_qrev failed: %d" % rc)
+    check(_lib().pagan_eigen_qrev(_dp(Q), _dp(pi), n, _dp(root), _dp(U), _dp(V)), "pagan_eigen_qrev")
     return root, U, V
-
-
-def _guide_check(rc, what):
-    if rc < 0:
-        from . import PaganError
-        raise PaganError(int(rc), what)
-    return rc
 
 
 def _c_strings(strings):
     return (C.c_char_p * len(strings))(*[s.encode() if isinstance(s, str) else bytes(s) for s in strings])
 
 
-def _guide_info(ci):
-    return {name: getattr(ci, name) for name, _ in CGuideInfo._fields_}
-
-
 def guide_kmer_length(data_type, max_len):
     """pagan_guide_kmer_length (host only): the default k for sequences of at most max_len cleaned letters."""
-    return _guide_check(_lib().pagan_guide_kmer_length(int(data_type), int(max_len)), "pagan_guide_kmer_length")
+    return check(_lib().pagan_guide_kmer_length(int(data_type), int(max_len)), "pagan_guide_kmer_length")
 
 
 def guide_distance_of(shared, m, k, data_type):
@@ -663,7 +476,7 @@ def guide_distance_of(shared, m, k, data_type):
 
 def guide_predict_bytes(n, total_len):
     """pagan_guide_predict_bytes (host only): device bytes guide_distances allocates at most."""
-    return _guide_check(_lib().pagan_guide_predict_bytes(int(n), int(total_len)), "pagan_guide_predict_bytes")
+    return check(_lib().pagan_guide_predict_bytes(int(n), int(total_len)), "pagan_guide_predict_bytes")
 
 
 def guide_distances(seqs, data_type=0, k=0):
@@ -674,18 +487,16 @@ def guide_distances(seqs, data_type=0, k=0):
     kmers = np.zeros(n, np.int64)
     dist = np.zeros((n, n), np.float64)
     ci = CGuideInfo()
-    i64p, f64p = C.POINTER(C.c_int64), C.POINTER(C.c_double)
-    _guide_check(_lib().pagan_guide_distances(n, _c_strings(seqs), int(data_type), int(k), shared.ctypes.data_as(i64p),
-                                              kmers.ctypes.data_as(i64p), dist.ctypes.data_as(f64p), C.byref(ci)),
-                 "pagan_guide_distances")
-    return shared, kmers, dist, _guide_info(ci)
+    check(_lib().pagan_guide_distances(n, _c_strings(seqs), int(data_type), int(k), shared.ctypes.data_as(_i64p),
+                                       kmers.ctypes.data_as(_i64p), _dp(dist), C.byref(ci)), "pagan_guide_distances")
+    return shared, kmers, dist, struct_dict(ci)
 
 
 def _newick_call(call, what, names):
     cap = sum(len(s) for s in names) + 64 * len(names) + 64        # (a branch prints as at most 24 characters)
     for _ in range(2):
         buf = C.create_string_buffer(cap)
-        need = _guide_check(call(buf, cap), what)
+        need = check(call(buf, cap), what)
         if need <= cap:
             return buf.value.decode()
         cap = need
@@ -703,7 +514,7 @@ def guide_tree(names, seqs, data_type=0, k=0, with_info=False):
     L = _lib()
     newick = _newick_call(lambda buf, cap: L.pagan_guide_tree(n, na, sa, int(data_type), int(k), buf, cap, C.byref(ci)),
                           "pagan_guide_tree", names)
-    return (newick, _guide_info(ci)) if with_info else newick
+    return (newick, struct_dict(ci)) if with_info else newick
 
 
 def guide_upgma(names, dist):
@@ -714,17 +525,12 @@ def guide_upgma(names, dist):
         raise ValueError("dist must be [%d, %d]" % (n, n))
     na = _c_strings(names)
     L = _lib()
-    return _newick_call(lambda buf, cap: L.pagan_guide_upgma(n, na, d.ctypes.data_as(C.POINTER(C.c_double)), buf, cap),
-                        "pagan_guide_upgma", names)
-
-
-def _aln_info(ci):
-    return {name: getattr(ci, name) for name, _ in CAlnInfo._fields_}
+    return _newick_call(lambda buf, cap: L.pagan_guide_upgma(n, na, _dp(d), buf, cap), "pagan_guide_upgma", names)
 
 
 def aln_predict_bytes(n, columns):
     """pagan_aln_predict_bytes (host only): device bytes aln_distances allocates at most for n rows of `columns` columns."""
-    return _guide_check(_lib().pagan_aln_predict_bytes(int(n), int(columns)), "pagan_aln_predict_bytes")
+    return check(_lib().pagan_aln_predict_bytes(int(n), int(columns)), "pagan_aln_predict_bytes")
 
 
 def aln_distances(rows, data_type=0):
@@ -736,10 +542,9 @@ def aln_distances(rows, data_type=0):
     match = np.zeros((n, n), np.int64)
     dist = np.zeros((n, n), np.float64)
     ci = CAlnInfo()
-    i64p, f64p = C.POINTER(C.c_int64), C.POINTER(C.c_double)
-    _guide_check(_lib().pagan_aln_distances(n, _c_strings(rows), int(data_type), both.ctypes.data_as(i64p), match.ctypes.data_as(i64p),
-                                            dist.ctypes.data_as(f64p), C.byref(ci)), "pagan_aln_distances")
-    return both, match, dist, _aln_info(ci)
+    check(_lib().pagan_aln_distances(n, _c_strings(rows), int(data_type), both.ctypes.data_as(_i64p), match.ctypes.data_as(_i64p),
+                                     _dp(dist), C.byref(ci)), "pagan_aln_distances")
+    return both, match, dist, struct_dict(ci)
 
 
 def aln_tree(names, rows, data_type=0, with_info=False):
@@ -752,14 +557,10 @@ def aln_tree(names, rows, data_type=0, with_info=False):
     ci = CAlnInfo()
     L = _lib()
     newick = _newick_call(lambda buf, cap: L.pagan_aln_tree(n, na, ra, int(data_type), buf, cap, C.byref(ci)), "pagan_aln_tree", names)
-    return (newick, _aln_info(ci)) if with_info else newick
+    return (newick, struct_dict(ci)) if with_info else newick
 
 
 ANC_STATES = {1: 4, 2: 20, 3: 61}
-
-
-def _anc_info(ci):
-    return {name: getattr(ci, name) for name, _ in CAncInfo._fields_}
 
 
 def _base_freq(base_freq):
@@ -776,9 +577,8 @@ def anc_pmatrix(data_type, t, base_freq=None):
     for data_type 1 / 2 / 3) for branch length t; base_freq (DNA only) as dna_model takes it."""
     S = ANC_STATES.get(int(data_type), 1)
     P, pi = np.zeros((S, S), np.float64), np.zeros(S, np.float64)
-    f64p = C.POINTER(C.c_double)
     _keep, bfp = _base_freq(base_freq)
-    _guide_check(_lib().pagan_anc_pmatrix(int(data_type), bfp, float(t), P.ctypes.data_as(f64p), pi.ctypes.data_as(f64p)), "pagan_anc_pmatrix")
+    check(_lib().pagan_anc_pmatrix(int(data_type), bfp, float(t), _dp(P), _dp(pi)), "pagan_anc_pmatrix")
     return P, pi
 
 
@@ -786,9 +586,8 @@ def anc_rate_matrix(data_type, base_freq=None):
     """pagan_anc_rate_matrix (host only): (Q [S, S], pi [S]) -- the rate matrix anc_pmatrix exponentiates, the model's made proper."""
     S = ANC_STATES.get(int(data_type), 1)
     Q, pi = np.zeros((S, S), np.float64), np.zeros(S, np.float64)
-    f64p = C.POINTER(C.c_double)
     _keep, bfp = _base_freq(base_freq)
-    _guide_check(_lib().pagan_anc_rate_matrix(int(data_type), bfp, Q.ctypes.data_as(f64p), pi.ctypes.data_as(f64p)), "pagan_anc_rate_matrix")
+    check(_lib().pagan_anc_rate_matrix(int(data_type), bfp, _dp(Q), _dp(pi)), "pagan_anc_rate_matrix")
     return Q, pi
 
 
@@ -797,7 +596,7 @@ def anc_encode_row(data_type, row):
     bits (0: missing data), protein and codon the state (255: missing data)."""
     raw = row.encode() if isinstance(row, str) else bytes(row)
     codes = np.zeros(max(len(raw), 1), np.uint8)
-    n = _guide_check(_lib().pagan_anc_encode_row(int(data_type), raw, codes.ctypes.data_as(C.POINTER(C.c_uint8))), "pagan_anc_encode_row")
+    n = check(_lib().pagan_anc_encode_row(int(data_type), raw, codes.ctypes.data_as(_u8p)), "pagan_anc_encode_row")
     return codes[:n].copy()
 
 
@@ -808,12 +607,12 @@ def anc_check_tree(left, right, branch):
     n = len(le) + 1
     if len(ri) != n - 1 or len(br) != 2 * n - 1:
         raise ValueError("left, right hold n - 1 entries and branch 2 n - 1")
-    _guide_check(_lib().pagan_anc_check_tree(n, _ip(le), _ip(ri), br.ctypes.data_as(C.POINTER(C.c_double))), "pagan_anc_check_tree")
+    check(_lib().pagan_anc_check_tree(n, _ip(le), _ip(ri), _dp(br)), "pagan_anc_check_tree")
 
 
 def anc_predict_bytes(n_leaves, columns, data_type, chunk_cols=0):
     """pagan_anc_predict_bytes (host only): device bytes anc_reconstruct allocates at most."""
-    return _guide_check(_lib().pagan_anc_predict_bytes(int(n_leaves), int(columns), int(data_type), int(chunk_cols)), "pagan_anc_predict_bytes")
+    return check(_lib().pagan_anc_predict_bytes(int(n_leaves), int(columns), int(data_type), int(chunk_cols)), "pagan_anc_predict_bytes")
 
 
 def anc_reconstruct(left, right, branch, rows, data_type=0, base_freq=None, post_nodes=()):
@@ -828,7 +627,6 @@ def anc_reconstruct(left, right, branch, rows, data_type=0, base_freq=None, post
         raise ValueError("left, right hold n - 1 entries and branch 2 n - 1")
     pn = np.ascontiguousarray(post_nodes, np.int32)
     chars = len(rows[0]) if n else 0
-    f64p, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
     _keep, bfp = _base_freq(base_freq)
     ci = CAncInfo()
     # the columns are known only once the data type is resolved: size for one character a column, cut afterwards
@@ -837,15 +635,14 @@ def anc_reconstruct(left, right, branch, rows, data_type=0, base_freq=None, post
     best, best_p = np.zeros((n - 1) * chars, np.uint8), np.zeros((n - 1) * chars, np.float32)
     has = np.zeros((2 * n - 1) * chars, np.uint8)
     post = np.zeros(len(pn) * chars * ANC_STATES[3], np.float64)
-    _guide_check(_lib().pagan_anc_reconstruct(n, _ip(le), _ip(ri), br.ctypes.data_as(f64p), _c_strings(rows), int(data_type), bfp, 0,
-                                              len(pn), _ip(pn), col_lik.ctypes.data_as(f64p), _ip(col_exp), col_loglik.ctypes.data_as(f64p),
-                                              C.byref(loglik), best.ctypes.data_as(u8p), _fp(best_p), has.ctypes.data_as(u8p),
-                                              post.ctypes.data_as(f64p), C.byref(ci)), "pagan_anc_reconstruct")
+    check(_lib().pagan_anc_reconstruct(n, _ip(le), _ip(ri), _dp(br), _c_strings(rows), int(data_type), bfp, 0, len(pn), _ip(pn),
+                                       _dp(col_lik), _ip(col_exp), _dp(col_loglik), C.byref(loglik), best.ctypes.data_as(_u8p),
+                                       _fp(best_p), has.ctypes.data_as(_u8p), _dp(post), C.byref(ci)), "pagan_anc_reconstruct")
     L, S = int(ci.columns), int(ci.states)
     return {"col_lik": col_lik[:L].copy(), "col_exp": col_exp[:L].copy(), "col_loglik": col_loglik[:L].copy(), "loglik": loglik.value,
             "best": best[:(n - 1) * L].reshape(n - 1, L).copy(), "best_p": best_p[:(n - 1) * L].reshape(n - 1, L).copy(),
             "has_data": has[:(2 * n - 1) * L].reshape(2 * n - 1, L).copy(), "post": post[:len(pn) * L * S].reshape(len(pn), L, S).copy(),
-            "info": _anc_info(ci)}
+            "info": struct_dict(ci)}
 
 
 class Ancestral:
@@ -859,20 +656,20 @@ class Ancestral:
         m = self._msa
         n = m._L.pagan_msa_alignment_length(m._h)
         buf = C.create_string_buffer(n + 1)
-        m._fb_check(m._L.pagan_msa_ancestral_row(m._h, node, buf), "pagan_msa_ancestral_row")
+        check(m._L.pagan_msa_ancestral_row(m._h, node, buf), "pagan_msa_ancestral_row")
         return buf.raw[:n].decode()
 
     def support(self, node):
         """pagan_msa_ancestral_support: the posterior of the shown state per column (float32), -1 at gaps."""
         m = self._msa
         buf = np.zeros(int(self.info["columns"]), np.float32)
-        m._fb_check(m._L.pagan_msa_ancestral_support(m._h, node, _fp(buf)), "pagan_msa_ancestral_support")
+        check(m._L.pagan_msa_ancestral_support(m._h, node, _fp(buf)), "pagan_msa_ancestral_support")
         return buf
 
     def write_fasta(self, path, chars_by_line=60):
         """pagan_msa_write_fasta_ancestral: write_fasta(include_internal=True)'s file with the overlaid rows."""
         m = self._msa
-        m._fb_check(m._L.pagan_msa_write_fasta_ancestral(m._h, str(path).encode(), chars_by_line), "pagan_msa_write_fasta_ancestral")
+        check(m._L.pagan_msa_write_fasta_ancestral(m._h, str(path).encode(), chars_by_line), "pagan_msa_write_fasta_ancestral")
 
 
 def differing_clades(newick_a, newick_b):
@@ -933,9 +730,10 @@ def _job_copy(j):
     return left, right, model, band
 
 
-class Pileup:
+class Pileup(Handle):
     """Reads_aligner::pileup_alignment mirror: read 0 is the reference, every further read is aligned (GPU) against the
     growing root and joins it when it overlaps well enough."""
+    _destroy = "pagan_pileup_destroy"
 
     def __init__(self, names, seqs, **opts):
         L = _lib()
@@ -946,13 +744,9 @@ class Pileup:
                 raise TypeError("unknown option %s" % k)
             setattr(o, k, v)
         self.n = len(names)
-        na = (C.c_char_p * self.n)(*[s.encode() for s in names])
-        sa = (C.c_char_p * self.n)(*[s.encode() for s in seqs])
+        na, sa = _c_strings(names), _c_strings(seqs)
         self._h = C.c_void_p()
-        rc = L.pagan_pileup_create(self.n, na, sa, C.byref(o), C.byref(self._h))
-        if rc != 0:
-            from . import PaganError
-            raise PaganError(rc, "pagan_pileup_create")
+        check(L.pagan_pileup_create(self.n, na, sa, C.byref(o), C.byref(self._h)), "pagan_pileup_create")
         self._L = L
 
     def set_batch_backend(self, fn):
@@ -961,10 +755,7 @@ class Pileup:
         self._L.pagan_pileup_set_batch_backend(self._h, self._backend, None)
 
     def align(self):
-        rc = self._L.pagan_pileup_align(self._h)
-        if rc != 0:
-            from . import PaganError
-            raise PaganError(rc, "pagan_pileup_align")
+        check(self._L.pagan_pileup_align(self._h), "pagan_pileup_align")
         return self
 
     @property
@@ -978,16 +769,12 @@ class Pileup:
 
     def step_job(self, k):
         j = abi.CJob()
-        rc = self._L.pagan_pileup_step_job(self._h, k, C.byref(j))
-        if rc != 0:
-            raise RuntimeError("pagan_pileup_step_job failed: %d" % rc)
+        check(self._L.pagan_pileup_step_job(self._h, k, C.byref(j)), "pagan_pileup_step_job")
         return _job_copy(j)
 
     def step_result(self, k):
         r = abi.CResult()
-        rc = self._L.pagan_pileup_step_result(self._h, k, C.byref(r))
-        if rc != 0:
-            raise RuntimeError("pagan_pileup_step_result failed: %d" % rc)
+        check(self._L.pagan_pileup_step_result(self._h, k, C.byref(r)), "pagan_pileup_step_result")
         return abi.Result(r)
 
     def alignment(self):
@@ -999,20 +786,10 @@ class Pileup:
             rows.append(buf.raw[:ln].decode())
         return rows
 
-    def close(self):
-        if self._h:
-            self._L.pagan_pileup_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Msa:
+class Msa(Handle):
     """Progressive alignment of sequences on a rooted binary guide tree (Node mirror)."""
+    _destroy = "pagan_msa_destroy"
 
     def __init__(self, names, seqs, newick=None, sample_on_device=0, posterior_decode=0, decode_gap_weight=0.5, expected_counts=0,
                  indel_model=None, **opts):
@@ -1037,39 +814,20 @@ class Msa:
         if newick is None:
             newick = guide_tree(names, seqs, data_type=o.data_type)
         self.newick = newick
-        na = (C.c_char_p * self.n)(*[s.encode() for s in names])
-        sa = (C.c_char_p * self.n)(*[s.encode() for s in seqs])
-        rc = L.pagan_msa_create(self.n, na, sa, newick.encode(), C.byref(o), C.byref(self._h))
-        if rc != 0:
-            from . import PaganError
-            raise PaganError(rc, "pagan_msa_create")
+        na, sa = _c_strings(names), _c_strings(seqs)
+        check(L.pagan_msa_create(self.n, na, sa, newick.encode(), C.byref(o), C.byref(self._h)), "pagan_msa_create")
         self._L = L
         if sample_on_device:
-            rc = L.pagan_msa_set_sampler(self._h, int(sample_on_device))
-            if rc != 0:
-                from . import PaganError
-                raise PaganError(rc, "pagan_msa_set_sampler")
+            check(L.pagan_msa_set_sampler(self._h, int(sample_on_device)), "pagan_msa_set_sampler")
         if posterior_decode:
-            rc = L.pagan_msa_set_decoder(self._h, int(posterior_decode), float(decode_gap_weight))
-            if rc != 0:
-                from . import PaganError
-                raise PaganError(rc, "pagan_msa_set_decoder")
+            check(L.pagan_msa_set_decoder(self._h, int(posterior_decode), float(decode_gap_weight)), "pagan_msa_set_decoder")
         if expected_counts:
-            rc = L.pagan_msa_set_counts(self._h, int(expected_counts))
-            if rc != 0:
-                from . import PaganError
-                raise PaganError(rc, "pagan_msa_set_counts")
+            check(L.pagan_msa_set_counts(self._h, int(expected_counts)), "pagan_msa_set_counts")
         if indel_model is not None:
-            rc = L.pagan_msa_set_indel_model(self._h, *[float(v) for v in indel_model])
-            if rc != 0:
-                from . import PaganError
-                raise PaganError(rc, "pagan_msa_set_indel_model")
+            check(L.pagan_msa_set_indel_model(self._h, *[float(v) for v in indel_model]), "pagan_msa_set_indel_model")
 
     def align(self):
-        rc = self._L.pagan_msa_align(self._h)
-        if rc != 0:
-            from . import PaganError
-            raise PaganError(rc, "pagan_msa_align")
+        check(self._L.pagan_msa_align(self._h), "pagan_msa_align")
         return self
 
     @property
@@ -1095,26 +853,17 @@ class Msa:
 
     def align_nodes(self, nodes):
         ids = np.ascontiguousarray(nodes, np.int32)
-        rc = self._L.pagan_msa_align_nodes(self._h, int(ids.shape[0]), _ip(ids))
-        if rc != 0:
-            from . import PaganError
-            raise PaganError(rc, "pagan_msa_align_nodes")
+        check(self._L.pagan_msa_align_nodes(self._h, int(ids.shape[0]), _ip(ids)), "pagan_msa_align_nodes")
 
     def export_result(self, node):
-        need = self._L.pagan_msa_export_result(self._h, node, None, 0)
-        if need < 0:
-            from . import PaganError
-            raise PaganError(int(need), "pagan_msa_export_result")
+        need = check(self._L.pagan_msa_export_result(self._h, node, None, 0), "pagan_msa_export_result")
         buf = np.zeros(need, np.uint8)
         self._L.pagan_msa_export_result(self._h, node, buf.ctypes.data_as(C.c_void_p), need)
         return buf
 
     def import_result(self, buf):
         b = np.ascontiguousarray(buf, np.uint8)
-        rc = self._L.pagan_msa_import_result(self._h, b.ctypes.data_as(C.c_void_p), int(b.shape[0]))
-        if rc != 0:
-            from . import PaganError
-            raise PaganError(rc, "pagan_msa_import_result")
+        check(self._L.pagan_msa_import_result(self._h, b.ctypes.data_as(C.c_void_p), int(b.shape[0])), "pagan_msa_import_result")
 
     def node_device(self, k):
         return self._L.pagan_msa_node_device(self._h, k)
@@ -1127,10 +876,7 @@ class Msa:
     def finish(self, lazy=False):
         """After the last round.  lazy: the parent graphs of imported nodes that nobody needed, and the rows, are built by
         the first call that asks for them (alignment(), write_fasta(), node_graph()) instead of now."""
-        rc = (self._L.pagan_msa_finish_lazy if lazy else self._L.pagan_msa_finish)(self._h)
-        if rc != 0:
-            from . import PaganError
-            raise PaganError(rc, "pagan_msa_finish")
+        check((self._L.pagan_msa_finish_lazy if lazy else self._L.pagan_msa_finish)(self._h), "pagan_msa_finish")
         return self
 
     @property
@@ -1146,64 +892,42 @@ class Msa:
     def node_cjob(self, k):
         """Borrowed CJob (pointers into the Msa; valid while it lives)."""
         j = abi.CJob()
-        rc = self._L.pagan_msa_node_job(self._h, k, C.byref(j))
-        if rc != 0:
-            raise RuntimeError("pagan_msa_node_job failed: %d" % rc)
+        check(self._L.pagan_msa_node_job(self._h, k, C.byref(j)), "pagan_msa_node_job")
         return j
 
     def node_job(self, k):
         """(Graph, Graph, Model, Band|None) copies of node k's aligner inputs."""
-        j = self.node_cjob(k)
-        left, right = _graph_from_view(j.left.contents), _graph_from_view(j.right.contents)
-        m = j.model.contents
-        S = m.n_states
-        table = np.ctypeslib.as_array(m.log_score, shape=(S * S,)).copy()
-        model = abi.Model(table.reshape(S, S).T, m.log_gap_open, m.log_gap_ext, m.log_gap_end_ext, m.log_non_gap)
-        band = None
-        if j.band:
-            b = j.band.contents
-            band = abi.Band(np.ctypeslib.as_array(b.upper, shape=(b.n,)).copy(),
-                            np.ctypeslib.as_array(b.lower, shape=(b.n,)).copy())
-        return left, right, model, band
+        return _job_copy(self.node_cjob(k))
 
     def node_result(self, k):
         r = abi.CResult()
-        rc = self._L.pagan_msa_node_result(self._h, k, C.byref(r))
-        if rc != 0:
-            raise RuntimeError("pagan_msa_node_result failed: %d" % rc)
+        check(self._L.pagan_msa_node_result(self._h, k, C.byref(r)), "pagan_msa_node_result")
         return abi.Result(r)
 
     # ---- what the forward/backward pass left at a node (full_probability= / sample_path=) ----
-    def _fb_check(self, rc, what):
-        if rc != 0:
-            from . import PaganError
-            raise PaganError(rc, what)
-
     def node_fb(self, k):
         """(log_fwd, log_bwd, device ms of the sweeps, device ms of support + marginals) of internal node k."""
         out = (C.c_double * 4)()
-        self._fb_check(self._L.pagan_msa_node_fb(self._h, k, out), "pagan_msa_node_fb")
+        check(self._L.pagan_msa_node_fb(self._h, k, out), "pagan_msa_node_fb")
         return tuple(out)
 
     def node_decode(self, k):
         """(objective, steps, device ms of fill + trace) of internal node k's decoded path (posterior_decode=1)."""
         out = (C.c_double * 3)()
-        self._fb_check(self._L.pagan_msa_node_decode(self._h, k, out), "pagan_msa_node_decode")
+        check(self._L.pagan_msa_node_decode(self._h, k, out), "pagan_msa_node_decode")
         return tuple(out)
 
     def node_counts(self, k, emissions=None):
         """Node k's expected counts (expected_counts=1): the dict FullProbability.expected_counts returns.  emissions: None
         takes the table where the walk keeps one (DNA)."""
         v = abi.CModelProb()
-        self._fb_check(self._L.pagan_msa_node_model_prob(self._h, k, C.byref(v)), "pagan_msa_node_model_prob")
+        check(self._L.pagan_msa_node_model_prob(self._h, k, C.byref(v)), "pagan_msa_node_model_prob")
         S = v.n_states
         if emissions is None:
             emissions = self.data_type == 1
-        f64p = C.POINTER(C.c_double)
         trans = np.zeros(12, np.float64)
         emit = np.zeros(S * S, np.float64) if emissions else None
-        self._fb_check(self._L.pagan_msa_node_counts(self._h, k, trans.ctypes.data_as(f64p), emit.ctypes.data_as(f64p) if emissions else None),
-                       "pagan_msa_node_counts")
+        check(self._L.pagan_msa_node_counts(self._h, k, _dp(trans), _dp(emit) if emissions else None), "pagan_msa_node_counts")
         return {"trans": trans[:9].reshape(3, 3).copy(), "end": trans[9:].copy(), "emit": emit.reshape(S, S).T.copy() if emissions else None}
 
     def expected_counts(self):
@@ -1223,36 +947,33 @@ class Msa:
     def node_support(self, k):
         """Posterior of every column's own cell along node k's path; -1 at skip columns."""
         out = np.zeros(self.node_result(k).cols.shape[0], np.float64)
-        self._fb_check(self._L.pagan_msa_node_support(self._h, k, out.ctypes.data_as(C.POINTER(C.c_double))), "pagan_msa_node_support")
+        check(self._L.pagan_msa_node_support(self._h, k, _dp(out)), "pagan_msa_node_support")
         return out
 
     def node_marginals(self, k):
         """Node k's site marginals (full_probability=2): the dict FullProbability.site_marginals returns."""
         info = self.node_info(k)
         Lx, Ly = info.left_sites - 1, info.right_sites - 1
-        f64p = C.POINTER(C.c_double)
         out = {"pX": np.zeros(Lx), "pM_left": np.zeros(Lx), "best_j": np.zeros(Lx, np.int32), "best_p_left": np.zeros(Lx),
                "pY": np.zeros(Ly), "pM_right": np.zeros(Ly), "best_i": np.zeros(Ly, np.int32), "best_p_right": np.zeros(Ly)}
-        args = [out[k_].ctypes.data_as(_i32p if k_.startswith("best_") and not k_.startswith("best_p") else f64p)
+        args = [out[k_].ctypes.data_as(_i32p if k_ in ("best_j", "best_i") else _f64p)
                 for k_ in ("pX", "pM_left", "best_j", "best_p_left", "pY", "pM_right", "best_i", "best_p_right")]
-        self._fb_check(self._L.pagan_msa_node_marginals(self._h, k, *args), "pagan_msa_node_marginals")
+        check(self._L.pagan_msa_node_marginals(self._h, k, *args), "pagan_msa_node_marginals")
         return out
 
     def node_model_prob(self, k):
         """abi.ModelProb copy of the probability-space model node k's forward/backward pass takes."""
         v = abi.CModelProb()
-        self._fb_check(self._L.pagan_msa_node_model_prob(self._h, k, C.byref(v)), "pagan_msa_node_model_prob")
+        check(self._L.pagan_msa_node_model_prob(self._h, k, C.byref(v)), "pagan_msa_node_model_prob")
         S = v.n_states
         score = np.ctypeslib.as_array(v.score, shape=(S * S,)).copy()
         return abi.ModelProb(score.reshape(S, S).T, v.gap_open, v.gap_ext, v.non_gap)
 
     def support_row(self, node):
         """Node `node`'s column support on the final alignment's columns (float32, -1 where the node has no column)."""
-        n = self._L.pagan_msa_alignment_length(self._h)
-        if n < 0:
-            self._fb_check(n, "pagan_msa_alignment_length")
+        n = check(self._L.pagan_msa_alignment_length(self._h), "pagan_msa_alignment_length")
         buf = np.zeros(n, np.float32)
-        self._fb_check(self._L.pagan_msa_support_row(self._h, node, _fp(buf)), "pagan_msa_support_row")
+        check(self._L.pagan_msa_support_row(self._h, node, _fp(buf)), "pagan_msa_support_row")
         return buf
 
     def node_graph(self, node):
@@ -1261,7 +982,7 @@ class Msa:
     def timing(self):
         t = CTiming()
         self._L.pagan_msa_timing_get(self._h, C.byref(t))
-        return {k: getattr(t, k) for k, _ in CTiming._fields_}
+        return struct_dict(t)
 
     def alignment(self):
         n = self._L.pagan_msa_alignment_length(self._h)
@@ -1278,7 +999,7 @@ class Msa:
         ci = CAlnInfo()
         newick = _newick_call(lambda buf, cap: self._L.pagan_msa_alignment_tree(self._h, buf, cap, C.byref(ci)),
                               "pagan_msa_alignment_tree", self.names)
-        return (newick, _aln_info(ci)) if with_info else newick
+        return (newick, struct_dict(ci)) if with_info else newick
 
     def ancestral(self):
         """pagan_msa_ancestral: marginal ancestral states of the finished walk on the current device -- its leaf rows, its tree,
@@ -1286,17 +1007,16 @@ class Msa:
         n = self._L.pagan_msa_alignment_length(self._h)
         col = np.zeros(max(n, 0), np.float64)
         loglik, ci = C.c_double(0.0), CAncInfo()
-        self._fb_check(self._L.pagan_msa_ancestral(self._h, 0, C.byref(loglik), col.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ci)),
-                       "pagan_msa_ancestral")
+        check(self._L.pagan_msa_ancestral(self._h, 0, C.byref(loglik), _dp(col), C.byref(ci)), "pagan_msa_ancestral")
         L = int(ci.columns)
-        bp, pp = C.POINTER(C.c_uint8)(), _f32p()
-        self._fb_check(self._L.pagan_msa_ancestral_best(self._h, C.byref(bp), C.byref(pp)), "pagan_msa_ancestral_best")
+        bp, pp = _u8p(), _f32p()
+        check(self._L.pagan_msa_ancestral_best(self._h, C.byref(bp), C.byref(pp)), "pagan_msa_ancestral_best")
         shape = (self.n - 1, L)
         if L:
             best, best_p = np.ctypeslib.as_array(bp, shape=shape).copy(), np.ctypeslib.as_array(pp, shape=shape).copy()
         else:
             best, best_p = np.zeros(shape, np.uint8), np.zeros(shape, np.float32)
-        return Ancestral(self, loglik.value, col[:L].copy(), best, best_p, _anc_info(ci))
+        return Ancestral(self, loglik.value, col[:L].copy(), best, best_p, struct_dict(ci))
 
     def alignment_all(self):
         """Rows of every node: leaves 0..n-1, then the internal nodes (ancestors) in alignment order."""
@@ -1311,18 +1031,4 @@ class Msa:
     def write_fasta(self, path, chars_by_line=60, include_internal=False):
         """The rows as FASTA in guide-tree order (Fasta_reader::write_fasta over Node::get_alignment); with
         include_internal the ancestors' rows too, in Node::get_all_nodes order."""
-        rc = self._L.pagan_msa_write_fasta_nodes(self._h, str(path).encode(), chars_by_line, 1 if include_internal else 0)
-        if rc != 0:
-            from . import PaganError
-            raise PaganError(rc, "pagan_msa_write_fasta")
-
-    def close(self):
-        if self._h:
-            self._L.pagan_msa_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        check(self._L.pagan_msa_write_fasta_nodes(self._h, str(path).encode(), chars_by_line, 1 if include_internal else 0), "pagan_msa_write_fasta")

@@ -50,7 +50,7 @@ def device_only(rows, t):
     def call():
         rc = L.pagan_aln_distances(len(rows), ra, t, None, None, None, C.byref(ci))
         assert rc == 0, rc
-        return host._aln_info(ci)
+        return host.struct_dict(ci)
     return call
 
 
