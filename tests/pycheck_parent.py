@@ -325,8 +325,29 @@ class Sequence:                                                       # sequence
                 (fo, np.array(fe, np.int32)))
 
 
+# the builder's branches by name, for Basic_alignment's optional counter (tests/parent_scenarios.py says which planted
+# input is there for which).  "pass2_runs" is a total, not a branch.
+RULES = (
+    "start_shorten", "stop_shorten_dup", "stop_shorten_new", "stop_shorten_new_beside_others", "dup_reset",
+    "drop_count", "drop_distance",
+    # transfer_child_edge_2's if-chain (:604-637).  Its 2nd and 3rd arms ask for an unused child edge and its implicit
+    # 4th (nothing changes) is what is left for a used one, so of the eight outcome x used pairs these five exist.
+    "history_ends_differ_used", "history_ends_differ_unused", "history_between_used_sites_unused",
+    "history_between_skipped_sites_unused", "history_fresh_used",
+    "child_weight_not_one", "plain_x_after_y", "plain_y_after_x",
+    "pass1_bwd_increment", "pass1_bwd_refused", "pass1_fwd_increment", "pass1_fwd_refused",
+    "pass2_runs", "pass2_no_bwd_edge", "pass2_at_or_below_limit", "pass2_over_limit_then_gapped",
+    "pass2_over_limit_then_stop_site", "pass2_matched_without_over_limit_edge", "pass2_delete_whole_run",
+    "pass2_delete_prefix_of_run", "pass2_edge_starts_before_run",
+    "coupling_own_first_edge_lost", "coupling_matched_site_edge_lost",
+)
+
+
 class Basic_alignment:
-    def __init__(self, left, right, left_branch_length, right_branch_length, parsimony, S, char_as, flags=0):
+    def __init__(self, left, right, left_branch_length, right_branch_length, parsimony, S, char_as, flags=0, counter=None):
+        """counter: None, or a mapping (collections.Counter) that takes one count per rule taken, by the names in RULES;
+        counting changes nothing that is built."""
+        self.counter = counter
         self.left, self.right = left, right
         self.left_branch_length, self.right_branch_length = f32(left_branch_length), f32(right_branch_length)
         self.parsimony, self.S, self.char_as = parsimony, S, char_as
@@ -343,6 +364,11 @@ class Basic_alignment:
             self.branch_skip_probability = f32(1)
         if flags & 2:
             self.reduced_terminal_gap_penalties = False
+
+    def hit(self, rule):
+        if self.counter is not None:
+            assert rule in RULES, rule
+            self.counter[rule] += 1
 
     def build_ancestral_sequence(self, sequence, path):               # basic_alignment.cpp:36-59
         self.create_ancestral_sequence(sequence, path)
@@ -426,6 +452,7 @@ class Basic_alignment:
                         self.transfer_child_edge(sequence, child, left_child_index, self.left_branch_length)
                 # (:250-284: edges_for_skipped_flanked_by_gaps is false)
                 if pstate in (xgapped, xskipped) and prev_path_state in (ygapped, yskipped):      # :286-296
+                    self.hit("plain_x_after_y")
                     edge = Edge(i - 1, i, 1.0)
                     sequence.push_back_edge(edge)
                     sequence.get_site_at(edge.start_site_index).add_new_fwd_edge_index(sequence.get_current_edge_index())
@@ -439,6 +466,7 @@ class Basic_alignment:
                         child = tsite.get_next_bwd_edge()
                         self.transfer_child_edge(sequence, child, right_child_index, self.right_branch_length)
                 if pstate in (ygapped, yskipped) and prev_path_state in (xgapped, xskipped):      # :350-358
+                    self.hit("plain_y_after_x")
                     edge = Edge(i - 1, i, 1.0)
                     sequence.push_back_edge(edge)
                     sequence.get_site_at(edge.start_site_index).add_new_fwd_edge_index(sequence.get_current_edge_index())
@@ -447,25 +475,35 @@ class Basic_alignment:
 
     def transfer_child_edge(self, sequence, child, child_index, branch_length):     # :510-569
         edge = Edge(child_index[child.start_site_index], child_index[child.end_site_index], 1.0)    # (weight_edges is false)
+        stop_shortened = False
         if self.reduced_terminal_gap_penalties:
             if sequence.get_site_at(edge.start_site_index).site_type == start_site and edge.end_site_index - edge.start_site_index > 1:
                 if child.end_site_index - child.start_site_index == 1:
+                    self.hit("start_shorten")
                     edge.start_site_index = edge.end_site_index - 1
             if sequence.get_site_at(edge.end_site_index).site_type == stop_site and edge.end_site_index - edge.start_site_index > 1:
                 if child.end_site_index - child.start_site_index == 1:
                     edge.end_site_index = edge.start_site_index + 1
+                    stop_shortened = True
         # (:540-563: pair_end_reads is false)
-        self.transfer_child_edge_2(sequence, edge, child, branch_length)
+        self.transfer_child_edge_2(sequence, edge, child, branch_length, stop_shortened=stop_shortened)
 
-    def transfer_child_edge_2(self, sequence, edge, child, branch_length, branch_weight=f32(1.0)):  # :572-653
+    def transfer_child_edge_2(self, sequence, edge, child, branch_length, branch_weight=f32(1.0), stop_shortened=False):  # :572-653
+        # (stop_shortened is the counters' alone: whether :535-539 moved this edge's end off the stop site)
         end = sequence.get_site_at(edge.end_site_index)
         if end.contains_bwd_edge(edge):                               # no identical copies
+            self.hit("stop_shorten_dup" if stop_shortened else "dup_reset")
             end.update_bwd_edge_details(edge)
             return
         if not child.used_in_alignment and child.branch_count_since_last_used + 1 > self.max_allowed_skip_branches:
+            self.hit("drop_count")
             return
         if not child.used_in_alignment and f32(child.branch_distance_since_last_used + f32(branch_length)) > self.max_allowed_skip_distance:
+            self.hit("drop_distance")
             return
+        used = "used" if child.used_in_alignment else "unused"
+        if child.posterior_weight != f32(1.0):
+            self.hit("child_weight_not_one")
         start = sequence.get_site_at(edge.start_site_index)
         dist_start, dist_end = start.branch_distance_since_last_used, end.branch_distance_since_last_used
         count_start, count_end = start.branch_count_since_last_used, end.branch_count_since_last_used
@@ -475,17 +513,26 @@ class Basic_alignment:
             # handed to multiply_weight(float)
             return f32(float(branch_weight) * float(child.posterior_weight) * float(self.branch_skip_probability))
         if dist_start != dist_end or count_start != count_end:
+            self.hit("history_ends_differ_" + used)
             edge.branch_distance_since_last_used = max(dist_start, dist_end)
             edge.branch_count_since_last_used = max(count_start, count_end)
             edge.multiply_weight(penalty())
         elif not child.used_in_alignment and count_start == 0 and count_end == 0:
+            self.hit("history_between_used_sites_unused")
             edge.branch_distance_since_last_used = f32(child.branch_distance_since_last_used + f32(branch_length))
             edge.branch_count_since_last_used = child.branch_count_since_last_used + 1
             edge.multiply_weight(penalty())
         elif not child.used_in_alignment:
+            self.hit("history_between_skipped_sites_unused")
             edge.branch_distance_since_last_used = f32(child.branch_distance_since_last_used + f32(branch_length))
             edge.branch_count_since_last_used = child.branch_count_since_last_used + 1
+        else:
+            self.hit("history_fresh_used")
         if not sequence.contains_this_bwd_edge_at_site(edge.end_site_index, edge):
+            if stop_shortened:
+                self.hit("stop_shorten_new")
+                if end.has_bwd_edge():
+                    self.hit("stop_shorten_new_beside_others")
             if not child.used_in_alignment:
                 edge.branch_count_as_skipped_edge = child.branch_count_as_skipped_edge
             else:
@@ -507,7 +554,10 @@ class Basic_alignment:
                 psite = sites[edge.start_site_index]
                 # `psite->get_path_state()==Site::start_site`: a path state compared with a site type's number (0)
                 if (psite.path_state == matched or psite.path_state == start_site) and tsite.path_state in (xskipped, yskipped):
+                    self.hit("pass1_bwd_increment")
                     edge.branch_count_as_skipped_edge += 1
+                elif tsite.path_state in (xskipped, yskipped):
+                    self.hit("pass1_bwd_refused")
             if tsite.has_fwd_edge():
                 edge = tsite.get_first_fwd_edge()
                 while tsite.has_next_fwd_edge():
@@ -516,22 +566,30 @@ class Basic_alignment:
                         edge = another
                 nsite = sites[edge.end_site_index]
                 if tsite.path_state in (xskipped, yskipped) and (nsite.path_state == matched or nsite.path_state == ends_site):
+                    self.hit("pass1_fwd_increment")
                     edge.branch_count_as_skipped_edge += 1
+                elif tsite.path_state in (xskipped, yskipped):
+                    self.hit("pass1_fwd_refused")
+        alone = self.decisions_against_undeleted_lists(sequence) if self.counter is not None else None
         non_skipped = True
         skip_start = -1
         for i in range(1, len(sites)):
             tsite = sites[i]
             tstate = tsite.path_state
             if non_skipped and tstate in (xskipped, yskipped):
+                run_first, run_edge = i, -1
                 if tsite.has_bwd_edge():
                     edge = tsite.get_first_bwd_edge()
                     while tsite.has_next_bwd_edge():
                         another = tsite.get_next_bwd_edge()
                         if another.start_site_index > edge.start_site_index:
                             edge = another
+                    run_edge = edge.index
                     if edge.branch_count_as_skipped_edge > self.max_allowed_match_skip_branches:
                         skip_start = i
                 non_skipped = False
+                if alone is not None:
+                    self.count_run(sequence, alone, run_first, run_edge, skip_start)
             if not non_skipped and skip_start >= 0 and tstate == matched:
                 edge_ind = -1
                 if tsite.has_bwd_edge():
@@ -550,6 +608,69 @@ class Basic_alignment:
                 non_skipped = True
                 skip_start = -1
 
+    # ---- the counters' side of pass 2: nothing below changes a graph ----
+    def run_behind(self, sequence, f):
+        m = f + 1
+        while sequence.sites[m].path_state in (xskipped, yskipped):
+            m += 1
+        return m
+
+    def decisions_against_undeleted_lists(self, sequence):
+        """{first site of a run: (edge of its own list that decides, last over-limit edge of the matched site's list or -1,
+        deleted interval)} with every list as pass 1 left it -- what each run would do if no other run deleted anything."""
+        sites, lim, out = sequence.sites, self.max_allowed_match_skip_branches, {}
+        def bwd(t):
+            k, v = t.first_bwd_edge_index, []
+            while k >= 0:
+                v.append(sequence.edges[k]); k = sequence.edges[k].next_bwd_edge_index
+            return v
+        for f in range(1, len(sites) - 1):
+            if sites[f].path_state not in (xskipped, yskipped) or sites[f - 1].path_state in (xskipped, yskipped):
+                continue
+            m = self.run_behind(sequence, f)
+            e0, last, a, b = -1, -1, 0, -1
+            for e in bwd(sites[f]):
+                if e0 < 0 or e.start_site_index > sequence.edges[e0].start_site_index:
+                    e0 = e.index
+            if e0 >= 0 and sequence.edges[e0].branch_count_as_skipped_edge > lim and sites[m].path_state == matched:
+                for e in bwd(sites[m]):
+                    if e.branch_count_as_skipped_edge > lim:
+                        last = e.index
+                if last >= 0 and sequence.edges[last].start_site_index >= f:
+                    a, b = f, sequence.edges[last].start_site_index
+            out[f] = (e0, last, (a, b))
+        return out
+
+    def count_run(self, sequence, alone, f, e0, skip_start):
+        """One run of skipped sites, at the moment the sequential scan has decided on its first site (the lists of the
+        matched site behind it cannot change any more before the scan gets there: deletions only reach backwards)."""
+        sites, lim = sequence.sites, self.max_allowed_match_skip_branches
+        self.hit("pass2_runs")
+        m = self.run_behind(sequence, f)
+        last, a, b = -1, 0, -1
+        if e0 < 0:
+            self.hit("pass2_no_bwd_edge")
+        elif skip_start < 0:
+            self.hit("pass2_at_or_below_limit")
+        elif sites[m].path_state != matched:
+            self.hit("pass2_over_limit_then_stop_site" if sites[m].site_type == stop_site else "pass2_over_limit_then_gapped")
+        else:
+            t = sites[m]
+            k = t.first_bwd_edge_index
+            while k >= 0:
+                if sequence.edges[k].branch_count_as_skipped_edge > lim:
+                    last = k
+                k = sequence.edges[k].next_bwd_edge_index
+            if last < 0:
+                self.hit("pass2_matched_without_over_limit_edge")
+            elif sequence.edges[last].start_site_index < f:
+                self.hit("pass2_edge_starts_before_run")
+            else:
+                a, b = f, sequence.edges[last].start_site_index
+                self.hit("pass2_delete_whole_run" if b == m - 1 else "pass2_delete_prefix_of_run")
+        if (a, b) != alone[f][2]:
+            self.hit("coupling_own_first_edge_lost" if e0 != alone[f][0] else "coupling_matched_site_edge_lost")
+
     def delete_edge_range(self, sequence, edge_ind, skip_start_site):  # :491-508
         edge = sequence.edges[edge_ind]
         this_site_index = edge.start_site_index
@@ -560,12 +681,12 @@ class Basic_alignment:
             this_site_index -= 1
 
 
-def build_parent(left, right, cols, left_used, right_used, lbl, rbl, parsimony, char_as, flags=0):
+def build_parent(left, right, cols, left_used, right_used, lbl, rbl, parsimony, char_as, flags=0, counter=None):
     """left / right: Sequence; cols: (n, 3) array of (left, right, path state).  Marks the children's used edges, as
-    OGraph.parent does, and returns the parent Sequence."""
+    OGraph.parent does, and returns the parent Sequence.  counter: see Basic_alignment."""
     left.mark_used(left_used)
     right.mark_used(right_used)
     S = int(round(len(parsimony) ** 0.5))
     seq = Sequence()
-    Basic_alignment(left, right, lbl, rbl, parsimony, S, char_as, flags).build_ancestral_sequence(seq, [tuple(int(x) for x in c) for c in cols])
+    Basic_alignment(left, right, lbl, rbl, parsimony, S, char_as, flags, counter).build_ancestral_sequence(seq, [tuple(int(x) for x in c) for c in cols])
     return seq

@@ -84,13 +84,15 @@ def test_banded_walk_under_the_three_settings(oracle, pg, flags):
 
 
 def test_caterpillar_deletes_ranges(oracle, pg):
-    """Deep caterpillar: the skip limits drop edges and the boundary pass deletes ranges (non_real sites); later runs of
-    skipped sites see lists that earlier deletions shortened, so the fixpoint needs more than one round somewhere."""
+    """Deep caterpillar: the skip limits drop edges and the boundary pass deletes ranges (non_real sites), every one of
+    them a whole run whose first-round decision is final (tests/test_parent_scenarios_cpu.py asserts that of these very
+    inputs).  The number of rounds says nothing here -- any deletion is followed by one quiet round -- and is not fixed
+    where it would: runs that depend on each other's deletions are planted in tests/test_parent_planted_gpu.py."""
     for n, seed in ((14, 2), (18, 6)):
         names, seqs, nwk = synth.evolve_caterpillar(n, 150, seed=seed)
         st = walk(synth.parse_newick(nwk), dict(zip(names, seqs)), oracle, base_freq(seqs))
-        assert st["nodes"] == n - 1 and st["nonreal"] > 0
-        assert st["rounds"] >= 2
+        assert st["nodes"] == n - 1 and st["nonreal"] > 0 and st["runs"] > 0
+        assert st["rounds"] >= 1 and st["outside"] == 0 and st["patched"] == 0
 
 
 def test_homopolymer_leaves(oracle, pg):
