@@ -42,7 +42,25 @@
 //     edge lists and the recent diagonal descriptors in LDS windows ahead of the slowest wave;
 //   - scores and back-pointers stream to HBM with stores nobody waits for; compute waves
 //     issue no vector-memory load outside class 2-4 diagonals.
+//
+// One translation unit (pg_pipe_smem is a static LDS object, the run functions are functions of their own on purpose).  The
+// waves that stand beside the compute chain are included parts, inside the anonymous namespace: dp_pipe_loader.inc (loader
+// wave) and dp_pipe_strip.inc (follower workgroups, strip feeder); the operand helpers, the assist waves, WaveCtx and the run
+// functions, which share helpers and macros with the kernel's step(), are in this file.  dp_pipe_stats.h is the statistics recorder.
+//
+// Build switches (-D; the product defines none of them):
+//   switch                      what it builds                                                      who uses it
+//   the statistics switches     the recorder and its variants: named and explained in               tools/build_stamps.sh, tools/pipe_stats.py and
+//                               dp_pipe_stats.h, the only file that tests them                      the probes
+//   PG_NO_HOT_ASM               hot_run's C++ step for every diagonal instead of the                A/B against the generated loop; the step itself is
+//                               hand-scheduled loop                                                 live code (a strip's terminal diagonals run it)
+//   PG_ASSIST_IDLE              assist waves that stage nothing (timing only, WRONG RESULTS)        tools/build_exp.sh
+//   PG_EXP_WIDE_SKIP            wide steps that are their flags and nothing else (timing only,      BENCH_r06's A/B, profiles/r06_attribution.log
+//                               WRONG RESULTS)
+//   PG_WIDE7_FETCH_BEHIND       wide_run7's L2 requests behind the lock step, as before round 6     BENCH_r06's A/B, profiles/r06_attribution.log
+//   PG_SPIN_LIMIT_LOG2=n        polls give up after 2^n spins (default 25)                          a quick abort while debugging a wait
 #include "dp_kcommon.h"
+#include "dp_pipe_stats.h"
 #include <type_traits>
 
 #define PNW 4
@@ -117,9 +135,7 @@ struct PipeSmem {
     int assist_done[PNA];        // last diagonal each assist wave has staged
     int as_list[PNA][64];        // rows of the multi-edge cells of the diagonal an assist wave is working on, compacted
     const int *pdsc;             // row strips: the parent job's dsc array (null otherwise): far_ask's view of the whole band
-#ifdef PG_PIPE_STATS
-    long long far_limit;         // (statistics builds) bytes of the job's score array: a far read outside it sets the abort flag instead
-#endif
+    PG_ST_SMEM                   // (statistics builds: dp_pipe_stats.h)
 };
 
 static_assert(sizeof(PipeSmem) <= 160 * 1024, "PipeSmem has to fit the 160 KB of LDS of a gfx950 compute unit");
@@ -180,16 +196,7 @@ __device__ __forceinline__ int poll_ge(const int *p, int need, int tag) {
 // the same as a function of its own: the run functions call it only when a cached flag stops covering a step
 __device__ __noinline__ int poll_ge_out(const int *p, int need, int tag) { return poll_ge(p, need, tag); }
 #define PTAG(kind) ((kind) | (wave << 4) | (d << 8))
-// (statistics builds) the strips of a job share its trace buffer: only the strip named in the debug flags' bits 12-15 records
-#define PG_STATS_MINE(job, flags) (!(job)->is_strip || (job)->strip_row0 / PG_STRIP_ROWS == (int)(((flags) >> 12) & 15u))
-#ifdef PG_PIPE_STATS
-#define POLLX(p, need, kind) ([&] { const long long t0_ = __builtin_readcyclecounter(); const int v_ = __builtin_amdgcn_readfirstlane(poll_ge_out(p, need, PTAG(kind))); st_poll_t[kind] += __builtin_readcyclecounter() - t0_; ++st_poll_n[kind]; return v_; }())
-#define POLL(p, need, kind) ([&] { const long long t0_ = __builtin_readcyclecounter(); const int v_ = poll_ge(p, need, PTAG(kind)); st_poll_t[kind] += __builtin_readcyclecounter() - t0_; ++st_poll_n[kind]; return v_; }())
-#else
-#define POLLX(p, need, kind) __builtin_amdgcn_readfirstlane(poll_ge_out(p, need, PTAG(kind)))
-#define POLL(p, need, kind) poll_ge(p, need, PTAG(kind))
-#endif
-
+// (the waits themselves: POLL -- poll_ge inline -- and POLLX -- poll_ge_out, its result made uniform --, dp_pipe_stats.h)
 __device__ __forceinline__ double dpp_shr1(double v, double lane0) {
     // lane n takes lane n-1's v; lane 0 keeps `lane0` (wave_shr:1 leaves the destination of a lane
     // without a source untouched when bound_ctrl is off)
@@ -199,171 +206,7 @@ __device__ __forceinline__ double dpp_shr1(double v, double lane0) {
     return __hiloint2double(hi, lo);
 }
 
-// ---- loader wave -------------------------------------------------------------------------
-template <bool LEFT>
-__device__ __forceinline__ void load_rec_chunk(int first, int lane, int n, gint_p st, gint_p off, gint_p src, gfloat_p lw, bool strip, bool norm,
-                                               PG_GLOBAL const unsigned char *hf) {
-    pg_i4 *rec = LEFT ? PM.recL : PM.recR;
-    int *eb = LEFT ? PM.ebL : PM.ebR;
-    int *es = LEFT ? PM.esL : PM.esR;
-    float *ew = LEFT ? PM.ewL : PM.ewR;
-    const int r = first + lane;
-    // two round trips for the usual chunk: offsets and states, then the sites' first two edges together with the chunk's
-    // edge list for the LDS window; a third (and on) only where a site has more than two edges
-    int b = 0, en = 0, w = 0;
-    unsigned flag = 0;                                             // far histories: the site's flag byte (0 where the job has none)
-    if (r < n) { b = off[r]; en = off[r + 1]; w = st[r] & 0xffff; if (hf) flag = hf[r]; }
-    const int ne = en - b;
-    const int rend = first + 64 < n ? first + 64 : n;
-    const int e0 = __builtin_amdgcn_readfirstlane(b), e1 = __builtin_amdgcn_readlane(en, rend - 1 - first);
-    int d0 = 0, d1 = 0;
-    float w0 = 0.0f, w1 = 0.0f;
-    if (ne >= 1) { d0 = r - src[b]; w0 = lw[b]; }
-    if (ne >= 2) { d1 = r - src[b + 1]; w1 = lw[b + 1]; }
-    for (int e = e0 + lane; e < e1; e += 128) {
-        const bool two = e + 64 < e1;
-        const int s0 = src[e];
-        const float x0 = lw[e];
-        int s1 = 0;
-        float x1 = 0.0f;
-        if (two) { s1 = src[e + 64]; x1 = lw[e + 64]; }
-        es[e & (PEC - 1)] = s0; ew[e & (PEC - 1)] = x0;
-        if (two) { es[(e + 64) & (PEC - 1)] = s1; ew[(e + 64) & (PEC - 1)] = x1; }
-    }
-    if (r < n) {
-        if (r > 0 && ne == 1 && d0 == 1 && w0 == 0.0f) w |= PR_SIMPLE;
-        w |= (ne < 127 ? ne : 127) << PR_NE_SHIFT;
-        if (norm && ne == 2 && (d0 == 1) != (d1 == 1)) {
-            if (d0 != 1) { const int td = d0; d0 = d1; d1 = td; const float tw = w0; w0 = w1; w1 = tw; }
-            w |= PR_TWO;
-        }
-        if (norm && ne == 3) {
-            // three edges, exactly one from the previous site, none past the ring's reach (dp_abi.hip, SiteFeat::is_three -- the same
-            // test): the site's list, in the record AND in the edge window, becomes (previous-site edge, other, other); values do not
-            // depend on a list's order, and every reader of the window sees the same permuted list (this lane's LDS writes follow
-            // the chunk's in the wave's order)
-            int d2 = r - src[b + 2];
-            float w2 = lw[b + 2];
-            const int n_adj = (d0 == 1) + (d1 == 1) + (d2 == 1);
-            const int far_ = d0 > d1 ? (d0 > d2 ? d0 : d2) : (d1 > d2 ? d1 : d2);
-            if (n_adj == 1 && far_ <= PAGE - 2) {
-                if (d1 == 1) { const int td = d0; d0 = d1; d1 = td; const float tw = w0; w0 = w1; w1 = tw; }
-                else if (d2 == 1) { const int td = d0; d0 = d2; d2 = td; const float tw = w0; w0 = w2; w2 = tw; }
-                es[b & (PEC - 1)] = r - d0; ew[b & (PEC - 1)] = w0;
-                es[(b + 1) & (PEC - 1)] = r - d1; ew[(b + 1) & (PEC - 1)] = w1;
-                es[(b + 2) & (PEC - 1)] = r - d2; ew[(b + 2) & (PEC - 1)] = w2;
-                w |= PR_TWO | PR_THREE;
-            }
-        }
-        pg_i4 v;
-        v.x = w; v.y = (d0 < 65535 ? d0 : 65535) | ((d1 < 65535 ? d1 : 65535) << 16);
-        v.z = __float_as_int(w0); v.w = __float_as_int(w1);
-        // row strips: the first site (no bwd edge) is recorded as a SIMPLE one -- one edge of weight 1 from a site before it.
-        // Whatever a cell of row 0 (column 0) reads of the row (column) before it is -inf (a ring column no wave writes, a lane
-        // outside the band, a row outside the band for far_ask), which is what the general rules give its X and M (Y and M);
-        // its y-gap (x-gap) chain is the straight code's at the terminal rate; the diagonals 0 and 1 and the cells that meet
-        // M(0,0) through an edge from site 0 are general steps (dp_abi.hip, plan_strips), and those read no record of site 0.
-        if (strip && r == 0) { v.x = (w & 0xffff) | PR_SIMPLE | (1 << PR_NE_SHIFT); v.y = 1; v.z = 0; v.w = 0; }
-        // far histories (dp_abi.hip, plan_far_hist; flag byte: bit 7 reader + bits 0-1 its line, bit 6 writer + bits 4-5 its line)
-        if (flag & 0x80u) v.x |= (int)(PR_FAR | ((flag & 3u) << 27));
-        if (flag & 0x40u) v.x |= (int)(PR_SRC | (((flag >> 4) & 3u) << 25));
-        rec[r & (PRW - 1)] = v;
-        eb[r & (PRW - 1)] = b;
-    }
-}
-
-// The site-record windows are filled as far ahead as they allow -- a record may replace the one PRW sites before it once
-// the slowest wave's diagonal has left that site behind (a band's first row and first column never fall) -- and at least as
-// far as the diagonal PLOOK ahead needs; the descriptor window follows PLOOK diagonals ahead.  One chunk of rows and one of
-// columns per round, each published as it lands.
-#define PREC_BACK 72              // 64 (a chunk) + 8: the records up to 8 sites before the slowest diagonal's first stay
-// follow[0] = 1 + the last diagonal whose scores have landed in L2 (PgDevJob::follow; what the follower workgroups wait
-// for): a wave's stores of diagonal d have landed once it completed d + PLAND; published every 16 diagonals or so
-// (wt, row strips: written through -- the strip below may poll from another XCD)
-__device__ __forceinline__ void publish_landed(PG_GLOBAL int *follow, int lane, int landed, bool wt = false) {
-    if (follow && lane == 0) {
-        if (wt) asm volatile("global_store_dword %0, %1, off sc1" :: "v"(follow), "v"(landed + 1) : "memory");
-        else asm volatile("global_store_dword %0, %1, off" :: "v"(follow), "v"(landed + 1) : "memory");
-    }
-}
-// Row strips (`strip`: the PgDevJob, null otherwise): records from the strip's first halo row / first column on, the
-// descriptor window from the PARENT's array (whole-band rows per diagonal, offsets in cells there), everything from d_first.
-__device__ __forceinline__ void pipe_loader(const View &J, cdesc8_p psc, int lane, PG_GLOBAL int *follow, const PgDevJob *strip, bool norm,
-                                            PG_GLOBAL const unsigned char *hfl, PG_GLOBAL const unsigned char *hfr) {
-    int rows = 0, cols = 0, diags = 0, published = -1;
-    PG_GLOBAL const pg_i4 *pdsc = nullptr;
-    if (strip) {
-        rows = strip->strip_row0 >= 64 ? strip->strip_row0 - 64 : 0;
-        cols = strip->col_first;
-        diags = strip->d_first >= 64 ? strip->d_first - 64 : 0;
-        published = strip->d_first - 1;
-        pdsc = (PG_GLOBAL const pg_i4 *)strip->pdsc;
-    }
-    for (;;) {
-        int pmin = flag_load(&PM.progress[0]);
-        for (int w = 1; w < PNW; ++w) { const int p = flag_load(&PM.progress[w]); pmin = p < pmin ? p : pmin; }
-        if (flag_load(&PM.abort_flag) != 0) { publish_landed(follow, lane, J.nd - 1, strip != nullptr); return; }   // (the job fails: the followers need not wait)
-        // A compute wave's flag for the LAST diagonal goes up as after any other step -- with its stores still in flight -- so
-        // the tail is published like the middle, PLAND behind the slowest wave, and the last diagonals only once every wave
-        // has said "drained for good": progress = nd, stored behind the s_waitcnt vmcnt(0) that ends its last interval.
-        if (pmin >= J.nd) { publish_landed(follow, lane, J.nd - 1, strip != nullptr); return; }
-        if (pmin - PLAND >= published + (strip ? 8 : PG_FOLLOW_CHUNK)) { published = pmin - PLAND; publish_landed(follow, lane, published, strip != nullptr); }
-        if (pmin + 1 >= J.nd) { __builtin_amdgcn_s_sleep(8); continue; }                          // nothing left to stage
-        const int dcur = pmin + 1;                                 // the slowest wave may be computing this one
-        const int da = dcur + PLOOK < J.nd - 1 ? dcur + PLOOK : J.nd - 1;
-        const pg_i8 ds = psc[da], dc = psc[dcur];
-        int want_rows = ds.y + 5, want_cols = da - ds.x + 4;       // rows <= hi+4, columns <= jmax+3 of diagonal da
-        if (dc.y >= dc.x) {
-            // as far ahead as the windows allow -- and no further: a record may only replace the one PRW sites before it, and those
-            // of the slowest wave's diagonal (from PREC_BACK - 64 sites before its first row / column on) are still read.  (Round 5:
-            // the look-ahead of PLOOK diagonals used to win over this bound; with diagonals of up to PG_PIPE_WINDOW cells it must not.)
-            const int far_rows = dc.x + PRW - PREC_BACK, far_cols = dcur - dc.y + PRW - PREC_BACK;
-            want_rows = far_rows;
-            want_cols = far_cols;
-            if (dc.y - dc.x + 1 > PG_PIPE_WINDOW) {
-                // a diagonal wider than the windows (class 5) takes its records from L2, but its waves still wait for "rows <= hi + 3
-                // loaded": just those, so that the first diagonal the windows cover again finds the records before its first row
-                const pg_i8 dn = psc[dcur + 1 < J.nd ? dcur + 1 : dcur];
-                const int near_rows = dn.y + 5, near_cols = dcur + 1 - dn.x + 4;
-                want_rows = want_rows > near_rows ? want_rows : near_rows;
-                want_cols = want_cols > near_cols ? want_cols : near_cols;
-            }
-        }
-        want_rows = want_rows < J.Lx ? want_rows : J.Lx;
-        want_cols = want_cols < J.Ly ? want_cols : J.Ly;
-        bool any = false;
-        // descriptors of the diagonals up to da: what a far read needs to find an old cell
-        // (entries older than dcur - PDR + PLOOK are overwritten; readers look back PDR_REACH at most)
-        if (diags <= da) {
-            while (diags <= da) {
-                const int t = diags + lane;
-                if (t <= da) {
-                    pg_i4 v;
-                    if (pdsc) {
-                        v = pdsc[t];
-                        const long long bo = 24ll * (((long long)v.w << 32) | (unsigned)v.z);
-                        v.z = (int)(bo & 0xffffffffLL); v.w = (int)(bo >> 32);
-                    } else v = *((PG_GLOBAL const pg_i4 *)psc + 2 * t);
-                    PM.dring[t & (PDR - 1)] = v;
-                }
-                diags = diags + 64 < da + 1 ? diags + 64 : da + 1;
-            }
-            flag_store(&PM.loaded[2], diags);
-            any = true;
-        }
-        if (rows < want_rows) {
-            load_rec_chunk<true>(rows, lane, J.Lx, J.stL, J.offL, J.srcL, J.lwL, strip != nullptr, norm, hfl);
-            rows += 64; any = true;
-            flag_store(&PM.loaded[0], rows);
-        }
-        if (cols < want_cols) {
-            load_rec_chunk<false>(cols, lane, J.Ly, J.stR, J.offR, J.srcR, J.lwR, strip != nullptr, norm, hfr);
-            cols += 64; any = true;
-            flag_store(&PM.loaded[1], cols);
-        }
-        if (!any) __builtin_amdgcn_s_sleep(8);
-    }
-}
+#include "dp_pipe_loader.inc"
 
 // ---- compute-wave helpers ------------------------------------------------------------------
 // bwd edge k of a site: distance back in sites and log-weight.  The first two come with the record.
@@ -390,14 +233,7 @@ struct FarAsk { bool need; long long boff; };                     // byte offset
                                  "global_load_dwordx2 %[" #m_ "], %[" #a "], off offset:16 sc1\n\t"
 __device__ __forceinline__ void far_fetch4(gdouble_w sc, const FarAsk &a0, const FarAsk &a1, const FarAsk &a2, const FarAsk &a3,
                                            pg_d2 &xy0, double &m0, pg_d2 &xy1, double &m1, pg_d2 &xy2, double &m2, pg_d2 &xy3, double &m3) {
-#ifdef PG_PIPE_STATS
-    {
-        const long long lim = PM.far_limit;
-        const bool bad = (a0.need && (a0.boff < 0 || a0.boff + 24 > lim)) || (a1.need && (a1.boff < 0 || a1.boff + 24 > lim)) ||
-                         (a2.need && (a2.boff < 0 || a2.boff + 24 > lim)) || (a3.need && (a3.boff < 0 || a3.boff + 24 > lim));
-        if (__builtin_amdgcn_ballot_w64(bad) != 0) { if (PM.abort_flag == 0) PM.abort_flag = 0x7f000004; return; }
-    }
-#endif
+    PG_ST_FAR_GUARD(PG_ST_FAR_OUTSIDE(a0) || PG_ST_FAR_OUTSIDE(a1) || PG_ST_FAR_OUTSIDE(a2) || PG_ST_FAR_OUTSIDE(a3), 0x7f000004);
     const unsigned long long k0 = __builtin_amdgcn_ballot_w64(a0.need), k1 = __builtin_amdgcn_ballot_w64(a1.need);
     const unsigned long long k2 = __builtin_amdgcn_ballot_w64(a2.need), k3 = __builtin_amdgcn_ballot_w64(a3.need);
     if ((k0 | k1 | k2 | k3) == 0) return;
@@ -413,14 +249,7 @@ __device__ __forceinline__ void far_fetch4(gdouble_w sc, const FarAsk &a0, const
                  : "memory");
 }
 __device__ __forceinline__ void far_fetch8(gdouble_w sc, const FarAsk (&a)[8], pg_d2 (&xy)[8], double (&m)[8]) {
-#ifdef PG_PIPE_STATS
-    {
-        const long long lim = PM.far_limit;
-        bool bad = false;
-        for (int k = 0; k < 8; ++k) bad = bad || (a[k].need && (a[k].boff < 0 || a[k].boff + 24 > lim));
-        if (__builtin_amdgcn_ballot_w64(bad) != 0) { if (PM.abort_flag == 0) PM.abort_flag = 0x7f000008; return; }
-    }
-#endif
+    PG_ST_FAR_GUARD(([&] { bool bad = false; for (int k = 0; k < 8; ++k) bad = bad || PG_ST_FAR_OUTSIDE(a[k]); return bad; }()), 0x7f000008);
     const unsigned long long k0 = __builtin_amdgcn_ballot_w64(a[0].need), k1 = __builtin_amdgcn_ballot_w64(a[1].need);
     const unsigned long long k2 = __builtin_amdgcn_ballot_w64(a[2].need), k3 = __builtin_amdgcn_ballot_w64(a[3].need);
     const unsigned long long k4 = __builtin_amdgcn_ballot_w64(a[4].need), k5 = __builtin_amdgcn_ballot_w64(a[5].need);
@@ -1193,17 +1022,7 @@ __device__ __noinline__ void pipe_assist_lean(const PgDevJob *__restrict__ job, 
     const int wave = PNW + a;                                      // names this wave in an abort tag
     int rows_ld = 0, cols_ld = 0, diags_ld = 0;
     int pw0 = -1, pw1 = -1, pw2 = -1, pw3 = -1;                   // cached progress of the compute waves
-#ifdef PG_PIPE_STATS
-    long long st_poll_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int st_poll_n[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    long long as_t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // [0] cycles outside the wait for the compute waves, [1] inside it
-    int as_n = 0, as_gen = 0, as_pairs = 0, as_cells = 0;          // diagonals staged; of those by the general code, whole; passes that held two; diagonals with cells staged by the general code
-    int as_why[6] = {0, 0, 0, 0, 0, 0};                            // passes sent to the general code: slots, site shape, other side, cell shape / site 0, recent operand off the ring, pool
-    long long as_t0 = __builtin_readcyclecounter();
-#define ASTAMP(k) do { const long long t_ = __builtin_readcyclecounter(); as_t[k] += t_ - as_t0; as_t0 = t_; } while (0)
-#else
-#define ASTAMP(k)
-#endif
+    PG_ST(PipeAssistStats st = pg_stats_assist_begin();)           // (ASTAMP's buckets here: 0 outside the wait for the compute waves, 1 inside it, 2..8 the pass)
     int *list = PM.as_list[a];
     const double NI_ = neg_inf();
     // the lane's slot
@@ -1299,9 +1118,7 @@ __device__ __noinline__ void pipe_assist_lean(const PgDevJob *__restrict__ job, 
                 trk_valid = false;
                 q_gen[0] = true;
                 scan_d = d + PNA * hop_a; q_next = desc_req(scan_d);
-#ifdef PG_PIPE_STATS
-                ++as_why[0];
-#endif
+                PG_ST(++st.why[0];)
                 return;
             }
             seen_row = hi_t + 1; seen_col = cmax_t + 1;
@@ -1351,12 +1168,8 @@ __device__ __noinline__ void pipe_assist_lean(const PgDevJob *__restrict__ job, 
             const int oa0 = o.y & 0xffff, oa1 = nO > 1 ? (int)((unsigned)o.y >> 16) : 1;
             const float of0 = __int_as_float(o.z), of1 = nO > 1 ? __int_as_float(o.w) : 0.0f;
             bool ok = !(on && (e_gen || nO < 1 || nO > 2 || oa0 >= 65535 || oa1 >= 65535));
-#ifdef PG_PIPE_STATS
-            if (__builtin_amdgcn_ballot_w64(on && e_gen) != 0) ++as_why[1];
-            else if (__builtin_amdgcn_ballot_w64(!ok) != 0) ++as_why[2];
-            const bool ok_before_slots = ok;
-            bool ok_recent = true;
-#endif
+            PG_ST(if (__builtin_amdgcn_ballot_w64(on && e_gen) != 0) ++st.why[1]; else if (__builtin_amdgcn_ballot_w64(!ok) != 0) ++st.why[2];)
+            PG_ST(const bool ok_before_slots = ok; bool ok_recent = true;)
             const int nL = on ? (e_left ? e_n : nO) : 1, nR = on ? (e_left ? nO : e_n) : 1;
             const int dL0 = !on ? 1 : (e_left ? e_a0 : oa0), dL1 = !on ? 1 : (e_left ? e_a1 : oa1), dL2 = (on && e_left) ? e_a2 : 1;
             const int dR0 = !on ? 1 : (e_left ? oa0 : e_a0), dR1 = !on ? 1 : (e_left ? oa1 : e_a1), dR2 = (on && !e_left) ? e_a2 : 1;
@@ -1383,15 +1196,9 @@ __device__ __noinline__ void pipe_assist_lean(const PgDevJob *__restrict__ job, 
                     s_ += s_ < 0 ? PRK : 0;
                     const int off = ring_off + (s_ * PNT + (p_ & (PNT - 1))) * 24;
                     v_off[k] = (present && resident) ? off : null_off;
-#ifdef PG_EXP_NOFAR                                                  // timing experiment (wrong results): operands that left the ring read as -inf
-                    const bool far = false;
-#else
                     const bool far = present && !resident;
-#endif
                     ok = ok && !(far && age < PAGE);               // a recent diagonal that is not in the ring (after a wide run): not landed yet
-#ifdef PG_PIPE_STATS
-                    ok_recent = ok_recent && !(far && age < PAGE);
-#endif
+                    PG_ST(ok_recent = ok_recent && !(far && age < PAGE);)
                     v_far[k] = far; any_far = any_far || far; f_age[k] = age; f_p[k] = p_;
                 };
                 // gap operands: the (at most two) edges of a side that do not start at the previous site
@@ -1425,10 +1232,8 @@ __device__ __noinline__ void pipe_assist_lean(const PgDevJob *__restrict__ job, 
                 if (on && ((naL0 && row == dL0) || (naL1 && row == dL1) || (naL2 && row == dL2) ||
                            (naR0 && j == dR0) || (naR1 && j == dR1) || (naR2 && j == dR2))) ok = false;
             }
-#ifdef PG_PIPE_STATS
-            if (__builtin_amdgcn_ballot_w64(on && ok_before_slots && !ok_recent) != 0) ++as_why[4];
-            else if (__builtin_amdgcn_ballot_w64(on && ok_before_slots && !ok) != 0) ++as_why[3];
-#endif
+            PG_ST(if (__builtin_amdgcn_ballot_w64(on && ok_before_slots && !ok_recent) != 0) ++st.why[4];
+                  else if (__builtin_amdgcn_ballot_w64(on && ok_before_slots && !ok) != 0) ++st.why[3];)
             // a cell this path does not take: the general code stages it when its diagonal is due
             q_bad = on && !ok;
             on = on && ok;
@@ -1459,9 +1264,7 @@ __device__ __noinline__ void pipe_assist_lean(const PgDevJob *__restrict__ job, 
                     }
                     n_pool += __builtin_popcountll(mk);
                 }
-#ifdef PG_PIPE_STATS
-                if (n_pool > PFAR_POOL) ++as_why[5];
-#endif
+                PG_ST(if (n_pool > PFAR_POOL) ++st.why[5];)
                 if (n_pool > PFAR_POOL) { q_gen[0] = true; q_gen[1] = pair; on = false; q_bad = false; }      // (more far cells than the pool holds)
                 else {
                     far_fetch8(sc_out, fa, fxy, fm_);
@@ -1492,9 +1295,7 @@ __device__ __noinline__ void pipe_assist_lean(const PgDevJob *__restrict__ job, 
         ASTAMP(1);
         if (q_gen[g]) {
             if (q_cls[g] == 2 && diags_ld < d) diags_ld = POLL(&PM.loaded[2], d, 5);
-#ifdef PG_PIPE_STATS
-            ++as_gen;
-#endif
+            PG_ST(++st.gen;)
             assist_general_diag(job, psc, a, lane, reduced_terminal, d, q_cls[g], q_lo[g], q_hi[g], q_mask[g], term_on);
         } else if (q_on && grp == g) {
             const char *base = (const char *)&PM;
@@ -1525,16 +1326,12 @@ __device__ __noinline__ void pipe_assist_lean(const PgDevJob *__restrict__ job, 
         ASTAMP(5);
         if (!q_gen[g] && __builtin_amdgcn_ballot_w64(q_bad && grp == g) != 0) {
             if (q_cls[g] == 2 && diags_ld < d) diags_ld = POLL(&PM.loaded[2], d, 5);
-#ifdef PG_PIPE_STATS
-            ++as_cells;
-#endif
+            PG_ST(++st.cells;)
             assist_general_cells(job, psc, a, lane, reduced_terminal, d, q_cls[g], q_mask[g], q_bad && grp == g, q_row, q_j, term_on);
         }
         ASTAMP(6);
         flag_store(&PM.assist_done[a], d);
-#ifdef PG_PIPE_STATS
-        ++as_n;
-#endif
+        PG_ST(++st.n;)
     };
 
     prepare();
@@ -1557,25 +1354,12 @@ __device__ __noinline__ void pipe_assist_lean(const PgDevJob *__restrict__ job, 
         }
         stage(0);
         if (q_d2 >= 0) {
-#ifdef PG_PIPE_STATS
-            ++as_pairs;
-#endif
+            PG_ST(++st.pairs;)
             stage(1);
         }
         prepare();
     }
-#ifdef PG_PIPE_STATS
-    if (lane == 0 && 3 * (job->Lx + job->Ly) >= 4096 && PG_STATS_MINE(job, flags)) {
-        PG_GLOBAL int *o = (PG_GLOBAL int *)job->trace + 3 * (job->Lx + job->Ly) - 1000 + 16 * a;
-        o[0] = as_n;
-        for (int k = 0; k < 12; ++k) o[1 + k] = (int)(as_t[k] >> 8);
-        o[13] = as_gen; o[14] = as_pairs; o[15] = as_cells;
-#ifndef PG_AS_BUCKETS                                              // (-DPG_AS_BUCKETS: the cycle buckets 2..6 of the lean path instead)
-        for (int k = 0; k < 6; ++k) o[1 + 2 + k] = as_why[k];     // (in the place of the unused cycle buckets 2..7)
-#endif
-    }
-#endif
-#undef ASTAMP
+    PG_ST(if (lane == 0) pg_stats_write_assist(job, flags, a, st, true);)
 }
 
 // ---- assist waves, large model tables: every multi-edge cell of the class 0..2 diagonals, staged with back-pointer words ----
@@ -1595,10 +1379,6 @@ __device__ __noinline__ void pipe_assist(const PgDevJob *__restrict__ job, cdesc
     const int wave = PNW + a;                                      // names this wave in an abort tag
     int rows_ld = 0, cols_ld = 0, diags_ld = 0;
     int pw0 = -1, pw1 = -1, pw2 = -1, pw3 = -1;                   // cached progress of the compute waves
-#ifdef PG_PIPE_STATS
-    long long st_poll_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int st_poll_n[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     int *list = PM.as_list[a];
     const double NI_ = neg_inf();
     // Software pipeline: everything a diagonal's batch needs that does NOT come out of the ring -- its descriptor, the scan
@@ -1624,18 +1404,8 @@ __device__ __noinline__ void pipe_assist(const PgDevJob *__restrict__ job, cdesc
     int scan_d = a;                                                // next diagonal whose descriptor has not been looked at
     if (STRIP) { const int d0 = job->d_first; scan_d = d0 + (a + 3 - d0 % 3) % 3; }       // (the strip's first diagonal of this wave's residue)
 
-#ifdef PG_PIPE_STATS
-    long long as_t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // cycles: prepare (rest), waiting for the compute waves, compute, publish; inside prepare: scan, batch, decode, far
-    int as_n = 0;
-    // (PG_ASSIST_RUNS_ONLY: only diagonals that directly follow this wave's previous one -- the inside of a class 2 run, where the
-    // assist waves are what the compute waves wait for -- are counted; otherwise the idle time between runs dominates the averages)
-    bool as_on = true;
-    int as_prev = -100;
-#define ASTAMP(k) do { const long long t_ = __builtin_readcyclecounter(); if (as_on) as_t[(k) == 12 ? 0 : (k)] += t_ - as_t0; as_t0 = t_; } while (0)
-    long long as_t0 = __builtin_readcyclecounter();
-#else
-#define ASTAMP(k)
-#endif
+    // (ASTAMP's buckets here: prepare (rest), waiting for the compute waves, compute, publish; inside prepare: scan, batch, decode, far)
+    PG_ST(PipeAssistStats st = pg_stats_assist_begin();)
     const AssistGen<TAB_LDS> gen = assist_gen<TAB_LDS>(job, psc, a, lane, reduced_terminal, term_on);     // (large tables: the general code, inline)
     // looks for the next diagonal of this wave with work and prepares it
     // descriptor of scan_d, requested a pass ahead -- as a VECTOR load (lanes 0..7 one word each): a scalar load shares its
@@ -1800,24 +1570,11 @@ __device__ __noinline__ void pipe_assist(const PgDevJob *__restrict__ job, cdesc
         ASTAMP(2);
         flag_store(&PM.assist_done[a], d);
         ASTAMP(3);
-#ifdef PG_PIPE_STATS
-        if (as_on) ++as_n;
-        as_prev = d;
-#endif
+        PG_ST(if (st.on) ++st.n; st.prev = d;)
         prepare();
-#ifdef PG_PIPE_STATS
-#ifdef PG_ASSIST_RUNS_ONLY
-        as_on = q_d == as_prev + PNA;
-#endif
-#endif
+        PG_ST(PG_ST_ASSIST_NEXT(q_d);)
     }
-#ifdef PG_PIPE_STATS
-    if (lane == 0 && 3 * (job->Lx + job->Ly) >= 4096) {
-        PG_GLOBAL int *o = (PG_GLOBAL int *)job->trace + 3 * (job->Lx + job->Ly) - 1000 + 16 * a;
-        o[0] = as_n;
-        for (int k = 0; k < 12; ++k) o[1 + k] = (int)(as_t[k] >> 8);
-    }
-#endif
+    PG_ST(if (lane == 0) pg_stats_write_assist(job, flags, a, st, false);)
 }
 
 
@@ -1842,10 +1599,7 @@ struct WaveCtx {
     float smf;                               // model score of (row, d - row)
     pg_i8 dA;                                // descriptor of diagonal d
     int p_up, p_dn, ok_until, rows_ld, cols_ld, diags_ld, as0, as1, as2;
-#ifdef PG_PIPE_STATS
-    long long st_cls_t[5], st_poll_t[10], st_w[4];
-    int st_cls_n[5], st_poll_n[10];
-#endif
+    PG_ST_CTX                                // (statistics builds: the wave's counters, dp_pipe_stats.h)
 };
 __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
@@ -1874,11 +1628,7 @@ __device__ __forceinline__ pg_i8 uniform_i8(const pg_i8 &v) {
 #define WCTX_OUT(c) \
     (c).d = d; (c).row = row; (c).p_up = p_up; (c).p_dn = p_dn; (c).ok_until = ok_until; (c).rows_ld = rows_ld; (c).cols_ld = cols_ld; \
     (c).diags_ld = diags_ld; (c).as0 = as0; (c).as1 = as1; (c).as2 = as2
-#ifdef PG_PIPE_STATS
-#define WCTX_STATS(c) long long (&st_cls_t)[5] = (c).st_cls_t; long long (&st_poll_t)[10] = (c).st_poll_t; int (&st_cls_n)[5] = (c).st_cls_n; int (&st_poll_n)[10] = (c).st_poll_n; long long (&st_w)[4] = (c).st_w; (void)st_w
-#else
-#define WCTX_STATS(c)
-#endif
+// (WCTX_STATS(c): the run works on (c).st -- dp_pipe_stats.h)
 
 // every VGPR from v136 up and the SGPRs s36..s87 belong to the hand-scheduled loop (tools/gen_hot_asm.py has the plan)
 #define PG_V8(a) "v" #a "0", "v" #a "1", "v" #a "2", "v" #a "3", "v" #a "4", "v" #a "5", "v" #a "6", "v" #a "7", "v" #a "8", "v" #a "9"
@@ -1976,9 +1726,7 @@ __device__ __noinline__ void hot_run(WaveCtx &C_) {
             // the loop stops in front of the first diagonal it may not run without looking at the loader's flags or past the
             // wave's interval
             const int stop = __builtin_amdgcn_readfirstlane(sleep < ok_until + 1 ? sleep : ok_until + 1);
-#ifdef PG_PIPE_STATS
-            const long long st_t_in = __builtin_readcyclecounter();
-#endif
+            PG_ST_CLOCK(st_t_in);
             int k0 = 0, k1 = 0, k2 = 0;        // diagnostic builds (PG_HOT_EXP=k): waits for the upstream wave, looks at its flag, waits for the downstream wave
 #define PG_HOT_OUTS [row] "+v"(row), [colx] "+v"(colx), [rowx] "+v"(rowx), [tm] "+v"(tm_io), [tx] "+v"(tx_io), \
                   [p0] "+v"(PX), [p1] "+v"(PY), [p2] "+v"(PMm), [c0] "+v"(CX), [c1] "+v"(CY), [c2] "+v"(CM), \
@@ -2015,28 +1763,9 @@ __device__ __noinline__ void hot_run(WaveCtx &C_) {
 #undef PG_HOT_OUTS
 #undef PG_HOT_INS
             d = __builtin_amdgcn_readfirstlane(d);
-            (void)d_in;
-#ifdef PG_PIPE_STATS
-            {   // one record per run of the loop (first diagonal, diagonal it stopped in front of, clock at entry and exit / 16,
-                // waits for the upstream wave | 48-look exits << 16): upper half of the job's trace buffer, per wave
-                const long long st_t_out = __builtin_readcyclecounter();
-                const int n3 = 3 * (Lx + Ly), r0 = (n3 / 4 * 3 + 15) & ~15, cap = (n3 - 1200 - r0 - 16) / 16;
-                if (cap > 0 && n3 >= 4096 && (tid & 63) == 0 && PG_STATS_MINE(C_.job, C_.flags)) {
-                    PG_GLOBAL int *tb = (PG_GLOBAL int *)C_.job->trace;
-                    const int slot = atomicAdd((int *)(tb + r0 + wave), 1);
-                    if (slot < cap) {
-                        PG_GLOBAL int *o = tb + r0 + 16 + 4 * (slot * 4 + wave);
-                        o[0] = d_in; o[1] = __builtin_amdgcn_readfirstlane(d) | ((k0 >> 16) ? 0x40000000 : 0); o[2] = (int)(st_t_in >> 4); o[3] = (int)(st_t_out >> 4);
-#ifdef PG_RUN_LOOKS                                                // (diagnostic: looks at the upstream flag / waits for the downstream wave in the place of the clocks' low bits)
-                        o[2] = (int)((st_t_out - st_t_in) >> 4); o[3] = k1 | ((k2 & 0xffff) << 20);
-#endif
-                    }
-                }
-            }
-            st_poll_n[9] += k0 & 0xffff; st_poll_n[6] += k1; st_poll_t[9] += (long long)(k2 & 0xffff) << 8; st_poll_n[5] += k0 >> 16; st_poll_t[5] += (long long)(k2 >> 16) << 8; st_poll_n[0] += 1; st_poll_t[0] += (long long)(d - d_in) << 8;
-#else
-            (void)k0; (void)k1; (void)k2;
-#endif
+            (void)d_in; (void)k0; (void)k1; (void)k2;
+            // (statistics builds: one record per run of the loop, and what the loop counted itself)
+            PG_ST(pg_stats_write_run(C_.job, C_.flags, 3 * (Lx + Ly), tid, wave, d_in, d, k0, st_t_in, __builtin_readcyclecounter()); pg_stats_hot_loop(st, k0, k1, k2, d - d_in);)
             // the operand pipeline of diagonal d from the LDS windows, the descriptor from memory
             cur = psc[d];
             hstg = d % PST;
@@ -2046,9 +1775,7 @@ __device__ __noinline__ void hot_run(WaveCtx &C_) {
             ti0 = ((rLc.x & 0xffff) + __umul24(cR0.x & 0xffff, S)) & 255;
             tMc = PM.tab2[ti0][0]; tXc = PM.tab2[ti0][1];
             if ((cur.s4 & CLS) > 2 || d >= sleep) { dA = cur; break; }
-#ifdef PG_PIPE_STATS
-            st_poll_n[7] += (__any(row <= cur.y + 1) ? 0 : 1);
-#endif
+            PG_ST(st.poll_n[7] += (__any(row <= cur.y + 1) ? 0 : 1);)
             // The loop stopped at a diagonal it could run but for a flag: wait here (polls that sleep, spin limits that
             // end in an error status) for everything diagonal d needs, then go back into it -- the arithmetic below is the
             // loop's C++ rendering, compiled in with -DPG_NO_HOT_ASM only.
@@ -2083,10 +1810,7 @@ __device__ __noinline__ void hot_run(WaveCtx &C_) {
         // (this C++ rendering of the step knows nothing of the far histories: a job planned with them -- PAGAN_DP_HIST is not 0 --
         //  must run the hand-scheduled loop; a -DPG_NO_HOT_ASM build that meets one says so instead of computing something else)
         if (!STRIP && (cur.s4 & 32)) { if (flag_load(&PM.abort_flag) == 0) flag_store(&PM.abort_flag, PTAG(13)); dA = cur; break; }
-#ifdef PG_PIPE_STATS
-        const long long st_step0 = __builtin_readcyclecounter();
-        const bool st_has = __any(row <= hi && row >= lo);
-#endif
+        PG_ST_STEP_BEGIN(row, lo, hi);
         // ---- flow control: flags are read only when the cached values stop covering this step (see step()) ----
         if (d > ok_until) {
             int need = hi + 3 < Lx - 1 ? hi + 3 : Lx - 1;
@@ -2192,7 +1916,6 @@ __device__ __noinline__ void hot_run(WaveCtx &C_) {
                 take_better(bm, pm, m2, p2, lS);
             }
         }
-#ifndef PG_X_NOC2
         else if (cls == 2) {
             // ================= class 2: merge what the assist wave of this diagonal staged (see step()) =================
             if (hstg == 0) { if (as0 < d) as0 = POLLX(&PM.assist_done[0], d, 8); }
@@ -2210,7 +1933,6 @@ __device__ __noinline__ void hot_run(WaveCtx &C_) {
             const bool tkm = msL || msR;
             bm = tkm ? em : bm;  pm = tkm ? sfm : pm;
         }
-#endif
         // ---- results: -inf outside the band; a state that stayed -inf has no back-pointer ----
         bx = active ? bx : NI; by = active ? by : NI; bm = active ? bm : NI;
         px = bx > NI ? px : PG_BP_NONE; py = by > NI ? py : PG_BP_NONE; pm = bm > NI ? pm : PG_BP_NONE;
@@ -2230,11 +1952,7 @@ __device__ __noinline__ void hot_run(WaveCtx &C_) {
             *(PG_GLOBAL u3 *)(brow + off12) = b3;
         }
         asm volatile("s_waitcnt vmcnt(24)" ::: "memory");  // all but the last 8 steps' stores have retired (far reads rely on it)
-#ifdef PG_X_OLDFLAG
-        flag_store(&PM.progress[wave], d);
-#else
         flag_store_inorder(&PM.progress[wave], d);
-#endif
         // ---- operand pipeline for the next steps: one LDS wait per step, at its top ----
         const pg_i4 cR2 = PM.recR[(d + 2 - row) & (PRW - 1)];
         const int ti1 = ((rLc.x & 0xffff) + __umul24(cR1.x & 0xffff, S)) & 255;
@@ -2242,12 +1960,7 @@ __device__ __noinline__ void hot_run(WaveCtx &C_) {
         const pg_i4 rLn = PM.recL[row & (PRW - 1)];
         PX = bx; PY = by; PMm = bm;
         CX = AX; CY = AY; CM = AM;
-#ifdef PG_PIPE_STATS
-        if (st_has) {
-            const long long dt = __builtin_readcyclecounter() - st_step0;
-            for (int c = 0; c < 5; ++c) if (c == cls) { st_cls_t[c] += dt; ++st_cls_n[c]; }
-        }
-#endif
+        PG_ST_STEP_END(cls);
         ++d;
         sb = sb + PROW_BYTES == PRING_BYTES ? 0 : sb + PROW_BYTES;
         hstg = hstg + 1 == PST ? 0 : hstg + 1;
@@ -2353,9 +2066,7 @@ __device__ __noinline__ void wide_run(WaveCtx &C_) {
     for (;;) {
         const int lo = cur.x, hi = cur.y;
         if (lo - 2 * wage - 4 - wbase >= wpos_n) wbase += wpos_n;      // (every row a step touches lies in [wbase, wbase + 3 * 384))
-#ifdef PG_PIPE_STATS
-        const long long st_step0 = __builtin_readcyclecounter();
-#endif
+        PG_ST_CLOCK(st_step0);
         {   // records of the diagonal's rows and columns, descriptors of every earlier diagonal
             const int nr_ = hi + 1 < Lx ? hi + 1 : Lx, nc_ = d - lo + 1 < Ly ? d - lo + 1 : Ly;
             if (rows_ld < nr_) rows_ld = POLLX(&PM.loaded[0], nr_, 1);
@@ -2365,9 +2076,7 @@ __device__ __noinline__ void wide_run(WaveCtx &C_) {
         // (inline polls: in lock step a neighbour is, as a rule, a fraction of a step away)
         if (p_up < d - 1) p_up = __builtin_amdgcn_readfirstlane(POLL(&PM.progress[up], d - 1, 4));
         if (p_dn < d - 2) p_dn = __builtin_amdgcn_readfirstlane(POLL(&PM.progress[dn], d - 2, 3));
-#ifdef PG_PIPE_STATS
-        const long long st_t1 = __builtin_readcyclecounter();
-#endif
+        PG_ST_CLOCK(st_t1);
         // the next diagonal's descriptor: staged by the loader (the window runs PLOOK diagonals ahead of the slowest wave)
         if (diags_ld < d + 2 && d + 1 < nd) diags_ld = POLLX(&PM.loaded[2], d + 2, 5);
         const pg_i4 nxt = PM.dring[(d + 1) & (PDR - 1)];
@@ -2486,17 +2195,13 @@ __device__ __noinline__ void wide_run(WaveCtx &C_) {
             fetch(6, b1 && r2, kR + 1, r - 1);
             fetch(7, b1 && l2 && r2, kL + kR, r - kL);
         }
-#ifdef PG_PIPE_STATS
-        const long long st_t2 = __builtin_readcyclecounter();
-#endif
+        PG_ST_CLOCK(st_t2);
         // what the wave asked L2 for, both sets: one statement per set, requests and wait (it does nothing if no lane asked)
         if (any_far) {
             far_fetch8(sc_out, o_f[0], o_xy[0], o_m[0]);
             far_fetch8(sc_out, o_f[1], o_xy[1], o_m[1]);
         }
-#ifdef PG_PIPE_STATS
-        const long long st_t3 = __builtin_readcyclecounter();
-#endif
+        PG_ST_CLOCK(st_t3);
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int r = wrow[q], j = d - r;
@@ -2584,13 +2289,7 @@ __device__ __noinline__ void wide_run(WaveCtx &C_) {
             n_hist2 = n_hist1; n_hist1 = n_now;
         }
         flag_store(&PM.progress[wave], d);
-#ifdef PG_PIPE_STATS
-        {
-            const long long st_t5 = __builtin_readcyclecounter();
-            st_cls_t[4] += st_t5 - st_step0; ++st_cls_n[4];
-            st_w[0] += st_t1 - st_step0; st_w[1] += st_t2 - st_t1; st_w[2] += st_t3 - st_t2; st_w[3] += st_t5 - st_t3;
-        }
-#endif
+        PG_ST_WIDE_END_BUCKETS(true);
         ++d;
         lo_prev = lo;
         if (d >= run_end || flag_load(&PM.abort_flag) != 0) break;
@@ -2658,14 +2357,8 @@ __device__ __forceinline__ bool site7(const pg_i4 &rec, int site, bool &two, boo
 // One cell's three scores from L2 as loads the compiler tracks (agent scope, as far_fetch's sc1): they may stay in flight
 // across other code -- the lock-step poll -- and the compiler waits where a value is first used.
 __device__ __forceinline__ void far_issue(gdouble_w sc, const FarAsk &a, unsigned long long (&q)[3]) {
-#ifdef PG_PIPE_STATS
-    // (as far_fetch8: a cell outside the job's score array sets the abort flag, and the arena's first cell is read instead)
-    const bool bad = a.need && (a.boff < 0 || a.boff + 24 > PM.far_limit);
-    if (__builtin_amdgcn_ballot_w64(bad) != 0 && PM.abort_flag == 0) PM.abort_flag = 0x7f000005;
-    PG_GLOBAL const unsigned long long *p = (PG_GLOBAL const unsigned long long *)((PG_GLOBAL const char *)sc + (a.need && !bad ? a.boff : 0ll));
-#else
-    PG_GLOBAL const unsigned long long *p = (PG_GLOBAL const unsigned long long *)((PG_GLOBAL const char *)sc + (a.need ? a.boff : 0ll));
-#endif
+    // (statistics builds, as far_fetch8: a cell outside the job's score array sets the abort flag, and the arena's first cell is read instead)
+    PG_GLOBAL const unsigned long long *p = (PG_GLOBAL const unsigned long long *)((PG_GLOBAL const char *)sc + (PG_ST_FAR_WANTED(a, 0x7f000005) ? a.boff : 0ll));
     q[0] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     q[1] = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     q[2] = __hip_atomic_load(p + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2729,9 +2422,7 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
     for (;;) {
         const int lo = cur.x, hi = cur.y;
         if (lo - 2 * wage - 4 - wbase >= wpos_n) wbase += wpos_n;
-#ifdef PG_PIPE_STATS
-        const long long st_step0 = __builtin_readcyclecounter();
-#endif
+        PG_ST_CLOCK(st_step0);
         {   // records of the diagonal's rows and columns, descriptors of every earlier diagonal
             const int nr_ = hi + 1 < Lx ? hi + 1 : Lx, nc_ = d - lo + 1 < Ly ? d - lo + 1 : Ly;
             if (rows_ld < nr_) rows_ld = POLLX(&PM.loaded[0], nr_, 1);
@@ -2833,9 +2524,7 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
                 }
             }
         }
-#ifdef PG_PIPE_STATS
-        const long long st_t1 = __builtin_readcyclecounter();
-#endif
+        PG_ST_CLOCK(st_t1);
 #ifdef PG_EXP_WIDE_SKIP                                             // timing experiment (WRONG RESULTS): a wide step is its flags and nothing else
         if (true) {
             flag_store(&PM.wflag[w7], d);
@@ -2892,9 +2581,7 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
                 o_xy[t].x = c[PG_X]; o_xy[t].y = c[PG_Y]; o_m[t] = c[PG_M];
             }
         }
-#ifdef PG_PIPE_STATS
-        const long long st_t2 = __builtin_readcyclecounter();
-#endif
+        PG_ST_CLOCK(st_t2);
         if (any_far) {
 #ifdef PG_WIDE7_FETCH_BEHIND                                       // A/B build: the requests behind the lock step, as before round 6
 #pragma unroll
@@ -2905,9 +2592,7 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
                 if (o_f[t].need) { o_xy[t].x = __longlong_as_double((long long)o_q[t][0]); o_xy[t].y = __longlong_as_double((long long)o_q[t][1]); o_m[t] = __longlong_as_double((long long)o_q[t][2]); }
             }
         }
-#ifdef PG_PIPE_STATS
-        const long long st_t3 = __builtin_readcyclecounter();
-#endif
+        PG_ST_CLOCK(st_t3);
         const bool active = kind != 0;
         const int n_now = __any(active) ? 2 : 0;                // stores this wave issues in this step
         double bx = NIw, by = NIw, bm = NIw;
@@ -3006,13 +2691,7 @@ __device__ __noinline__ void wide_run7(WaveCtx &C_) {
         // the next step's registers: this cell is its (row, j-1), this step's (row-1, j) its (row-1, j-1)
         Px = bx; Py = by; Pm = bm;
         Cx = Ux; Cy = Uy; Cm = Um;
-#ifdef PG_PIPE_STATS
-        if (w7 < PNW) {
-            const long long st_t5 = __builtin_readcyclecounter();
-            st_cls_t[4] += st_t5 - st_step0; ++st_cls_n[4];
-            st_w[0] += st_t1 - st_step0; st_w[1] += st_t2 - st_t1; st_w[2] += st_t3 - st_t2; st_w[3] += st_t5 - st_t3;
-        }
-#endif
+        PG_ST_WIDE_END_BUCKETS(w7 < PNW);                       // (the assist waves' steps are not counted)
         ++d;
         wsb += wrow_bytes; wsb = wsb == wring_bytes ? 0 : wsb;
         lo_prev = lo;
@@ -3077,17 +2756,11 @@ __device__ __noinline__ void widest_run7(WaveCtx &C_) {
             }
         }
         const pg_i8 cur = psc[d];
-#ifdef PG_PIPE_STATS
-        const long long st_step0 = __builtin_readcyclecounter();
-#endif
-#ifndef PG_EXP_WIDEST_SKIP                                          // (timing experiment, WRONG RESULTS: a class 5 step is its flags and nothing else)
+        PG_ST_CLOCK(st_step0);
         widest_step(job, psc, d, cur.x, cur.y, tid, no_terminal_edges, reduced_terminal, PW7L);
-#endif
         flag_store(&PM.wflag[w7], d);
         if (w7 < PNW) flag_store(&PM.progress[w7], d);
-#ifdef PG_PIPE_STATS
-        if (w7 < PNW) { st_cls_t[4] += __builtin_readcyclecounter() - st_step0; ++st_cls_n[4]; }
-#endif
+        PG_ST_WIDE_END(w7 < PNW);
         ++d;
         if (d >= run_end || flag_load(&PM.abort_flag) != 0) break;
     }
@@ -3114,236 +2787,12 @@ __device__ __noinline__ pg_i4 assist_wide_run(const PgDevJob *__restrict__ job, 
     C_.dA = psc[d0];
     C_.p_up = -1; C_.p_dn = -1; C_.ok_until = -1; C_.rows_ld = rows_ld; C_.cols_ld = cols_ld; C_.diags_ld = diags_ld;
     C_.as0 = 0; C_.as1 = 0; C_.as2 = 0;
-#ifdef PG_PIPE_STATS
-    for (int k = 0; k < 5; ++k) { C_.st_cls_t[k] = 0; C_.st_cls_n[k] = 0; }
-    for (int k = 0; k < 10; ++k) { C_.st_poll_t[k] = 0; C_.st_poll_n[k] = 0; }
-    for (int k = 0; k < 4; ++k) C_.st_w[k] = 0;
-#endif
+    PG_ST(C_.st = PipeWaveStats{};)
     if ((C_.dA.s4 & 15) == 5) widest_run7(C_); else wide_run7(C_);
     return pg_i4{C_.d, C_.rows_ld, C_.cols_ld, C_.diags_ld};
 }
 
-#ifdef PG_PIPE_STATS
-#ifndef PG_STAT_CLASS
-#define PG_STAT_CLASS 0      // the class whose steps the phase stamps cover (-DPG_STAT_CLASS=1 for multi-edge steps)
-#endif
-#define PSTAMP(k) do { const long long t_ = __builtin_readcyclecounter(); if (st_on) st_acc[k] += t_ - st_t; st_t = t_; } while (0)
-#else
-#define PSTAMP(k)
-#endif
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Follower workgroups (blockIdx.x >= n_fill of the same dispatch): back-pointers behind the fill.
-//
-// The fill stores scores only; the back-pointers are a function of the stored scores (pg_backptr, dp_kernels.hip) that needs
-// no wave of the dependency chain.  A banded fill occupies 1 - 31 compute units for 45 - 170 ms, so the pass runs WHILE the
-// fill goes on, on units it leaves idle: every wave of a follower workgroup claims chunks of PG_FOLLOW_CHUNK diagonals of a
-// job (an atomic counter per job), waits until the scores of the chunk's predecessors have landed (follow[0], published by
-// the job's loader wave) and writes the chunk's back-pointers.  The kernel ends a few microseconds after the last fill
-// workgroup instead of being followed by a pass over every cell.
-//
-// Scores are read from L2 (sc1 loads: a line of the frontier may sit in this unit's L1 from an earlier diagonal).  L2 is per
-// XCD: a follower serves only fill workgroups of its own XCD.  Workgroups of a dispatch go round the XCDs by index, so
-// follower g looks at the jobs w with w % 8 == g % 8 and checks the XCC id the fill workgroup published; a job whose id
-// differs, or never shows, is left alone.  Every wait is bounded; what no follower wrote (bp_done[chunk] == 0) pg_backptr
-// writes after the kernel, so a follower that gives up costs time, not results.
-__device__ __forceinline__ int peek_l2(PG_GLOBAL const int *p) {
-    int v;
-    asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(p) : "memory");
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ unsigned my_xcc_id() {
-    unsigned x;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
-    return x & 15u;
-}
-
-__device__ __noinline__ void follow_chunk(const PgDevJob *__restrict__ job, int chunk, int lane, unsigned flags) {
-    const View J = load_view(job);
-    const bool no_terminal_edges = flags & 1u;
-    const bool reduced_terminal = !(flags & 2u);
-    const int first = chunk * PG_FOLLOW_CHUNK, end = first + PG_FOLLOW_CHUNK < J.nd ? first + PG_FOLLOW_CHUNK : J.nd;
-    for (int d = first; d < end; ++d) {
-        const pg_i4 cur = J.dsc[d];
-        const int lo = cur.x, hi = cur.y;
-        if (hi < lo) continue;
-        const long long base = ((long long)cur.w << 32) | (unsigned)cur.z;
-        Diag d1 = {0, -1, 0}, d2 = {0, -1, 0};
-        if (d > 0) { const pg_i4 p = J.dsc[d - 1]; d1 = {p.x, p.y, ((long long)p.w << 32) | (unsigned)p.z}; }
-        if (d > 1) { const pg_i4 p = J.dsc[d - 2]; d2 = {p.x, p.y, ((long long)p.w << 32) | (unsigned)p.z}; }
-        for (int i = lo + lane; i <= hi; i += 64) {
-            const int j = d - i;
-            const long long at = base + (i - lo);
-            int l0 = 0, l1 = 0, r0 = 0, r1 = 0;
-            if (i > 0) { l0 = J.offL[i]; l1 = J.offL[i + 1]; }
-            if (j > 0) { r0 = J.offR[j]; r1 = J.offR[j + 1]; }
-            float sm = 0.0f;
-            if (i > 0 && j > 0 && l1 > l0 && r1 > r0) sm = J.table[J.stL[i] + J.stR[j] * J.S];       // VA:1363
-            double bx, by, bm;
-            unsigned px, py, pm;
-            cell_any(J, i, j, l1 - l0, r1 - r0, sm, no_terminal_edges, reduced_terminal,
-                     [&](int p, int q, double &xs, double &ys, double &ms) {
-                         const long long ix = hbm_index(J, d, d1, d2, p, q);
-                         xs = ys = ms = neg_inf();
-                         if (ix >= 0) far_cell((PG_GLOBAL const double *)(J.sc + 3 * ix), xs, ys, ms);
-                     },
-                     [&](int k, int &p, double &lw) { p = J.srcL[l0 + k]; lw = (double)J.lwL[l0 + k]; },
-                     [&](int k, int &q, double &rw) { q = J.srcR[r0 + k]; rw = (double)J.lwR[r0 + k]; },
-                     bx, by, bm, px, py, pm);
-            typedef unsigned u3 __attribute__((ext_vector_type(3)));
-            u3 b; b.x = px; b.y = py; b.z = pm;
-            *(PG_GLOBAL u3 *)(J.bp + 3 * at) = b;
-            if (flags & PG_FLAG_SCORE_CHECK) {
-                // the recurrence holds at this cell, bit for bit (dp_kernels.hip, pg_backptr has the reasoning): the cell's own
-                // scores have landed with its diagonal (the chunk is claimed behind the landed counter)
-                double sx, sy, sm_;
-                far_cell((PG_GLOBAL const double *)(J.sc + 3 * at), sx, sy, sm_);
-                const bool same = __double_as_longlong(bx) == __double_as_longlong(sx) && __double_as_longlong(by) == __double_as_longlong(sy) &&
-                                  __double_as_longlong(bm) == __double_as_longlong(sm_);
-                if (!same) report_fill_status(job, PG_FILL_SCORE_MISMATCH);
-            }
-        }
-    }
-    if (lane == 0) ((PG_GLOBAL unsigned char *)job->bp_done)[chunk] = 1;
-}
-
-__device__ __noinline__ void pipe_follower(const PgDevJob *__restrict__ jobs, const int *__restrict__ which, int n_fill, unsigned flags) {
-    const int lane = threadIdx.x & 63;
-    const unsigned xcc = my_xcc_id();
-    // the jobs of this dispatch whose fill workgroup runs on this XCD (at most four: 31 jobs a dispatch)
-    int mine[4], n_mine = 0;
-    for (int w = (int)(blockIdx.x & 7u); w < n_fill && n_mine < 4; w += 8) {
-        const PgDevJob *__restrict__ job = jobs + which[w];
-        if (!job->follow) continue;
-        int id = 0;
-        for (int spin = 0; spin < 20000 && (id = peek_l2((PG_GLOBAL const int *)job->follow + 1)) == 0; ++spin) __builtin_amdgcn_s_sleep(32);
-        if (id == (int)xcc + 1) mine[n_mine++] = which[w];
-    }
-    unsigned left = (1u << n_mine) - 1u;
-    int idle = 0;
-    const int start = (int)(threadIdx.x >> 6);                    // the waves of a workgroup start at different jobs
-    while (left != 0 && idle < 200000) {
-        bool worked = false;
-        for (int t = 0; t < n_mine; ++t) {
-            const int k = (t + start) % n_mine;
-            if (!(left & (1u << k))) continue;
-            const PgDevJob *__restrict__ job = jobs + mine[k];
-            PG_GLOBAL int *fw = (PG_GLOBAL int *)job->follow;
-            const int nd = job->nd, n_chunks = (nd + PG_FOLLOW_CHUNK - 1) / PG_FOLLOW_CHUNK;
-            const int next = peek_l2(fw + 2);
-            if (next >= n_chunks) { left &= ~(1u << k); continue; }
-            // a chunk's cells read the diagonals below its last one: claim it once those have landed
-            // (with the score check the chunk's own last diagonal is read too: one more)
-            const int chk = (flags & PG_FLAG_SCORE_CHECK) ? 1 : 0;
-            const int last = ((next + 1) * PG_FOLLOW_CHUNK - 1 < nd - 1 ? (next + 1) * PG_FOLLOW_CHUNK - 1 : nd - 1) + chk;
-            if (peek_l2(fw) < last) continue;                      // (follow[0] = landed + 1 >= last: diagonals <= last - 1 are there)
-            int c = 0;
-            if (lane == 0) c = __hip_atomic_fetch_add(fw + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            c = __builtin_amdgcn_readfirstlane(c);
-            if (c >= n_chunks) { left &= ~(1u << k); continue; }
-            // (another wave may have taken `next` in between: c is a later chunk, wait for it)
-            const int lastc = ((c + 1) * PG_FOLLOW_CHUNK - 1 < nd - 1 ? (c + 1) * PG_FOLLOW_CHUNK - 1 : nd - 1) + chk;
-            int spin = 0;
-            while (peek_l2(fw) < lastc && spin < 200000) { __builtin_amdgcn_s_sleep(32); ++spin; }
-            if (spin >= 200000) return;                            // the fill stopped publishing: pg_backptr writes this chunk
-            follow_chunk(job, c, lane, flags);
-            worked = true;
-        }
-        if (worked) idle = 0; else { __builtin_amdgcn_s_sleep(64); ++idle; }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Row strips: a wide job (a full matrix, a band wider than the lanes) as a chain of banded jobs.
-//
-// A strip is PG_STRIP_ROWS = 192 rows of the matrix over all their columns: to this kernel a band whose first and last
-// row stand still.  Rows map to lanes as ever (row % 256), so a strip's rows fill three compute waves; the fourth -- the
-// wave "upstream" of the strip's first row -- is its FEEDER: it owns the 64 rows above the strip, computes nothing, and
-// writes the cells of the last PHALO = 16 of them (a ring operand lies at most PAGE - 1 rows up; the other columns stay
-// -inf and are never read), read back from the scores the strip above stored, into its ring columns diagonal by diagonal,
-// publishing its progress like any compute wave.  To the strip's waves the rows above are in the ring exactly as if a
-// wave had computed them: lane 0 of the first wave takes row-1 from the feeder's lane 63 (the hot loop checks the feeder's
-// flag as it checks any upstream wave's), multi-edge cells find their ring operands above the strip in the ring, and ring
-// rows are reused under the same per-diagonal rule.  A strip starts when the one above has landed the diagonals its first
-// cells read, and then follows it a few dozen diagonals behind: the job's anti-diagonal sweeps all its strips at once.
-// Strip -> strip visibility (round 5): a strip's scores and its "landed" counter are written THROUGH to memory (sc1 stores:
-// store_scores, the strips' assembly loop, publish_landed) and read with sc1 loads (far_fetch*, peek_l2), so the strips of a
-// job run on whatever XCD the dispatcher gives them -- HIP promises no placement.  Round 4's form is behind
-// PAGAN_DP_STRIP_SPREAD=0: a job's strips at workgroup indices of one residue mod 8 (one XCD as dispatches are observed to
-// go), each strip publishing its XCC id and the feeder below checking it (tag 11; the host's re-runs: dp_abi.hip).
-#define PHALO 16                  // rows above the strip the feeder keeps in the ring: a ring operand lies at most PAGE - 1 <= 16 rows up
-#define PFEED 32                  // diagonals the feeder requests from L2 at a time: 4 per load (lane = diagonal % 4, row), 8 loads, one round trip
-static_assert(PHALO >= PAGE - 1 && 64 / PHALO * 8 == PFEED, "feeder geometry");
-__device__ __noinline__ void strip_feeder(const PgDevJob *__restrict__ job, cdesc8_p psc, int tid, int wave, unsigned flags) {
-    const int lane = tid & 63;
-    wave = __builtin_amdgcn_readfirstlane(wave);
-    const int nd = job->nd, d0 = job->d_first;
-    const int hq = lane / PHALO, hr = lane % PHALO;                // this lane's diagonal (of four) and halo row in a request
-    const int row = job->strip_row0 - PHALO + hr;
-    const int col = row & (PNT - 1);                               // its ring column (the last PHALO lanes' of this wave)
-    const int dn = (wave + 1) % PNW;
-    PG_GLOBAL const int *prev = (PG_GLOBAL const int *)job->prev_follow;
-    const int prev_last = job->prev_nd - 1;
-    PG_GLOBAL const pg_i4 *pdsc = (PG_GLOBAL const pg_i4 *)job->pdsc;
-    const gdouble_w sc = (gdouble_w)job->sc;
-    const double NI = neg_inf();
-    int d = d0;                                                    // (names the diagonal in an abort tag)
-    flag_store(&PM.arrived[wave], nd);                             // no stores to drain: never what a rendezvous waits for
-    if (!(flags & PG_FLAG_STRIPS_SPREAD)) {
-        // PAGAN_DP_STRIP_SPREAD=0 (round 4's placement): the strip above runs on this XCD
-        int id = 0, spin = 0;
-        while ((id = peek_l2(prev + 1)) == 0 && spin < (1 << 22) && flag_load(&PM.abort_flag) == 0) { __builtin_amdgcn_s_sleep(16); ++spin; }
-        // (debug flag 0x800, tests: as if it did not -- the host clears the bit when it launches the strips alone)
-        if ((id != (int)my_xcc_id() + 1 || (flags & 0x800u)) && flag_load(&PM.abort_flag) == 0) flag_store(&PM.abort_flag, PTAG(11));
-    }
-    int landed1 = 0, p_dn = d0 - 1, slot = d0 % PRK;
-    for (int t0 = d0; t0 < nd && flag_load(&PM.abort_flag) == 0; t0 += PFEED) {
-        const int t1 = t0 + PFEED < nd ? t0 + PFEED : nd;
-        d = t0;
-        // what the strip above stored of the diagonals t0 .. t1-1 has landed (its counter ends at its own last diagonal)
-        const int need1 = (t1 - 1 < prev_last ? t1 - 1 : prev_last) + 1;
-        if (landed1 < need1) {
-            int spin = 0;
-            while ((landed1 = peek_l2(prev)) < need1) {
-                __builtin_amdgcn_s_sleep(4);
-                if (++spin > PSPIN_LIMIT / 8 || flag_load(&PM.abort_flag) != 0) {
-                    if (flag_load(&PM.abort_flag) == 0) flag_store(&PM.abort_flag, PTAG(12));
-                    break;
-                }
-            }
-            if (landed1 < need1) break;
-        }
-        FarAsk fa[8];
-        pg_d2 xy[8];
-        double m[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {                              // request k: the diagonals t0 + 4k .. t0 + 4k + 3, this lane's t0 + 4k + hq
-            const int t = t0 + 4 * k + hq;
-            const pg_i4 ds = pdsc[t < nd ? t : nd - 1];            // the whole band's rows on t, the offset (in cells) of its first
-            fa[k].need = t < t1 && row >= ds.x && row <= ds.y;
-            fa[k].boff = 24ll * ((((long long)ds.w << 32) | (unsigned)ds.z) + (row - ds.x));
-            xy[k].x = NI; xy[k].y = NI; m[k] = NI;
-        }
-        // the batch's ring-reuse rule (descriptor word 7: what the downstream wave must have completed, as for any wave) in one load
-        const int s7v = ((PG_GLOBAL const int *)psc)[8 * (t0 + (lane & 31) < nd ? t0 + (lane & 31) : nd - 1) + 7];
-        far_fetch8(sc, fa, xy, m);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-#pragma unroll
-            for (int q = 0; q < 64 / PHALO; ++q) {
-                const int t = t0 + 4 * k + q;
-                if (t >= t1) break;
-                d = t;
-                const int s7 = __builtin_amdgcn_readlane(s7v, 4 * k + q);
-                if (s7 > p_dn) p_dn = poll_ge(&PM.progress[dn], s7, PTAG(3));
-                if (hq == q) { PM.sc[slot][col][PG_X] = xy[k].x; PM.sc[slot][col][PG_Y] = xy[k].y; PM.sc[slot][col][PG_M] = m[k]; }
-                flag_store_inorder(&PM.progress[wave], t);          // (behind the cell: a wave's LDS operations execute in order)
-                slot = slot + 1 == PRK ? 0 : slot + 1;
-            }
-        }
-    }
-    flag_store(&PM.progress[wave], nd);
-}
+#include "dp_pipe_strip.inc"
 
 template <bool TAB_LDS, bool STRIP>
 __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restrict__ jobs, const int *__restrict__ which,
@@ -3374,21 +2823,11 @@ __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restric
     if (tid < PNW) { PM.progress[tid] = STRIP ? job->d_first - 1 : -1; PM.arrived[tid] = STRIP ? job->d_first - 1 : -1; }
     if (tid == 0) { PM.loaded[0] = 0; PM.loaded[1] = 0; PM.loaded[2] = 0; PM.abort_flag = 0; PM.pdsc = STRIP ? job->pdsc : nullptr; }
     if (tid < 8) { PM.wflag[tid] = -1; PM.warrived[tid] = -1; }
-#ifdef PG_PIPE_STATS
-    if (tid == 0) PM.far_limit = 24ll * job->cells;
-#endif
+    PG_ST(if (tid == 0) PM.far_limit = 24ll * job->cells;)
     if (tid < PNA) PM.assist_done[tid] = -1;
     __syncthreads();
 
-#ifdef PG_PIPE_STATS
-    if (tid < 4 && 3 * (job->Lx + job->Ly) >= 4096 && PG_STATS_MINE(job, flags))           // slot counters of the per-run records (hot_run)
-        ((PG_GLOBAL int *)job->trace)[((3 * (job->Lx + job->Ly) / 4 * 3 + 15) & ~15) + tid] = 0;
-    if (lane == 0 && 3 * (job->Lx + job->Ly) >= 4096 && PG_STATS_MINE(job, flags)) {       // which SIMD / CU every wave of the workgroup landed on
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        ((PG_GLOBAL int *)job->trace)[3 * (job->Lx + job->Ly) - 1100 + (tid >> 6)] = (int)hwid;
-    }
-#endif
+    PG_ST(pg_stats_begin(job, flags, tid);)
     if (tid >= PNT + 64 * PNA) {
         const View J = load_view(job);
         pipe_loader(J, psc, lane, (PG_GLOBAL int *)job->follow, STRIP ? job : nullptr, TAB_LDS,
@@ -3434,15 +2873,7 @@ __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restric
     const int bslot = (tid + PNT - 1) & (PNT - 1);                 // ring column of row-1 (lane 0: the upstream wave's lane 63)
     int rows_ld = 0, cols_ld = 0, diags_ld = 0;
     int as0 = -1, as1 = -1, as2 = -1;                              // cached progress of the assist waves (wave a: diagonals d % 3 == a)
-#ifdef PG_PIPE_STATS
-    long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t = 0, st_cls_t[5] = {0, 0, 0, 0, 0};
-    int st_cls_n[5] = {0, 0, 0, 0, 0};
-    long long st_w[4] = {0, 0, 0, 0};
-    long long st_poll_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int st_poll_n[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int st_n = 0;
-    bool st_on = false;
-#endif
+    PG_ST(PipeWaveStats st = {}; PipePhaseStats ph = {};)
 
     for (int iv = 0;; iv += 2) {
         const int wake = sched[iv], sleep = sched[iv + 1];
@@ -3532,10 +2963,7 @@ __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restric
             constexpr bool HOT = decltype(hot_tag)::value;
             const int lo = cur.x, hi = cur.y, cls = cur.s4 & 15;
             PSTAMP(6);
-#ifdef PG_PIPE_STATS
-            const long long st_step0 = __builtin_readcyclecounter();
-            const bool st_has = __any(row <= hi && row >= lo);
-#endif
+            PG_ST_STEP_BEGIN(row, lo, hi);
             // ---- flow control: flags are read only when the cached values stop covering this step ----
             if (d > ok_until) {
                 int need = hi + 3 < Lx - 1 ? hi + 3 : Lx - 1;
@@ -3558,18 +2986,12 @@ __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restric
                 if (diags_ld < d) diags_ld = POLL(&PM.loaded[2], d, 5);      // descriptor window covers every earlier diagonal
                 {
                     // rendezvous: every awake wave has completed d-1 and its stores have landed
-#ifdef PG_PIPE_STATS
-                    const long long w0 = __builtin_readcyclecounter();
-#endif
+                    PG_ST_CLOCK(w0);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef PG_PIPE_STATS
-                    const long long w1 = __builtin_readcyclecounter();
-#endif
+                    PG_ST_CLOCK(w1);
                     flag_store(&PM.arrived[wave], d);
                     for (int w = 0; w < PNW; ++w) POLL(&PM.arrived[w], d, 7);
-#ifdef PG_PIPE_STATS
-                    if (cls == 4) { st_w[0] += w1 - w0; st_w[1] += __builtin_readcyclecounter() - w1; }
-#endif
+                    PG_ST(if (cls == 4) { st.w[0] += w1 - w0; st.w[1] += __builtin_readcyclecounter() - w1; })
                     p_up = d - 1 > p_up ? d - 1 : p_up;
                     p_dn = d - 1 > p_dn ? d - 1 : p_dn;
                 }
@@ -3668,9 +3090,7 @@ __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restric
                 PSTAMP(4);
             } else if (cls <= 3) {
                 const unsigned resmask = ((unsigned)cur.s4 >> 5) & 0x7fffu;
-#ifndef PG_EXP_GENERAL_SKIP                                         // (timing experiment, WRONG RESULTS: a general step computes nothing)
                 if (active) gen_cell(d, slot, resmask, row, j, bx, by, bm, px, py, pm);
-#endif
                 commit_cell<STRIP>(sc_out, bp_out, cur, slot, tid, row - lo, active, bx, by, bm, px, py, pm);
                 if (TAB_LDS && !STRIP && (cur.s4 & 32) && active)      // (a history interval crosses this general step: hist_append)
                     hist_append(PM.recL[row & (PRW - 1)], PM.recR[j & (PRW - 1)], row, j, bx, by, bm);
@@ -3679,9 +3099,7 @@ __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restric
                 // ...; cells come from L2 (all waves are here and drained), simple interior cells with their
                 // three predecessors requested together, the others by the general rules; nothing enters the ring ----
                 const unsigned resmask = ((unsigned)cur.s4 >> 5) & 0x7fffu;
-#ifdef PG_PIPE_STATS
-                const long long w2 = __builtin_readcyclecounter();
-#endif
+                PG_ST_CLOCK(w2);
                 const pg_i8 p1 = psc[d - 1], p2 = psc[d - 2];              // a wide diagonal has d > 240
                 const long long off1 = ((long long)p1.w << 32) | (unsigned)p1.z, off2 = ((long long)p2.w << 32) | (unsigned)p2.z;
                 const long long soff = ((long long)cur.w << 32) | (unsigned)cur.z;
@@ -3736,20 +3154,14 @@ __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restric
                     u3 b3; b3.x = qx; b3.y = qy; b3.z = qm;
                     *(PG_GLOBAL u3 *)(brow + 12u * off) = b3;
                 }
-#ifdef PG_PIPE_STATS
-                const long long w3 = __builtin_readcyclecounter();
-#endif
+                PG_ST_CLOCK(w3);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef PG_PIPE_STATS
-                st_w[2] += w3 - w2; st_w[3] += __builtin_readcyclecounter() - w3;
-#endif
+                PG_ST(st.w[2] += w3 - w2; st.w[3] += __builtin_readcyclecounter() - w3;)
                 have = false;
                 hi_prev = -2;
             } else {
                 // ---- wider than the record windows: every cell from HBM/L2 operands, graph arrays included ----
-#ifndef PG_EXP_WIDEST_SKIP                                          // (timing experiment, WRONG RESULTS: a class 5 step is its rendezvous and nothing else)
                 widest_step(job, psc, d, lo, hi, tid, no_terminal_edges, reduced_terminal);
-#endif
                 have = false;                                      // the record window may have lapped this lane's row
                 hi_prev = -2;
             }
@@ -3770,12 +3182,7 @@ __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restric
             slot = slot + 1 == PRK ? 0 : slot + 1;
             stg = stg + 1 == PST ? 0 : stg + 1;
             PSTAMP(5);
-#ifdef PG_PIPE_STATS
-            if (st_has) {
-                const long long dt = __builtin_readcyclecounter() - st_step0;
-                for (int c = 0; c < 5; ++c) if (c == cls) { st_cls_t[c] += dt; ++st_cls_n[c]; }
-            }
-#endif
+            PG_ST_STEP_END(cls);
         };
 
 
@@ -3784,11 +3191,7 @@ __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restric
             // a wait somewhere ran into its spin limit: every wave leaves as fast as it can (what it would compute from here on is
             // built on operands nobody waited for); the status is reported below
             if (flag_load(&PM.abort_flag) != 0) { d = nd; break; }
-#ifdef PG_PIPE_STATS
-            st_on = (dA.s4 & 15) == PG_STAT_CLASS && __any(row <= dA.y && row >= dA.x);
-            st_t = __builtin_readcyclecounter();
-            if (st_on) st_n += 2;
-#endif
+            PG_ST_PHASE_BEGIN(dA, row);
             if (TAB_LDS && (STRIP ? (dA.s4 & 7) <= 2 : ((dA.s4 & 15) <= 2 || (dA.s4 & 15) == 4 || ((dA.s4 & 15) == 5 && (dA.s4 & (1 << 19)))))) {      // model table in LDS: classes 0..2, 4 and seven-wave runs of 5 as functions of their own
                 WaveCtx C_;
                 C_.job = job; C_.psc = psc; C_.sc_out = sc_out; C_.bp_out = bp_out;
@@ -3800,18 +3203,10 @@ __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restric
                 C_.ca = ca; C_.cb = cb; C_.smf = smf; C_.dA = dA;
                 C_.p_up = p_up; C_.p_dn = p_dn; C_.ok_until = ok_until; C_.rows_ld = rows_ld; C_.cols_ld = cols_ld; C_.diags_ld = diags_ld;
                 C_.as0 = as0; C_.as1 = as1; C_.as2 = as2;
-#ifdef PG_PIPE_STATS
-                for (int k = 0; k < 5; ++k) { C_.st_cls_t[k] = st_cls_t[k]; C_.st_cls_n[k] = st_cls_n[k]; }
-                for (int k = 0; k < 10; ++k) { C_.st_poll_t[k] = st_poll_t[k]; C_.st_poll_n[k] = st_poll_n[k]; }
-                for (int k = 0; k < 4; ++k) C_.st_w[k] = st_w[k];
-#endif
+                PG_ST(C_.st = st;)
                 if (!STRIP && (dA.s4 & 15) == 5) widest_run7(C_);
                 else if (!STRIP && (dA.s4 & 15) == 4) { if (dA.s4 & (1 << 19)) wide_run7(C_); else wide_run(C_); } else hot_run<STRIP>(C_);
-#ifdef PG_PIPE_STATS
-                for (int k = 0; k < 5; ++k) { st_cls_t[k] = C_.st_cls_t[k]; st_cls_n[k] = C_.st_cls_n[k]; }
-                for (int k = 0; k < 10; ++k) { st_poll_t[k] = C_.st_poll_t[k]; st_poll_n[k] = C_.st_poll_n[k]; }
-                for (int k = 0; k < 4; ++k) st_w[k] = C_.st_w[k];
-#endif
+                PG_ST(st = C_.st;)
                 d = __builtin_amdgcn_readfirstlane(C_.d); row = C_.row;
                 r1x = C_.px; r1y = C_.py; r1m = C_.pm; r2x = C_.cx; r2y = C_.cy; r2m = C_.cm;
                 ca = C_.ca; cb = C_.cb; smf = C_.smf; dA = uniform_i8(C_.dA);
@@ -3840,19 +3235,7 @@ __global__ __launch_bounds__(PBLOCK) void pg_fill_pipe(const PgDevJob *__restric
             }
         }
     }
-#ifdef PG_PIPE_STATS
-    if (lane == 0 && 3 * (Lx + Ly) >= 4096 && PG_STATS_MINE(job, flags)) {     // the counters borrow the tail of the trace buffer: long jobs only
-        PG_GLOBAL int *o = (PG_GLOBAL int *)job->trace + 3 * (Lx + Ly) - 200 + 12 * wave;
-        o[0] = st_n;
-        for (int k = 0; k < 7; ++k) o[1 + k] = (int)(st_acc[k] >> 4);
-        PG_GLOBAL int *q = (PG_GLOBAL int *)job->trace + 3 * (Lx + Ly) - 400 + 12 * wave;
-        for (int c = 0; c < 5; ++c) { q[c] = st_cls_n[c]; q[5 + c] = (int)(st_cls_t[c] >> 8); }
-        PG_GLOBAL int *u = (PG_GLOBAL int *)job->trace + 3 * (Lx + Ly) - 600 + 4 * wave;
-        for (int c = 0; c < 4; ++c) u[c] = (int)(st_w[c] >> 8);
-        PG_GLOBAL int *v = (PG_GLOBAL int *)job->trace + 3 * (Lx + Ly) - 800 + 20 * wave;
-        for (int c = 0; c < 10; ++c) { v[c] = st_poll_n[c]; v[10 + c] = (int)(st_poll_t[c] >> 8); }
-    }
-#endif
+    PG_ST(if (lane == 0) pg_stats_write_wave(job, flags, 3 * (Lx + Ly), wave, st, ph);)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // every wave reports an abort it sees when it leaves (the host staged 0): wave 0 may be done long before a
     // later wave's wait runs into its spin limit, and after an abort every wait passes, so a wave that continued

@@ -11,6 +11,7 @@ strip = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 os.environ["PAGAN_DP_DEBUG_FLAGS"] = hex(strip << 12)
 import numpy as np
 import bench
+import pipe_stats
 import pagan2_msa_amd as pg
 from pagan2_msa_amd import host
 
@@ -35,23 +36,19 @@ if stamps:
     n_int = 3 * (l.n_sites + r.n_sites - 2)
     raw = np.zeros(n_int, np.int32)
     pg.lib().pagan_batch_debug_trace(batch._h, 0, raw.ctypes.data_as(C.c_void_p), raw.nbytes)
-    b2 = raw[n_int - 400:]
+    st = pipe_stats.decode(raw)
     for w in range(4):
-        n = b2[12 * w: 12 * w + 5].astype(np.int64); t = b2[12 * w + 5: 12 * w + 10].astype(np.int64) * 256
+        n, t = st["class_steps"][w], st["class_cycles"][w]
         print("wave %d steps with cells by class (n, Mcycles, cycles/step): " % w +
               "  ".join("c%d %d %.1fM %.0f" % (c, n[c], t[c] / 1e6, t[c] / max(n[c], 1)) for c in range(5)))
-    b4 = raw[n_int - 800:]
-    kinds = {0: "asm loop entries / diagonals run in it (M)", 1: "loader rows", 2: "loader cols", 3: "downstream (ring row reuse)", 4: "upstream (row above)", 5: "descriptor window / asm: exits after 48 looks at the upstream flag (count), ... downstream (M)",
-             6: "far: all waves 8 steps behind / asm: looks at the upstream flag (count)", 7: "rendezvous / asm: exits with no row near the band (count)", 8: "assist wave (staged multi-edge candidates)", 9: "asm: upstream waits (count) / downstream waits (M = count / 1e6)"}
+    kinds = pipe_stats.WAIT_KINDS
     for w in range(4):
-        n = b4[20 * w: 20 * w + 10].astype(np.int64); t = b4[20 * w + 10: 20 * w + 20].astype(np.int64) * 256
+        n, t = st["wait_count"][w], st["wait_cycles"][w]
         print("wave %d waits (count, Mcycles): " % w + "; ".join("%s %d %.2fM" % (kinds[kk], n[kk], t[kk] / 1e6) for kk in sorted(kinds)))
-    b5 = raw[n_int - 1000:]
     for a_ in range(3):
-        n = max(int(b5[16 * a_]), 1)
-        t = b5[16 * a_ + 1: 16 * a_ + 13].astype(np.int64) * 256 / n
-        print("assist %d: %d diagonals; cycles/diagonal by bucket 0..11:" % (a_, n), " ".join("%.0f" % x for x in t[:12]))
-        print("assist %d: %d of its diagonals went to the general code whole, %d had cells staged by it; %d passes held two diagonals; passes sent there for: slots %d, a site's shape %d, "
-              "the other side %d, the cell's shape or an edge from site 0 %d, a recent operand off the ring %d, the pool %d" %
-              ((a_, int(b5[16 * a_ + 13]), int(b5[16 * a_ + 15]), int(b5[16 * a_ + 14])) + tuple(int(x) for x in b5[16 * a_ + 3: 16 * a_ + 9])))
+        n = max(int(st["assist_diagonals"][a_]), 1)
+        print("assist %d: %d diagonals; cycles/diagonal by bucket 0..11:" % (a_, n), " ".join("%.0f" % x for x in st["assist_cycles"][a_] / n))
+        print("assist %d: %d of its diagonals went to the general code whole, %d had cells staged by it; %d passes held two diagonals; passes sent there for: " %
+              (a_, int(st["assist_general_whole"][a_]), int(st["assist_general_cells"][a_]), int(st["assist_pairs"][a_])) +
+              ", ".join("%s %d" % (pipe_stats.ASSIST_WHY[k_], int(st["assist_why"][a_][k_])) for k_ in range(6)))
 batch.close()
