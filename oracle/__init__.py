@@ -39,6 +39,8 @@ def lib():
         i32p, f32p, f64p = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double)
         L.oracle_dp_align.argtypes = [gp, gp, mp, bp, op, rp]
         L.oracle_dp_align.restype = C.c_int
+        L.oracle_dp_matrices.argtypes = [gp, gp, mp, bp, op, C.c_int64, f64p, i32p, C.POINTER(C.c_uint8), i32p, i32p]
+        L.oracle_dp_matrices.restype = C.c_int
         L.oracle_result_free.argtypes = [rp]
         L.oracle_result_free.restype = None
         L.oracle_graph_leaf.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
@@ -112,6 +114,31 @@ def dp_align(left, right, model, band=None, flags=0):
         return abi.Result(res)
     finally:
         L.oracle_result_free(C.byref(res))
+
+
+def dp_matrices(left, right, model, band=None, flags=0):
+    """The three matrices dp_align fills (same fill, same end corner), in the oracle's own layout: row-major over the band,
+    row x owning columns begin[x] .. end[x].  Returns a dict of
+      score [cells, 3] float64   X, Y, M
+      ptr   [cells, 3, 5] int32  matrix, x_ind, y_ind, x_edge_ind, y_edge_ind (matrix -1: no predecessor)
+      ties  [cells, 3] uint8     later candidates that equalled the winning score and did not replace it
+      begin, end [Lx] int32      the band as the matrices clamp it."""
+    L = lib()
+    Lx, Ly = left.n_sites - 1, right.n_sites - 1
+    if band is not None:
+        width = np.minimum(band.lower[:Lx].astype(np.int64), Ly - 1) - np.maximum(band.upper[:Lx].astype(np.int64), 0) + 1
+        cells = int(np.maximum(width, 0).sum())
+    else:
+        cells = Lx * Ly
+    out = {"score": np.empty((cells, 3), np.float64), "ptr": np.empty((cells, 3, 5), np.int32), "ties": np.empty((cells, 3), np.uint8),
+           "begin": np.zeros(Lx, np.int32), "end": np.zeros(Lx, np.int32)}
+    opts = abi.COpts(flags, -1)
+    rc = L.oracle_dp_matrices(C.byref(left.c), C.byref(right.c), C.byref(model.c), C.byref(band.c) if band is not None else None,
+                              C.byref(opts), cells, out["score"].ctypes.data_as(C.POINTER(C.c_double)), _ip(out["ptr"]),
+                              out["ties"].ctypes.data_as(C.POINTER(C.c_uint8)), _ip(out["begin"]), _ip(out["end"]))
+    if rc != 0:
+        raise RuntimeError("oracle_dp_matrices failed with code %d" % rc)
+    return out
 
 
 def _ip(a):

@@ -28,6 +28,9 @@
 //                              insert_preexisting_gap etc.      viterbi_alignment.h:127-200
 //   columns()               <- create_ancestral_sequence's l_pos/r_pos walk
 //                              src/main/basic_alignment.cpp:73-171
+//   fill()                  <- align()'s matrices, corner, loops   VA:187-296; behind both entry
+//                              points, oracle_dp_align and oracle_dp_matrices (which hands out the
+//                              matrices with a count of the ties the strict `>` turned away)
 #include "../include/pagan_dp.h"
 
 #include <cmath>
@@ -46,6 +49,9 @@ const double NEG_INF = -HUGE_VAL;
 struct Cell {
     double score = NEG_INF;
     int x_ind = -1, y_ind = -1, x_edge_ind = -1, y_edge_ind = -1, matrix = -1;
+    // not in the reference: later candidates that equalled the winning score and, by the strict `>` of
+    // first_is_bigger, did not replace it (saturating).  Counted for oracle_dp_matrices; nothing reads it back.
+    uint8_t ties = 0;
 };
 
 // TM:185-233: row x owns columns [begin[x], end[x]]; anything else reads `empty`.
@@ -91,6 +97,12 @@ struct Aligner {
         if (a == NEG_INF && b == NEG_INF) return false;
         return a > b;
     }
+    // bigger(s, max->score) for a candidate of cell `max`, counting the ties the strict comparison turns away
+    static bool wins(double s, Cell *max) {
+        if (bigger(s, max->score)) { max->ties = 0; return true; }
+        if (s == max->score && s != NEG_INF && max->ties < 255) max->ties++;
+        return false;
+    }
     // BA.h:490-513 (pair_end_reads is never set: BA.h:565, so that branch is dead)
     float open_pen(int prev_site) const {
         if (reduced_terminal && prev_site == 0) return 0;
@@ -114,7 +126,7 @@ struct Aligner {
             // score_gap_ext VA:2116-2156 (edge weight deliberately not added, VA:2118,2121)
             {
                 double s = rd(Z) + (end_gap ? mod->log_gap_end_ext : mod->log_gap_ext);
-                if (bigger(s, max->score)) {
+                if (wins(s, max)) {
                     max->score = s;
                     if (is_x) { max->matrix = PAGAN_X_MAT; max->x_ind = prev; max->x_edge_ind = eid; }
                     else      { max->matrix = PAGAN_Y_MAT; max->y_ind = prev; max->y_edge_ind = eid; }
@@ -123,7 +135,7 @@ struct Aligner {
             // score_gap_double VA:2158-2188
             {
                 double s = rd(W) + close_pen() + mod->log_gap_open;
-                if (bigger(s, max->score)) {
+                if (wins(s, max)) {
                     max->score = s;
                     if (is_x) { max->matrix = PAGAN_Y_MAT; max->x_ind = prev; max->x_edge_ind = eid; }
                     else      { max->matrix = PAGAN_X_MAT; max->y_ind = prev; max->y_edge_ind = eid; }
@@ -132,7 +144,7 @@ struct Aligner {
             // score_gap_open VA:2190-2219
             {
                 double s = rd(M) + mod->log_non_gap + open_pen(prev);
-                if (bigger(s, max->score)) {
+                if (wins(s, max)) {
                     max->score = s;
                     max->matrix = PAGAN_M_MAT;
                     if (is_x) { max->x_ind = prev; max->x_edge_ind = eid; }
@@ -149,7 +161,7 @@ struct Aligner {
         double rw = R->bwd_logw[k2];
         int rp = R->bwd_src[k2];
         double s = B.at(lp, rp).score + log_match + lw + rw;
-        if (bigger(s, max->score)) {
+        if (wins(s, max)) {
             max->score = s;
             max->x_ind = lp; max->y_ind = rp;
             max->x_edge_ind = L->bwd_eid[k1]; max->y_edge_ind = R->bwd_eid[k2];
@@ -191,7 +203,7 @@ struct Aligner {
     void gap_close(const pagan_graph *g, int k, bool is_x, Cell *max) {
         int prev = g->bwd_src[k];
         double s = (is_x ? X.at(prev, Ly - 1).score : Y.at(Lx - 1, prev).score) + close_pen();
-        if (bigger(s, max->score)) {
+        if (wins(s, max)) {
             max->score = s;
             if (is_x) { max->matrix = PAGAN_X_MAT; max->x_ind = prev; max->x_edge_ind = g->bwd_eid[k]; max->y_edge_ind = -1; }
             else      { max->matrix = PAGAN_Y_MAT; max->y_ind = prev; max->y_edge_ind = g->bwd_eid[k]; max->x_edge_ind = -1; }
@@ -320,20 +332,12 @@ int check_graph(const pagan_graph *g) {
     return PAGAN_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-// Same contract as pagan_dp_align (include/pagan_dp.h), computed on the CPU.
-// out->fill_ms / trace_ms hold CPU wall milliseconds.
-int oracle_dp_align(const pagan_graph *left, const pagan_graph *right, const pagan_model *model,
-                    const pagan_band *band, const pagan_opts *opts, pagan_result *out) {
-    if (!left || !right || !model || !out) return PAGAN_E_ARG;
+// What both entry points run: the checks, the three matrices filled in the reference's order, the end corner.
+int fill(Aligner &a, const pagan_graph *left, const pagan_graph *right, const pagan_model *model,
+         const pagan_band *band, const pagan_opts *opts, Cell *max_end, int64_t *n_cells) {
     int rc;
     if ((rc = check_graph(left)) != PAGAN_OK) return rc;
     if ((rc = check_graph(right)) != PAGAN_OK) return rc;
-    std::memset(out, 0, sizeof(*out));
-    Aligner a;
     a.L = left; a.R = right; a.mod = model;
     uint32_t flags = opts ? opts->flags : 0;
     a.no_terminal_edges = flags & PAGAN_OPT_NO_TERMINAL_EDGES;
@@ -343,7 +347,6 @@ int oracle_dp_align(const pagan_graph *left, const pagan_graph *right, const pag
     for (int s = 1; s < a.Lx; s++) if (left->state[s] < 0 || left->state[s] >= model->n_states) return PAGAN_E_MODEL;
     for (int s = 1; s < a.Ly; s++) if (right->state[s] < 0 || right->state[s] >= model->n_states) return PAGAN_E_MODEL;
 
-    auto t0 = std::chrono::steady_clock::now();
     a.M.init(a.Lx, a.Ly, band); a.X.init(a.Lx, a.Ly, band); a.Y.init(a.Lx, a.Ly, band);
     // initialise_array_corner VA:725-736 (X,Y corner stay -inf by construction).  A band
     // that excludes (0,0) would make the reference write 0 into the shared out-of-tunnel
@@ -359,8 +362,27 @@ int oracle_dp_align(const pagan_graph *left, const pagan_graph *right, const pag
         for (int i = 0; i < a.Lx; i++)               // predecessor has p<i or q<j, so row-major gives
             for (int j = 0; j < a.Ly; j++) { a.fill_cell(i, j); cells++; }   // the same cells (and is cache-friendly)
     }
+    a.end_corner(max_end);                           // VA:289-296
+    *n_cells = cells;
+    return PAGAN_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+// Same contract as pagan_dp_align (include/pagan_dp.h), computed on the CPU.
+// out->fill_ms / trace_ms hold CPU wall milliseconds.
+int oracle_dp_align(const pagan_graph *left, const pagan_graph *right, const pagan_model *model,
+                    const pagan_band *band, const pagan_opts *opts, pagan_result *out) {
+    if (!left || !right || !model || !out) return PAGAN_E_ARG;
+    std::memset(out, 0, sizeof(*out));
+    Aligner a;
     Cell max_end;
-    a.end_corner(&max_end);                          // VA:289-296
+    int64_t cells = 0;
+    auto t0 = std::chrono::steady_clock::now();
+    int rc = fill(a, left, right, model, band, opts, &max_end, &cells);
+    if (rc != PAGAN_OK) return rc;
     auto t1 = std::chrono::steady_clock::now();
 
     out->cells = cells;
@@ -395,6 +417,33 @@ int oracle_dp_align(const pagan_graph *left, const pagan_graph *right, const pag
     };
     collect(lused, &out->n_left_used, &out->left_used);
     collect(rused, &out->n_right_used, &out->right_used);
+    return PAGAN_OK;
+}
+
+// The matrices oracle_dp_align fills and drops, in their own layout: row-major over the band, row x owning columns
+// begin[x] .. end[x] as BandMatrix::init clamps them.  score[cells][3] and ties[cells][3] in the order X, Y, M;
+// ptr[cells][3][5] = matrix, x_ind, y_ind, x_edge_ind, y_edge_ind (matrix == -1: the cell has no predecessor).
+// `cells` is the caller's count of in-band cells and must be the oracle's own.
+int oracle_dp_matrices(const pagan_graph *left, const pagan_graph *right, const pagan_model *model,
+                       const pagan_band *band, const pagan_opts *opts, int64_t cells, double *score, int32_t *ptr,
+                       uint8_t *ties, int32_t *begin, int32_t *end) {
+    if (!left || !right || !model || !score || !ptr || !ties || !begin || !end) return PAGAN_E_ARG;
+    Aligner a;
+    Cell max_end;
+    int64_t filled = 0;
+    int rc = fill(a, left, right, model, band, opts, &max_end, &filled);
+    if (rc != PAGAN_OK) return rc;
+    if (cells != a.M.off[a.Lx] || cells != filled) return PAGAN_E_ARG;
+    const BandMatrix *mats[3] = {&a.X, &a.Y, &a.M};              // PAGAN_X_MAT, PAGAN_Y_MAT, PAGAN_M_MAT
+    for (int64_t c = 0; c < cells; c++)
+        for (int m = 0; m < 3; m++) {
+            const Cell &e = mats[m]->cells[(size_t)c];
+            score[3 * c + m] = e.score;
+            ties[3 * c + m] = e.ties;
+            int32_t *q = ptr + 15 * c + 5 * m;
+            q[0] = e.matrix; q[1] = e.x_ind; q[2] = e.y_ind; q[3] = e.x_edge_ind; q[4] = e.y_edge_ind;
+        }
+    for (int x = 0; x < a.Lx; x++) { begin[x] = a.M.begin[x]; end[x] = a.M.end[x]; }
     return PAGAN_OK;
 }
 

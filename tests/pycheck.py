@@ -400,6 +400,22 @@ class ViterbiAlignment:
                 break
         return stack[::-1]
 
+    # ---- the filled matrices, for a cell-by-cell comparison with another reading ----
+    def matrices(self):
+        """After align(): (score [cells, 3] float64, ptr [cells, 3, 5] int32) over the tunnel's cells in row-major order (row i
+        owns columns lo[i] .. hi[i]), the matrices in the order of Matrix_pt (X, Y, M), a pointer as matrix, x_ind, y_ind,
+        x_edge_ind, y_edge_ind -- the Matrix_pointer fields as they stand, untouched cells as the constructor leaves them."""
+        stores = (self.xgap, self.ygap, self.match)
+        cells = [(i, j) for i in range(self.Lx) for j in range(self.match.lo[i], self.match.hi[i] + 1)]
+        score = np.empty((len(cells), 3), np.float64)
+        ptr = np.empty((len(cells), 3, 5), np.int32)
+        for c, (i, j) in enumerate(cells):
+            for m, store in enumerate(stores):
+                e = store.at(i, j)
+                score[c, m] = e.score
+                ptr[c, m] = (e.matrix, e.x_ind, e.y_ind, e.x_edge_ind, e.y_edge_ind)
+        return score, ptr
+
     # ---- what the parent-graph builder consumes (create_ancestral_sequence, basic_alignment.cpp:73-171) ----
     def columns(self, path):
         cols, l_pos, r_pos = [], 1, 1

@@ -117,6 +117,7 @@ def test_ring_kernel_behind_its_switch(pg, oracle, monkeypatch):
 
 
 def test_pipe_and_ring_store_identical_scores(pg, monkeypatch):
+    """Kernel against kernel; tests/test_dp_matrices_gpu.py is where the ring kernel's own scores are checked against the oracle."""
     job = banded_job(5)
     scores = {}
     for kernel in ("ring", "pipe"):
@@ -151,7 +152,8 @@ def test_backpointer_pass_writes_what_the_comparing_kernels_write(pg, monkeypatc
     """pg_backptr re-derives every cell's back-pointers from the stored scores (the banded fill's hot loop stores scores
     only).  Reference for the words: the older ring kernel, which evaluates every candidate with compare-and-replace
     in the reference's order and writes its own back-pointers; every word of every cell must agree -- classes 0-5, dead
-    sites, far edges."""
+    sites, far edges.  The reference kernel itself -- and with it every word compared here -- is held against the oracle's
+    matrices in tests/test_dp_matrices_gpu.py."""
     job = banded_job(seed, **kw)
     monkeypatch.setenv("PAGAN_DP_COMPACT", "0")      # the device arrays are read back as the caller's matrices
     words = {}
@@ -168,6 +170,7 @@ def test_backpointer_pass_writes_what_the_comparing_kernels_write(pg, monkeypatc
 
 @pytest.mark.parametrize("flags", [0, abi.OPT_NO_TERMINAL_EDGES, abi.OPT_NO_REDUCED_TERMINAL_PEN])
 def test_backpointer_pass_under_the_option_bits(pg, oracle, monkeypatch, flags):
+    """Kernel against kernel; tests/test_dp_matrices_gpu.py is where the reference kernel's words are checked against the oracle."""
     job = banded_job(7, n=400, box=False)
     words = {}
     for mode, kernel in (("fill", "ring"), ("pass", "pipe")):
@@ -200,7 +203,8 @@ def test_back_pointers_are_written_behind_the_fill_and_equal_the_pass_afterwards
     """The follower workgroups of pg_fill_pipe write the back-pointers of the diagonals whose scores have landed while the
     fill is still running (poisoned arena: a chunk read too early would see NaN scores); pg_backptr afterwards only writes
     what they left.  Same words as with the followers switched off (PAGAN_DP_FOLLOW=0: pg_backptr writes everything), and
-    most chunks must have come from the followers."""
+    most chunks must have come from the followers.  Mode against mode; tests/test_dp_matrices_gpu.py holds the words of both
+    modes against the oracle's matrices."""
     jobs = [banded_job(s) for s in (0, 1, 3)] + [banded_job(2, max_span=8)]
     words, followed = {}, {}
     for mode in ("0", "1"):

@@ -83,6 +83,9 @@ def test_option_bits(pg, oracle, flags):
 
 
 def test_tiles_and_wavefront_store_identical_scores(pg, monkeypatch):
+    """Kernel against kernel.  (A full matrix of 260 x 240 has no more than 128 cells per diagonal on average, so the router gives
+    it to the banded kernel under either setting; tests/test_dp_matrices_gpu.py holds the tiled and the wavefront kernel's stored
+    matrices against the oracle, on jobs whose route it asserts.)"""
     left = synth.random_graph(260, 15, 31, p_extra=0.12, max_deg=4, max_span=50)
     right = synth.random_graph(240, 15, 32, p_extra=0.12, max_deg=4, max_span=50)
     job = (left, right, synth.random_model(15, 9), None)
