@@ -559,6 +559,86 @@ int     pagan_msa_write_fasta_ancestral(const pagan_msa *m, const char *path, in
 /* Borrowed views (valid until the next pagan_msa_ancestral or pagan_msa_destroy) of the kept best [(n-1) * L] and best_p. */
 int     pagan_msa_ancestral_best(const pagan_msa *m, const uint8_t **best, const float **best_p);
 
+/* ---- branch lengths by maximum likelihood: the derivatives of the log likelihood on the device, the fit on the host ---
+ * (csrc/dp_anc_brlen.inc, csrc/host_anc.cpp; DESIGN.md "Branch lengths by maximum likelihood").  The reference takes its branch
+ * lengths from external programs (bppdist, raxml, fasttree: src/utils/bppdist_tree.*, raxml_tree.*, fasttree_tree.*); none of
+ * that is restated.
+ *
+ * The model, the tree rules, the leaf encoding, P(t), L, O, m_b, W and the rescaling are exactly those of "ancestral states by
+ * marginal likelihood" above; the two passes are that section's, unchanged.
+ * Derivative matrices: D_r(t)[i][j] = sum_k U[i,k] root[k]^r exp(t root[k]) V[k,j], k outermost, in fp64, for r = 1, 2, NOT clamped
+ * (root[k]^2 is root[k] * root[k]; the factor root[k]^r exp(t root[k]) is formed first, then times U[i,k], then times V[k,j]).  D_0 is
+ * pagan_anc_pmatrix's P(t) itself, clamp included, so f_0 below is the likelihood the up pass computes.
+ * Per branch and column: c any node but the root, v its parent, b its sibling.  y_r[s] = sum_t D_r(t_c)[s][t] L_c[t], t ascending
+ * (a leaf's L_c: the indicator of its state set); f_r = sum_s W[s] y_r[s], s ascending, W[s] = O_v[s] m_b[s], O_root = pi.  The
+ * column is informative for c when has_data[c] is set, some leaf outside c's subtree holds data -- a flag carried down the tree:
+ * out_has[root] = false, out_has[c] = out_has[v] || has_data[b] -- and f_0 > 0.  An informative column contributes f_1 / f_0 to
+ * g1[c] and f_2 / f_0 - (f_1 / f_0)^2 to g2[c]; every other column contributes the exact 0.  informative[c] counts them.  L and O
+ * enter as the passes left them: the powers of two of the rescaling cancel in the quotients and are never applied.
+ * Order of the column sum: columns 64 q .. 64 q + 63 of the alignment are block q (columns past the end contribute 0).  Within a
+ * block x[i] is column 64 q + i's contribution, and for d = 32, 16, 8, 4, 2, 1 in turn x[i] = x[i] + x[i + d] for all i < d; the
+ * block's sum is x[0].  The blocks are then added left to right, sum = sum + block q for q = 0, 1, ..., from 0.  Chunks are
+ * multiples of 64 columns, so g1 and g2 are the same bytes from run to run and for every chunk size.
+ * The root: its two branches are one parameter tau = t_l + t_r (the pulley principle: the model is reversible).  The device
+ * reports the sums of both children; the fit uses the left child's for tau, keeps tau within [t_min, t_max] like any branch and
+ * splits it as t_l = tau p, t_r = tau - t_l with p = t_l / (t_l + t_r) of branch_in (1/2 where both are 0).
+ * Step rule (pagan_anc_branch_step): non-finite t, g1 or g2, or g1 == 0 && g2 == 0 (no information): t.  Otherwise s = t - g1 / g2
+ * where g2 < 0 (Newton), else 2 t where g1 > 0, else t / 2; s is kept within [t / 4, 4 t], then within [t_min, t_max].
+ * Fit: the lengths start from branch_in, every parameter kept within [t_min, t_max].  One up pass gives their loglik.  A round:
+ * the down pass, g1 / g2 of all branches at once, the step of all parameters at once.  Where max |t' - t| / max(t, t_min) over
+ * the parameters is <= tol the fit stops CONVERGED at t.  Otherwise the candidate t + alpha (t' - t) (alpha = 1: t' itself) gets
+ * an up pass of its own, alpha = 1, 1/2, ..., 1/32; the first whose loglik is not lower than the accepted one is accepted and
+ * the next round starts from it; none: STALLED at t.  After max_rounds rounds: MAX_ROUNDS.  The accepted logliks never decrease,
+ * and each is bit for bit pagan_anc_reconstruct's loglik at those lengths.
+ * The rows are uploaded and encoded once a call and their codes stay on the device; the partials and outside vectors are kept
+ * for one chunk (PAGAN_ANC_CHUNK_COLS as above).  Device, errors: as for pagan_anc_reconstruct -- no host path.               */
+#define PAGAN_ANC_FIT_CONVERGED  0
+#define PAGAN_ANC_FIT_MAX_ROUNDS 1
+#define PAGAN_ANC_FIT_STALLED    2
+typedef struct pagan_anc_fit_opts {
+    double  t_min, t_max;        /* bounds of every parameter: 1e-6, 10; 0 < t_min <= t_max                      */
+    double  tol;                 /* the relative change that counts as none: 1e-6; >= 0                          */
+    int32_t max_rounds;          /* 32; >= 0                                                                     */
+    int32_t reserved;            /* 0                                                                            */
+} pagan_anc_fit_opts;
+typedef struct pagan_anc_fit_info {
+    int32_t status;              /* PAGAN_ANC_FIT_*                                                              */
+    int32_t rounds;              /* derivative evaluations made                                                  */
+    int32_t up_passes;           /* up passes over the whole alignment, retries included                         */
+    int32_t chunks;              /* column chunks of one pass                                                    */
+    int32_t data_type, states;   /* as pagan_anc_info                                                            */
+    int64_t columns, chunk_cols;
+    int64_t device_bytes;        /* what the call allocated on the device                                        */
+    double  loglik_start, loglik_end;    /* of the lengths the fit started from and of those it returns          */
+    double  encode_ms, up_ms, down_ms, branch_ms, fold_ms;   /* device time of the stages, summed over the call  */
+    double  total_ms;            /* host wall time of the call: what exceeds the stages is the host's share      */
+} pagan_anc_fit_info;
+/* Host only.  D_order(t) [S * S] row-major, order 1 or 2, as defined above.  Returns S, or PAGAN_E_ARG as pagan_anc_pmatrix
+ * does and for another order.                                                                                              */
+int     pagan_anc_pmatrix_deriv(int32_t data_type, const float *base_freq, double t, int32_t order, double *D);
+/* Host only, plain arithmetic: the step rule above. */
+double  pagan_anc_branch_step(double t, double g1, double g2, double t_min, double t_max);
+/* One evaluation on the device: g1, g2 [2n-1] and informative [2n-1] by node id, the root's entries 0; loglik as
+ * pagan_anc_reconstruct's.  Any output may be NULL.  info: rounds 1, up_passes 1, status 0.                               */
+int     pagan_anc_branch_derivs(int32_t n_leaves, const int32_t *left, const int32_t *right, const double *branch,
+                                const char *const *rows, int32_t data_type, const float *base_freq, double *g1, double *g2,
+                                int64_t *informative, double *loglik, pagan_anc_fit_info *info);
+/* The fit.  opts NULL: the defaults; PAGAN_E_ARG for bounds, a tolerance or a round count outside the ranges above.
+ * branch_out [2n-1] (the root's entry 0).  loglik_hist [hist_cap] (may be NULL): the accepted logliks, the start first; the
+ * call returns how many there are (rounds accepted + 1; only the first hist_cap are written), or a negative code.             */
+int     pagan_anc_fit_branches(int32_t n_leaves, const int32_t *left, const int32_t *right, const double *branch_in,
+                               const char *const *rows, int32_t data_type, const float *base_freq, const pagan_anc_fit_opts *opts,
+                               double *branch_out, double *loglik_hist, int32_t hist_cap, pagan_anc_fit_info *info);
+/* Host only.  Device bytes of a pagan_anc_fit_branches or pagan_anc_branch_derivs call, under pagan_anc_predict_bytes' contract:
+ * exact when every branch length is distinct, never less than what a call allocates.                                          */
+int64_t pagan_anc_fit_predict_bytes(int32_t n_leaves, int64_t columns, int32_t data_type, int64_t chunk_cols);
+/* The fit over a finished walk: its leaf rows, its tree, for DNA its base frequencies as pagan_msa_ancestral takes them, starting
+ * from the lengths the walk aligned under.  branch_out [2n-1] by node id (may be NULL).  newick_out: the walk's topology and
+ * names with the fitted lengths printed %.17g; returns the bytes the string needs with its NUL (> cap: the string was not
+ * written, the rest was), or a negative code.  The walk itself is not changed.  PAGAN_E_ARG before the rows exist.            */
+int64_t pagan_msa_fit_branches(const pagan_msa *m, const pagan_anc_fit_opts *opts, double *branch_out, char *newick_out,
+                               int64_t cap, pagan_anc_fit_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -436,3 +437,5 @@ int pagan_anc_reconstruct(int32_t n_leaves, const int32_t *left, const int32_t *
 }
 
 } // extern "C"
+
+#include "dp_anc_brlen.inc"

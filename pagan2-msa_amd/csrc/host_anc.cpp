@@ -145,6 +145,41 @@ AncLayout::AncLayout(int64_t n, int S, int chars_per_col, int64_t C, int64_t mat
     total = c.cur;
 }
 
+void anc_pmatrix_deriv(const ModelFactory &mf, double t, int order, double *D) {
+    const int n = mf.char_as;
+    std::fill(D, D + (size_t)n * n, 0.0);
+    for (int k = 0; k < n; ++k) {                                  // anc_pmatrix's sum with root[k]^order in every term; no clamp
+        const double e1 = (order == 1 ? mf.root[k] : mf.root[k] * mf.root[k]) * std::exp(t * mf.root[k]);
+        for (int i = 0; i < n; ++i) {
+            const double e2 = mf.U[(size_t)i * n + k] * e1;
+            for (int j = 0; j < n; ++j) D[(size_t)i * n + j] += e2 * mf.V[(size_t)k * n + j];
+        }
+    }
+}
+
+AncFitLayout::AncFitLayout(int64_t n, int S, int chars_per_col, int64_t C, int64_t chunks, int64_t matrices) {
+    pgdev::Carve c{nullptr};
+    const size_t in = (size_t)(n - 1), cols = (size_t)C, nb = (size_t)(2 * n - 2), mat = (size_t)matrices * S * S * sizeof(double);
+    raw = c.skip((size_t)n * cols * chars_per_col);
+    table = c.skip(256 + 64);
+    codes = c.skip((size_t)chunks * n * cols);
+    has = c.skip((size_t)chunks * (2 * n - 1) * cols);
+    out_has = c.skip((size_t)chunks * (2 * n - 1) * cols);
+    part = c.skip(in * S * cols * sizeof(double));
+    outs = c.skip(in * S * cols * sizeof(double));
+    P = c.skip(mat); PT = c.skip(mat); D1T = c.skip(mat); D2T = c.skip(mat);
+    pi = c.skip((size_t)S * sizeof(double));
+    nodes = c.skip(5 * in * sizeof(int32_t));
+    branches = c.skip(5 * nb * sizeof(int32_t));
+    col_lik = c.skip(cols * sizeof(double));
+    col_exp = c.skip(cols * sizeof(int32_t));
+    best = c.skip(in * cols);
+    best_p = c.skip(in * cols * sizeof(float));
+    block_sums = c.skip(cols / 64 * nb * 3 * sizeof(double));
+    sums = c.skip(nb * 3 * sizeof(double));
+    total = c.cur;
+}
+
 } // namespace pagan
 
 using namespace pagan;
@@ -207,6 +242,37 @@ int64_t pagan_anc_predict_bytes(int32_t n_leaves, int64_t columns, int32_t data_
     if (!S || n_leaves < 2 || n_leaves > PAGAN_GUIDE_MAX_SEQS || columns < 0 || columns >= (1ll << 31)) return PAGAN_E_ARG;
     const int64_t C = anc_chunk_cols(n_leaves, columns, S, chunk_cols, AncSwitches::read());
     return (int64_t)AncLayout(n_leaves, S, data_type == 3 ? 3 : 1, C, 2 * (int64_t)n_leaves - 2, n_leaves - 1).total;
+}
+
+int pagan_anc_pmatrix_deriv(int32_t data_type, const float *base_freq, double t, int32_t order, double *D) {
+    const int S = anc_states(data_type);
+    if (!S || !std::isfinite(t) || t < 0 || (order != 1 && order != 2)) return PAGAN_E_ARG;
+    try {
+        ModelFactory mf;
+        if (anc_factory(data_type, base_freq, &mf) != PAGAN_OK) return PAGAN_E_INTERNAL;
+        if (D) anc_pmatrix_deriv(mf, t, order, D);
+        return S;
+    } catch (const std::bad_alloc &) {
+        return PAGAN_E_NOMEM;
+    }
+}
+
+double pagan_anc_branch_step(double t, double g1, double g2, double t_min, double t_max) {
+    if (!std::isfinite(t) || !std::isfinite(g1) || !std::isfinite(g2)) return t;
+    if (g1 == 0 && g2 == 0) return t;                              // no information
+    double s = g2 < 0 ? t - g1 / g2 : g1 > 0 ? 2 * t : t / 2;       // Newton where the curve is concave, else double or halve
+    if (s < t / 4) s = t / 4;
+    if (s > 4 * t) s = 4 * t;
+    if (s < t_min) s = t_min;
+    if (s > t_max) s = t_max;
+    return s;
+}
+
+int64_t pagan_anc_fit_predict_bytes(int32_t n_leaves, int64_t columns, int32_t data_type, int64_t chunk_cols) {
+    const int S = anc_states(data_type);
+    if (!S || n_leaves < 2 || n_leaves > PAGAN_GUIDE_MAX_SEQS || columns < 0 || columns >= (1ll << 31)) return PAGAN_E_ARG;
+    const int64_t C = anc_chunk_cols(n_leaves, columns, S, chunk_cols, AncSwitches::read());
+    return (int64_t)AncFitLayout(n_leaves, S, data_type == 3 ? 3 : 1, C, std::max<int64_t>(1, (columns + C - 1) / C), 2 * (int64_t)n_leaves - 2).total;
 }
 
 } // extern "C"

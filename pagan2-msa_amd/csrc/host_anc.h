@@ -41,6 +41,17 @@ struct AncLayout {
     AncLayout(int64_t n, int S, int chars_per_col, int64_t C, int64_t matrices, int64_t n_post);
 };
 
+// ---- branch lengths by maximum likelihood (include/pagan_host.h, "branch lengths by maximum likelihood") ----------------
+// D_order(t) [S * S] row-major, order 1 or 2: anc_pmatrix's sum with root[k]^order in every term, not clamped
+void anc_pmatrix_deriv(const ModelFactory &mf, double t, int order, double *D);
+
+// the device buffers of one fit or derivative call; the codes, has_data and out_has of all `chunks` chunks stay resident, the
+// rest is one chunk's
+struct AncFitLayout {
+    size_t raw, table, codes, has, out_has, part, outs, P, PT, D1T, D2T, pi, nodes, branches, col_lik, col_exp, best, best_p, block_sums, sums, total;
+    AncFitLayout(int64_t n, int S, int chars_per_col, int64_t C, int64_t chunks, int64_t matrices);
+};
+
 } // namespace pagan
 
 #endif

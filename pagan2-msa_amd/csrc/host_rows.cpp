@@ -300,6 +300,52 @@ int pagan_msa_ancestral_best(const pagan_msa *m, const uint8_t **best, const flo
     return PAGAN_OK;
 }
 
+// ---- branch lengths by maximum likelihood (csrc/dp_anc_brlen.inc) over the finished walk ----------------------------------
+// pagan_msa_ancestral's inputs -- the walk's tree in its public ids, the lengths it aligned under, its rows and base
+// frequencies -- and a Newick of the same topology and names with the fitted lengths.
+int64_t pagan_msa_fit_branches(const pagan_msa *m, const pagan_anc_fit_opts *opts, double *branch_out, char *newick_out, int64_t cap,
+                               pagan_anc_fit_info *info) {
+    if (!m || !m->aligned || (cap > 0 && !newick_out)) return PAGAN_E_ARG;
+    if (const int rc = rows_of(m)) return rc;
+    try {
+        const int n = m->n_leaves;
+        std::vector<int32_t> left(n - 1), right(n - 1);
+        std::vector<double> branch((size_t)2 * n - 1, 0.0), fitted((size_t)2 * n - 1, 0.0);
+        std::vector<const char *> rows(n);
+        for (int k = 0; k < n - 1; ++k) {
+            const TreeNode &t = m->tree[m->tree_of_id[n + k]];
+            left[k] = m->id_of_tree[t.left]; right[k] = m->id_of_tree[t.right];
+        }
+        for (int id = 0; id < 2 * n - 1; ++id) branch[id] = m->tree[m->tree_of_id[id]].dist;
+        for (int k = 0; k < n; ++k) rows[k] = m->rows[k].c_str();
+        float bf[4] = {0.25f, 0.25f, 0.25f, 0.25f};
+        if (m->mf.type == kDna) for (int k = 0; k < 4; ++k) bf[k] = (float)m->mf.pi[k];
+        const int rc = pagan_anc_fit_branches(n, left.data(), right.data(), branch.data(), rows.data(), pagan_msa_data_type(m), bf, opts,
+                                              fitted.data(), nullptr, 0, info);
+        if (rc < 0) return rc;
+        if (branch_out) std::copy(fitted.begin(), fitted.end(), branch_out);
+        // the tree in post-order without recursion: (tree index, children written?)
+        std::string out;
+        char num[40];
+        std::vector<std::pair<int, int>> stack{{m->root, 0}};
+        while (!stack.empty()) {
+            auto &[t, stage] = stack.back();
+            const TreeNode &node = m->tree[t];
+            if (node.left >= 0 && stage == 0) { out += '('; stage = 1; stack.push_back({node.left, 0}); continue; }
+            if (node.left >= 0 && stage == 1) { out += ','; stage = 2; stack.push_back({node.right, 0}); continue; }
+            if (node.left >= 0) out += ')'; else out += node.name;
+            if (t != m->root) { std::snprintf(num, sizeof(num), ":%.17g", fitted[m->id_of_tree[t]]); out += num; }
+            stack.pop_back();
+        }
+        out += ';';
+        const int64_t need = (int64_t)out.size() + 1;
+        if (need <= cap) std::memcpy(newick_out, out.c_str(), (size_t)need);
+        return need;
+    } catch (const std::bad_alloc &) {
+        return PAGAN_E_NOMEM;
+    }
+}
+
 void *pagan_msa_node_graph(const pagan_msa *m, int32_t node) {
     if (!m || node < 0 || node >= (int)m->graph.size()) return nullptr;
     if (!m->graph[node] && m->done[node]) {                        // (an imported node's graph: built when somebody asks for it)

@@ -74,6 +74,18 @@ class CAncInfo(C.Structure):
                 ("encode_ms", C.c_double), ("up_ms", C.c_double), ("down_ms", C.c_double)]
 
 
+class CAncFitOpts(C.Structure):
+    _fields_ = [("t_min", C.c_double), ("t_max", C.c_double), ("tol", C.c_double), ("max_rounds", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CAncFitInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("rounds", C.c_int32), ("up_passes", C.c_int32), ("chunks", C.c_int32),
+                ("data_type", C.c_int32), ("states", C.c_int32), ("columns", C.c_int64), ("chunk_cols", C.c_int64),
+                ("device_bytes", C.c_int64), ("loglik_start", C.c_double), ("loglik_end", C.c_double),
+                ("encode_ms", C.c_double), ("up_ms", C.c_double), ("down_ms", C.c_double), ("branch_ms", C.c_double),
+                ("fold_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 GUIDE_MAX_SEQS = 65536
 GUIDE_PAIR_CHUNK = 64
 ALN_TILE = 64
@@ -82,7 +94,7 @@ ALN_SPLIT_WORDS = 8
 # C struct name -> mirror, for every struct the two headers declare with a body
 STRUCTS = dict(abi.STRUCTS, pagan_msa_opts=CMsaOpts, pagan_node_info=CNodeInfo, pagan_msa_timing=CTiming,
                pagan_pileup_opts=CPileupOpts, pagan_pileup_step=CPileupStep, pagan_guide_info=CGuideInfo,
-               pagan_aln_info=CAlnInfo, pagan_anc_info=CAncInfo)
+               pagan_aln_info=CAlnInfo, pagan_anc_info=CAncInfo, pagan_anc_fit_opts=CAncFitOpts, pagan_anc_fit_info=CAncFitInfo)
 
 # Every entry point of include/pagan_host.h in the header's order: name -> (restype, (argtypes...)).  A new entry point is
 # one line here; tests/test_abi_cpu.py holds the table against the header's prototypes.
@@ -185,6 +197,12 @@ PROTOTYPES = {
     "pagan_msa_ancestral_support": (cint, (vp, i32, _f32p)),
     "pagan_msa_write_fasta_ancestral": (cint, (vp, cp, i32)),
     "pagan_msa_ancestral_best": (cint, (vp, C.POINTER(_u8p), C.POINTER(_f32p))),
+    "pagan_anc_pmatrix_deriv": (cint, (i32, _f32p, f64, i32, _f64p)),
+    "pagan_anc_branch_step": (f64, (f64, f64, f64, f64, f64)),
+    "pagan_anc_branch_derivs": (cint, (i32, _i32p, _i32p, _f64p, cpp, i32, _f32p, _f64p, _f64p, _i64p, _f64p, C.POINTER(CAncFitInfo))),
+    "pagan_anc_fit_branches": (cint, (i32, _i32p, _i32p, _f64p, cpp, i32, _f32p, C.POINTER(CAncFitOpts), _f64p, _f64p, i32, C.POINTER(CAncFitInfo))),
+    "pagan_anc_fit_predict_bytes": (i64, (i32, i64, i32, i64)),
+    "pagan_msa_fit_branches": (i64, (vp, C.POINTER(CAncFitOpts), _f64p, cp, i64, C.POINTER(CAncFitInfo))),
 }
 HOST_EXPORTED = list(PROTOTYPES)
 
@@ -645,6 +663,74 @@ def anc_reconstruct(left, right, branch, rows, data_type=0, base_freq=None, post
             "info": struct_dict(ci)}
 
 
+ANC_FIT_CONVERGED, ANC_FIT_MAX_ROUNDS, ANC_FIT_STALLED = 0, 1, 2
+ANC_FIT_STATUS = {ANC_FIT_CONVERGED: "converged", ANC_FIT_MAX_ROUNDS: "max_rounds", ANC_FIT_STALLED: "stalled"}
+
+
+def anc_pmatrix_deriv(data_type, t, order, base_freq=None):
+    """pagan_anc_pmatrix_deriv (host only): D_order(t) [S, S], order 1 or 2 -- the eigen sum of anc_pmatrix with root^order in
+    every term, not clamped (include/pagan_host.h, "branch lengths by maximum likelihood")."""
+    S = ANC_STATES.get(int(data_type), 1)
+    D = np.zeros((S, S), np.float64)
+    _keep, bfp = _base_freq(base_freq)
+    check(_lib().pagan_anc_pmatrix_deriv(int(data_type), bfp, float(t), int(order), _dp(D)), "pagan_anc_pmatrix_deriv")
+    return D
+
+
+def anc_branch_step(t, g1, g2, t_min=1e-6, t_max=10.0):
+    """pagan_anc_branch_step (host only): the fit's step rule for one branch."""
+    return float(_lib().pagan_anc_branch_step(float(t), float(g1), float(g2), float(t_min), float(t_max)))
+
+
+def _anc_tree_args(left, right, branch, rows):
+    le, ri = np.ascontiguousarray(left, np.int32), np.ascontiguousarray(right, np.int32)
+    br = np.ascontiguousarray(branch, np.float64)
+    n = len(rows)
+    if len(le) != n - 1 or len(ri) != n - 1 or len(br) != 2 * n - 1:
+        raise ValueError("left, right hold n - 1 entries and branch 2 n - 1")
+    return n, le, ri, br
+
+
+def _anc_fit_opts(t_min, t_max, tol, max_rounds):
+    return CAncFitOpts(float(t_min), float(t_max), float(tol), int(max_rounds), 0)
+
+
+def _anc_fit_info(ci):
+    info = struct_dict(ci)
+    info["status"] = ANC_FIT_STATUS.get(info["status"], info["status"])
+    return info
+
+
+def anc_branch_derivs(left, right, branch, rows, data_type=0, base_freq=None):
+    """pagan_anc_branch_derivs: one evaluation on the current device.  Returns a dict: g1, g2 (float64), informative (int64)
+    [2 n - 1] by node id, the root's entries 0; loglik (anc_reconstruct's); info."""
+    n, le, ri, br = _anc_tree_args(left, right, branch, rows)
+    _keep, bfp = _base_freq(base_freq)
+    g1, g2, inf = np.zeros(2 * n - 1, np.float64), np.zeros(2 * n - 1, np.float64), np.zeros(2 * n - 1, np.int64)
+    loglik, ci = C.c_double(0.0), CAncFitInfo()
+    check(_lib().pagan_anc_branch_derivs(n, _ip(le), _ip(ri), _dp(br), _c_strings(rows), int(data_type), bfp, _dp(g1), _dp(g2),
+                                         inf.ctypes.data_as(_i64p), C.byref(loglik), C.byref(ci)), "pagan_anc_branch_derivs")
+    return {"g1": g1, "g2": g2, "informative": inf, "loglik": loglik.value, "info": _anc_fit_info(ci)}
+
+
+def anc_fit_branches(left, right, branch, rows, data_type=0, base_freq=None, t_min=1e-6, t_max=10.0, tol=1e-6, max_rounds=32):
+    """pagan_anc_fit_branches: the branch lengths of largest likelihood for the rows on the tree, from `branch`, on the current
+    device.  Returns a dict: branch [2 n - 1] (the root's entry 0), loglik (the accepted log likelihoods, the start first: never
+    decreasing), info (status as "converged" / "max_rounds" / "stalled", rounds, up_passes, loglik_start, loglik_end, ...)."""
+    n, le, ri, br = _anc_tree_args(left, right, branch, rows)
+    _keep, bfp = _base_freq(base_freq)
+    o = _anc_fit_opts(t_min, t_max, tol, max_rounds)
+    out, hist, ci = np.zeros(2 * n - 1, np.float64), np.zeros(int(max(max_rounds, 0)) + 1, np.float64), CAncFitInfo()
+    k = check(_lib().pagan_anc_fit_branches(n, _ip(le), _ip(ri), _dp(br), _c_strings(rows), int(data_type), bfp, C.byref(o), _dp(out),
+                                            _dp(hist), len(hist), C.byref(ci)), "pagan_anc_fit_branches")
+    return {"branch": out, "loglik": hist[:k].copy(), "info": _anc_fit_info(ci)}
+
+
+def anc_fit_predict_bytes(n_leaves, columns, data_type, chunk_cols=0):
+    """pagan_anc_fit_predict_bytes (host only): device bytes anc_fit_branches or anc_branch_derivs allocates at most."""
+    return check(_lib().pagan_anc_fit_predict_bytes(int(n_leaves), int(columns), int(data_type), int(chunk_cols)), "pagan_anc_fit_predict_bytes")
+
+
 class Ancestral:
     """What Msa.ancestral() leaves: loglik, col_loglik [L], best / best_p [n - 1, L], info, and the overlaid rows."""
 
@@ -690,28 +776,83 @@ def differing_clades(newick_a, newick_b):
     return len(clades(newick_a) - clades(newick_b))
 
 
-def align_refined(names, seqs, rounds=1, newick=None, **msa_kwargs):
+def newick_arrays(names, newick):
+    """(left, right, branch) of a rooted binary Newick in the walk's ids: leaf k is names[k], the internal nodes n, n + 1, ... in the
+    order their brackets close, branch [2 n - 1] the length above every node as written (the root's 0)."""
+    from . import synth
+    n = len(names)
+    index = {name: k for k, name in enumerate(names)}
+    left, right, branch = [], [], [0.0] * (2 * n - 1)
+
+    def visit(t):
+        if t[0] == "leaf":
+            v = index[t[1]]
+        else:
+            a, b = visit(t[1]), visit(t[2])
+            v = n + len(left)
+            left.append(a)
+            right.append(b)
+        branch[v] = float(t[-1])
+        return v
+    if visit(synth.parse_newick(newick)) != 2 * n - 2:
+        raise ValueError("the tree does not hold every name once")
+    branch[-1] = 0.0
+    return left, right, branch
+
+
+def arrays_newick(names, left, right, branch):
+    """newick_arrays' inverse: the tree as a Newick string, the lengths printed %.17g (the root's is not printed)."""
+    n = len(names)
+    text = list(names) + [None] * (n - 1)
+    for k in range(n - 1):
+        text[n + k] = "(%s:%.17g,%s:%.17g)" % (text[left[k]], branch[left[k]], text[right[k]], branch[right[k]])
+    return text[2 * n - 2] + ";"
+
+
+def dna_base_frequencies(seqs):
+    """The walk's empirical base frequencies of DNA sequences: the counts of A, C, G, T as floats, each over their float sum."""
+    counts = [np.float32(min(sum(s.count(c) for s in seqs), 1 << 24)) for c in "ACGT"]
+    total = counts[0] + counts[1] + counts[2] + counts[3]
+    return [c / total for c in counts]
+
+
+def align_refined(names, seqs, rounds=1, newick=None, branch_lengths=None, **msa_kwargs):
     """Align, read the guide tree off the alignment, align again on it: walks once exactly as Msa(names, seqs, newick,
     **msa_kwargs).align() does, then up to `rounds` times takes T = msa.alignment_tree() and walks again on T, stopping when
     T is the tree just walked (the walk is deterministic: a fixpoint).  Returns the last Msa (the earlier ones are closed) with
     .history: one dict per walk -- newick, alignment_length, score (the sum of the node scores) and changed_clades (the clades
-    of its tree the previous walk's tree does not have; 0 for the first)."""
+    of its tree the previous walk's tree does not have; 0 for the first).
+    branch_lengths="ml": T keeps alignment_tree()'s topology and takes its lengths from anc_fit_branches over the current
+    alignment's rows, started from alignment_tree()'s lengths (DNA: under the walk's base frequencies); every history entry
+    gains loglik (Msa.ancestral()'s, of the walk's alignment under the lengths it aligned with) and fit (status, rounds,
+    loglik_start, loglik_end of the fit that made its tree; None for the first walk)."""
+    if branch_lengths not in (None, "ml"):
+        raise ValueError("branch_lengths is None or 'ml'")
+    ml = branch_lengths == "ml"
     msa = Msa(names, seqs, newick, **msa_kwargs).align()
     history = []
 
-    def record(m, before):
+    def record(m, before, fit=None):
         history.append({"newick": m.newick, "alignment_length": len(m.alignment()[0]),
                         "score": float(sum(m.node_info(k).score for k in range(m.n_internal))),
                         "changed_clades": 0 if before is None else differing_clades(m.newick, before)})
+        if ml:
+            history[-1]["loglik"] = m.ancestral().loglik
+            history[-1]["fit"] = None if fit is None else {k: fit["info"][k] for k in ("status", "rounds", "loglik_start", "loglik_end")}
     record(msa, None)
     for _ in range(int(rounds)):
-        tree = msa.alignment_tree()
+        tree, fit = msa.alignment_tree(), None
+        if ml:
+            left, right, branch = newick_arrays(list(names), tree)
+            data_type = msa.data_type
+            fit = anc_fit_branches(left, right, branch, msa.alignment(), data_type, dna_base_frequencies(seqs) if data_type == 1 else None)
+            tree = arrays_newick(list(names), left, right, fit["branch"])
         if tree == msa.newick:
             break
         before = msa.newick
         msa.close()
         msa = Msa(names, seqs, tree, **msa_kwargs).align()
-        record(msa, before)
+        record(msa, before, fit)
     msa.history = history
     return msa
 
@@ -1017,6 +1158,16 @@ class Msa(Handle):
         else:
             best, best_p = np.zeros(shape, np.uint8), np.zeros(shape, np.float32)
         return Ancestral(self, loglik.value, col[:L].copy(), best, best_p, struct_dict(ci))
+
+    def fit_branches(self, t_min=1e-6, t_max=10.0, tol=1e-6, max_rounds=32):
+        """pagan_msa_fit_branches: the branch lengths of largest likelihood for the finished walk's alignment on its tree, from the
+        lengths it aligned under, on the current device.  Returns a dict: branch [2 n - 1] by node id, newick (the walk's
+        topology and names with the fitted lengths), info (anc_fit_branches').  The walk itself is not changed."""
+        o, ci = _anc_fit_opts(t_min, t_max, tol, max_rounds), CAncFitInfo()
+        out = np.zeros(2 * self.n - 1, np.float64)
+        newick = _newick_call(lambda buf, cap: self._L.pagan_msa_fit_branches(self._h, C.byref(o), _dp(out), buf, cap, C.byref(ci)),
+                              "pagan_msa_fit_branches", self.names)
+        return {"branch": out, "newick": newick, "info": _anc_fit_info(ci)}
 
     def alignment_all(self):
         """Rows of every node: leaves 0..n-1, then the internal nodes (ancestors) in alignment order."""
