@@ -144,7 +144,8 @@ def by_definition(left, right, branch, rows, base_freq):
 
 
 def pruning(left, right, branch, rows, data_type, base_freq=None, down=True):
-    """Any tree, any data type.  The same dict as by_definition (post is None with down=False)."""
+    """Any tree, any data type.  The same dict as by_definition (post is None with down=False), and "top" [n - 1][L]: the largest
+    entry of every internal node's partial, not rescaled (what the header's exponents follow from: exponents())."""
     n, S = len(rows), STATES[data_type]
     mats, pi = _model(branch, data_type, base_freq)
     sets = [leaf_sets(r, data_type) for r in rows]
@@ -170,6 +171,7 @@ def pruning(left, right, branch, rows, data_type, base_freq=None, down=True):
 
     for k in range(n - 1):
         part[n + k] = message(left[k]) * message(right[k])
+    top = [list(part[n + k].max(axis=0)) for k in range(n - 1)]
     root = 2 * n - 2
     lik = []
     for col in range(L):
@@ -178,7 +180,7 @@ def pruning(left, right, branch, rows, data_type, base_freq=None, down=True):
             total += pi[s] * part[root][s, col]
         lik.append(total if has[root, col] else D1)
     if not down:
-        return {"lik": lik, "post": None, "has_data": has}
+        return {"lik": lik, "post": None, "has_data": has, "top": top}
     outs = {root: np.array([[pi[s]] * L for s in range(S)], dtype=object)}
     post = [None] * (n - 1)
     for k in range(n - 2, -1, -1):
@@ -189,7 +191,40 @@ def pruning(left, right, branch, rows, data_type, base_freq=None, down=True):
             if c >= n:
                 W = outs[v] * message(b)
                 outs[c] = mats[float(branch[c])].T.dot(W)
-    return {"lik": lik, "post": post, "has_data": has}
+    return {"lik": lik, "post": post, "has_data": has, "top": top}
+
+
+def binary_exponent(x):
+    """(e, exact) for a Decimal x > 0: 2^(e - 1) <= x < 2^e (frexp's exponent), and whether x is that power of two itself."""
+    e = int((x.ln() / Decimal(2).ln()).to_integral_value(rounding="ROUND_FLOOR")) + 1
+    while x < Decimal(2) ** (e - 1):
+        e -= 1
+    while x >= Decimal(2) ** e:
+        e += 1
+    return e, x == Decimal(2) ** (e - 1)
+
+
+def exponents(left, right, reading, tol):
+    """(col_exp [L], safe [L]) by the header's rule from the partials no one rescaled: the vector of a node with data below it is
+    multiplied by 2^-e, e the binary exponent of its largest entry, and powers of two are exact, so the exponents of a subtree
+    add up to the binary exponent of the unscaled partial's largest entry (where that is 0, or the node has no data, the node
+    adds 0 to its children's sums).  safe: no largest entry on the way lies within tol of a power of two without being one, so
+    that a rounding error within tol cannot have moved an exponent."""
+    n, has, top = len(left) + 1, reading["has_data"], reading["top"]
+    L = len(top[0])
+    E = [[0] * L for _ in range(2 * n - 1)]
+    safe = [True] * L
+    for k in range(n - 1):
+        for col in range(L):
+            m = top[k][col]
+            if has[n + k, col] and m > 0:
+                e, exact = binary_exponent(m)
+                E[n + k][col] = e
+                if not exact and min(m - Decimal(2) ** (e - 1), Decimal(2) ** e - m) <= Decimal(tol) * m:
+                    safe[col] = False
+            else:
+                E[n + k][col] = E[left[k]][col] + E[right[k]][col]
+    return E[2 * n - 2], safe
 
 
 def best_of(post_col):

@@ -173,40 +173,67 @@ def full_step(left, right, branch, g1, g2, t_min=T_MIN, t_max=T_MAX):
     return stepped, tau, tau_step, moved
 
 
-def fit(left, right, branch_in, rows, data_type, base_freq=None, t_min=T_MIN, t_max=T_MAX, tol=TOL, max_rounds=MAX_ROUNDS):
-    """The header's fit with the reading's own g1, g2 and loglik.  Returns dict(branch, loglik (the accepted ones), status, rounds)."""
-    free, rl, rr = parameters(left, right, branch_in)
-
-    def bounded(x):
-        return min(max(x, t_min), t_max)
+def proportion(left, right, branch_in):
+    """p: the root's left branch over the sum of its two in branch_in, 1/2 where both are 0."""
+    rl, rr = left[-1], right[-1]
     tau_in = branch_in[rl] + branch_in[rr]
-    p = branch_in[rl] / tau_in if tau_in > 0 else 0.5
+    return branch_in[rl] / tau_in if tau_in > 0 else 0.5
 
-    def split(tau, to):
-        to[rl] = tau * p
-        to[rr] = tau - to[rl]
+
+def start(left, right, branch_in, t_min=T_MIN, t_max=T_MAX):
+    """The lengths the fit starts from, on Python floats: every free branch kept within [t_min, t_max]; tau likewise, and where that
+    moved it, split as t_l = tau p, t_r = tau - t_l; the root's own entry 0."""
+    free, rl, rr = parameters(left, right, branch_in)
     t = [float(x) for x in branch_in]
     t[-1] = 0.0
     for c in free:
-        t[c] = bounded(t[c])
-    if bounded(tau_in) != tau_in:
-        split(bounded(tau_in), t)
+        t[c] = min(max(t[c], t_min), t_max)
+    tau_in = branch_in[rl] + branch_in[rr]
+    tau = min(max(tau_in, t_min), t_max)
+    if tau != tau_in:
+        t[rl] = tau * proportion(left, right, branch_in)
+        t[rr] = tau - t[rl]
+    return t
+
+
+def candidate(left, right, t, stepped, tau, tau_step, alpha, p, t_min=T_MIN, t_max=T_MAX):
+    """The header's candidate t + alpha (t' - t) on Python floats (alpha = 1: t' itself), every parameter kept within its bounds,
+    tau split by p."""
+    free, rl, rr = parameters(left, right, t)
+
+    def bounded(x):
+        return min(max(x, t_min), t_max)
+    cand = list(t)
+    for c in free:
+        cand[c] = stepped[c] if alpha == 1.0 else bounded(t[c] + alpha * (stepped[c] - t[c]))
+    new_tau = tau_step if alpha == 1.0 else bounded(tau + alpha * (tau_step - tau))
+    cand[rl] = new_tau * p
+    cand[rr] = new_tau - cand[rl]
+    return cand
+
+
+def fit(left, right, branch_in, rows, data_type, base_freq=None, t_min=T_MIN, t_max=T_MAX, tol=TOL, max_rounds=MAX_ROUNDS):
+    """The header's fit with the reading's own g1, g2 and loglik.  Returns dict(branch, loglik (the accepted ones), status, rounds,
+    decisions): decisions[r] lists round r's candidates in the order they were tried as (alpha, the candidate's log likelihood
+    minus the accepted one it was held against); the last of a round is the accepted one unless the round stalled, and a round
+    that converged has none."""
+    p = proportion(left, right, branch_in)
+    t = start(left, right, branch_in, t_min, t_max)
     ll = evaluate(left, right, t, rows, data_type, base_freq, derivs=False)["loglik"]
-    hist, status, rounds = [ll], "max_rounds", 0
+    hist, status, rounds, decisions = [ll], "max_rounds", 0, []
     for _ in range(max_rounds):
         r = evaluate(left, right, t, rows, data_type, base_freq)
         rounds += 1
         stepped, tau, tau_step, moved = full_step(left, right, t, r["g1"], r["g2"], t_min, t_max)
+        decisions.append([])
         if moved <= tol:
             status = "converged"
             break
         alpha, accepted = 1.0, False
         for _ in range(6):
-            cand = list(t)
-            for c in free:
-                cand[c] = stepped[c] if alpha == 1.0 else bounded(t[c] + alpha * (stepped[c] - t[c]))
-            split(tau_step if alpha == 1.0 else bounded(tau + alpha * (tau_step - tau)), cand)
+            cand = candidate(left, right, t, stepped, tau, tau_step, alpha, p, t_min, t_max)
             llc = evaluate(left, right, cand, rows, data_type, base_freq, derivs=False)["loglik"]
+            decisions[-1].append((alpha, float(llc - ll)))
             if not llc < ll:
                 accepted = True
                 break
@@ -216,7 +243,7 @@ def fit(left, right, branch_in, rows, data_type, base_freq=None, t_min=T_MIN, t_
             break
         t, ll = cand, llc
         hist.append(ll)
-    return {"branch": t, "loglik": hist, "status": status, "rounds": rounds}
+    return {"branch": t, "loglik": hist, "status": status, "rounds": rounds, "decisions": decisions}
 
 
 # ---- rows simulated on a tree, and the cases the CPU and the GPU tests share ---------------------------------------------------------
@@ -252,6 +279,34 @@ def _named(name):
         L = int(arg)
         left, right, branch = A.random_tree(8, np.random.default_rng(730 + L))
         rows = A.random_rows(8, L, 1, 740 + L, share=0.2)
+    elif kind == "codon" and arg == "tree":              # the four-wave kernel on a random tree: leaves beside internal siblings
+        left, right, branch = A.random_tree(5, np.random.default_rng(752))
+        rows, t, bf = A.random_rows(5, 65, 3, 753), 3, None
+    elif kind == "onesided" and arg:                     # the construction below on the four-wave kernels, 20 columns
+        t, bf = {"protein": 2, "codon": 3}[arg], None
+        left, right, branch = A.balanced4([0.05, 0.12, 0.3, 0.08, 0.11, 0.21])
+        gap = "---" if t == 3 else "-"
+        width = len(gap)
+        text = A.random_rows(4, 20, t, 754 + t, share=0.1)
+        rows = [[r[i:i + width] for i in range(0, len(r), width)] for r in text]
+        for col in range(0, 20, 5):
+            rows[0][col] = rows[1][col] = gap            # nothing under node 4
+        for col in range(3, 20, 7):
+            rows[0][col] = rows[1][col] = rows[2][col] = gap         # a single leaf holds data
+        for col in (10, 11):
+            for r in range(4):
+                rows[r][col] = gap
+        rows = ["".join(r) for r in rows]
+    elif kind == "sim" and arg in ("protein", "codon"):  # the fit on the four-wave kernels; a gap in every ninth column
+        t, bf = {"protein": 2, "codon": 3}[arg], None
+        n = {2: 4, 3: 3}[t]
+        tree_seed, rows_seed = {2: (802, 812), 3: (833, 843)}[t]     # (803, 813 for codons converge as well, in 16 rounds)
+        left, right, branch = A.random_tree(n, np.random.default_rng(tree_seed), lo=0.03, hi=0.4)
+        width = 3 if t == 3 else 1
+        rows = [list(r) for r in simulate(left, right, branch, 65, t, None, rows_seed)]
+        for col in range(0, 65, 9):
+            rows[(col // 9) % n][col * width:(col + 1) * width] = "-" * width
+        rows = ["".join(r) for r in rows]
     elif kind == "onesided":                             # columns with data on one side of the root only, and all-missing columns
         left, right, branch = A.balanced4([0.05, 0.12, 0.3, 0.08, 0.11, 0.21])
         rows = [list(r) for r in A.random_rows(4, 70, 1, 750, share=0.1)]
@@ -274,6 +329,10 @@ def _named(name):
         left, right, branch = [0, 2, 4], [1, 3, 5], [0.1, 0.08, 0.15, 0.2, 0.12, 0.09, 0.0]
         rows = simulate(left, right, branch, 65, 1, bf, 790)
         rows[1] = rows[0]
+    elif kind == "unrelated" and arg == "protein":       # the same on the four-wave kernels: the reading halves a step in round 9
+        t, bf = 2, None
+        left, right, branch = A.random_tree(4, np.random.default_rng(799))
+        rows = A.random_rows(4, 64, 2, 800, share=0.0)
     elif kind == "unrelated":                            # random rows: no tree behind them
         left, right, branch = A.random_tree(4, np.random.default_rng(795))
         rows = A.random_rows(4, 64, 1, 796, share=0.0)
@@ -299,14 +358,33 @@ def fitted(name):
     return fit(c["left"], c["right"], c["branch"], c["rows"], c["data_type"], c["base_freq"])
 
 
+def kinds(left, right):
+    """The kinds of branch in a tree: {(the child is internal, its sibling is internal, its parent is the root)}."""
+    n = len(left) + 1
+    out = set()
+    for k in range(n - 1):
+        for a, b in ((left[k], right[k]), (right[k], left[k])):
+            out.add((a >= n, b >= n, k == n - 2))
+    return out
+
+
 EDGE_COLUMNS = (1, 63, 64, 65, 130)
 DERIV_CASES = (["pair:%d" % L for L in EDGE_COLUMNS] + ["three:%d" % L for L in EDGE_COLUMNS] + ["eight:%d" % L for L in EDGE_COLUMNS]
-               + ["onesided", "lengths", "impossible", "zero", "long", "balanced:protein", "balanced:codon", "deep:dna"])
+               + ["onesided", "lengths", "impossible", "zero", "long", "balanced:protein", "balanced:codon", "deep:dna"]
+               # the four-wave pa_branch on every kind of branch, on the informative rule, zero lengths and impossible columns
+               + ["protein", "codon", "chunks:protein", "zero:protein", "zero:codon", "impossible:protein", "impossible:codon",
+                  "codon:tree", "onesided:protein", "onesided:codon"])
+FOUR_WAVE_CASES = {2: ["balanced:protein", "protein", "chunks:protein", "zero:protein", "impossible:protein", "onesided:protein"],
+                   3: ["balanced:codon", "codon", "zero:codon", "impossible:codon", "codon:tree", "onesided:codon"]}
 # The fit is a Jacobi iteration: on a tree with a short internal branch between long ones the steps of neighbouring branches
 # overshoot in turn and the error shrinks by about 0.9 a round, so that 32 rounds are too few from n = 6 on (DESIGN.md, "Branch
-# lengths by maximum likelihood").  The cases fitted here converge in 16 to 19 rounds.
-SIM_CASES = ["sim:3", "sim:5"]
+# lengths by maximum likelihood").  The DNA cases fitted here converge in 16 to 19 rounds; sim:protein (S = 20, 4 leaves) in 13 and
+# sim:codon (S = 61, 3 leaves) in 10 of the reading's rounds, no step halved (2 s and 7 s of the reading on one core).
+SIM_CASES = ["sim:3", "sim:5", "sim:protein", "sim:codon"]
 FIT_CASES = SIM_CASES + ["pair:65", "pair:130", "twins"]
 # Rows with no tree behind them: the surface is flat and far from concave at lengths above 1, branches run into t_max, and the
 # iteration need not settle in 32 rounds.  What holds for them is the contract alone: bounds kept, log likelihoods never falling.
 UNRELATED_CASES = ["unrelated", "three:130"]
+# {case: rounds}: the fits followed round by round (tests/test_brlen_gpu.py); within these rounds the reading halves steps and
+# decides every candidate by a margin of 1e-6 or more (tests/test_brlen_cpu.py)
+LINE_SEARCH_CASES = {"unrelated": 16, "unrelated:protein": 12}

@@ -147,6 +147,71 @@ def test_the_readings_fit(name):
     assert abs(f["branch"][rl] / tau - c["branch"][rl] / tau_in) <= 1e-15
 
 
+def test_the_cases_reach_the_line_search():
+    """A condition on the input of tests/test_brlen_gpu.py's round-by-round test, checked with the reading alone: within 16 rounds
+    `unrelated` (4 leaves, 64 columns, DNA) halves a step in at least four rounds and twice in at least one, and no candidate,
+    rejected or accepted, comes within 1e-6 of the log likelihood it is held against -- at least 1000 times columns *
+    pycheck_anc.tolerance, the bound on the device's log likelihood error, so the device decides as the reading does.  None of the
+    other fitted cases ever halves (which is why this one is there)."""
+    c = B.case("unrelated")
+    assert len(c["rows"]) == 4 and len(c["rows"][0]) == 64 and c["data_type"] == 1
+    assert 1e-6 >= 1000 * 64 * A.tolerance(c["left"], c["right"], 4)
+    f = B.fit(c["left"], c["right"], c["branch"], c["rows"], c["data_type"], c["base_freq"], max_rounds=16)
+    tried = f["decisions"]
+    assert f["rounds"] == 16 == len(tried) and f["status"] == "max_rounds"
+    assert sum(1 for d in tried if len(d) > 1) >= 4 and max(len(d) for d in tried) >= 3
+    for r, d in enumerate(tried):
+        assert [a for a, _ in d] == [2.0 ** -i for i in range(len(d))]
+        assert all(diff <= -1e-6 for _, diff in d[:-1]) and d[-1][1] >= 1e-6, (r, d)
+    print("halvings by round:", [len(d) - 1 for d in tried], "smallest margin: %.3g" % min(abs(x) for d in tried for _, x in d))
+    # the same on the four-wave kernels: 4 leaves, 64 random protein columns, a step halved within 12 rounds
+    c = B.case("unrelated:protein")
+    assert len(c["rows"]) == 4 and len(c["rows"][0]) == 64 and c["data_type"] == 2 and B.LINE_SEARCH_CASES == {"unrelated": 16, "unrelated:protein": 12}
+    assert 1e-6 >= 1000 * 64 * A.tolerance(c["left"], c["right"], 20)
+    tried = B.fit(c["left"], c["right"], c["branch"], c["rows"], c["data_type"], c["base_freq"], max_rounds=12)["decisions"]
+    assert len(tried) == 12 and sum(1 for d in tried if len(d) > 1) >= 1
+    for r, d in enumerate(tried):
+        assert all(diff <= -1e-6 for _, diff in d[:-1]) and d[-1][1] >= 1e-6, (r, d)
+    print("protein, halvings by round:", [len(d) - 1 for d in tried], "smallest margin: %.3g" % min(abs(x) for d in tried for _, x in d))
+    for name in B.FIT_CASES:
+        assert all(len(d) <= 1 for d in B.fitted(name)["decisions"]), name
+
+
+def test_the_four_wave_cases_cover_every_kind_of_branch():
+    """Trees alone (no reading): over the S = 20 cases together and over the S = 61 cases together a leaf and an internal child each
+    occur beside a leaf and beside an internal sibling, and an internal child both under the root and under an inner node."""
+    for t, names in B.FOUR_WAVE_CASES.items():
+        seen = set()
+        for name in names:
+            c = B._named(name) or A.case(name)
+            assert c["data_type"] == t and name in B.DERIV_CASES
+            seen |= B.kinds(c["left"], c["right"])
+        assert {k[:2] for k in seen} == {(False, False), (False, True), (True, False), (True, True)}, t
+        assert {k[2] for k in seen if k[0]} == {False, True}, t
+    c = B._named("codon:tree")                           # a random tree: what the balanced ones lack
+    assert len(c["rows"]) == 5 and len(c["rows"][0]) == 3 * 65 and {(False, True), (True, False)} <= {k[:2] for k in B.kinds(c["left"], c["right"])}
+    for name in ("sim:protein", "sim:codon"):            # a gap in every ninth column
+        c = B._named(name)
+        w = 3 if c["data_type"] == 3 else 1
+        assert len(c["rows"]) == {2: 4, 3: 3}[c["data_type"]] and len(c["rows"][0]) == 65 * w and c["base_freq"] is None
+        assert all(sum(r[col * w:(col + 1) * w] == "-" * w for r in c["rows"]) == (col % 9 == 0) for col in range(65))
+
+
+def test_the_start_by_hand():
+    """pycheck_brlen.start against the header's sentence on numbers written out: every free branch within [t_min, t_max], tau
+    within them and split in branch_in's proportion (1/2 where both are 0), lengths inside the bounds untouched."""
+    left, right = [0, 2, 4], [1, 3, 5]
+    assert B.start(left, right, [0.0, 50.0, 0.3, 2e-7, 0.0, 0.13, 7.0]) == [1e-6, 10.0, 0.3, 1e-6, 0.0, 0.13, 0.0]
+    assert B.start(left, right, [0.1, 0.2, 0.3, 0.4, 5.0, 15.0, 0.0]) == [0.1, 0.2, 0.3, 0.4, 10.0 * 0.25, 10.0 - 10.0 * 0.25, 0.0]
+    assert B.start([0], [1], [0.0, 0.0, 0.0]) == [5e-7, 1e-6 - 5e-7, 0.0]
+    assert B.start([0], [1], [0.0, 3e-7, 0.0]) == [0.0, 1e-6, 0.0]
+    assert B.start([0], [1], [10.0, 20.0, 0.0]) == [10.0 * (10.0 / 30.0), 10.0 - 10.0 * (10.0 / 30.0), 0.0]
+    assert B.start([0], [1], [0.3, 0.4, 0.0], 0.1, 0.1) == [0.1 * (0.3 / 0.7), 0.1 - 0.1 * (0.3 / 0.7), 0.0]
+    # the fit of the reading starts there
+    f = B.fit([0], [1], [10.0, 20.0, 0.0], ["ACGT", "ACGA"], 1, None, max_rounds=0)
+    assert f["branch"] == B.start([0], [1], [10.0, 20.0, 0.0]) and f["rounds"] == 0 and f["decisions"] == []
+
+
 # ---- refusals, no device --------------------------------------------------------------------------------------------------------
 
 def _oracle_backend(oracle):
