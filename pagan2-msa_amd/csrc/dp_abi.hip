@@ -32,7 +32,7 @@ template <int BLOCK> __global__ void pg_fill_wavefront(const PgDevJob *jobs, con
 template <bool TAB_LDS> __global__ void pg_fill_ring(const PgDevJob *jobs, const int *which, unsigned flags);
 template <bool TAB_LDS, bool STRIP> __global__ void pg_fill_pipe(const PgDevJob *jobs, const int *which, unsigned flags, int n_fill);
 __global__ void pg_fill_tiles(const PgDevJob *jobs, const int *tiles, unsigned flags);
-__global__ void pg_fill_tiles_flow(const PgDevJob *jobs, const int *tiles, int n_tiles, int n_diag, int *flow, unsigned flags, int use_water);
+__global__ void pg_fill_tiles_flow(const PgDevJob *jobs, const int *tiles, int n_tiles, int n_diag, int *flow, unsigned flags, int schedule);
 __global__ void pg_end_corner(const PgDevJob *jobs, const int *tiles_gave_up);
 __global__ void pg_backptr(const PgDevJob *jobs, const int *which, unsigned flags, int diags_per_block);
 __global__ void pg_trace_spec(const PgDevJob *jobs);
@@ -276,6 +276,19 @@ static int bp_diags_per_block(int max_nd, int other_dims) {
     return dpb;
 }
 
+// When a tile of pg_fill_tiles_flow may start, for a batch of n_tiles tiles on n_diag tile anti-diagonals and a
+// chip of n_cu compute units.  Tiles that are no staircase need the watermark.  Otherwise a tile runs 80 steps behind its
+// neighbours, except at both ends of tiles per anti-diagonal : compute units:
+//   more than 1.75 x  the compute units are the bound either way, and the lag's progress flags and block-wise halo cost 15 %
+//                     (measured on cfg5: 575 tiles per diagonal 65 -> 56 ms without the lag, 320 per diagonal 46 -> 48 ms);
+//   fewer than 0.5 x  the chain of tile anti-diagonals is the bound (the top of a deep tree): blocks of 8 steps, 72 steps behind
+//                     for twice the flags (cfg5 -3 %).
+static PgTileSchedule tile_schedule(int n_tiles, int n_diag, int n_cu, bool tiles_water, bool tiles_nolag) {
+    if (tiles_water) return PG_TILES_WATERMARK;
+    if (4ll * n_tiles >= 7ll * n_cu * n_diag || tiles_nolag) return PG_TILES_NOLAG;
+    return 2ll * n_tiles < (long long)n_cu * n_diag ? PG_TILES_LAG8 : PG_TILES_LAG16;
+}
+
 // The strips' launch (one workgroup per strip): the jobs whose model table fits LDS, then the others'
 int launch_strips(pagan_batch *b, hipStream_t st, unsigned flags) {
     HIP_TRY(hipMemsetAsync(b->arena.dev + b->sfollow_begin, 0, b->sfollow_bytes, st));
@@ -412,19 +425,16 @@ int launch_fill(pagan_batch *b, const DpSwitches &sw) {
         if (b->tiles_flow) {
             // one persistent wave per compute unit (a tile fills the LDS) drains the batch's tiles in dependency order
             const int n_tiles = b->tile_off.back(), n_diag = (int)b->tile_off.size() - 1;
-            // (last argument) tiles run 80 steps behind their neighbours unless the batch has so many tiles per anti-diagonal
-            // that the compute units are the bound either way (measured on cfg5: 575 per diagonal 65 -> 56 ms without the lag,
-            // 320 per diagonal 46 -> 48 ms: the switch sits at 1.75 x the number of compute units)
             // no more waves than can have a tile to work on: the tiles of two anti-diagonals (a tile runs 80 steps behind
             // its neighbours) -- a persistent wave holds its compute unit's LDS, which the batch's banded jobs need too
             int widest = 1;
             for (int t = 0; t < n_diag; ++t) widest = std::max(widest, b->tile_off[t + 1] - b->tile_off[t]);
-            const int waves = std::min({n_tiles, n_cu_dev[b->device & 63].load(), 2 * widest + 8});
+            const int n_cu = n_cu_dev[b->device & 63].load();
+            const int waves = std::min({n_tiles, n_cu, 2 * widest + 8});
             HIP_TRY(hipMemsetAsync(b->d_flow, 0, sizeof(int) * b->flow_ints, st));
             hipLaunchKernelGGL(pg_fill_tiles_flow, dim3(waves), dim3(64), pg_tiles_lds_bytes(),
                                st, b->d_jobs, b->d_tiles, n_tiles, n_diag, b->d_flow, b->flags,
-                               b->tiles_water ? 1 : (4ll * n_tiles >= 7ll * n_cu_dev[b->device & 63].load() * n_diag || b->tiles_nolag ? 2 :
-                                                      (2ll * n_tiles < (long long)n_cu_dev[b->device & 63].load() * n_diag ? 3 : 0)));
+                               (int)tile_schedule(n_tiles, n_diag, n_cu, b->tiles_water, b->tiles_nolag));
         } else {
             for (size_t t = 0; t + 1 < b->tile_off.size(); ++t) {
                 const int cnt = b->tile_off[t + 1] - b->tile_off[t];

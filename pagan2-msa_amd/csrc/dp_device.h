@@ -38,6 +38,8 @@
 #define PG_BP_CELLS 1024      // ... and cells of each of them (grid.z covers the rest of a wide diagonal)
 #define PG_STATUS_PATH_CHECK 3 // endcell[0]: a visited cell's stored score / back-pointer differs from its re-evaluation (pg_trace_check)
 #define PG_FLAG_SCORE_CHECK 0x200u   // kernel flag: pg_backptr / the follower workgroups compare every cell's re-evaluated scores with the stored ones
+#define PG_FLAG_TILES_XCD0 0x200u    // kernel flag, diagnostic: only the waves of XCD 0 take tiles.  The SAME bit as PG_FLAG_SCORE_CHECK: pg_fill_tiles_flow
+                                     // reads it as this (its jobs' scores are checked by pg_backptr), every other kernel as the score check
 #define PG_FLAG_STRIPS_SPREAD 0x10000u   // kernel flag (pg_fill_pipe<., true>): a job's strips run on any XCD (strip_feeder does not ask where the strip above runs)
 #define PG_FILL_SCORE_MISMATCH 0x7c  // fill_status: ... and found a difference (pagan_batch_fetch runs the batch once more without followers, then reports)
 #define PG_FILL_OTHER_XCD 0x20000000  // fill_status, sticky: a row strip found the strip above on another XCD (the abort tags stay below bit 28)
@@ -68,6 +70,13 @@
 
 #define PG_TILE 64               // dp_tiles.hip: side of the square tiles a wide matrix is cut into (one wave each)
 #define PG_TILE_EDGES 512        // ... and how many bwd edges the sites of one tile row / tile column may have together
+// ... and when a tile of pg_fill_tiles_flow may start: the host picks one schedule per batch (dp_abi.hip: tile_schedule)
+enum PgTileSchedule {
+    PG_TILES_LAG16 = 0,          // staircase jobs: 80 steps behind the tiles above and to the left, the halo in blocks of 16 steps
+    PG_TILES_WATERMARK = 1,      // some job's tiles are no staircase: after those two have finished and every diagonal <= its own - 2 is done
+    PG_TILES_NOLAG = 2,          // staircase jobs: after the three neighbours have finished
+    PG_TILES_LAG8 = 3,           // staircase jobs: 72 steps behind, blocks of 8 steps (twice the progress flags)
+};
 
 struct PgDevJob {
     int Lx, Ly;              // matrix dimensions (sites minus the stop site)

@@ -1,19 +1,21 @@
 // dp_tiles.hip -- gfx950 fill kernel for wide matrices (no band, or a band wider than dp_pipe.hip takes):
-// the matrix is cut into PG_TILE x PG_TILE tiles, one wave per tile, one launch per tile anti-diagonal.
+// the matrix is cut into PG_TILE x PG_TILE tiles, one wave per tile.
 //
 // Why: an anti-diagonal of a full matrix is thousands of cells wide -- more than one compute unit can
 // take per step (2,000 cells x ~200 instructions is ~2.7 us of one CU's ALU time) -- while the matrix as a
 // whole has work for every CU of the chip.  Tile (a,b) needs tiles (a',b') with a' <= a, b' <= b only
-// (bwd edges point to earlier sites), so all tiles with the same a+b are independent: launch t runs
-// them concurrently, one wave each, for all wide alignments of the batch at once.  Kernel boundaries
-// order the launches, so there is no spinning between workgroups and nothing to get visibility wrong.
+// (bwd edges point to earlier sites), so all tiles with the same a+b are independent, for all wide alignments
+// of the batch at once.  The default is ONE launch per batch (pg_fill_tiles_flow, below): a persistent wave
+// per compute unit takes tiles from a queue in anti-diagonal order and waits for its tile's neighbours --
+// to finish, or, under the lagged start (tile_body<true>), to be far enough ahead.  PAGAN_DP_TILES=launches
+// keeps the first form, a launch per tile anti-diagonal (pg_fill_tiles), where kernel boundaries do the ordering.
 //
 // Inside a tile the wave sweeps the tile's own anti-diagonals: lane r owns row i0 + r, step s handles
 // column j0 + s - r.  The scores of the WHOLE tile plus a halo of eight rows above and eight columns left
-// of it (loaded from HBM at the start) live in LDS, so every predecessor inside the tile or within eight
-// sites of it is an LDS read; a bwd edge that reaches further back reads HBM (written by an earlier
-// launch).  The prologue issues its loads in three dependent rounds, each in flight together (after a kernel
-// boundary every first touch goes to memory).  Results go
+// of it (loaded from HBM at the start, or block by block under the lagged start) live in LDS, so every
+// predecessor inside the tile or within eight sites of it is an LDS read; a bwd edge that reaches further back
+// reads a far line in LDS or HBM (written by an earlier tile).  The prologue issues its loads in three
+// dependent rounds, each in flight together (a tile's first touches all go to memory).  Results go
 // to HBM in the batch's diagonal-major layout (dp_device.h) as they are produced; the wave never waits
 // for them: the only loads inside the step loop (operands from before the halo) are inline asm with their own
 // wait (dp_kcommon.h: far_*) -- a load the compiler can see makes its waitcnt insertion put a vmcnt(0), a wait
@@ -28,8 +30,10 @@
 //            active lanes run the reference's loops (the straight-line block would come on top of them, the
 //            loops cost what their longest trip costs): edges from LDS windows, the next one requested ahead,
 //            (left, right) pairs as one flattened loop, operands from LDS or HBM.
-// Back-pointers follow strict-greater in candidate order (first_is_bigger, basic_alignment.h:449-462); values
-// are v_max_f64 maxima, which is why jobs with negative-zero parameters go to the comparing HBM wavefront.
+// The step computes scores only (PG_TAKE, below): values are v_max_f64 maxima, which is why jobs with negative-zero
+// parameters go to the comparing HBM wavefront, and every back-pointer is re-derived from the stored scores by
+// pg_backptr (dp_kernels.hip) behind the fill.
+// A statistics build counts tiles, steps and waits at the PG_TS_* points: dp_tiles_stats.h.
 //
 // LDS: (72 x 72 + 1) cells x 24 B = 124,440 B + column records 2 KB + descriptors 4 KB + edge windows 9 KB +
 // model scores 16 KB + table 1 KB = 157 KB of 160 -> one tile per CU.
@@ -38,6 +42,7 @@
 #include "dp_device.h"
 
 #include "dp_kcommon.h"
+#include "dp_tiles_stats.h"
 #include <type_traits>
 
 #define TS PG_TILE
@@ -82,14 +87,14 @@ struct TileSmem {
 #define SITE_COUNT 0xffff             // PG_MAX_SLOT < 65536
 struct SiteRec { pg_i4 r, e; };
 
-// One candidate, in candidate order: it takes the back-pointer only if strictly greater (first_is_bigger,
-// basic_alignment.h:449-462); the value is the maximum either way (v_max_f64: one instruction where a
-// compare-and-select of a double costs two more).  v_max_f64 may flip the sign of a zero, so the host keeps jobs
-// with a negative zero among their parameters off this kernel (dp_abi.hip: has_negative_zero).
-// Round 3: SCORES ONLY.  A back-pointer is a function of scores that are final once the fill has passed the cell, and
-// pg_backptr (dp_kernels.hip) re-derives all of them after the fill; here a candidate only raises its state's value, so the
-// winner's code (and the compare + select that tracked it) is gone from every path of the tile step.
-#define PG_TAKE(best, bp, c, code) do { best = __builtin_fmax(best, (c)); } while (0)
+// One candidate.  The step computes SCORES ONLY: a back-pointer is a function of scores that are final once the fill has
+// passed the cell, and pg_backptr (dp_kernels.hip) re-derives all of them after the fill, so here a candidate only raises its
+// state's value (v_max_f64: one instruction where a compare-and-select of a double costs two more).  The candidates stand in
+// the reference's order all the same (the first of equals keeps the back-pointer there: first_is_bigger,
+// basic_alignment.h:449-462) -- a maximum does not depend on it, but it is the order pg_backptr and the reference are read in.
+// v_max_f64 may flip the sign of a zero, so the host keeps jobs with a negative zero among their parameters off this kernel
+// (dp_plan.cpp: has_negative_zero).
+#define PG_TAKE(best, c) do { best = __builtin_fmax(best, (c)); } while (0)
 
 } // namespace
 
@@ -134,6 +139,8 @@ __device__ __forceinline__ void flow_wait(int *p, int need, int *giveup, int *st
 // back, which were TLAG steps ahead of those.
 #define TBLK 16                    // (TH + TBLK) * TH + TBLK * TH <= 5 * 64: halo_block's five cells per lane
 #define TDONE (1 << 20)
+// cell n of a lane's batch of lagged loads (halo_block, line_block): 24 B from %[pn], L2-coherent, for the lanes of mask %[kn] only
+#define PG_CELL_LD(n) "s_and_b64 exec, %[sv], %[k" #n "]\n\tglobal_load_dwordx4 %[x" #n "], %[p" #n "], off sc1\n\tglobal_load_dwordx2 %[u" #n "], %[p" #n "], off offset:16 sc1\n\t"
 // TAB: the job's model table fits LDS (S <= 16) -- a compile-time fact of the body (the far lines and the table look-up exist
 // for such jobs only; a protein walk paid for the other kind's branches and look-ups in every generic step)
 template <bool LAG, int TB, bool TAB>
@@ -145,13 +152,7 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
     const int i0 = T.y * TS, j0 = T.z * TS;
     const int r = (int)threadIdx.x;
     const int i = i0 + r;
-#ifdef PG_TILE_STATS
-    // diagnostic build (tools/build_stamps.sh): cycles and step counts summed over all tiles of the job at the
-    // tail of its trace buffer: [0] tiles, [1] prologue, [2..4] steps simple / near / near + general, [5..7] their cycles
-    unsigned long long st_n[3] = {0, 0, 0}, st_t[3] = {0, 0, 0};
-    unsigned st_far = 0, st_far_steps = 0, st_far_max = 0, st_pairs_max = 0;
-    const unsigned long long st_begin = __builtin_amdgcn_s_memtime();
-#endif
+    PG_TS_TILE_BEGIN;
     const double NI = neg_inf();
     constexpr bool tab_lds = TAB;        // DNA: 15 states; a protein table (211 x 211) stays in HBM/L2
 
@@ -358,9 +359,7 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
     pg_i4 D = TM.dsc[TDB];
     pg_i4 c = pg_i4{0, 0, 0, 0}, ce = pg_i4{0, 0, 0, 0};
     if (r == 0) { c = TM.col[0]; ce = TM.cole[0]; }
-#ifdef PG_TILE_STATS
-    const unsigned long long st_loop = __builtin_amdgcn_s_memtime();
-#endif
+    PG_TS_LOOP_BEGIN;
     // LAG: the halo cells of one block of steps (k = s / TB, s < TS): columns j0 + TB k ... of the TH rows above (the
     // first block also takes the corner), rows i0 + TB k ... of the TH columns to the left
     auto halo_block = [&](int k) {
@@ -391,15 +390,13 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
         const unsigned long long k4 = __builtin_amdgcn_ballot_w64(hv_[4]);
         if ((k0 | k1 | k2 | k3 | k4) == 0) return;
         unsigned long long sv;
-#define PG_HALO_LD(n) "s_and_b64 exec, %[sv], %[k" #n "]\n\tglobal_load_dwordx4 %[x" #n "], %[p" #n "], off sc1\n\tglobal_load_dwordx2 %[u" #n "], %[p" #n "], off offset:16 sc1\n\t"
-        asm volatile("s_mov_b64 %[sv], exec\n\t" PG_HALO_LD(0) PG_HALO_LD(1) PG_HALO_LD(2) PG_HALO_LD(3) PG_HALO_LD(4)
+        asm volatile("s_mov_b64 %[sv], exec\n\t" PG_CELL_LD(0) PG_CELL_LD(1) PG_CELL_LD(2) PG_CELL_LD(3) PG_CELL_LD(4)
                      "s_mov_b64 exec, %[sv]\n\ts_waitcnt vmcnt(0)"
                      : [x0] "+v"(hxy_[0]), [u0] "+v"(hm_[0]), [x1] "+v"(hxy_[1]), [u1] "+v"(hm_[1]), [x2] "+v"(hxy_[2]), [u2] "+v"(hm_[2]),
                        [x3] "+v"(hxy_[3]), [u3] "+v"(hm_[3]), [x4] "+v"(hxy_[4]), [u4] "+v"(hm_[4]), [sv] "=&s"(sv)
                      : [p0] "v"(hp_[0]), [p1] "v"(hp_[1]), [p2] "v"(hp_[2]), [p3] "v"(hp_[3]), [p4] "v"(hp_[4]),
                        [k0] "s"(k0), [k1] "s"(k1), [k2] "s"(k2), [k3] "s"(k3), [k4] "s"(k4)
                      : "memory");
-#undef PG_HALO_LD
 #pragma unroll
         for (int u = 0; u < 5; ++u)
             if (hv_[u]) { TM.sc[hat_[u]][0] = hxy_[u].x; TM.sc[hat_[u]][1] = hxy_[u].y; TM.sc[hat_[u]][2] = hm_[u]; }
@@ -434,13 +431,11 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
         const unsigned long long k2 = __builtin_amdgcn_ballot_w64(hv_[2]);
         if ((k0 | k1 | k2) == 0) return;
         unsigned long long sv;
-#define PG_LINE_LD(n) "s_and_b64 exec, %[sv], %[k" #n "]\n\tglobal_load_dwordx4 %[x" #n "], %[p" #n "], off sc1\n\tglobal_load_dwordx2 %[u" #n "], %[p" #n "], off offset:16 sc1\n\t"
-        asm volatile("s_mov_b64 %[sv], exec\n\t" PG_LINE_LD(0) PG_LINE_LD(1) PG_LINE_LD(2)
+        asm volatile("s_mov_b64 %[sv], exec\n\t" PG_CELL_LD(0) PG_CELL_LD(1) PG_CELL_LD(2)
                      "s_mov_b64 exec, %[sv]\n\ts_waitcnt vmcnt(0)"
                      : [x0] "+v"(hxy_[0]), [u0] "+v"(hm_[0]), [x1] "+v"(hxy_[1]), [u1] "+v"(hm_[1]), [x2] "+v"(hxy_[2]), [u2] "+v"(hm_[2]), [sv] "=&s"(sv)
                      : [p0] "v"(hp_[0]), [p1] "v"(hp_[1]), [p2] "v"(hp_[2]), [k0] "s"(k0), [k1] "s"(k1), [k2] "s"(k2)
                      : "memory");
-#undef PG_LINE_LD
 #pragma unroll
         for (int u = 0; u < 3; ++u)
             if (hv_[u]) { TM.farl[hl_[u]][hc_[u]][0] = hxy_[u].x; TM.farl[hl_[u]][hc_[u]][1] = hxy_[u].y; TM.farl[hl_[u]][hc_[u]][2] = hm_[u]; }
@@ -450,30 +445,18 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
         flow_wait(&prog[which], need, giveup, jobs[T.x].fill_status);
     };
     for (int s = 0; s <= s_last; ++s) {
-#ifdef PG_TILE_STATS
-        const unsigned long long st_a = __builtin_amdgcn_s_memtime();
-        int st_kind = -1;
-#endif
+        PG_TS_STEP_BEGIN;
         if (LAG && s < TS && (s & (TB - 1)) == 0) {
             const int need = s + TB - 1 + TS;                   // the neighbours' steps <= s + TB - 1 + 63 are published
-#ifdef PG_TILE_STATS
-            const unsigned long long lw0 = __builtin_amdgcn_s_memtime();
-#endif
+            PG_TS_LAG_WAIT_BEGIN;
             wait_prog(up, need < 2 * TS - 1 ? need : TDONE);
             wait_prog(lf, need < 2 * TS - 1 ? need : TDONE);
-#ifdef PG_TILE_STATS
-            const unsigned long long lw1 = __builtin_amdgcn_s_memtime();
-#endif
+            PG_TS_LAG_WAIT_END;
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             halo_block(s / TB);
             line_block(s / TB);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifdef PG_TILE_STATS
-            if (r == 0 && 3 * (J.Lx + J.Ly) >= 4096) {      // (long jobs only: the counters borrow the tail of the trace buffer) [13] waiting for the neighbours' progress, [14] acquire + halo block
-                unsigned long long *out = (unsigned long long *)(jobs[T.x].trace + ((3 * (J.Lx + J.Ly) - 64) & ~1));
-                atomicAdd(out + 13, lw1 - lw0); atomicAdd(out + 14, __builtin_amdgcn_s_memtime() - lw1);
-            }
-#endif
+            PG_TS_LAG_END(jobs + T.x, 3 * (J.Lx + J.Ly));
         }
         const pg_i4 Dn = TM.dsc[TDB + s + 1];
         const int jj = s - r;
@@ -488,10 +471,7 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
             const bool two = (row.r.z & c.z & SITE_TWO) != 0;
             const bool anyfar = ((row.r.z | c.z) & (SITE_FAR0 | SITE_FAR1)) != 0;
             double bx = NI, by = NI, bm = NI;
-            unsigned px = PG_BP_NONE, py = PG_BP_NONE, pm = PG_BP_NONE;
-#ifdef PG_TILE_STATS
-            st_kind = __builtin_amdgcn_ballot_w64(active && !simple) == 0 ? 0 : (__builtin_amdgcn_ballot_w64(active && !(two && !anyfar)) == 0 ? 1 : 2);
-#endif
+            PG_TS_STEP_KIND(active, simple, two && !anyfar);
             if (__builtin_amdgcn_ballot_w64(active && !simple) == 0) {
                 if (active) {
                     // (i-1,j), (i,j-1), (i-1,j-1)
@@ -504,22 +484,22 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
                     {
                         const bool end_gap = (j == J.Ly - 1) && !no_terminal_edges;          // VA:864-868 (j > 0 here)
                         const double ext = (double)(end_gap ? J.gE : J.ge);
-                        PG_TAKE(bx, px, ux + ext, pack_bp(PG_X, 0, 0, true, false));
-                        PG_TAKE(bx, px, (uy + 0.0) + go, pack_bp(PG_Y, 0, 0, true, false));
-                        PG_TAKE(bx, px, (um + ng) + openX0, pack_bp(PG_M, 0, 0, true, false));
+                        PG_TAKE(bx, ux + ext);                                               // X, then Y, then M
+                        PG_TAKE(bx, (uy + 0.0) + go);
+                        PG_TAKE(bx, (um + ng) + openX0);
                     }
                     {
                         const double open = (reduced_terminal && j == 1) ? 0.0 : go;
-                        PG_TAKE(by, py, ly + extY, pack_bp(PG_Y, 0, 0, false, true));
-                        PG_TAKE(by, py, (lx + 0.0) + go, pack_bp(PG_X, 0, 0, false, true));
-                        PG_TAKE(by, py, (lm + ng) + open, pack_bp(PG_M, 0, 0, false, true));
+                        PG_TAKE(by, ly + extY);                                              // Y, X, M
+                        PG_TAKE(by, (lx + 0.0) + go);
+                        PG_TAKE(by, (lm + ng) + open);
                     }
                     {
                         const double tM = (double)(2 * J.ng) + (double)sm;                   // VA:1364
                         const double tX = (double)(0.0f + J.ng) + (double)sm;                // VA:1366-1367
-                        PG_TAKE(bm, pm, ((gm + tM) + lw0) + rw, pack_bp(PG_M, 0, 0, true, true));
-                        PG_TAKE(bm, pm, ((gx + tX) + lw0) + rw, pack_bp(PG_X, 0, 0, true, true));
-                        PG_TAKE(bm, pm, ((gy + tX) + lw0) + rw, pack_bp(PG_Y, 0, 0, true, true));
+                        PG_TAKE(bm, ((gm + tM) + lw0) + rw);                                 // M, X, Y
+                        PG_TAKE(bm, ((gx + tX) + lw0) + rw);
+                        PG_TAKE(bm, ((gy + tX) + lw0) + rw);
                     }
                 }
             } else {
@@ -553,45 +533,38 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
                     const double b1x = TM.sc[aB1][0], b1y = TM.sc[aB1][1], b1m = TM.sc[aB1][2];
                     const float sm = (i > 0 && j > 0) ? model_score(jj, c.x) : 0.0f;
                     const double extX = (double)(((j == 0 || j == J.Ly - 1) && !no_terminal_edges) ? J.gE : J.ge);   // VA:864-868
-                    const unsigned adjG = left ? PG_BP_ADJL : PG_BP_ADJR, adjS = left ? PG_BP_ADJR : PG_BP_ADJL;
-                    const unsigned selfG = left ? PG_X : PG_Y, crossG = left ? PG_Y : PG_X;
-                    const int kshift = left ? 4 : 18;
-                    const int nearG = left ? i - 1 : j - 1;                          // the site an adjacent edge of that side starts at
                     double gs = NI, ssb = NI;
-                    unsigned pg = PG_BP_NONE, ps = PG_BP_NONE;
                     {   // the simple side's gap state: one operand, own state first (VA:898-915 / 927-944)
                         const double extS = left ? extY : extX;
                         const int srcS = left ? j - 1 : i - 1;
                         const double open = (reduced_terminal && srcS == 0) ? 0.0 : go;
-                        PG_TAKE(ssb, ps, (left ? sy : sx) + extS, crossG | adjS);
-                        PG_TAKE(ssb, ps, ((left ? sx : sy) + 0.0) + go, selfG | adjS);
-                        PG_TAKE(ssb, ps, (ss + ng) + open, PG_M | adjS);
+                        PG_TAKE(ssb, (left ? sy : sx) + extS);
+                        PG_TAKE(ssb, ((left ? sx : sy) + 0.0) + go);
+                        PG_TAKE(ssb, (ss + ng) + open);
                     }
                     {   // the other side's gap state: per edge own state, the other gap state, M
                         const double extG = left ? extX : extY;
-                        const unsigned e0 = g0 == nearG ? adjG : 0u, e1 = (g1 == nearG ? adjG : 0u) | (1u << kshift);
                         const double o0 = (reduced_terminal && g0 == 0) ? 0.0 : go, o1 = (reduced_terminal && g1 == 0) ? 0.0 : go;
-                        PG_TAKE(gs, pg, (left ? a0x : a0y) + extG, e0 | selfG);
-                        PG_TAKE(gs, pg, ((left ? a0y : a0x) + 0.0) + go, e0 | crossG);
-                        PG_TAKE(gs, pg, (a0m + ng) + o0, e0 | PG_M);
-                        PG_TAKE(gs, pg, (left ? a1x : a1y) + extG, e1 | selfG);
-                        PG_TAKE(gs, pg, ((left ? a1y : a1x) + 0.0) + go, e1 | crossG);
-                        PG_TAKE(gs, pg, (a1m + ng) + o1, e1 | PG_M);
+                        PG_TAKE(gs, (left ? a0x : a0y) + extG);
+                        PG_TAKE(gs, ((left ? a0y : a0x) + 0.0) + go);
+                        PG_TAKE(gs, (a0m + ng) + o0);
+                        PG_TAKE(gs, (left ? a1x : a1y) + extG);
+                        PG_TAKE(gs, ((left ? a1y : a1x) + 0.0) + go);
+                        PG_TAKE(gs, (a1m + ng) + o1);
                     }
-                    {   // M: the (left edge, right edge) pairs in list order (VA:1396-1433)
+                    {   // M: the (left edge, right edge) pairs in list order (VA:1396-1433), each from M, X, Y
                         const double tM = (double)(2 * J.ng) + (double)sm;                   // VA:1364
                         const double tX = (double)(0.0f + J.ng) + (double)sm;                // VA:1366-1367
                         const double lwA0 = left ? gw0 : sw, rwA0 = left ? sw : gw0, lwA1 = left ? gw1 : sw, rwA1 = left ? sw : gw1;
-                        const unsigned e0 = (g0 == nearG ? adjG : 0u) | adjS, e1 = (g1 == nearG ? adjG : 0u) | (1u << kshift) | adjS;
-                        PG_TAKE(bm, pm, ((b0m + tM) + lwA0) + rwA0, e0 | PG_M);
-                        PG_TAKE(bm, pm, ((b0x + tX) + lwA0) + rwA0, e0 | PG_X);
-                        PG_TAKE(bm, pm, ((b0y + tX) + lwA0) + rwA0, e0 | PG_Y);
-                        PG_TAKE(bm, pm, ((b1m + tM) + lwA1) + rwA1, e1 | PG_M);
-                        PG_TAKE(bm, pm, ((b1x + tX) + lwA1) + rwA1, e1 | PG_X);
-                        PG_TAKE(bm, pm, ((b1y + tX) + lwA1) + rwA1, e1 | PG_Y);
+                        PG_TAKE(bm, ((b0m + tM) + lwA0) + rwA0);
+                        PG_TAKE(bm, ((b0x + tX) + lwA0) + rwA0);
+                        PG_TAKE(bm, ((b0y + tX) + lwA0) + rwA0);
+                        PG_TAKE(bm, ((b1m + tM) + lwA1) + rwA1);
+                        PG_TAKE(bm, ((b1x + tX) + lwA1) + rwA1);
+                        PG_TAKE(bm, ((b1y + tX) + lwA1) + rwA1);
                     }
-                    bx = left ? gs : ssb; px = left ? pg : ps;
-                    by = left ? ssb : gs; py = left ? ps : pg;
+                    bx = left ? gs : ssb;
+                    by = left ? ssb : gs;
                 }
                 if (active && near && !half) {
                     // At most two bwd edges per site, all eight operand cells in LDS: straight-line, the cell of an
@@ -608,51 +581,44 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
                         const double x1 = TM.sc[aX1][0], y1 = TM.sc[aX1][1], m1 = TM.sc[aX1][2];
                         const bool end_gap = (j == 0 || j == J.Ly - 1) && !no_terminal_edges;    // VA:864-868
                         const double ext = (double)(end_gap ? J.gE : J.ge);
-                        PG_TAKE(bx, px, x0 + ext, pack_bp(PG_X, 0, 0, p0 == i - 1, false));
-                        PG_TAKE(bx, px, (y0 + 0.0) + go, pack_bp(PG_Y, 0, 0, p0 == i - 1, false));
-                        PG_TAKE(bx, px, (m0 + ng) + openX0, pack_bp(PG_M, 0, 0, p0 == i - 1, false));
-                        PG_TAKE(bx, px, x1 + ext, pack_bp(PG_X, 1, 0, p1 == i - 1, false));
-                        PG_TAKE(bx, px, (y1 + 0.0) + go, pack_bp(PG_Y, 1, 0, p1 == i - 1, false));
-                        PG_TAKE(bx, px, (m1 + ng) + openX1, pack_bp(PG_M, 1, 0, p1 == i - 1, false));
+                        PG_TAKE(bx, x0 + ext);
+                        PG_TAKE(bx, (y0 + 0.0) + go);
+                        PG_TAKE(bx, (m0 + ng) + openX0);
+                        PG_TAKE(bx, x1 + ext);
+                        PG_TAKE(bx, (y1 + 0.0) + go);
+                        PG_TAKE(bx, (m1 + ng) + openX1);
                     }
                     {
                         const double x0 = TM.sc[aY0][0], y0 = TM.sc[aY0][1], m0 = TM.sc[aY0][2];
                         const double x1 = TM.sc[aY1][0], y1 = TM.sc[aY1][1], m1 = TM.sc[aY1][2];
                         const double open0 = (reduced_terminal && q0 == 0) ? 0.0 : go, open1 = (reduced_terminal && q1 == 0) ? 0.0 : go;
-                        PG_TAKE(by, py, y0 + extY, pack_bp(PG_Y, 0, 0, false, q0 == j - 1));
-                        PG_TAKE(by, py, (x0 + 0.0) + go, pack_bp(PG_X, 0, 0, false, q0 == j - 1));
-                        PG_TAKE(by, py, (m0 + ng) + open0, pack_bp(PG_M, 0, 0, false, q0 == j - 1));
-                        PG_TAKE(by, py, y1 + extY, pack_bp(PG_Y, 0, 1, false, q1 == j - 1));
-                        PG_TAKE(by, py, (x1 + 0.0) + go, pack_bp(PG_X, 0, 1, false, q1 == j - 1));
-                        PG_TAKE(by, py, (m1 + ng) + open1, pack_bp(PG_M, 0, 1, false, q1 == j - 1));
+                        PG_TAKE(by, y0 + extY);
+                        PG_TAKE(by, (x0 + 0.0) + go);
+                        PG_TAKE(by, (m0 + ng) + open0);
+                        PG_TAKE(by, y1 + extY);
+                        PG_TAKE(by, (x1 + 0.0) + go);
+                        PG_TAKE(by, (m1 + ng) + open1);
                     }
                     {
                         const double tM = (double)(2 * J.ng) + (double)sm;                   // VA:1364
                         const double tX = (double)(0.0f + J.ng) + (double)sm;                // VA:1366-1367
-#define PG_PAIR(a, k1, k2, lw, rw, pp, qq)                                                                          \
-                        {                                                                                           \
-                            const double x_ = TM.sc[a][0], y_ = TM.sc[a][1], m_ = TM.sc[a][2];                      \
-                            PG_TAKE(bm, pm, ((m_ + tM) + lw) + rw, pack_bp(PG_M, k1, k2, pp == i - 1, qq == j - 1)); \
-                            PG_TAKE(bm, pm, ((x_ + tX) + lw) + rw, pack_bp(PG_X, k1, k2, pp == i - 1, qq == j - 1)); \
-                            PG_TAKE(bm, pm, ((y_ + tX) + lw) + rw, pack_bp(PG_Y, k1, k2, pp == i - 1, qq == j - 1)); \
+#define PG_PAIR(a, lw, rw)                                                                      \
+                        {                                                                       \
+                            const double x_ = TM.sc[a][0], y_ = TM.sc[a][1], m_ = TM.sc[a][2];  \
+                            PG_TAKE(bm, ((m_ + tM) + lw) + rw);                                 \
+                            PG_TAKE(bm, ((x_ + tX) + lw) + rw);                                 \
+                            PG_TAKE(bm, ((y_ + tX) + lw) + rw);                                 \
                         }
-                        PG_PAIR(aM00, 0, 0, lw0, rw0, p0, q0)
-                        PG_PAIR(aM01, 0, 1, lw0, rw1, p0, q1)
-                        PG_PAIR(aM10, 1, 0, lw1, rw0, p1, q0)
-                        PG_PAIR(aM11, 1, 1, lw1, rw1, p1, q1)
+                        PG_PAIR(aM00, lw0, rw0)
+                        PG_PAIR(aM01, lw0, rw1)
+                        PG_PAIR(aM10, lw1, rw0)
+                        PG_PAIR(aM11, lw1, rw1)
 #undef PG_PAIR
                     }
                     if (i == 0 && j == 0) bm = 0.0;                                          // initialise_array_corner, VA:725-736
                 }
                 if (!near) {
-#ifdef PG_TILE_STATS
-                    const unsigned far_before = st_far;
-                    {
-                        int pr_ = active ? (int)(nl > 0 ? nl : 1) * (int)(nr > 0 ? nr : 1) : 0;
-                        for (int o_ = 32; o_ > 0; o_ >>= 1) pr_ = max(pr_, __shfl_xor(pr_, o_));
-                        st_pairs_max += pr_;
-                    }
-#endif
+                    PG_TS_LOOPS_BEGIN(active ? (nl > 0 ? nl : 1) * (nr > 0 ? nr : 1) : 0);
                     // (compiled twice: with the far lines' look-ups for small-table jobs, without them for the others -- a protein
                     //  walk paid 10 % for look-ups it never uses)
                     auto loops = [&](auto with_lines) {
@@ -672,18 +638,14 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
                                 const double *c_ = TM.farl[sr][p - (i0 - 1)];
                                 xs = c_[0]; ys = c_[1]; ms = c_[2];
                             } else {
-#ifdef PG_TILE_STATS
-                                ++st_far;
-#endif
+                                PG_TS_FAR_FETCH;
                                 const int w = p + q - (dbase - TDB);
                                 const pg_i4 F = w >= 0 ? TM.dsc[w] : far_desc(((PG_GLOBAL const pg_i4 *)(unsigned long long)J.dsc) + (p + q));
                                 xs = ys = ms = NI;
-#ifndef PG_TILE_EXP_NOFAR                                       // (timing experiment, wrong results: what would the generic steps cost without their far loads?)
                                 if (p >= F.x && p <= F.y) {
                                     const long long ix = (((long long)F.w << 32) | (unsigned)F.z) + (p - F.x);
                                     far_cell(J.sc + 3 * ix, xs, ys, ms);
                                 }
-#endif
                             }
                         };
                         typedef int i2 __attribute__((ext_vector_type(2)));
@@ -703,10 +665,9 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
                                 if (k + 1 < nl) fetch(pn, j, LINES ? TM.lineL[eLi + k + 1] : 255, 255, nx, ny, nm);
                                 en = *(const i2 *)TM.eL[eLi + k + 2];
                                 const double open = (reduced_terminal && p == 0) ? 0.0 : go;
-                                const unsigned base = ((unsigned)k << 4) | (p == i - 1 ? PG_BP_ADJL : 0u);
-                                PG_TAKE(bx, px, xs + ext, base | PG_X);
-                                PG_TAKE(bx, px, (ys + 0.0) + go, base | PG_Y);
-                                PG_TAKE(bx, px, (ms + ng) + open, base | PG_M);
+                                PG_TAKE(bx, xs + ext);
+                                PG_TAKE(bx, (ys + 0.0) + go);
+                                PG_TAKE(bx, (ms + ng) + open);
                                 p = pn; xs = nx; ys = ny; ms = nm;
                             }
                         }
@@ -721,10 +682,9 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
                                 if (k + 1 < nr) fetch(i, qn, 255, LINES ? TM.lineR[eRi + k + 1] : 255, nx, ny, nm);
                                 en = *(const i2 *)TM.eR[eRi + k + 2];
                                 const double open = (reduced_terminal && q == 0) ? 0.0 : go;
-                                const unsigned base = ((unsigned)k << 18) | (q == j - 1 ? PG_BP_ADJR : 0u);
-                                PG_TAKE(by, py, ys + extY, base | PG_Y);
-                                PG_TAKE(by, py, (xs + 0.0) + go, base | PG_X);
-                                PG_TAKE(by, py, (ms + ng) + open, base | PG_M);
+                                PG_TAKE(by, ys + extY);
+                                PG_TAKE(by, (xs + 0.0) + go);
+                                PG_TAKE(by, (ms + ng) + open);
                                 q = qn; xs = nx; ys = ny; ms = nm;
                             }
                         }
@@ -740,30 +700,23 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
                             for (int t = 0; t < pairs; ++t) {
                                 const int p = e1.x, q = e2.x;
                                 const double lw = (double)__int_as_float(e1.y), rw = (double)__int_as_float(e2.y);
-                                const unsigned base = ((unsigned)k1 << 4) | ((unsigned)k2 << 18) | (p == i - 1 ? PG_BP_ADJL : 0u) |
-                                                      (q == j - 1 ? PG_BP_ADJR : 0u);
                                 const int sl_ = LINES ? TM.lineL[eLi + k1] : 255, sr_ = LINES ? TM.lineR[eRi + k2] : 255;
-                                const bool wrap = k2 + 1 == nr;
-                                k2 = wrap ? 0 : k2 + 1;
+                                const int k2n = k2 + 1;
+                                const bool wrap = k2n == nr;
+                                k2 = wrap ? 0 : k2n;
                                 k1 = wrap ? k1 + 1 : k1;
                                 e1 = *(const i2 *)TM.eL[eLi + k1];
                                 e2 = *(const i2 *)TM.eR[eRi + k2];
                                 double xs, ys, ms;
                                 fetch(p, q, sl_, sr_, xs, ys, ms);
-                                PG_TAKE(bm, pm, ((ms + tM) + lw) + rw, base | PG_M);
-                                PG_TAKE(bm, pm, ((xs + tX) + lw) + rw, base | PG_X);
-                                PG_TAKE(bm, pm, ((ys + tX) + lw) + rw, base | PG_Y);
+                                PG_TAKE(bm, ((ms + tM) + lw) + rw);
+                                PG_TAKE(bm, ((xs + tX) + lw) + rw);
+                                PG_TAKE(bm, ((ys + tX) + lw) + rw);
                             }
                         }
                     };
                     if (active) loops(std::integral_constant<bool, TAB>());
-#ifdef PG_TILE_STATS
-                    {   // fetches from beyond the LDS window in this step: the wave's largest count, and whether there was any
-                        int f_ = (int)(st_far - far_before);
-                        for (int o_ = 32; o_ > 0; o_ >>= 1) f_ = max(f_, __shfl_xor(f_, o_));
-                        st_far_max += f_; st_far_steps += f_ > 0;
-                    }
-#endif
+                    PG_TS_LOOPS_END;
                 }
             }
             if (active) {
@@ -776,7 +729,6 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
                     *(PG_GLOBAL d2 *)o_ = xy;
                     o_[2] = bm;
                 }
-                (void)px; (void)py; (void)pm;
             }
         }
         D = Dn; c = cn; ce = cen;
@@ -786,26 +738,9 @@ __device__ __noinline__ void tile_body(const PgDevJob *__restrict__ jobs, const 
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // (waits for the wave's stores, writes the L2 back)
             if (r == 0) __hip_atomic_store(&prog[self], s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-#ifdef PG_TILE_STATS
-        if (st_kind >= 0) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const unsigned long long dt = __builtin_amdgcn_s_memtime() - st_a;
-            if (st_kind == 0) { ++st_n[0]; st_t[0] += dt; } else if (st_kind == 1) { ++st_n[1]; st_t[1] += dt; } else { ++st_n[2]; st_t[2] += dt; }
-        }
-#endif
+        PG_TS_STEP_END;
     }
-#ifdef PG_TILE_STATS
-    if (r == 0 && 3 * (J.Lx + J.Ly) >= 4096) {
-        unsigned long long *out = (unsigned long long *)(jobs[T.x].trace + ((3 * (J.Lx + J.Ly) - 64) & ~1));
-        atomicAdd(out + 0, 1ull);
-        atomicAdd(out + 1, st_loop - st_begin);
-        for (int k = 0; k < 3; ++k) { atomicAdd(out + 2 + k, st_n[k]); atomicAdd(out + 5 + k, st_t[k]); }
-        // [15] generic steps with a fetch from beyond the LDS window, [16] such fetches of the busiest lane summed over those steps,
-        // [17] (left, right) edge pairs of the busiest lane summed over the generic steps
-        atomicAdd(out + 15, (unsigned long long)st_far_steps); atomicAdd(out + 16, (unsigned long long)st_far_max); atomicAdd(out + 17, (unsigned long long)st_pairs_max);
-        atomicAdd(out + 8, __builtin_amdgcn_s_memtime() - st_begin);
-    }
-#endif
+    PG_TS_TILE_END(jobs + T.x, 3 * (J.Lx + J.Ly));
 }
 
 // tiles[blockIdx.x] = {job, tile row a, tile column b, -}: one launch per tile anti-diagonal (PAGAN_DP_TILES=launches)
@@ -823,11 +758,11 @@ __global__ __launch_bounds__(64) void pg_fill_tiles(const PgDevJob *__restrict__
 // positions from the host; -1: not in the band).  Where the tiles of every job form a staircase -- each tile row a
 // contiguous run of columns, first and last column never falling, consecutive rows touching (the host checks; any band
 // the anchors make does) -- that is enough: by induction every tile (a',b') <= (a,b) is done then, i.e. every tile a bwd
-// edge of this tile's cells can reach.  Otherwise (`use_water` 1) a tile also waits until every tile of the diagonals <= t-2
-// is done (`fin[t']` counts finished tiles; a wave keeps a watermark).  `use_water` 0: staircase jobs, tiles start 80 steps
-// behind their neighbours (tile_body<true>); 2: staircase jobs, a tile waits for its neighbours to finish -- the host picks
-// it when the batch has more than 1.75 x as many tiles per anti-diagonal as the chip has compute units (the lag buys
-// nothing then and its progress flags and block-wise halo cost 15 %).
+// edge of this tile's cells can reach.  Otherwise (PG_TILES_WATERMARK) a tile also waits until every tile of the diagonals
+// <= t-2 is done (`fin[t']` counts finished tiles; a wave keeps a watermark).  Staircase jobs take one of three `schedule`s
+// (dp_device.h: PgTileSchedule; the host picks per batch, dp_abi.hip: tile_schedule): PG_TILES_LAG16, tiles start 80 steps
+// behind their neighbours (tile_body<true, 16>); PG_TILES_LAG8, 72 steps behind with twice the progress flags
+// (tile_body<true, 8>); PG_TILES_NOLAG, a tile waits for its neighbours to finish.
 // A wave only ever waits for tiles that were handed out before its own -- to waves that are running -- so the queue drains.
 // Visibility across the XCDs' L2s: the finishing wave's stores are released at agent scope before its flags are set, the
 // starting wave acquires at agent scope after it has seen them (the compiler's gfx950 memory model: write-back of the
@@ -838,13 +773,13 @@ __global__ __launch_bounds__(64) void pg_fill_tiles(const PgDevJob *__restrict__
 // finished), then the give-up flag (flow_wait).
 __global__ __launch_bounds__(64) void pg_fill_tiles_flow(const PgDevJob *__restrict__ jobs, const int *__restrict__ tiles,
                                                          int n_tiles, int n_diag, int *__restrict__ flow, unsigned flags,
-                                                         int use_water) {
+                                                         int schedule) {
     const int *left = tiles + 4 * ((size_t)n_tiles + 1);
     const int *diag = left + n_tiles;
     const int *first = diag + n_tiles;
     int *fin = flow + 1, *done = flow + 1 + n_diag;
     int water = 0;                                             // every diagonal < water is complete
-    if (flags & 0x200u) {                                      // diagnostic (PAGAN_DP_DEBUG_FLAGS=0x200): the waves of XCD 0 only -- do the
+    if (flags & PG_FLAG_TILES_XCD0) {                          // diagnostic (PAGAN_DP_DEBUG_FLAGS=0x200): the waves of XCD 0 only -- do the
         unsigned x;                                            // reads of other tiles' cells cost what they cost because they cross XCDs?
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
         if ((x & 15u) != 0) return;
@@ -859,47 +794,30 @@ __global__ __launch_bounds__(64) void pg_fill_tiles_flow(const PgDevJob *__restr
         const int t = T.y + T.z;
         auto wait_ge = [&](int *p, int need) { flow_wait(p, need, giveup, jobs[T.x].fill_status); };
         if (__hip_atomic_load(giveup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-#ifdef PG_TILE_STATS
-        const unsigned long long fs0 = __builtin_amdgcn_s_memtime();
-#endif
-        if (use_water == 1) for (; water <= t - 2; ++water) wait_ge(&fin[water], first[water + 1] - first[water]);
+        PG_TS_CLOCK(fs0);
+        if (schedule == PG_TILES_WATERMARK) for (; water <= t - 2; ++water) wait_ge(&fin[water], first[water + 1] - first[water]);
         const int lf = left[idx], dg = diag[idx];
-#ifdef PG_TILE_STATS
-        const unsigned long long fs1 = __builtin_amdgcn_s_memtime();
-#endif
-        const bool lag = use_water == 0 || use_water == 3;
+        PG_TS_CLOCK(fs1);
+        const bool lag = schedule == PG_TILES_LAG16 || schedule == PG_TILES_LAG8;
         if (!lag) {
             if (T.w >= 0) wait_ge(&done[T.w], TDONE);
             if (lf >= 0) wait_ge(&done[lf], TDONE);
-            if (use_water == 2 && dg >= 0) wait_ge(&done[dg], TDONE);
+            if (schedule == PG_TILES_NOLAG && dg >= 0) wait_ge(&done[dg], TDONE);
         } else if (T.w < 0 && lf < 0 && dg >= 0) wait_ge(&done[dg], TDONE);    // (the band enters through the corner)
-#ifdef PG_TILE_STATS
-        const unsigned long long fs2 = __builtin_amdgcn_s_memtime();
-#endif
+        PG_TS_CLOCK(fs2);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         const bool small_table = jobs[T.x].S <= 16;
         if (!lag) { if (small_table) tile_body<false, TBLK, true>(jobs, T, flags); else tile_body<false, TBLK, false>(jobs, T, flags); }
-        else if (use_water == 3) {
+        else if (schedule == PG_TILES_LAG8) {
             if (small_table) tile_body<true, 8, true>(jobs, T, flags, done, idx, T.w, lf, giveup);
             else tile_body<true, 8, false>(jobs, T, flags, done, idx, T.w, lf, giveup);
         } else {
             if (small_table) tile_body<true, TBLK, true>(jobs, T, flags, done, idx, T.w, lf, giveup);
             else tile_body<true, TBLK, false>(jobs, T, flags, done, idx, T.w, lf, giveup);
         }
-#ifdef PG_TILE_STATS
-        const unsigned long long fs3 = __builtin_amdgcn_s_memtime();
-#endif
+        PG_TS_CLOCK(fs3);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");     // (waits for the wave's stores, writes the L2 back)
-#ifdef PG_TILE_STATS
-        if (threadIdx.x == 0) {      // [9] waiting for whole diagonals, [10] for the neighbours, [11] acquire + tile, [12] release
-            const View Jv = load_view(jobs + T.x);
-            if (3 * (Jv.Lx + Jv.Ly) >= 4096) {
-            unsigned long long *out = (unsigned long long *)(jobs[T.x].trace + ((3 * (Jv.Lx + Jv.Ly) - 64) & ~1));
-            atomicAdd(out + 9, fs1 - fs0); atomicAdd(out + 10, fs2 - fs1); atomicAdd(out + 11, fs3 - fs2);
-            atomicAdd(out + 12, __builtin_amdgcn_s_memtime() - fs3);
-            }
-        }
-#endif
+        PG_TS_FLOW_END(jobs + T.x, fs0, fs1, fs2, fs3);
         if (threadIdx.x == 0) {
             __hip_atomic_store(&done[idx], TDONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_fetch_add(&fin[t], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -29,38 +29,45 @@ WAIT_KINDS = {0: "asm loop entries / diagonals run in it (M)", 1: "loader rows",
 ASSIST_WHY = ("slots", "a site's shape", "the other side", "the cell's shape or an edge from site 0", "a recent operand off the ring", "the pool")
 
 
-def layout(path=HEADER):
-    """{name: value} of the header's PG_ST_* constants (the plain `#define NAME integer` lines)."""
+def read_header(path, prefix, names, formulas):
+    """{name: value} of a statistics header's `prefix`* constants (the plain `#define NAME integer` lines); `names` and the
+    function-like macros `formulas` have to be among them (the tiled fill's recorder, dp_tiles_stats.h, is read with this too:
+    tools/probe_tile_stats.py)"""
     with open(path) as f:
         text = f.read()
-    found = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(PG_ST_[A-Z0-9_]+)\s+(\d+)\b", text, re.M)}
-    # ... and its two function-like macros of n3, as text (run_base, run_cap evaluate them)
-    found["formulas"] = {m.group(1): m.group(2) for m in re.finditer(r"^#define\s+(PG_ST_RUN_[A-Z]+)\(n3\)\s+(.+)$", text, re.M)}
-    missing = [n for n in NAMES if n not in found] + [n for n in ("PG_ST_RUN_BASE", "PG_ST_RUN_CAP") if n not in found["formulas"]]
+    found = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(%s[A-Z0-9_]+)\s+(\d+)\b" % prefix, text, re.M)}
+    # ... and its function-like macros of n3, as text (formula() evaluates them)
+    found["formulas"] = {m.group(1): m.group(2) for m in re.finditer(r"^#define\s+(%s[A-Z_]+)\(n3\)\s+(.+)$" % prefix, text, re.M)}
+    missing = [n for n in names if n not in found] + [n for n in formulas if n not in found["formulas"]]
     if missing:
-        raise KeyError("dp_pipe_stats.h does not define " + ", ".join(missing))
+        raise KeyError(os.path.basename(path) + " does not define " + ", ".join(missing))
     return found
 
 
-def _formula(name, n3, L):
+def layout(path=HEADER):
+    """{name: value} of the header's PG_ST_* constants"""
+    return read_header(path, "PG_ST_", NAMES, ("PG_ST_RUN_BASE", "PG_ST_RUN_CAP"))
+
+
+def formula(name, n3, L):
     """the header's function-like macro `name(n3)`, evaluated: its text with the constants put in (C's int division is Python's //
-    for the non-negative operands here; the one macro the other uses is expanded first)"""
+    for the non-negative operands here; a macro that another uses is expanded first)"""
     body = L["formulas"][name]
     for other, text in L["formulas"].items():
         body = body.replace("%s(n3)" % other, "(%s)" % text)
-    body = re.sub(r"PG_ST_[A-Z0-9_]+", lambda m: str(L[m.group(0)]), body).replace("/", "//")
+    body = re.sub(r"PG_[A-Z0-9_]+", lambda m: str(L[m.group(0)]), body).replace("/", "//")
     return eval(body, {"__builtins__": {}}, {"n3": n3})
 
 
 def run_base(n3, L):
     """first int of the per-run records' region (the header's PG_ST_RUN_BASE)"""
-    return _formula("PG_ST_RUN_BASE", n3, L)
+    return formula("PG_ST_RUN_BASE", n3, L)
 
 
 def run_cap(n3, L):
     """records per wave that fit in front of the reserve (the header's PG_ST_RUN_CAP; <= 0: none)"""
     # (C truncates a negative quotient towards zero, Python floors it: only the sign matters below zero, and it is the same)
-    return _formula("PG_ST_RUN_CAP", n3, L)
+    return formula("PG_ST_RUN_CAP", n3, L)
 
 
 def regions(n3, L):
