@@ -639,6 +639,76 @@ int64_t pagan_anc_fit_predict_bytes(int32_t n_leaves, int64_t columns, int32_t d
 int64_t pagan_msa_fit_branches(const pagan_msa *m, const pagan_anc_fit_opts *opts, double *branch_out, char *newick_out,
                                int64_t cap, pagan_anc_fit_info *info);
 
+/* ---- neighbour joining: the join loop on the device, the rooting and the printing on the host -------------------------
+ * (csrc/dp_nj.hip, csrc/host_nj.cpp; DESIGN.md "Neighbour joining").  The alternative to pagan_guide_upgma for lineages that do
+ * not keep a molecular clock.  The reference takes such trees from external programs (bppdist method=bionj, raxml, fasttree);
+ * none of that is restated.  Every operation below is an fp64 +, -, *, / in the order written, never contracted, so that a
+ * second reading reproduces every byte (tests/pycheck_nj.py).
+ *
+ * Input: pagan_guide_upgma's -- dist [n * n] read at [i * n + j] for i < j, finite and >= 0, names by the same rules;
+ * 2 <= n <= PAGAN_NJ_MAX_SEQS (the resident fp64 matrix is then 2 GiB).  Anything else: PAGAN_E_ARG before anything is allocated.
+ * Clusters: the leaves are clusters 0 .. n-1, the cluster join t = 0, 1, ... makes is n + t; r, the number of active clusters,
+ * starts at n; d(a, a) = 0.
+ * Row sums: R_i = sum_k d(i, k) in one fixed order: x[l] = sum_q d(i, 64 q + l), l = 0..63, from +0 with q ascending (the diagonal
+ * and indices >= n contribute the exact 0); then for s = 32, 16, 8, 4, 2, 1 in turn x[l] = x[l] + x[l + s] for all l < s;
+ * R_i = x[0].  After that R is carried forward and never summed again.
+ * A join, while r > 3: for active a, b with id a < id b, Q(a, b) = ((double)(r - 2) * d(a, b) - R_a) - R_b.  The pair of smallest Q
+ * is joined (ties: the lowest first id, then the lowest second id).  With i < j the joined ids and u = n + t:
+ *   len_i = d(i,j) / 2 + (R_i - R_j) / (2 * (double)(r - 2)),  len_j = d(i,j) - len_i   (raw: either may be negative);
+ *   for every other active k: d(u,k) = ((d(i,k) + d(j,k)) - d(i,j)) / 2,  R_k = ((R_k - d(i,k)) - d(j,k)) + d(u,k);
+ *   R_u = ((R_i + R_j) - (double)r * d(i,j)) / 2;  r decreases by one.
+ * The join record is (i, j, len_i, len_j).
+ * The star, at r = 3 (n >= 3), a < b < c the remaining ids: len_a = ((d(a,b) + d(a,c)) - d(b,c)) / 2,
+ * len_b = ((d(a,b) + d(b,c)) - d(a,c)) / 2, len_c = ((d(a,c) + d(b,c)) - d(a,b)) / 2, raw as well.  All three Q are equal at
+ * r = 3, so the star is never a join; the star node's id is 2 n - 3.  n = 2: no join and no star -- star_ids = {0, 1, -1},
+ * star_len = {d / 2, d / 2, 0}, and the tree is (name0:d/2,name1:d/2);
+ * Rooting (host only; every length first clamped to max(0, len), as UPGMA's are; a length that is not finite: PAGAN_E_ARG):
+ *   the tree hangs from the star node; low(v) is the smallest leaf index below v; a node's children are taken in ascending low;
+ *   far(leaf) = 0; for an internal v every child c offers far(c) + len(c), far(v) is the largest offer (a later child replaces an
+ *   earlier one only when strictly larger), the second largest offer is taken by the same rule among the other children, and
+ *   span(v) is the sum of the two.  The top node is the internal v of largest span, over the internal nodes in id order, a later
+ *   one winning only when strictly larger; half = span / 2.  From the top node descend along the child of the largest offer while
+ *   far(c) > half: the first c with far(c) <= half carries the root on the edge above it, below = min(max(half - far(c), 0), len(c))
+ *   on c's side and above = len(c) - below on the other; the rest of the tree is hung again from that point.  The star node
+ *   stays in the tree as an ordinary binary node (two children and the edge above it), also where above = 0 puts the root on it.
+ *   Printed as a rooted binary tree: the left child of every node is the one of smaller low; lengths %.17g.
+ *
+ * Device (pagan_nj_joins, pagan_nj_tree): the symmetric matrix is resident, rows contiguous; the active clusters are kept in the
+ * slots 0 .. r-1 (a join puts the new cluster in the lower of the pair's slots and the cluster of slot r-1 in the other).  A join
+ * is three dependent launches on one stream -- scan (a wave a row: the row's best (Q, lower id, higher id) over the slots after
+ * it), pick (one workgroup: the best row, the join record) and merge (a thread a slot: the new row and column, R) -- and all
+ * 3 (n - 3) of them are enqueued without waiting; the host synchronises once and downloads the log once.  One allocation a call.
+ * The caller's current device, left current; without a device PAGAN_E_NODEVICE for every n (there is no host path for the join
+ * loop); PAGAN_E_NOMEM / PAGAN_E_INTERNAL for a HIP error.  Device time: loop_ms is always measured, by two events; an event
+ * between any two launches costs about what a launch costs, so scan_ms, pick_ms and merge_ms are measured only with
+ * PAGAN_NJ_EVENTS=1 in the environment and are 0 otherwise.                                                                   */
+#define PAGAN_NJ_MAX_SEQS 16384
+typedef struct pagan_nj_info {
+    int32_t n;                   /* clusters at the start                                                        */
+    int32_t joins;               /* n - 3 (0 for n = 2)                                                          */
+    int32_t launches;            /* kernels enqueued: the row sums and three a join                              */
+    int32_t reserved;            /* 0                                                                            */
+    int64_t device_bytes;        /* what the call allocated on the device                                        */
+    int64_t scan_entries;        /* matrix entries the scans read, summed over the joins                         */
+    double  scan_ms, pick_ms, merge_ms;  /* device time of the stages, summed over the joins (PAGAN_NJ_EVENTS=1: an event
+                                    between any two launches; no launch waits for the host), 0 otherwise         */
+    double  loop_ms;             /* device time from the first scan to the last merge, two events                */
+    double  root_ms;             /* host time of pagan_nj_newick (pagan_nj_tree), 0 otherwise                    */
+} pagan_nj_info;
+/* The device half.  join_ids, join_len [(n - 3) * 2]: join t's (i, j) and (len_i, len_j) at [2 t], [2 t + 1] (may be NULL where
+ * n <= 3); star_ids, star_len [3] as defined above.  info may be NULL.                                                        */
+int     pagan_nj_joins(int32_t n, const double *dist, int32_t *join_ids, double *join_len, int32_t star_ids[3], double star_len[3],
+                       pagan_nj_info *info);
+/* Host only: clamps, roots and prints what pagan_nj_joins returned.  PAGAN_E_ARG also for joins that are no tree (an id that is
+ * not active at its join, i >= j, star ids that are not the three clusters left).  Returns what pagan_guide_upgma returns, under
+ * the same contract.                                                                                                          */
+int64_t pagan_nj_newick(int32_t n, const char *const *names, const int32_t *join_ids, const double *join_len,
+                        const int32_t star_ids[3], const double star_len[3], char *newick_out, int64_t cap);
+/* pagan_nj_joins, then pagan_nj_newick.  Returns as pagan_nj_newick. */
+int64_t pagan_nj_tree(int32_t n, const char *const *names, const double *dist, char *newick_out, int64_t cap, pagan_nj_info *info);
+/* Host only, exact: the device bytes a pagan_nj_joins call allocates for n clusters.  PAGAN_E_ARG beyond the limits. */
+int64_t pagan_nj_predict_bytes(int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,8 +12,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpagan_dp.so")
-SOURCES = ["dp_abi.hip", "dp_plan.cpp", "dp_kernels.hip", "dp_pipe.hip", "dp_tiles.hip", "dp_fb.hip", "dp_fb_plan.cpp", "dp_anchors.hip", "dp_parent.hip", "dp_guide.hip", "dp_alndist.hip", "dp_anc.hip", "host_model.cpp", "host_graph.cpp",
-           "host_anchors.cpp", "host_tree.cpp", "host_rows.cpp", "host_capi.cpp", "host_pileup.cpp", "host_guide.cpp", "host_anc.cpp"]
+SOURCES = ["dp_abi.hip", "dp_plan.cpp", "dp_kernels.hip", "dp_pipe.hip", "dp_tiles.hip", "dp_fb.hip", "dp_fb_plan.cpp", "dp_anchors.hip", "dp_parent.hip", "dp_guide.hip", "dp_alndist.hip", "dp_anc.hip", "dp_nj.hip", "host_model.cpp", "host_graph.cpp",
+           "host_anchors.cpp", "host_tree.cpp", "host_rows.cpp", "host_capi.cpp", "host_pileup.cpp", "host_guide.cpp", "host_anc.cpp", "host_nj.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-Wall", "-Wno-unused-result", "-Wno-unused-value", "-pthread"]
 

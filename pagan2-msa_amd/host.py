@@ -86,7 +86,15 @@ class CAncFitInfo(C.Structure):
                 ("fold_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class CNjInfo(C.Structure):
+    _fields_ = [("n", C.c_int32), ("joins", C.c_int32), ("launches", C.c_int32), ("reserved", C.c_int32),
+                ("device_bytes", C.c_int64), ("scan_entries", C.c_int64), ("scan_ms", C.c_double), ("pick_ms", C.c_double),
+                ("merge_ms", C.c_double), ("loop_ms", C.c_double), ("root_ms", C.c_double)]
+
+
 GUIDE_MAX_SEQS = 65536
+NJ_MAX_SEQS = 16384
+TREE_METHODS = ("upgma", "nj")
 GUIDE_PAIR_CHUNK = 64
 ALN_TILE = 64
 ALN_SPLIT_WORDS = 8
@@ -94,7 +102,8 @@ ALN_SPLIT_WORDS = 8
 # C struct name -> mirror, for every struct the two headers declare with a body
 STRUCTS = dict(abi.STRUCTS, pagan_msa_opts=CMsaOpts, pagan_node_info=CNodeInfo, pagan_msa_timing=CTiming,
                pagan_pileup_opts=CPileupOpts, pagan_pileup_step=CPileupStep, pagan_guide_info=CGuideInfo,
-               pagan_aln_info=CAlnInfo, pagan_anc_info=CAncInfo, pagan_anc_fit_opts=CAncFitOpts, pagan_anc_fit_info=CAncFitInfo)
+               pagan_aln_info=CAlnInfo, pagan_anc_info=CAncInfo, pagan_anc_fit_opts=CAncFitOpts, pagan_anc_fit_info=CAncFitInfo,
+               pagan_nj_info=CNjInfo)
 
 # Every entry point of include/pagan_host.h in the header's order: name -> (restype, (argtypes...)).  A new entry point is
 # one line here; tests/test_abi_cpu.py holds the table against the header's prototypes.
@@ -203,6 +212,10 @@ PROTOTYPES = {
     "pagan_anc_fit_branches": (cint, (i32, _i32p, _i32p, _f64p, cpp, i32, _f32p, C.POINTER(CAncFitOpts), _f64p, _f64p, i32, C.POINTER(CAncFitInfo))),
     "pagan_anc_fit_predict_bytes": (i64, (i32, i64, i32, i64)),
     "pagan_msa_fit_branches": (i64, (vp, C.POINTER(CAncFitOpts), _f64p, cp, i64, C.POINTER(CAncFitInfo))),
+    "pagan_nj_joins": (cint, (i32, _f64p, _i32p, _f64p, _i32p, _f64p, C.POINTER(CNjInfo))),
+    "pagan_nj_newick": (i64, (i32, cpp, _i32p, _f64p, _i32p, _f64p, cp, i64)),
+    "pagan_nj_tree": (i64, (i32, cpp, _f64p, cp, i64, C.POINTER(CNjInfo))),
+    "pagan_nj_predict_bytes": (i64, (i32,)),
 }
 HOST_EXPORTED = list(PROTOTYPES)
 
@@ -521,12 +534,22 @@ def _newick_call(call, what, names):
     raise RuntimeError("%s: the string's size changed between two calls" % what)
 
 
-def guide_tree(names, seqs, data_type=0, k=0, with_info=False):
+def _tree_method(method):
+    if method not in TREE_METHODS:
+        raise ValueError("the tree method is 'upgma' or 'nj'")
+    return method == "nj"
+
+
+def guide_tree(names, seqs, data_type=0, k=0, with_info=False, method="upgma"):
     """pagan_guide_tree: the rooted binary UPGMA tree over guide_distances' matrix as a Newick string (with_info: and the info
-    dict), ready for Msa."""
+    dict), ready for Msa.  method="nj": nj_tree over the same matrix (the info dict: guide_distances', with nj_tree's as "nj")."""
     n = len(names)
     if len(seqs) != n:
         raise ValueError("names and sequences differ in number")
+    if _tree_method(method):
+        _, _, dist, info = guide_distances(seqs, data_type, k)
+        newick, info["nj"] = nj_tree(names, dist, with_info=True)
+        return (newick, info) if with_info else newick
     na, sa = _c_strings(names), _c_strings(seqs)
     ci = CGuideInfo()
     L = _lib()
@@ -565,16 +588,75 @@ def aln_distances(rows, data_type=0):
     return both, match, dist, struct_dict(ci)
 
 
-def aln_tree(names, rows, data_type=0, with_info=False):
+def aln_tree(names, rows, data_type=0, with_info=False, method="upgma"):
     """pagan_aln_tree: the rooted binary UPGMA tree over aln_distances' matrix as a Newick string (with_info: and the info dict),
-    ready for Msa."""
+    ready for Msa.  method="nj": nj_tree over the same matrix (the info dict: aln_distances', with nj_tree's as "nj")."""
     n = len(names)
     if len(rows) != n:
         raise ValueError("names and rows differ in number")
+    if _tree_method(method):
+        _, _, dist, info = aln_distances(rows, data_type)
+        newick, info["nj"] = nj_tree(names, dist, with_info=True)
+        return (newick, info) if with_info else newick
     na, ra = _c_strings(names), _c_strings(rows)
     ci = CAlnInfo()
     L = _lib()
     newick = _newick_call(lambda buf, cap: L.pagan_aln_tree(n, na, ra, int(data_type), buf, cap, C.byref(ci)), "pagan_aln_tree", names)
+    return (newick, struct_dict(ci)) if with_info else newick
+
+
+def nj_predict_bytes(n):
+    """pagan_nj_predict_bytes (host only): the device bytes nj_joins allocates for n clusters, exactly."""
+    return check(_lib().pagan_nj_predict_bytes(int(n)), "pagan_nj_predict_bytes")
+
+
+def _nj_dist(n, dist):
+    d = np.ascontiguousarray(dist, np.float64)
+    if d.shape != (n, n):
+        raise ValueError("dist must be [%d, %d]" % (n, n))
+    return d
+
+
+def nj_joins(dist):
+    """pagan_nj_joins: the joins of neighbour joining over a distance matrix [n, n] (its upper triangle is read), made on the
+    current device: (join_ids [n - 3, 2] int32, join_len [n - 3, 2] float64, star_ids [3] int32, star_len [3] float64, info dict)
+    as include/pagan_host.h defines them; the lengths are raw."""
+    n = len(dist)
+    d = _nj_dist(n, dist)
+    joins = max(n - 3, 0)
+    ids, lens = np.zeros((joins, 2), np.int32), np.zeros((joins, 2), np.float64)
+    star_ids, star_len = np.zeros(3, np.int32), np.zeros(3, np.float64)
+    ci = CNjInfo()
+    check(_lib().pagan_nj_joins(n, _dp(d), _ip(ids) if joins else None, _dp(lens) if joins else None, _ip(star_ids), _dp(star_len),
+                                C.byref(ci)), "pagan_nj_joins")
+    return ids, lens, star_ids, star_len, struct_dict(ci)
+
+
+def nj_newick(names, join_ids, join_len, star_ids, star_len):
+    """pagan_nj_newick (host only): the joins' tree with its lengths clamped at 0, rooted at the midpoint of its longest path and
+    printed as a rooted binary Newick string, the left child of every node the one with the smaller lowest leaf."""
+    n = len(names)
+    joins = max(n - 3, 0)
+    ids = np.ascontiguousarray(join_ids, np.int32).reshape(-1)
+    lens = np.ascontiguousarray(join_len, np.float64).reshape(-1)
+    sid, slen = np.ascontiguousarray(star_ids, np.int32).reshape(-1), np.ascontiguousarray(star_len, np.float64).reshape(-1)
+    if len(ids) != 2 * joins or len(lens) != 2 * joins or len(sid) != 3 or len(slen) != 3:
+        raise ValueError("%d names take %d joins and a star of three" % (n, joins))
+    na = _c_strings(names)
+    L = _lib()
+    return _newick_call(lambda buf, cap: L.pagan_nj_newick(n, na, _ip(ids) if joins else None, _dp(lens) if joins else None, _ip(sid),
+                                                           _dp(slen), buf, cap), "pagan_nj_newick", names)
+
+
+def nj_tree(names, dist, with_info=False):
+    """pagan_nj_tree: nj_newick over nj_joins -- the rooted binary neighbour-joining tree over a distance matrix [n, n] as a
+    Newick string (with_info: and the info dict), ready for Msa."""
+    n = len(names)
+    d = _nj_dist(n, dist)
+    na = _c_strings(names)
+    ci = CNjInfo()
+    L = _lib()
+    newick = _newick_call(lambda buf, cap: L.pagan_nj_tree(n, na, _dp(d), buf, cap, C.byref(ci)), "pagan_nj_tree", names)
     return (newick, struct_dict(ci)) if with_info else newick
 
 
@@ -816,7 +898,7 @@ def dna_base_frequencies(seqs):
     return [c / total for c in counts]
 
 
-def align_refined(names, seqs, rounds=1, newick=None, branch_lengths=None, **msa_kwargs):
+def align_refined(names, seqs, rounds=1, newick=None, branch_lengths=None, tree_method="upgma", **msa_kwargs):
     """Align, read the guide tree off the alignment, align again on it: walks once exactly as Msa(names, seqs, newick,
     **msa_kwargs).align() does, then up to `rounds` times takes T = msa.alignment_tree() and walks again on T, stopping when
     T is the tree just walked (the walk is deterministic: a fixpoint).  Returns the last Msa (the earlier ones are closed) with
@@ -825,11 +907,14 @@ def align_refined(names, seqs, rounds=1, newick=None, branch_lengths=None, **msa
     branch_lengths="ml": T keeps alignment_tree()'s topology and takes its lengths from anc_fit_branches over the current
     alignment's rows, started from alignment_tree()'s lengths (DNA: under the walk's base frequencies); every history entry
     gains loglik (Msa.ancestral()'s, of the walk's alignment under the lengths it aligned with) and fit (status, rounds,
-    loglik_start, loglik_end of the fit that made its tree; None for the first walk)."""
+    loglik_start, loglik_end of the fit that made its tree; None for the first walk).
+    tree_method="nj": the first tree (where no newick is given) and every tree read off an alignment are neighbour-joining trees
+    (Msa's tree_method, alignment_tree's method); it composes with branch_lengths="ml"."""
     if branch_lengths not in (None, "ml"):
         raise ValueError("branch_lengths is None or 'ml'")
+    _tree_method(tree_method)
     ml = branch_lengths == "ml"
-    msa = Msa(names, seqs, newick, **msa_kwargs).align()
+    msa = Msa(names, seqs, newick, tree_method=tree_method, **msa_kwargs).align()
     history = []
 
     def record(m, before, fit=None):
@@ -841,7 +926,7 @@ def align_refined(names, seqs, rounds=1, newick=None, branch_lengths=None, **msa
             history[-1]["fit"] = None if fit is None else {k: fit["info"][k] for k in ("status", "rounds", "loglik_start", "loglik_end")}
     record(msa, None)
     for _ in range(int(rounds)):
-        tree, fit = msa.alignment_tree(), None
+        tree, fit = msa.alignment_tree(method=tree_method), None
         if ml:
             left, right, branch = newick_arrays(list(names), tree)
             data_type = msa.data_type
@@ -933,15 +1018,16 @@ class Msa(Handle):
     _destroy = "pagan_msa_destroy"
 
     def __init__(self, names, seqs, newick=None, sample_on_device=0, posterior_decode=0, decode_gap_weight=0.5, expected_counts=0,
-                 indel_model=None, **opts):
+                 indel_model=None, tree_method="upgma", **opts):
         """newick=None: the guide tree is made from the sequences (guide_tree with the walk's data_type, on the current
-        device); either way the tree walked is kept as self.newick.
+        device; tree_method="nj": by neighbour joining); either way the tree walked is kept as self.newick.
         opts: fields of pagan_msa_opts.  sample_on_device=1 (pagan_msa_set_sampler): with sample_path set, the nodes' paths
         are drawn by pg_fb_sample on the device instead of on the host behind a download of the forward matrix.
         posterior_decode=1 (pagan_msa_set_decoder): a node's result is the maximum expected accuracy path of its posteriors,
         gaps weighted by decode_gap_weight.  expected_counts=1 (pagan_msa_set_counts): every node's forward/backward pass also
         leaves its expected transition counts (node_counts, expected_counts).  indel_model=(ins_rate, del_rate, gap_ext,
         end_gap_ext) (pagan_msa_set_indel_model): the walk's indel model; a negative entry keeps the data type's default."""
+        _tree_method(tree_method)
         L = _lib()
         o = CMsaOpts()
         L.pagan_msa_default_opts(C.byref(o))
@@ -953,7 +1039,7 @@ class Msa(Handle):
         self.names = list(names)
         self._h = C.c_void_p()
         if newick is None:
-            newick = guide_tree(names, seqs, data_type=o.data_type)
+            newick = guide_tree(names, seqs, data_type=o.data_type, method=tree_method)
         self.newick = newick
         na, sa = _c_strings(names), _c_strings(seqs)
         check(L.pagan_msa_create(self.n, na, sa, newick.encode(), C.byref(o), C.byref(self._h)), "pagan_msa_create")
@@ -1134,9 +1220,13 @@ class Msa(Handle):
             rows.append(buf.raw[:n].decode())
         return rows
 
-    def alignment_tree(self, with_info=False):
+    def alignment_tree(self, with_info=False, method="upgma"):
         """pagan_msa_alignment_tree: the guide tree made from this walk's own alignment -- aln_tree over the leaf rows under the
-        walk's names and data type (with_info: and the info dict).  PaganError(PAGAN_E_ARG) before the rows exist."""
+        walk's names and data type (with_info: and the info dict).  PaganError(PAGAN_E_ARG) before the rows exist.
+        method="nj": aln_tree(method="nj") over the same rows."""
+        if _tree_method(method):
+            check(self._L.pagan_msa_alignment_length(self._h), "pagan_msa_alignment_tree")
+            return aln_tree(self.names, self.alignment(), data_type=self.data_type, with_info=with_info, method="nj")
         ci = CAlnInfo()
         newick = _newick_call(lambda buf, cap: self._L.pagan_msa_alignment_tree(self._h, buf, cap, C.byref(ci)),
                               "pagan_msa_alignment_tree", self.names)
