@@ -639,6 +639,113 @@ int64_t pagan_anc_fit_predict_bytes(int32_t n_leaves, int64_t columns, int32_t d
 int64_t pagan_msa_fit_branches(const pagan_msa *m, const pagan_anc_fit_opts *opts, double *branch_out, char *newick_out,
                                int64_t cap, pagan_anc_fit_info *info);
 
+/* ---- tree search by nearest-neighbour interchange: the gains of every edge at once on the device, the search on the host --
+ * (csrc/dp_anc_nni.inc, csrc/host_anc.cpp; DESIGN.md "Tree search by nearest-neighbour interchange").  The reference gets its
+ * likelihood trees from external programs (raxml, fasttree: src/utils/raxml_tree.*, fasttree_tree.*); none of that is restated.
+ *
+ * The model, the tree rules, the leaf encoding, P(t), L, O, the message and the rescaling are exactly those of "ancestral states by
+ * marginal likelihood" above: m_x[s] = sum_t P(t_x)[s][t] L_x[t], t ascending, the exact 1 for a child without data.  The two passes
+ * are that section's, unchanged.
+ * Candidates, by internal node c = n + k.  Ordinary: c is internal and its parent v is not the root; a = left[c], d = right[c], b
+ * is c's sibling; T[s] = O_v[s], P_mid = P(t_c).  Root edge: both children rl = left[root], rr = right[root] of the root are
+ * internal; one candidate, at c = rl; a = left[rl], d = right[rl], e = left[rr], b = right[rr]; T[s] = pi[s] * m_e[s],
+ * P_mid = pagan_anc_pmatrix(t_rl + t_rr), one matrix made on the host like any other (with the model's reversibility this is full
+ * pruning of the rearranged tree; the three arrangements share P_mid and are consistent with one another).  Every other internal
+ * node has no candidate: a swap around a child of the root whose sibling is a leaf, or around the root, only re-roots the tree.
+ * Per column, for the arrangement k = 0 (as is), k = 1 (a and b exchanged), k = 2 (d and b exchanged):
+ *   u_0[t] = m_a[t] * m_d[t], u_1[t] = m_b[t] * m_d[t], u_2[t] = m_a[t] * m_b[t];  X_0 = m_b, X_1 = m_a, X_2 = m_d;
+ *   y_k[s] = sum_t P_mid[s][t] u_k[t], t ascending from 0 -- and the exact 1 for every s where neither of the two nodes u_k is
+ *   made of holds data in the column: they are the children of a node without data, which contributes the exact factor 1 as it
+ *   does in the up pass (rows of P sum to 1 only to a few 1e-15);  f_k = sum_s (T[s] * X_k[s]) * y_k[s], s ascending from 0.
+ * L and O enter as the passes left them: every f_k holds each vector once, so the powers of two cancel in the quotient and are
+ * never applied.  Ratio, k = 1, 2: where f_0 > 0 and f_k > 0, r_k = f_k / f_0; otherwise r_k is the exact 1 and the column counts
+ * in degenerate[c][k].  Columns past the end of the alignment give the exact 1 and count nowhere.
+ * Column product, without a logarithm on the device: (m, e) = frexp(r).  Columns 64 q .. 64 q + 63 are block q; for d = 32, 16, 8,
+ * 4, 2, 1 in turn and every i < d: m[i] = m[i] * m[i + d], (m[i], de) = frexp(m[i]), e[i] = e[i] + e[i + d] + de; the block's pair
+ * is (m[0], e[0]).  The blocks are multiplied left to right in the same way onto a running pair (M, E) that starts at (0.5, 1):
+ * M = M * m_q, (M, de) = frexp(M), E = E + e_q + de.  The running pair survives from chunk to chunk, so (M, E) is the same bytes
+ * for every chunk size.  On the host gain[c][k] = log(M) + E * log(2): the log likelihood of arrangement k minus that of the tree
+ * as it is, at the branch lengths as they are.
+ * Applying a swap (host only): branch[] is indexed by node id and does not change -- lengths travel with their subtrees.  k = 1
+ * puts b into c's left slot and a into the slot b had; k = 2 does the same with c's right slot and d.  The internal nodes are then
+ * renumbered in post-order (left subtree, right subtree, the node; leaves keep their ids), so that children come before parents
+ * again and the root is 2n - 2; perm[old id] = new id.
+ * Selecting swaps (host only, arithmetic on the gains): a candidate's better k is 1 unless gain[c][2] > gain[c][1]; it qualifies
+ * when degenerate is 0 for that k and that gain exceeds min_gain.  The qualifying candidates are taken in order of descending gain
+ * (ties: the lower c first); one is skipped when an endpoint of its edge -- {c, v}, for the root edge {rl, rr, root} -- belongs to
+ * an edge already taken.
+ * Search: the up pass gives ll of the start tree.  A round: the down pass, the gains, the selection.  Nothing selected: CONVERGED.
+ * Otherwise all selected swaps are applied (their edges share no node, so they are applied on the round's ids in the order
+ * selected and renumbered once) and an up pass gives the new tree's loglik; where that is lower than ll, the first selected swap
+ * is applied alone (its gain is the exact difference up to rounding), and where that is lower too the search ends STALLED at the
+ * round's start tree.  With fit_rounds > 0 the accepted tree's lengths then get pagan_anc_fit_branches' own loop, capped at
+ * fit_rounds rounds, and ll becomes its loglik_end -- unless that is lower than ll, which only the fit's start can cause (it
+ * first brings every length within [t_min, t_max]): then the tree keeps the lengths it has.  After max_rounds rounds: MAX_ROUNDS.  The accepted logliks never decrease,
+ * and with fit_rounds = 0 each is bit for bit pagan_anc_reconstruct's loglik of that tree.
+ * The rows are uploaded and encoded once a call; when the tree changes, the node table, the candidate table and the matrices are
+ * uploaded again.  Device, errors: as for pagan_anc_fit_branches -- no host path.                                              */
+#define PAGAN_ANC_NNI_CONVERGED  0
+#define PAGAN_ANC_NNI_MAX_ROUNDS 1
+#define PAGAN_ANC_NNI_STALLED    2
+typedef struct pagan_anc_nni_opts {
+    double  min_gain;            /* a swap must gain more than this: 1e-3; >= 0                                  */
+    double  t_min, t_max, tol;   /* of the fit (pagan_anc_fit_opts): 1e-6, 10, 1e-6                              */
+    int32_t max_rounds;          /* 32; >= 0                                                                     */
+    int32_t fit_rounds;          /* rounds of the fit after every accepted round: 0 (no fit); >= 0               */
+    int32_t reserved;            /* 0                                                                            */
+} pagan_anc_nni_opts;
+typedef struct pagan_anc_nni_info {
+    int32_t status;              /* PAGAN_ANC_NNI_* (pagan_anc_nni_gains: 0)                                     */
+    int32_t rounds;              /* gain evaluations made                                                        */
+    int32_t up_passes;           /* up passes over the whole alignment, the fit's included                       */
+    int32_t chunks;              /* column chunks of one pass                                                    */
+    int32_t data_type, states;   /* as pagan_anc_info                                                            */
+    int32_t candidates;          /* of the last evaluation's tree                                                */
+    int32_t swaps;               /* swaps applied                                                                */
+    int64_t columns, chunk_cols;
+    int64_t device_bytes;        /* what the call allocated on the device                                        */
+    double  loglik_start, loglik_end;
+    double  encode_ms, up_ms, down_ms, nni_ms, fold_ms;      /* device time of the stages, summed over the call  */
+    double  fit_ms;              /* device time of the fit's branch sums and their fold                          */
+    double  total_ms;            /* host wall time of the call                                                   */
+} pagan_anc_nni_info;
+typedef struct pagan_anc_nni_swap {
+    int32_t round;               /* the round that applied it, from 0                                            */
+    int32_t node;                /* c, in that round's ids                                                       */
+    int32_t k;                   /* 1 or 2                                                                       */
+    int32_t joint;               /* 1: applied together with the round's other swaps; 0: alone, after those lowered the loglik */
+    double  gain;
+} pagan_anc_nni_swap;
+/* One evaluation on the device, by internal node (row k: node n + k): kind [n-1] (0 no candidate, 1 ordinary, 2 the root edge);
+ * M, gain [(n-1) * 2] and E, degenerate [(n-1) * 2] at [2 k] for arrangement 1 and [2 k + 1] for arrangement 2 -- (0.5, 1), gain 0
+ * and 0 where there is no candidate; loglik as pagan_anc_reconstruct's.  Any output may be NULL.  info: rounds 1, up_passes 1.  */
+int     pagan_anc_nni_gains(int32_t n_leaves, const int32_t *left, const int32_t *right, const double *branch,
+                            const char *const *rows, int32_t data_type, const float *base_freq, int32_t *kind, double *M,
+                            int64_t *E, double *gain, int64_t *degenerate, double *loglik, pagan_anc_nni_info *info);
+/* Host only.  The swap k (1 or 2) at the candidate `node`, then the renumbering: left_out, right_out [n-1], branch_out [2n-1],
+ * perm [2n-1] (may be NULL).  PAGAN_E_TREE as pagan_anc_check_tree; PAGAN_E_ARG for a node without a candidate or another k.   */
+int     pagan_anc_nni_apply(int32_t n_leaves, const int32_t *left, const int32_t *right, const double *branch, int32_t node,
+                            int32_t k, int32_t *left_out, int32_t *right_out, double *branch_out, int32_t *perm);
+/* Host only.  The selection above from gain, degenerate [(n-1) * 2]: nodes_out, k_out [n-1] in the order taken; returns how many,
+ * or PAGAN_E_ARG (a null array, min_gain negative or not a number), PAGAN_E_TREE.                                              */
+int     pagan_anc_nni_select(int32_t n_leaves, const int32_t *left, const int32_t *right, const double *gain,
+                             const int64_t *degenerate, double min_gain, int32_t *nodes_out, int32_t *k_out);
+/* The search.  opts NULL: the defaults; PAGAN_E_ARG for a value outside the ranges above.  left_out, right_out [n-1], branch_out
+ * [2n-1]: the final tree.  loglik_hist [hist_cap] (may be NULL): the accepted logliks, the start first; the call returns how many
+ * there are (accepted rounds + 1; only the first hist_cap are written), or a negative code.  swaps [swap_cap] (may be NULL): the
+ * swaps applied, in order; *n_swaps how many there are (only the first swap_cap are written).                                  */
+int     pagan_anc_nni_search(int32_t n_leaves, const int32_t *left, const int32_t *right, const double *branch,
+                             const char *const *rows, int32_t data_type, const float *base_freq, const pagan_anc_nni_opts *opts,
+                             int32_t *left_out, int32_t *right_out, double *branch_out, double *loglik_hist, int32_t hist_cap,
+                             pagan_anc_nni_swap *swaps, int32_t swap_cap, int32_t *n_swaps, pagan_anc_nni_info *info);
+/* Host only.  Device bytes of a pagan_anc_nni_search or pagan_anc_nni_gains call, under pagan_anc_fit_predict_bytes' contract. */
+int64_t pagan_anc_nni_predict_bytes(int32_t n_leaves, int64_t columns, int32_t data_type, int64_t chunk_cols);
+/* The search over a finished walk, from its tree and the lengths it aligned under, as pagan_msa_fit_branches takes them.
+ * newick_out: the tree found under the walk's names, lengths %.17g; returns the bytes the string needs with its NUL (> cap: the
+ * string was not written), or a negative code.  The walk itself is not changed.  PAGAN_E_ARG before the rows exist.            */
+int64_t pagan_msa_search_tree(const pagan_msa *m, const pagan_anc_nni_opts *opts, char *newick_out, int64_t cap,
+                              pagan_anc_nni_info *info);
+
 /* ---- neighbour joining: the join loop on the device, the rooting and the printing on the host -------------------------
  * (csrc/dp_nj.hip, csrc/host_nj.cpp; DESIGN.md "Neighbour joining").  The alternative to pagan_guide_upgma for lineages that do
  * not keep a molecular clock.  The reference takes such trees from external programs (bppdist method=bionj, raxml, fasttree);

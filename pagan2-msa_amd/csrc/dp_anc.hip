@@ -439,3 +439,4 @@ int pagan_anc_reconstruct(int32_t n_leaves, const int32_t *left, const int32_t *
 } // extern "C"
 
 #include "dp_anc_brlen.inc"
+#include "dp_anc_nni.inc"

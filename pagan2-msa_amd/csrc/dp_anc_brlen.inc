@@ -170,7 +170,9 @@ struct BrlenRun {
     std::vector<double> P, PT, D1T, D2T, lik;
     std::vector<int32_t> nodes, branches, expo;
     bool out_has_done = false;
+    int extra_matrices = 0;         // (set before setup) room behind the matrices of the distinct lengths that set_lengths leaves alone
 
+    void set_tree(const int32_t *left_, const int32_t *right_);
     int setup(int32_t n_, const int32_t *left_, const int32_t *right_, const double *branch, const char *const *rows, int32_t data_type, const float *base_freq);
     int set_lengths(const double *branch);
     int pass(Mode mode, double *loglik);
@@ -183,7 +185,7 @@ int BrlenRun::setup(int32_t n_, const int32_t *left_, const int32_t *right_, con
     if (rc != PAGAN_OK) return rc;
     rc = anc_check_tree(n_, left_, right_, branch);
     if (rc != PAGAN_OK) return rc;
-    n = n_; in = n - 1; nb = 2 * n - 2; left = left_; right = right_;
+    n = n_; in = n - 1; nb = 2 * n - 2;
     S = anc_states(type); cpc = type == 3 ? 3 : 1;
     if (chars % cpc) return PAGAN_E_ARG;
     L = chars / cpc;
@@ -191,18 +193,10 @@ int BrlenRun::setup(int32_t n_, const int32_t *left_, const int32_t *right_, con
     C = anc_chunk_cols(n, L, S, 0, AncSwitches::read());
     chunks = std::max<int64_t>(1, (L + C - 1) / C);
     if ((uint64_t)(C / 64) * (uint64_t)nb > 0x7fffffffull) return PAGAN_E_ARG;       // pa_branch's grid
-    lay = AncFitLayout(n, S, cpc, C, chunks, nb);
+    lay = AncFitLayout(n, S, cpc, C, chunks, nb + extra_matrices);
     std::memset(&info, 0, sizeof(info));
     info.data_type = type; info.states = S; info.columns = L; info.chunk_cols = C; info.chunks = (int32_t)chunks; info.device_bytes = (int64_t)lay.total;
-    nodes.assign((size_t)5 * in, -1);
-    branches.assign((size_t)5 * nb, 0);
-    for (int k = 0; k < in; ++k) {
-        nodes[k] = left[k]; nodes[(size_t)in + k] = right[k];
-        for (int side = 0; side < 2; ++side) {
-            const int32_t c = side ? right[k] : left[k], b = side ? left[k] : right[k];
-            branches[c] = c; branches[(size_t)nb + c] = k; branches[(size_t)2 * nb + c] = b;      // (branch c: the one above node c)
-        }
-    }
+    set_tree(left_, right_);
     lik.resize((size_t)C); expo.resize((size_t)C);
 
     int ndev = 0, device = -1;
@@ -236,6 +230,21 @@ int BrlenRun::setup(int32_t n_, const int32_t *left_, const int32_t *right_, con
         info.encode_ms += ms;
     }
     return PAGAN_OK;
+}
+
+// the topology's half of the node and branch tables (set_lengths fills in the matrices); out_has follows the tree
+void BrlenRun::set_tree(const int32_t *left_, const int32_t *right_) {
+    left = left_; right = right_;
+    nodes.assign((size_t)5 * in, -1);
+    branches.assign((size_t)5 * nb, 0);
+    for (int k = 0; k < in; ++k) {
+        nodes[k] = left[k]; nodes[(size_t)in + k] = right[k];
+        for (int side = 0; side < 2; ++side) {
+            const int32_t c = side ? right[k] : left[k], b = side ? left[k] : right[k];
+            branches[c] = c; branches[(size_t)nb + c] = k; branches[(size_t)2 * nb + c] = b;      // (branch c: the one above node c)
+        }
+    }
+    out_has_done = false;
 }
 
 // the matrices of these lengths, one set per distinct length, and the tables that name them; the stream is idle on entry and on return
@@ -364,25 +373,21 @@ int branch_derivs(int32_t n, const int32_t *left, const int32_t *right, const do
     return PAGAN_OK;
 }
 
-int fit_branches(int32_t n, const int32_t *left, const int32_t *right, const double *branch_in, const char *const *rows, int32_t data_type,
-                 const float *base_freq, const pagan_anc_fit_opts *opts, double *branch_out, double *hist_out, int32_t hist_cap, pagan_anc_fit_info *info_out) {
-    const double t0 = wall_s();
-    pagan_anc_fit_opts o{1e-6, 10.0, 1e-6, 32, 0};
-    if (opts) o = *opts;
-    if (!(o.t_min > 0) || !(o.t_max >= o.t_min) || !std::isfinite(o.t_max) || !(o.tol >= 0) || o.max_rounds < 0 || hist_cap < 0) return PAGAN_E_ARG;
-    BrlenRun R;
-    int rc = R.setup(n, left, right, branch_in, rows, data_type, base_freq);
-    if (rc != PAGAN_OK) return rc;
-    const int nb = R.nb, rl = left[n - 2], rr = right[n - 2];
+// The fit's loop on a run that is set up: from branch_in, at most o.max_rounds rounds.  t [2n-1] the lengths it ends at, hist the
+// accepted logliks (the start first), ll the last of them.
+int fit_loop(BrlenRun &R, const pagan_anc_fit_opts &o, const double *branch_in, std::vector<double> &t, std::vector<double> &hist, double *ll_out, int *status_out) {
+    int rc;
+    const int n = R.n, nb = R.nb, rl = R.left[n - 2], rr = R.right[n - 2];
     auto bounded = [&](double x) { return std::min(std::max(x, o.t_min), o.t_max); };
     // the parameters: every branch but the root's two, and tau in their place; p is the root's proportion of branch_in
-    std::vector<double> t(branch_in, branch_in + nb + 1), step((size_t)nb + 1), cand((size_t)nb + 1), g1((size_t)nb + 1), g2((size_t)nb + 1);
+    std::vector<double> step((size_t)nb + 1), cand((size_t)nb + 1), g1((size_t)nb + 1), g2((size_t)nb + 1);
+    t.assign(branch_in, branch_in + nb + 1);
     t[nb] = 0.0;
     const double tau_in = branch_in[rl] + branch_in[rr], p = tau_in > 0 ? branch_in[rl] / tau_in : 0.5;
     auto split = [&](double tau, std::vector<double> &to) { to[rl] = tau * p; to[rr] = tau - to[rl]; };
     for (int c = 0; c < nb; ++c) if (c != rl && c != rr) t[c] = bounded(t[c]);
     if (bounded(tau_in) != tau_in) split(bounded(tau_in), t);
-    std::vector<double> hist;
+    hist.clear();
     double ll = 0.0;
     if ((rc = R.set_lengths(t.data())) != PAGAN_OK) return rc;
     if ((rc = R.pass(BrlenRun::UP_ONLY, &ll)) != PAGAN_OK) return rc;
@@ -414,6 +419,27 @@ int fit_branches(int32_t n, const int32_t *left, const int32_t *right, const dou
         t = cand; ll = llc;
         hist.push_back(ll);
     }
+    *ll_out = ll; *status_out = status;
+    return PAGAN_OK;
+}
+
+inline bool fit_opts_ok(const pagan_anc_fit_opts &o) {
+    return o.t_min > 0 && o.t_max >= o.t_min && std::isfinite(o.t_max) && o.tol >= 0 && o.max_rounds >= 0;
+}
+
+int fit_branches(int32_t n, const int32_t *left, const int32_t *right, const double *branch_in, const char *const *rows, int32_t data_type,
+                 const float *base_freq, const pagan_anc_fit_opts *opts, double *branch_out, double *hist_out, int32_t hist_cap, pagan_anc_fit_info *info_out) {
+    const double t0 = wall_s();
+    pagan_anc_fit_opts o{1e-6, 10.0, 1e-6, 32, 0};
+    if (opts) o = *opts;
+    if (!fit_opts_ok(o) || hist_cap < 0) return PAGAN_E_ARG;
+    BrlenRun R;
+    int rc = R.setup(n, left, right, branch_in, rows, data_type, base_freq);
+    if (rc != PAGAN_OK) return rc;
+    std::vector<double> t, hist;
+    double ll = 0.0;
+    int status = 0;
+    if ((rc = fit_loop(R, o, branch_in, t, hist, &ll, &status)) != PAGAN_OK) return rc;
     if (branch_out) std::copy(t.begin(), t.end(), branch_out);
     for (size_t k = 0; k < hist.size() && (int64_t)k < hist_cap && hist_out; ++k) hist_out[k] = hist[k];
     R.info.status = status; R.info.loglik_start = hist.front(); R.info.loglik_end = ll;

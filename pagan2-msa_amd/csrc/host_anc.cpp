@@ -180,6 +180,92 @@ AncFitLayout::AncFitLayout(int64_t n, int S, int chars_per_col, int64_t C, int64
     total = c.cur;
 }
 
+AncNniLayout::AncNniLayout(int64_t n, int64_t C) {
+    pgdev::Carve c{nullptr};
+    const size_t in = (size_t)(n - 1), blocks = (size_t)C / 64;
+    cand = c.skip((size_t)kNniCandFields * in * sizeof(int32_t));
+    block_m = c.skip(blocks * 2 * in * sizeof(double));
+    block_e = c.skip(blocks * 4 * in * sizeof(int32_t));
+    run_m = c.skip(2 * in * sizeof(double));
+    run_e = c.skip(4 * in * sizeof(int64_t));
+    total = c.cur;
+}
+
+void nni_kinds(int32_t n, const int32_t *left, const int32_t *right, int32_t *kind, int32_t *parent) {
+    const int32_t root = 2 * n - 2;
+    std::vector<int32_t> par((size_t)2 * n - 1, -1);
+    for (int k = 0; k < n - 1; ++k) par[left[k]] = par[right[k]] = n + k;
+    for (int k = 0; k < n - 1; ++k) kind[k] = n + k != root && par[n + k] != root ? 1 : 0;
+    if (n >= 3 && left[n - 2] >= n && right[n - 2] >= n) kind[left[n - 2] - n] = 2;
+    if (parent) std::copy(par.begin(), par.end(), parent);
+}
+
+void nni_swap_in_place(int32_t n, std::vector<int32_t> &left, std::vector<int32_t> &right, int32_t node, int32_t k) {
+    const int32_t rl = left[n - 2], rr = right[n - 2];
+    std::vector<int32_t> &slot = k == 1 ? left : right;            // c's slot that takes b; what it held goes where b was
+    if (node == rl && rr >= n) {                                   // the root edge: b = right[rr]
+        std::swap(slot[node - n], right[rr - n]);
+        return;
+    }
+    int32_t v = -1;
+    for (int q = 0; q < n - 1 && v < 0; ++q) if (left[q] == node || right[q] == node) v = n + q;
+    std::vector<int32_t> &sib = left[v - n] == node ? right : left;
+    std::swap(slot[node - n], sib[v - n]);
+}
+
+void nni_renumber(int32_t n, const std::vector<int32_t> &left, const std::vector<int32_t> &right, const double *branch,
+                  int32_t *left_out, int32_t *right_out, double *branch_out, int32_t *perm) {
+    std::vector<int32_t> id((size_t)2 * n - 1, -1);
+    for (int k = 0; k < n; ++k) id[k] = k;
+    int32_t next = n;
+    std::vector<std::pair<int32_t, int>> stack{{2 * n - 2, 0}};      // (old id, children visited)
+    while (!stack.empty()) {
+        auto &[v, stage] = stack.back();
+        if (v < n) { stack.pop_back(); continue; }
+        if (stage == 0) { stage = 1; stack.push_back({left[v - n], 0}); continue; }
+        if (stage == 1) { stage = 2; stack.push_back({right[v - n], 0}); continue; }
+        id[v] = next++;
+        stack.pop_back();
+    }
+    for (int k = 0; k < n - 1; ++k) {
+        left_out[id[n + k] - n] = id[left[k]];
+        right_out[id[n + k] - n] = id[right[k]];
+    }
+    for (int v = 0; v < 2 * n - 1; ++v) {
+        branch_out[id[v]] = branch[v];
+        if (perm) perm[v] = id[v];
+    }
+}
+
+int nni_select(int32_t n, const int32_t *left, const int32_t *right, const double *gain, const int64_t *degenerate, double min_gain,
+               int32_t *nodes_out, int32_t *k_out) {
+    const int in = n - 1;
+    std::vector<int32_t> kind(in), parent((size_t)2 * n - 1);
+    nni_kinds(n, left, right, kind.data(), parent.data());
+    struct Pick { double gain; int32_t c, k; };
+    std::vector<Pick> picks;
+    for (int q = 0; q < in; ++q) {
+        if (!kind[q]) continue;
+        const int k = gain[2 * q + 1] > gain[2 * q] ? 2 : 1;
+        const double g = gain[2 * q + k - 1];
+        if (degenerate[2 * q + k - 1] == 0 && g > min_gain) picks.push_back({g, n + q, k});
+    }
+    std::stable_sort(picks.begin(), picks.end(), [](const Pick &x, const Pick &y) { return x.gain > y.gain; });   // (ties: the lower c stays first)
+    std::vector<char> taken((size_t)2 * n - 1, 0);
+    int count = 0;
+    for (const Pick &p : picks) {
+        int32_t ends[3] = {p.c, parent[p.c], -1};
+        if (kind[p.c - n] == 2) { ends[1] = right[n - 2]; ends[2] = 2 * n - 2; }
+        bool free_edge = true;
+        for (const int32_t e : ends) if (e >= 0 && taken[e]) free_edge = false;
+        if (!free_edge) continue;
+        for (const int32_t e : ends) if (e >= 0) taken[e] = 1;
+        nodes_out[count] = p.c; k_out[count] = p.k;
+        ++count;
+    }
+    return count;
+}
+
 } // namespace pagan
 
 using namespace pagan;
@@ -273,6 +359,51 @@ int64_t pagan_anc_fit_predict_bytes(int32_t n_leaves, int64_t columns, int32_t d
     if (!S || n_leaves < 2 || n_leaves > PAGAN_GUIDE_MAX_SEQS || columns < 0 || columns >= (1ll << 31)) return PAGAN_E_ARG;
     const int64_t C = anc_chunk_cols(n_leaves, columns, S, chunk_cols, AncSwitches::read());
     return (int64_t)AncFitLayout(n_leaves, S, data_type == 3 ? 3 : 1, C, std::max<int64_t>(1, (columns + C - 1) / C), 2 * (int64_t)n_leaves - 2).total;
+}
+
+int pagan_anc_nni_apply(int32_t n_leaves, const int32_t *left, const int32_t *right, const double *branch, int32_t node, int32_t k,
+                        int32_t *left_out, int32_t *right_out, double *branch_out, int32_t *perm) {
+    try {
+        const int rc = anc_check_tree(n_leaves, left, right, branch);
+        if (rc != PAGAN_OK) return rc;
+        const int32_t n = n_leaves;
+        if (!left_out || !right_out || !branch_out || node < n || node > 2 * n - 2 || (k != 1 && k != 2)) return PAGAN_E_ARG;
+        std::vector<int32_t> kind((size_t)n - 1), l(left, left + n - 1), r(right, right + n - 1);
+        nni_kinds(n, left, right, kind.data(), nullptr);
+        if (!kind[node - n]) return PAGAN_E_ARG;
+        nni_swap_in_place(n, l, r, node, k);
+        std::vector<int32_t> lo((size_t)n - 1), ro((size_t)n - 1);   // (the outputs may be the inputs)
+        std::vector<double> bo((size_t)2 * n - 1);
+        std::vector<int32_t> pm((size_t)2 * n - 1);
+        nni_renumber(n, l, r, branch, lo.data(), ro.data(), bo.data(), pm.data());
+        bo[(size_t)2 * n - 2] = 0.0;
+        std::copy(lo.begin(), lo.end(), left_out); std::copy(ro.begin(), ro.end(), right_out); std::copy(bo.begin(), bo.end(), branch_out);
+        if (perm) std::copy(pm.begin(), pm.end(), perm);
+        return PAGAN_OK;
+    } catch (const std::bad_alloc &) {
+        return PAGAN_E_NOMEM;
+    }
+}
+
+int pagan_anc_nni_select(int32_t n_leaves, const int32_t *left, const int32_t *right, const double *gain, const int64_t *degenerate,
+                         double min_gain, int32_t *nodes_out, int32_t *k_out) {
+    try {
+        if (n_leaves < 2 || !left || !right || !gain || !degenerate || !nodes_out || !k_out || !(min_gain >= 0)) return PAGAN_E_ARG;
+        std::vector<double> no_lengths((size_t)2 * n_leaves - 1, 0.0);
+        const int rc = anc_check_tree(n_leaves, left, right, no_lengths.data());
+        if (rc != PAGAN_OK) return rc;
+        return nni_select(n_leaves, left, right, gain, degenerate, min_gain, nodes_out, k_out);
+    } catch (const std::bad_alloc &) {
+        return PAGAN_E_NOMEM;
+    }
+}
+
+int64_t pagan_anc_nni_predict_bytes(int32_t n_leaves, int64_t columns, int32_t data_type, int64_t chunk_cols) {
+    const int S = anc_states(data_type);
+    if (!S || n_leaves < 2 || n_leaves > PAGAN_GUIDE_MAX_SEQS || columns < 0 || columns >= (1ll << 31)) return PAGAN_E_ARG;
+    const int64_t C = anc_chunk_cols(n_leaves, columns, S, chunk_cols, AncSwitches::read());
+    return (int64_t)(AncFitLayout(n_leaves, S, data_type == 3 ? 3 : 1, C, std::max<int64_t>(1, (columns + C - 1) / C), 2 * (int64_t)n_leaves - 1).total +
+                     AncNniLayout(n_leaves, C).total);
 }
 
 } // extern "C"

@@ -52,6 +52,28 @@ struct AncFitLayout {
     AncFitLayout(int64_t n, int S, int chars_per_col, int64_t C, int64_t chunks, int64_t matrices);
 };
 
+// ---- tree search by nearest-neighbour interchange (include/pagan_host.h, "tree search by nearest-neighbour interchange") ----
+constexpr int kNniCandFields = 11;   // the candidate table's rows: a, d, b, e (-1: ordinary), the matrices of a, d, b, e, P_mid's,
+                                     // the parent's index among the internal nodes (-1: the root edge), the node c itself
+
+// what a search keeps beside the fit's buffers (AncFitLayout with one matrix more, for the root edge's P_mid), in an allocation
+// of its own.  in = n - 1 slots for the candidates, whatever the tree.
+struct AncNniLayout {
+    size_t cand, block_m, block_e, run_m, run_e, total;    // [11][in] int32, [C/64][2][in] fp64, [C/64][4][in] int32, [2][in] fp64, [4][in] int64
+    AncNniLayout(int64_t n, int64_t C);
+};
+
+// kind [n-1] by internal node: 0 no candidate, 1 ordinary, 2 the root edge (at left[root]); parent [2n-1] (the root's -1) may be null
+void nni_kinds(int32_t n, const int32_t *left, const int32_t *right, int32_t *kind, int32_t *parent);
+// one swap in place, on ids that stay (no renumbering); node and k are taken as valid
+void nni_swap_in_place(int32_t n, std::vector<int32_t> &left, std::vector<int32_t> &right, int32_t node, int32_t k);
+// the internal nodes renumbered in post-order (left subtree, right subtree, the node); perm [2n-1]: the new id of every old one
+void nni_renumber(int32_t n, const std::vector<int32_t> &left, const std::vector<int32_t> &right, const double *branch,
+                  int32_t *left_out, int32_t *right_out, double *branch_out, int32_t *perm);
+// the selection; nodes_out, k_out [n-1]; returns how many
+int nni_select(int32_t n, const int32_t *left, const int32_t *right, const double *gain, const int64_t *degenerate, double min_gain,
+               int32_t *nodes_out, int32_t *k_out);
+
 } // namespace pagan
 
 #endif

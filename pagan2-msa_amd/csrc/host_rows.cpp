@@ -346,6 +346,53 @@ int64_t pagan_msa_fit_branches(const pagan_msa *m, const pagan_anc_fit_opts *opt
     }
 }
 
+// ---- tree search by nearest-neighbour interchange (csrc/dp_anc_nni.inc) over the finished walk -----------------------------
+// pagan_msa_fit_branches' inputs; the tree found is printed from its arrays, since its topology is no longer the walk's.
+int64_t pagan_msa_search_tree(const pagan_msa *m, const pagan_anc_nni_opts *opts, char *newick_out, int64_t cap, pagan_anc_nni_info *info) {
+    if (!m || !m->aligned || (cap > 0 && !newick_out)) return PAGAN_E_ARG;
+    if (const int rc = rows_of(m)) return rc;
+    try {
+        const int n = m->n_leaves;
+        std::vector<int32_t> left(n - 1), right(n - 1);
+        std::vector<double> branch((size_t)2 * n - 1, 0.0);
+        std::vector<const char *> rows(n);
+        for (int k = 0; k < n - 1; ++k) {
+            const TreeNode &t = m->tree[m->tree_of_id[n + k]];
+            left[k] = m->id_of_tree[t.left]; right[k] = m->id_of_tree[t.right];
+        }
+        for (int id = 0; id < 2 * n - 1; ++id) branch[id] = m->tree[m->tree_of_id[id]].dist;
+        for (int k = 0; k < n; ++k) rows[k] = m->rows[k].c_str();
+        float bf[4] = {0.25f, 0.25f, 0.25f, 0.25f};
+        if (m->mf.type == kDna) for (int k = 0; k < 4; ++k) bf[k] = (float)m->mf.pi[k];
+        std::vector<int32_t> lo(n - 1), ro(n - 1);
+        std::vector<double> bo((size_t)2 * n - 1, 0.0);
+        const int rc = pagan_anc_nni_search(n, left.data(), right.data(), branch.data(), rows.data(), pagan_msa_data_type(m), bf, opts, lo.data(),
+                                            ro.data(), bo.data(), nullptr, 0, nullptr, 0, nullptr, info);
+        if (rc < 0) return rc;
+        // children come before parents: a node's text is made of its children's
+        std::vector<std::string> text((size_t)2 * n - 1);
+        char num[40];
+        for (int k = 0; k < n; ++k) text[k] = m->names[k];
+        for (int k = 0; k < n - 1; ++k) {
+            std::string &out = text[(size_t)n + k];
+            out = "(";
+            for (const int32_t c : {lo[k], ro[k]}) {
+                out += text[c];
+                text[c].clear();
+                std::snprintf(num, sizeof(num), ":%.17g", bo[c]);
+                out += num;
+                out += c == lo[k] ? "," : ")";
+            }
+        }
+        const std::string out = text[(size_t)2 * n - 2] + ";";
+        const int64_t need = (int64_t)out.size() + 1;
+        if (need <= cap) std::memcpy(newick_out, out.c_str(), (size_t)need);
+        return need;
+    } catch (const std::bad_alloc &) {
+        return PAGAN_E_NOMEM;
+    }
+}
+
 void *pagan_msa_node_graph(const pagan_msa *m, int32_t node) {
     if (!m || node < 0 || node >= (int)m->graph.size()) return nullptr;
     if (!m->graph[node] && m->done[node]) {                        // (an imported node's graph: built when somebody asks for it)

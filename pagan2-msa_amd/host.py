@@ -86,6 +86,24 @@ class CAncFitInfo(C.Structure):
                 ("fold_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class CAncNniOpts(C.Structure):
+    _fields_ = [("min_gain", C.c_double), ("t_min", C.c_double), ("t_max", C.c_double), ("tol", C.c_double),
+                ("max_rounds", C.c_int32), ("fit_rounds", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CAncNniInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("rounds", C.c_int32), ("up_passes", C.c_int32), ("chunks", C.c_int32),
+                ("data_type", C.c_int32), ("states", C.c_int32), ("candidates", C.c_int32), ("swaps", C.c_int32),
+                ("columns", C.c_int64), ("chunk_cols", C.c_int64), ("device_bytes", C.c_int64),
+                ("loglik_start", C.c_double), ("loglik_end", C.c_double),
+                ("encode_ms", C.c_double), ("up_ms", C.c_double), ("down_ms", C.c_double), ("nni_ms", C.c_double),
+                ("fold_ms", C.c_double), ("fit_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class CAncNniSwap(C.Structure):
+    _fields_ = [("round", C.c_int32), ("node", C.c_int32), ("k", C.c_int32), ("joint", C.c_int32), ("gain", C.c_double)]
+
+
 class CNjInfo(C.Structure):
     _fields_ = [("n", C.c_int32), ("joins", C.c_int32), ("launches", C.c_int32), ("reserved", C.c_int32),
                 ("device_bytes", C.c_int64), ("scan_entries", C.c_int64), ("scan_ms", C.c_double), ("pick_ms", C.c_double),
@@ -103,7 +121,7 @@ ALN_SPLIT_WORDS = 8
 STRUCTS = dict(abi.STRUCTS, pagan_msa_opts=CMsaOpts, pagan_node_info=CNodeInfo, pagan_msa_timing=CTiming,
                pagan_pileup_opts=CPileupOpts, pagan_pileup_step=CPileupStep, pagan_guide_info=CGuideInfo,
                pagan_aln_info=CAlnInfo, pagan_anc_info=CAncInfo, pagan_anc_fit_opts=CAncFitOpts, pagan_anc_fit_info=CAncFitInfo,
-               pagan_nj_info=CNjInfo)
+               pagan_anc_nni_opts=CAncNniOpts, pagan_anc_nni_info=CAncNniInfo, pagan_anc_nni_swap=CAncNniSwap, pagan_nj_info=CNjInfo)
 
 # Every entry point of include/pagan_host.h in the header's order: name -> (restype, (argtypes...)).  A new entry point is
 # one line here; tests/test_abi_cpu.py holds the table against the header's prototypes.
@@ -212,6 +230,13 @@ PROTOTYPES = {
     "pagan_anc_fit_branches": (cint, (i32, _i32p, _i32p, _f64p, cpp, i32, _f32p, C.POINTER(CAncFitOpts), _f64p, _f64p, i32, C.POINTER(CAncFitInfo))),
     "pagan_anc_fit_predict_bytes": (i64, (i32, i64, i32, i64)),
     "pagan_msa_fit_branches": (i64, (vp, C.POINTER(CAncFitOpts), _f64p, cp, i64, C.POINTER(CAncFitInfo))),
+    "pagan_anc_nni_gains": (cint, (i32, _i32p, _i32p, _f64p, cpp, i32, _f32p, _i32p, _f64p, _i64p, _f64p, _i64p, _f64p, C.POINTER(CAncNniInfo))),
+    "pagan_anc_nni_apply": (cint, (i32, _i32p, _i32p, _f64p, i32, i32, _i32p, _i32p, _f64p, _i32p)),
+    "pagan_anc_nni_select": (cint, (i32, _i32p, _i32p, _f64p, _i64p, f64, _i32p, _i32p)),
+    "pagan_anc_nni_search": (cint, (i32, _i32p, _i32p, _f64p, cpp, i32, _f32p, C.POINTER(CAncNniOpts), _i32p, _i32p, _f64p, _f64p, i32,
+                                    C.POINTER(CAncNniSwap), i32, _i32p, C.POINTER(CAncNniInfo))),
+    "pagan_anc_nni_predict_bytes": (i64, (i32, i64, i32, i64)),
+    "pagan_msa_search_tree": (i64, (vp, C.POINTER(CAncNniOpts), cp, i64, C.POINTER(CAncNniInfo))),
     "pagan_nj_joins": (cint, (i32, _f64p, _i32p, _f64p, _i32p, _f64p, C.POINTER(CNjInfo))),
     "pagan_nj_newick": (i64, (i32, cpp, _i32p, _f64p, _i32p, _f64p, cp, i64)),
     "pagan_nj_tree": (i64, (i32, cpp, _f64p, cp, i64, C.POINTER(CNjInfo))),
@@ -813,6 +838,90 @@ def anc_fit_predict_bytes(n_leaves, columns, data_type, chunk_cols=0):
     return check(_lib().pagan_anc_fit_predict_bytes(int(n_leaves), int(columns), int(data_type), int(chunk_cols)), "pagan_anc_fit_predict_bytes")
 
 
+ANC_NNI_CONVERGED, ANC_NNI_MAX_ROUNDS, ANC_NNI_STALLED = 0, 1, 2
+ANC_NNI_FIT_ROUNDS = 8           # align_refined(tree_search="nni", branch_lengths="ml"): the fit's rounds after every accepted round
+ANC_NNI_STATUS = {ANC_NNI_CONVERGED: "converged", ANC_NNI_MAX_ROUNDS: "max_rounds", ANC_NNI_STALLED: "stalled"}
+
+
+def _anc_nni_opts(min_gain, max_rounds, fit_rounds, t_min, t_max, tol):
+    return CAncNniOpts(float(min_gain), float(t_min), float(t_max), float(tol), int(max_rounds), int(fit_rounds), 0)
+
+
+def _anc_nni_info(ci):
+    info = struct_dict(ci)
+    info["status"] = ANC_NNI_STATUS.get(info["status"], info["status"])
+    return info
+
+
+def anc_nni_gains(left, right, branch, rows, data_type=0, base_freq=None):
+    """pagan_anc_nni_gains: the log likelihood gains of both nearest-neighbour interchanges around every internal edge, one
+    evaluation on the current device.  Returns a dict, row k for internal node n + k: kind (int32 [n - 1]: 0 no candidate, 1
+    ordinary, 2 the root edge), M, gain (float64) and E, degenerate (int64) [n - 1, 2] (column 0: a and b exchanged, column 1:
+    d and b); loglik (anc_reconstruct's); info."""
+    n, le, ri, br = _anc_tree_args(left, right, branch, rows)
+    _keep, bfp = _base_freq(base_freq)
+    kind = np.zeros(n - 1, np.int32)
+    M, gain = np.zeros((n - 1, 2), np.float64), np.zeros((n - 1, 2), np.float64)
+    E, deg = np.zeros((n - 1, 2), np.int64), np.zeros((n - 1, 2), np.int64)
+    loglik, ci = C.c_double(0.0), CAncNniInfo()
+    check(_lib().pagan_anc_nni_gains(n, _ip(le), _ip(ri), _dp(br), _c_strings(rows), int(data_type), bfp, _ip(kind), _dp(M),
+                                     E.ctypes.data_as(_i64p), _dp(gain), deg.ctypes.data_as(_i64p), C.byref(loglik), C.byref(ci)),
+          "pagan_anc_nni_gains")
+    return {"kind": kind, "M": M, "E": E, "gain": gain, "degenerate": deg, "loglik": loglik.value, "info": _anc_nni_info(ci)}
+
+
+def anc_nni_apply(left, right, branch, node, k):
+    """pagan_anc_nni_apply (host only): the swap k (1: a and b, 2: d and b) at the candidate `node`, the internal nodes renumbered in
+    post-order.  Returns (left, right, branch, perm) as lists; perm[old id] = new id."""
+    le, ri = np.ascontiguousarray(left, np.int32), np.ascontiguousarray(right, np.int32)
+    br = np.ascontiguousarray(branch, np.float64)
+    n = len(le) + 1
+    if len(ri) != n - 1 or len(br) != 2 * n - 1:
+        raise ValueError("left, right hold n - 1 entries and branch 2 n - 1")
+    lo, ro, bo, perm = np.zeros(n - 1, np.int32), np.zeros(n - 1, np.int32), np.zeros(2 * n - 1, np.float64), np.zeros(2 * n - 1, np.int32)
+    check(_lib().pagan_anc_nni_apply(n, _ip(le), _ip(ri), _dp(br), int(node), int(k), _ip(lo), _ip(ro), _dp(bo), _ip(perm)), "pagan_anc_nni_apply")
+    return [int(x) for x in lo], [int(x) for x in ro], [float(x) for x in bo], [int(x) for x in perm]
+
+
+def anc_nni_select(left, right, gain, degenerate, min_gain=1e-3):
+    """pagan_anc_nni_select (host only): the swaps a round applies, from gain and degenerate [n - 1, 2] as anc_nni_gains returns
+    them: [(node, k)] in the order taken -- descending gain, no two edges sharing a node."""
+    le, ri = np.ascontiguousarray(left, np.int32), np.ascontiguousarray(right, np.int32)
+    n = len(le) + 1
+    g, d = np.ascontiguousarray(gain, np.float64).reshape(-1), np.ascontiguousarray(degenerate, np.int64).reshape(-1)
+    if len(ri) != n - 1 or len(g) != 2 * (n - 1) or len(d) != 2 * (n - 1):
+        raise ValueError("left, right hold n - 1 entries, gain and degenerate (n - 1) x 2")
+    nodes, ks = np.zeros(n - 1, np.int32), np.zeros(n - 1, np.int32)
+    count = check(_lib().pagan_anc_nni_select(n, _ip(le), _ip(ri), _dp(g), d.ctypes.data_as(_i64p), float(min_gain), _ip(nodes), _ip(ks)),
+                  "pagan_anc_nni_select")
+    return [(int(nodes[i]), int(ks[i])) for i in range(count)]
+
+
+def anc_nni_search(left, right, branch, rows, data_type=0, base_freq=None, min_gain=1e-3, max_rounds=32, fit_rounds=0, t_min=1e-6,
+                   t_max=10.0, tol=1e-6):
+    """pagan_anc_nni_search: the likelihood tree search by nearest-neighbour interchanges from the given tree, on the current device.
+    Returns a dict: left, right, branch (the final tree, lists), loglik (the accepted log likelihoods, the start first: never
+    decreasing), swaps (dicts: round, node in that round's ids, k, joint, gain), info (status as "converged" / "max_rounds" /
+    "stalled", rounds, swaps, loglik_start, loglik_end, the stages' device ms, ...)."""
+    n, le, ri, br = _anc_tree_args(left, right, branch, rows)
+    _keep, bfp = _base_freq(base_freq)
+    o = _anc_nni_opts(min_gain, max_rounds, fit_rounds, t_min, t_max, tol)
+    rounds = int(max(max_rounds, 0))
+    lo, ro, bo = np.zeros(n - 1, np.int32), np.zeros(n - 1, np.int32), np.zeros(2 * n - 1, np.float64)
+    hist, ci, count = np.zeros(rounds + 1, np.float64), CAncNniInfo(), C.c_int32(0)
+    cap = rounds * max(n - 1, 1)
+    swaps = (CAncNniSwap * max(cap, 1))()
+    k = check(_lib().pagan_anc_nni_search(n, _ip(le), _ip(ri), _dp(br), _c_strings(rows), int(data_type), bfp, C.byref(o), _ip(lo), _ip(ro),
+                                          _dp(bo), _dp(hist), len(hist), swaps, cap, C.byref(count), C.byref(ci)), "pagan_anc_nni_search")
+    return {"left": [int(x) for x in lo], "right": [int(x) for x in ro], "branch": [float(x) for x in bo], "loglik": hist[:k].copy(),
+            "swaps": [struct_dict(swaps[i]) for i in range(min(count.value, cap))], "info": _anc_nni_info(ci)}
+
+
+def anc_nni_predict_bytes(n_leaves, columns, data_type, chunk_cols=0):
+    """pagan_anc_nni_predict_bytes (host only): device bytes anc_nni_search or anc_nni_gains allocates at most."""
+    return check(_lib().pagan_anc_nni_predict_bytes(int(n_leaves), int(columns), int(data_type), int(chunk_cols)), "pagan_anc_nni_predict_bytes")
+
+
 class Ancestral:
     """What Msa.ancestral() leaves: loglik, col_loglik [L], best / best_p [n - 1, L], info, and the overlaid rows."""
 
@@ -898,7 +1007,7 @@ def dna_base_frequencies(seqs):
     return [c / total for c in counts]
 
 
-def align_refined(names, seqs, rounds=1, newick=None, branch_lengths=None, tree_method="upgma", **msa_kwargs):
+def align_refined(names, seqs, rounds=1, newick=None, branch_lengths=None, tree_method="upgma", tree_search=None, **msa_kwargs):
     """Align, read the guide tree off the alignment, align again on it: walks once exactly as Msa(names, seqs, newick,
     **msa_kwargs).align() does, then up to `rounds` times takes T = msa.alignment_tree() and walks again on T, stopping when
     T is the tree just walked (the walk is deterministic: a fixpoint).  Returns the last Msa (the earlier ones are closed) with
@@ -909,35 +1018,49 @@ def align_refined(names, seqs, rounds=1, newick=None, branch_lengths=None, tree_
     gains loglik (Msa.ancestral()'s, of the walk's alignment under the lengths it aligned with) and fit (status, rounds,
     loglik_start, loglik_end of the fit that made its tree; None for the first walk).
     tree_method="nj": the first tree (where no newick is given) and every tree read off an alignment are neighbour-joining trees
-    (Msa's tree_method, alignment_tree's method); it composes with branch_lengths="ml"."""
+    (Msa's tree_method, alignment_tree's method); it composes with branch_lengths="ml".
+    tree_search="nni": after T is read off the alignment (and fitted, with branch_lengths="ml"), anc_nni_search runs from T over the
+    current alignment's rows -- with "ml" with fit_rounds=ANC_NNI_FIT_ROUNDS, so that every accepted tree's lengths are fitted -- and
+    the walk goes on the tree it finds; every history entry gains search (status, rounds, swaps, loglik_start, loglik_end of the
+    search that made its tree; None for the first walk)."""
     if branch_lengths not in (None, "ml"):
         raise ValueError("branch_lengths is None or 'ml'")
+    if tree_search not in (None, "nni"):
+        raise ValueError("tree_search is None or 'nni'")
     _tree_method(tree_method)
     ml = branch_lengths == "ml"
     msa = Msa(names, seqs, newick, tree_method=tree_method, **msa_kwargs).align()
     history = []
 
-    def record(m, before, fit=None):
+    def record(m, before, fit=None, search=None):
         history.append({"newick": m.newick, "alignment_length": len(m.alignment()[0]),
                         "score": float(sum(m.node_info(k).score for k in range(m.n_internal))),
                         "changed_clades": 0 if before is None else differing_clades(m.newick, before)})
         if ml:
             history[-1]["loglik"] = m.ancestral().loglik
             history[-1]["fit"] = None if fit is None else {k: fit["info"][k] for k in ("status", "rounds", "loglik_start", "loglik_end")}
+        if tree_search:
+            history[-1]["search"] = None if search is None else {k: search["info"][k] for k in ("status", "rounds", "swaps", "loglik_start", "loglik_end")}
     record(msa, None)
     for _ in range(int(rounds)):
-        tree, fit = msa.alignment_tree(method=tree_method), None
-        if ml:
+        tree, fit, search = msa.alignment_tree(method=tree_method), None, None
+        if ml or tree_search:
             left, right, branch = newick_arrays(list(names), tree)
             data_type = msa.data_type
-            fit = anc_fit_branches(left, right, branch, msa.alignment(), data_type, dna_base_frequencies(seqs) if data_type == 1 else None)
-            tree = arrays_newick(list(names), left, right, fit["branch"])
+            base_freq = dna_base_frequencies(seqs) if data_type == 1 else None
+        if ml:
+            fit = anc_fit_branches(left, right, branch, msa.alignment(), data_type, base_freq)
+            branch = fit["branch"]
+            tree = arrays_newick(list(names), left, right, branch)
+        if tree_search:
+            search = anc_nni_search(left, right, branch, msa.alignment(), data_type, base_freq, fit_rounds=ANC_NNI_FIT_ROUNDS if ml else 0)
+            tree = arrays_newick(list(names), search["left"], search["right"], search["branch"])
         if tree == msa.newick:
             break
         before = msa.newick
         msa.close()
         msa = Msa(names, seqs, tree, **msa_kwargs).align()
-        record(msa, before, fit)
+        record(msa, before, fit, search)
     msa.history = history
     return msa
 
@@ -1258,6 +1381,15 @@ class Msa(Handle):
         newick = _newick_call(lambda buf, cap: self._L.pagan_msa_fit_branches(self._h, C.byref(o), _dp(out), buf, cap, C.byref(ci)),
                               "pagan_msa_fit_branches", self.names)
         return {"branch": out, "newick": newick, "info": _anc_fit_info(ci)}
+
+    def search_tree(self, min_gain=1e-3, max_rounds=32, fit_rounds=0, t_min=1e-6, t_max=10.0, tol=1e-6):
+        """pagan_msa_search_tree: anc_nni_search over the finished walk's alignment, from its tree and the lengths it aligned
+        under, on the current device.  Returns a dict: newick (the tree found, under the walk's names), info (anc_nni_search's).
+        The walk itself is not changed."""
+        o, ci = _anc_nni_opts(min_gain, max_rounds, fit_rounds, t_min, t_max, tol), CAncNniInfo()
+        newick = _newick_call(lambda buf, cap: self._L.pagan_msa_search_tree(self._h, C.byref(o), buf, cap, C.byref(ci)),
+                              "pagan_msa_search_tree", self.names)
+        return {"newick": newick, "info": _anc_nni_info(ci)}
 
     def alignment_all(self):
         """Rows of every node: leaves 0..n-1, then the internal nodes (ancestors) in alignment order."""
