@@ -388,6 +388,13 @@ int64_t pagan_fb_counts_predict_bytes(int32_t left_sites, int32_t right_sites, i
 /* Host only: the device bytes pagan_fb_run takes for a pair (F and B at 24 B a cell each, the diagonals' index, the lists);
  * an estimate from above as far as the lists go (four edges a site).  A caller cuts a level's pairs into batches by it.      */
 int64_t pagan_fb_predict_bytes(int32_t left_sites, int32_t right_sites, const pagan_band *band);
+/* Host only: the same for a model of n_states states.  pagan_fb_predict_bytes allows for a score table of up to 211 x 211
+ * logs (8 B each); this adds what 8 * n_states^2 exceeds that by, and the pool's sixteenth of it -- 0 up to 211 states, about
+ * 30 MB for the codon table's 1892.  PAGAN_E_ARG for n_states < 1.                                                          */
+int64_t pagan_fb_predict_bytes_states(int32_t left_sites, int32_t right_sites, const pagan_band *band, int32_t n_states);
+/* the bytes the handle's pass asked of the device pool for its one arena (inputs, score table, F and B): what
+ * pagan_fb_predict_bytes_states estimates from above                                                                         */
+int  pagan_fb_device_bytes(const pagan_fb *fb, int64_t *bytes);
 /* Host only: n uniform numbers in [0, 1) with 53 bits, a pure function of (seed, node, s):
  *     mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31
  *     u[s] = (mix(mix(mix(seed) ^ node) ^ s) >> 11) / 2^53          (64-bit unsigned arithmetic; node sign-extended)
@@ -465,6 +472,9 @@ int  pagan_fb_decoded_result(pagan_fb_decoded *d, pagan_result *out);
 int  pagan_fb_decoded_dump(pagan_fb_decoded *d, double *dst);
 /* device time of the fill and of the trace, milliseconds: a batch's launches booked at its first pair, 0 at the others    */
 int  pagan_fb_decoded_ms(const pagan_fb_decoded *d, double ms[2]);
+/* diagnostic: the threads of the workgroup that filled the pair's matrix, and whether the ring instance it ran on looks the
+ * score table up on a match step (1: the table has an entry of probability 0; 0: no lookup is compiled, or the fill ran)     */
+int  pagan_fb_decoded_launch(const pagan_fb_decoded *d, int32_t *threads, int32_t *table_lookup);
 /* Host only: the fill a pair would take under the current environment: 1 pg_fb_ring_decode (two plain sequences, widest
  * diagonal <= 1,024 cells, PAGAN_FB_DECODE_RING not 0), 0 pg_fb_decode_fill                                                */
 int  pagan_fb_debug_decode_route(const pagan_graph *left, const pagan_graph *right, const pagan_band *band);

@@ -147,7 +147,7 @@ int     pagan_msa_set_batch_backend(pagan_msa *m, pagan_batch_fn fn, void *user)
  * first node.  Call before aligning.                                                                                        */
 int     pagan_msa_set_sampler(pagan_msa *m, int32_t on_device);
 /* Posterior decoding in the walk (a setter: pagan_msa_opts does not grow).  on = 1: there is no Viterbi batch, as under
- * sample_path; a unit's nodes go through pagan_fb_run_batch in sub-batches cut by pagan_fb_predict_bytes +
+ * sample_path; a unit's nodes go through pagan_fb_run_batch in sub-batches cut by pagan_fb_predict_bytes_states +
  * pagan_fb_decode_predict_bytes, each sub-batch through one pagan_fb_decode_batch(n, fbs, gap_weight, 0), and a node's result is
  * the replay of its maximum expected accuracy path (pagan_dp.h): score = log full probability, support along the decoded path,
  * a band whose full probability is 0 retried without the band.  Together with sample_path: PAGAN_E_ARG at align time; with the

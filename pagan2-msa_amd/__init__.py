@@ -157,6 +157,13 @@ class FullProbability(Handle):
         self.schedule = self._L.pagan_fb_schedule(self._h)   # 0 one-workgroup kernels, 1 blocks, 2 LDS ring (plain sequences), 3 deep ring (graph pairs in a tunnel)
         self.shape = (left.n_sites - 1, right.n_sites - 1, 3)
 
+    @property
+    def device_bytes(self):
+        """pagan_fb_device_bytes: what the pass asked of the device pool for its arena."""
+        n = C.c_int64()
+        check(self._L.pagan_fb_device_bytes(self._h, C.byref(n)), "pagan_fb_device_bytes")
+        return n.value
+
     def _dump(self, which):
         out = np.zeros(self.shape, np.float64)
         check(self._L.pagan_fb_dump(self._h, which, _dp(out)), "pagan_fb_dump")
@@ -325,6 +332,12 @@ class DecodedPath(Handle):
         out = np.zeros(self.shape, np.float64)
         check(self._L.pagan_fb_decoded_dump(self._h, _dp(out)), "pagan_fb_decoded_dump")
         return out
+
+    def launch(self):
+        """pagan_fb_decoded_launch: (threads of the fill's workgroup, the ring instance looked the score table up)."""
+        t, tab = C.c_int32(), C.c_int32()
+        check(self._L.pagan_fb_decoded_launch(self._h, C.byref(t), C.byref(tab)), "pagan_fb_decoded_launch")
+        return t.value, bool(tab.value)
 
     def ms(self):
         """Device ms of the fill and of the trace, booked at the batch's first pair."""
@@ -550,8 +563,11 @@ def sample_uniforms_path(seed, node, path, n):
     return u
 
 
-def fb_predict_bytes(left_sites, right_sites, band=None):
-    return lib().pagan_fb_predict_bytes(left_sites, right_sites, _band(band))
+def fb_predict_bytes(left_sites, right_sites, band=None, n_states=None):
+    """pagan_fb_predict_bytes; with n_states pagan_fb_predict_bytes_states (a score table beyond 211 x 211 counted)."""
+    if n_states is None:
+        return lib().pagan_fb_predict_bytes(left_sites, right_sites, _band(band))
+    return lib().pagan_fb_predict_bytes_states(left_sites, right_sites, _band(band), int(n_states))
 
 
 def debug_far(left, right, band=None):

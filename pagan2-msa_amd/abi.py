@@ -242,6 +242,8 @@ PROTOTYPES = {
     "pagan_fb_counts_ms": (cint, (vp, _f64p)),
     "pagan_fb_counts_predict_bytes": (i64, (i32, i32, i32)),
     "pagan_fb_predict_bytes": (i64, (i32, i32, bp)),
+    "pagan_fb_predict_bytes_states": (i64, (i32, i32, bp, i32)),
+    "pagan_fb_device_bytes": (cint, (vp, C.POINTER(C.c_int64))),
     "pagan_sample_uniforms": (cint, (u64, i32, i32, _f64p)),
     "pagan_sample_uniforms_path": (cint, (u64, i32, i32, i32, _f64p)),
     "pagan_fb_sample_paths_batch": (cint, (i32, vpp, u64, _i32p, i32, u32, vpp)),
@@ -260,6 +262,7 @@ PROTOTYPES = {
     "pagan_fb_decoded_result": (cint, (vp, rp)),
     "pagan_fb_decoded_dump": (cint, (vp, _f64p)),
     "pagan_fb_decoded_ms": (cint, (vp, _f64p)),
+    "pagan_fb_decoded_launch": (cint, (vp, _i32p, _i32p)),
     "pagan_fb_debug_decode_route": (cint, (gp, gp, bp)),
     "pagan_fb_decode_predict_bytes": (i64, (i32, i32, bp)),
     "pagan_fb_decoded_destroy": (None, (vp,)),

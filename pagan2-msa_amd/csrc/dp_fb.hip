@@ -932,6 +932,7 @@ struct pagan_fb {
     RowBand rb;
     char *arena = nullptr;
     size_t arena_cap = 0;
+    size_t arena_bytes = 0;                             // what fb_stage asked of the pool (pagan_fb_device_bytes)
     double *dF = nullptr, *dB = nullptr;
     double totals[2] = {0, 0};
     float kernel_ms[2] = {0, 0};                        // pg_fb_forward, pg_fb_backward (HIP events)
@@ -1081,7 +1082,7 @@ static int fb_stage(FbPlan &plan, const pagan_graph *left, const pagan_graph *ri
     const double th2 = fb_now();
     FB_TRY(hipMemcpy(fb->arena, stage.data(), in_bytes, hipMemcpyHostToDevice));
     st->t_host[0] += th1 - th0; st->t_host[1] = th2 - th1; st->t_host[2] = fb_now() - th2;
-    st->arena_bytes = lay.cur;
+    st->arena_bytes = fb->arena_bytes = lay.cur;
     return PAGAN_OK;
 }
 
@@ -1345,6 +1346,12 @@ int pagan_fb_run(const pagan_graph *left, const pagan_graph *right, const pagan_
 int pagan_fb_kernel_ms(const pagan_fb *fb, double ms[2]) {
     if (!fb || !ms) return PAGAN_E_ARG;
     ms[0] = fb->kernel_ms[0]; ms[1] = fb->kernel_ms[1];
+    return PAGAN_OK;
+}
+
+int pagan_fb_device_bytes(const pagan_fb *fb, int64_t *bytes) {
+    if (!fb || !bytes) return PAGAN_E_ARG;
+    *bytes = (int64_t)fb->arena_bytes;
     return PAGAN_OK;
 }
 
@@ -1986,6 +1993,7 @@ struct pagan_fb_decoded : FbPaths {
     size_t arena_cap = 0;
     float ms[2] = {0, 0};                               // fill, trace (HIP events), at the batch's first pair
     int schedule = 0;                                   // 0 pg_fb_decode_fill, 1 pg_fb_ring_decode
+    int threads = 0, tab = 0;                           // the fill launch's workgroup size; the ring instance looked the table up
     ~pagan_fb_decoded() { give_slab(fb_arena_pool, device, arena, arena_cap); }
 };
 
@@ -2052,6 +2060,7 @@ int pagan_fb_decode_batch(int32_t n, pagan_fb *const *fbs, double gap_weight, ui
     const PgFbDecode *recs = c.dev<const PgFbDecode>(o_recs);
     FB_DO(c.upload());
     FB_DO(c.begin());
+    for (int k = 0; k < n; ++k) { hs[k]->threads = block[k] ? block[k] : fill_block; hs[k]->tab = block[k] && !tabfin[k] ? 1 : 0; }
     if (n_fill > 0) hipLaunchKernelGGL(pg_fb_decode_fill, dim3((unsigned)n_fill), dim3((unsigned)fill_block), 0, nullptr, jobs, recs);
     for (int q = n_fill; q < n;) {
         const int b = block[order[q]], key = launch_key(order[q]);
@@ -2093,6 +2102,13 @@ int pagan_fb_decoded_summary(const pagan_fb_decoded *d, int32_t *status, double 
     if (n_steps) *n_steps = sm[FB_SUM_STEPS];
     if (counts) { counts[0] = sm[FB_SUM_M]; counts[1] = sm[FB_SUM_X]; counts[2] = sm[FB_SUM_Y]; }
     if (schedule) *schedule = d->schedule;
+    return PAGAN_OK;
+}
+
+int pagan_fb_decoded_launch(const pagan_fb_decoded *d, int32_t *threads, int32_t *table_lookup) {
+    if (!d) return PAGAN_E_ARG;
+    if (threads) *threads = d->threads;
+    if (table_lookup) *table_lookup = d->tab;
     return PAGAN_OK;
 }
 

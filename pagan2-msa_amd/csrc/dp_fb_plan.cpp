@@ -291,4 +291,14 @@ int64_t pagan_fb_predict_bytes(int32_t left_sites, int32_t right_sites, const pa
     return need + need / 16;
 }
 
+// The constant above was sized for the protein table (211 x 211 logs: 356,168 B of its 532,480); a larger table -- the codon
+// model's 1892 x 1892: 28,637,312 B -- comes on top, with the pool's sixteenth.
+int64_t pagan_fb_predict_bytes_states(int32_t left_sites, int32_t right_sites, const pagan_band *band, int32_t n_states) {
+    if (n_states < 1) return PAGAN_E_ARG;
+    const int64_t base = pagan_fb_predict_bytes(left_sites, right_sites, band);
+    if (base < 0) return base;
+    const int64_t more = std::max<int64_t>(0, 8 * (int64_t)n_states * n_states - 8 * 211 * 211);
+    return base + more + more / 16;
+}
+
 } // extern "C"

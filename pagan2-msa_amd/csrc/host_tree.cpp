@@ -168,7 +168,7 @@ int fb_cut(const pagan_msa *m, const FbMode &md, const std::vector<int> &ks, siz
     for (; *at < ks.size(); ++*at) {
         const NodeJob &j = m->work[ks[*at]].job;
         const pagan_band *band = j.band();
-        int64_t need = pagan_fb_predict_bytes(j.gl.n_sites, j.gr.n_sites, band);
+        int64_t need = pagan_fb_predict_bytes_states(j.gl.n_sites, j.gr.n_sites, band, m->mf.S);
         if (need < 0) return (int)need;
         if (md.decode) {
             const int64_t more = pagan_fb_decode_predict_bytes(j.gl.n_sites, j.gr.n_sites, band);

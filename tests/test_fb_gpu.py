@@ -8,6 +8,8 @@ import pytest
 import pagan2_msa_amd as pgm
 from pagan2_msa_amd import abi, host, synth
 
+import fb_tables
+
 pytestmark = pytest.mark.gpu
 LOG_TOL = 1e-9
 
@@ -270,4 +272,44 @@ def test_ring_sweeps_cell_by_cell(pg, oracle, monkeypatch):
         assert fb.groups == 0 and fb.log_fwd == f and fb.log_bwd == b
         _lf, _lb, post, _logf = oracle.fb(left, right, m, band=band)
         assert np.allclose(fb.posterior(), post, rtol=1e-7, atol=1e-12)
+        fb.close()
+
+
+def test_sweeps_under_the_codon_table(pg, oracle, monkeypatch):
+    """K1892 (fb_tables.py): two codon leaves, one with a stop codon, one with a partial last triplet, under the codon model's
+    1892 x 1892 table made asymmetric -- 28.6 MB of logs a pair, read from memory by every match.  The one-workgroup sweeps by
+    default; the LDS-ring sweeps with PAGAN_FB_RING_MIN_ND=0 (fb_score's branch for a table that is not in LDS).  Then K1892g,
+    the root job of a four-leaf codon walk under the same table."""
+    p = fb_tables.codon_leaf_pair(oracle)
+    assert p.mp.n_states == 1892 and not np.array_equal(p.mp.score, p.mp.score.T)
+    for env, schedule in (({}, 0), ({"PAGAN_FB_RING_MIN_ND": "0"}, 2)):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        assert pgm.fb_route(p.left, p.right, p.band)[0] == schedule
+        fb, _post, _logf = check_pair(oracle, *p.args())
+        assert fb.schedule == schedule
+        fb.close()
+    g = fb_tables.walk_root_pair(3, oracle)                      # K1892g: graph against graph, pair codes among the states
+    monkeypatch.delenv("PAGAN_FB_RING_MIN_ND")
+    fb, _post, _logf = check_pair(oracle, *g.args())
+    assert fb.schedule == 0
+    fb.close()
+
+
+def test_the_arena_fits_its_prediction(pg, oracle):
+    """What a pass asked of the device pool (pagan_fb_device_bytes) against what the walk cuts its sub-batches by, for a table of
+    15, 211 and 1892 states.  Up to 211 states pagan_fb_predict_bytes_states is pagan_fb_predict_bytes; the codon table's
+    28,637,312 B are beyond that function's constant.  "Taken" is what the pass asked of the pool; the prediction also holds
+    the pool's own allowance of a sixteenth, so the comparison has that much slack and does not pin the allowance itself."""
+    leaves = fb_tables.leaf_pairs()
+    for p in (leaves["R257"], leaves["Q257z"], fb_tables.codon_leaf_pair(oracle)):
+        S = p.mp.n_states
+        fb = pgm.FullProbability(*p.args())
+        taken = fb.device_bytes
+        old = pgm.fb_predict_bytes(p.left.n_sites, p.right.n_sites, p.band)
+        predicted = pgm.fb_predict_bytes(p.left.n_sites, p.right.n_sites, p.band, n_states=S)
+        print("S %d, %d x %d cells: the arena took %d B, predicted %d B (without the table's size: %d B)" % (S, p.Lx, p.Ly, taken, predicted, old))
+        assert taken >= 48 * fb.cells + 8 * S * S
+        assert taken <= predicted, (S, taken, predicted)
+        assert (predicted == old) == (S <= 211)
         fb.close()

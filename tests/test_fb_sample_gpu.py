@@ -14,6 +14,8 @@ import pytest
 import pagan2_msa_amd as pgm
 from pagan2_msa_amd import abi, host, synth
 
+import fb_tables
+
 pytestmark = pytest.mark.gpu
 LOG_TOL = 1e-9
 SEED = 5
@@ -45,6 +47,15 @@ def pairs(pg, oracle):
         out.append(Pair("B%d" % k, left, right, host.model_prob(1, msa.node_info(k).dist, base_freq=bf), band, 8 + k))
     multi = [int((np.diff(p.left.bwd_off) > 1).sum() + (np.diff(p.right.bwd_off) > 1).sum()) for p in out]
     assert multi[2] > 0 and multi[3] > 0, multi
+    # behind them (the tests above index the first four): tables of 211 and 1892 states, asymmetric, with zeros (fb_tables.py) --
+    # pg_fb_sample's score lookup from memory, which a symmetric table without a zero cannot tell from its transpose
+    extra = dict(fb_tables.leaf_pairs(), **fb_tables.graph_pairs())
+    extra["K1892"] = fb_tables.codon_leaf_pair(oracle)
+    extra["G211w"], extra["K1892g"] = fb_tables.walk_root_pair(2), fb_tables.walk_root_pair(3, oracle)
+    for node, name in enumerate(("Q64z", "G211", "G211z", "K1892", "G211w", "K1892g"), 20):
+        q = extra[name]
+        out.append(Pair(name, q.left, q.right, q.mp, q.band, node))
+        assert np.isfinite(out[-1].fb.log_fwd) and q.mp.n_states > 16
     for p in out:
         p.ref = []
         for q in range(N_REF):
@@ -72,7 +83,7 @@ def test_path_for_path_against_the_host_sampler(pg, oracle, pairs, n_paths):
             assert res.status == 0 and res.score == p.fb.log_fwd and res.same_alignment(want_res), (p.name, q)
             assert np.array_equal(res.cols, want_res.cols) and np.array_equal(res.left_used, want_res.left_used)
             assert np.array_equal(res.right_used, want_res.right_used)
-            if p.band is not None and n_paths == 200:        # B: the oracle's sampler on the same numbers, the same cells
+            if (p.band is not None or p.name == "K1892g") and n_paths == 200:        # B, K1892g: the oracle's sampler on the same numbers, the same cells
                 ocells, _end = oracle.sample_path(p.left, p.right, p.mp, p.ologf, u)
                 assert np.array_equal(got, ocells), (p.name, q)
         allv, alln = sp.visited_all()                        # one copy of the trace buffer: the same cells again
@@ -155,6 +166,31 @@ def test_summaries(pg, pairs):
         sp.close()
 
 
+def test_zero_entries_are_never_matched(pg, pairs):
+    """The pairs under a table with zeros: every path is drawn (status 0), no path holds a match cell whose entry is 0 -- while
+    the transposed entry of some matched cell is 0, so a transposed lookup would have had to refuse that step --, and on the leaf
+    pairs log_q is the path's probability from the table as [left state, right state]."""
+    for p in pairs:
+        if p.name not in ("Q64z", "G211z", "K1892"):
+            continue
+        sp = p.fb.sample_paths(SEED, p.node, N_REF)
+        sm = sp.summary()
+        assert np.all(sm["status"] == 0), (p.name, sm["status"])
+        transposed_zero = 0
+        for q in range(N_REF):
+            v = sp.visited(q)
+            m = v[v[:, 2] == 2]
+            a, b = p.left.state[m[:, 0]], p.right.state[m[:, 1]]
+            assert np.all(p.mp.score[a, b] > 0), (p.name, q)
+            transposed_zero += int((p.mp.score[b, a] == 0).sum())
+            if p.name != "G211z":
+                want = _log_q_of(p, sp.result(q).end[0], v)
+                assert abs(sm["log_q"][q] - want) <= LOG_TOL * max(1.0, abs(want)), (p.name, q, sm["log_q"][q], want)
+        print("%s: %d matched cells in %d paths whose transposed entry is 0" % (p.name, transposed_zero, N_REF))
+        assert transposed_zero > 0 or p.name == "K1892"         # (the codon table has no zero: its asymmetry shows in log_q)
+        sp.close()
+
+
 @pytest.mark.parametrize("which, K, seed, node", [(0, 4096, 11, 5), (0, 4096, 12, 5), (1, 2048, 21, 12), (2, 2048, 21, 13), (3, 2048, 21, 14)])
 def test_the_sampler_draws_from_the_posterior(pg, pairs, which, K, seed, node):
     """Visits of every (i, j, state) over K paths against the posterior of the same pass: |f - p| <= 5 sqrt(p (1 - p) / K) + 4 / K
@@ -221,10 +257,11 @@ def test_zero_probability_and_arguments(pg, pairs):
 
 
 def _walk_trees():
-    """the two trees of test_msa_fb_gpu.py"""
+    """the two trees of test_msa_fb_gpu.py, and four protein leaves of ~60 residues (211 states: the samplers' lookup from memory)"""
     a = synth.evolve_balanced(8, 400, branch=0.04, sub=0.04, indel_start=0.01, mean_len=4, seed=46)
     b = synth.evolve_balanced(4, 3000, branch=0.01, sub=0.01, indel_start=0.008, mean_len=4, seed=61)
-    return [(a, {"use_anchors": 0}), (b, {"use_anchors": 1})]
+    c = synth.evolve_balanced(4, 60, branch=0.08, sub=0.1, indel_start=0.03, mean_len=3, seed=57, alphabet=fb_tables.AA)
+    return [(a, {"use_anchors": 0}), (b, {"use_anchors": 1}), (c, {"use_anchors": 0, "data_type": 2})]
 
 
 def test_the_walk_samples_the_same_paths_on_the_device(pg):
@@ -246,3 +283,37 @@ def test_the_walk_samples_the_same_paths_on_the_device(pg):
                 assert np.float64(walk.node_info(k).score).tobytes() == np.float64(on_host.node_info(k).score).tobytes()
                 assert walk.node_support(k).tobytes() == on_host.node_support(k).tobytes(), k
                 assert walk.node_fb(k)[:2] == on_host.node_fb(k)[:2] and walk.node_fb(k)[3] >= 0
+
+
+def test_the_protein_walk_samples_every_node_as_the_stand_alone_chain(pg):
+    """Four protein leaves of ~60 residues (211 states: the samplers' score lookup reads memory) with sample_path=1, once on the
+    host sampler and once on the device's: every node of either walk is what the stand-alone chain gives on node_job(k) and
+    node_model_prob(k) -- FullProbability, then sample_path on pagan_sample_uniforms(seed, n + k, ...) and path 0 of sample_paths
+    under the same key --, columns, used edges, score and support."""
+    names, seqs, nwk = synth.evolve_balanced(4, 60, branch=0.08, sub=0.1, indel_start=0.03, mean_len=3, seed=57, alphabet=fb_tables.AA)
+    n, seed = len(names), 3
+    opts = {"data_type": 2, "use_anchors": 0, "sample_path": 1, "sample_seed": seed}
+    on_host = host.Msa(names, seqs, nwk, **opts).align()
+    on_dev = host.Msa(names, seqs, nwk, sample_on_device=1, **opts).align()
+    assert on_host.n_internal == 3 and on_host.alignment_all() == on_dev.alignment_all()
+    top = 0
+    for k in range(3):
+        left, right, _model, band = on_host.node_job(k)
+        mp = on_host.node_model_prob(k)
+        assert mp.n_states == 211
+        top = max(top, int(left.state[1:-1].max()), int(right.state[1:-1].max()))
+        fb = pgm.FullProbability(left, right, mp, band)
+        by_host, _visited = fb.sample_path(host.sample_uniforms(seed, n + k, left.n_sites + right.n_sites - 1))
+        sp = fb.sample_paths(seed, n + k, 1)
+        by_dev = sp.result(0)
+        assert by_host.status == by_dev.status == 0 and sp.summary()["status"][0] == 0
+        for walk in (on_host, on_dev):
+            got = walk.node_result(k)
+            for want in (by_host, by_dev):
+                assert got.status == 0 and np.array_equal(got.cols, want.cols), k
+                assert np.array_equal(got.left_used, want.left_used) and np.array_equal(got.right_used, want.right_used), k
+            assert walk.node_info(k).score == fb.log_fwd == walk.node_fb(k)[0], k
+            assert walk.node_support(k).tobytes() == fb.path_support(by_host.cols).tobytes(), k
+        sp.close()
+        fb.close()
+    assert top >= 20                                             # (an ancestral state entered the root's pair)

@@ -184,6 +184,89 @@ def test_the_predictors_values_are_pinned(pg):
         assert tuple(pgm.fb_counts_predict_bytes(lx, ly, s) for s in (15, 211)) == counts, what
 
 
+def test_the_predictor_with_states_adds_the_table_beyond_211(pg):
+    """pagan_fb_predict_bytes_states: the pinned function's value up to 211 states, beyond that 17/16 of what 8 S^2 exceeds the
+    protein table's 8 * 211^2 by; the codon pair of test_fb_gpu.py (41 x 40 sites) comes out above its table alone."""
+    for (lx, ly, half), fb, _decode, _sample, _counts in PINNED_BYTES[:3]:
+        for S in (1, 15, 211):
+            assert pgm.fb_predict_bytes(lx, ly, None, n_states=S) == fb, (lx, ly, S)
+        for S in (212, 1892):
+            more = 8 * S * S - 8 * 211 * 211
+            assert pgm.fb_predict_bytes(lx, ly, None, n_states=S) == fb + more + more // 16, (lx, ly, S)
+    assert pgm.fb_predict_bytes(41, 40, None, n_states=1892) > 8 * 1892 * 1892 * 17 // 16
+    assert pgm.fb_predict_bytes(41, 40, None, n_states=0) == abi.PAGAN_E_ARG
+    assert pgm.fb_predict_bytes(1, 5, None, n_states=15) < 0
+    assert pgm.lib().pagan_fb_device_bytes(None, None) == abi.PAGAN_E_ARG
+
+
+def test_the_reading_uses_the_table_as_left_state_by_right_state():
+    """4 x 4 protein residues under an asymmetric table with zeros (fb_tables.py): the second reading, held to brute force over
+    every path, takes score[left state, right state].  The pair is made so that the transposed table gives another optimum: the
+    residues at (1, 1) are (a, b) with score[a, b] = 0 < score[b, a], those at (2, 2) the other way round."""
+    import fb_tables
+    prot, prot_z = fb_tables.protein_tables()
+    z = prot_z.score
+    a, b = next((a, b) for a in range(20) for b in range(20) if a != b and z[a, b] == 0 and z[b, a] > 0)
+    leaf_alpha, _ = host.alphabets(2)
+    letter = lambda s: leaf_alpha[s]
+    others = [s for s in range(20) if s not in (a, b)]
+    ls, rs = [a, b, others[0], others[1]], [b, a, others[0], others[1]]
+    left, right = (host.HGraph.leaf("".join(letter(s) for s in q), leaf_alpha).flatten() for q in (ls, rs))
+    assert list(left.state[1:-1]) == ls and list(right.state[1:-1]) == rs
+    flipped = abi.ModelProb(z.T.copy(), prot_z.gap_open, prot_z.gap_ext, prot_z.non_gap)
+    got = {}
+    for name, mp in (("as it is", prot_z), ("transposed", flipped)):
+        ex = pycheck_fb.Exact(left, right, mp)
+        post = ex.posterior()
+        mea = pycheck_mea.Mea(ex, post, 0.5)
+        best, n_paths = pycheck_mea.brute_force(ex, post, 0.5)
+        assert mea.status == 0 and n_paths > 100 and abs(mea.objective - best) <= 1e-12
+        got[name] = (mea, post)
+    (m1, p1), (m2, p2) = got["as it is"], got["transposed"]
+    assert p1[1, 1, M] == 0 and np.isneginf(m1.A[1, 1, M]) and p1[2, 2, M] > 0 and np.isfinite(m1.A[2, 2, M])
+    assert p2[1, 1, M] > 0 and np.isfinite(m2.A[1, 1, M]) and p2[2, 2, M] == 0 and np.isneginf(m2.A[2, 2, M])
+    assert abs(m1.objective - m2.objective) > 1e-6
+    # a fill that looks no entry up at all reaches no other optimum (fb_tables.zeros_bite says why): it is the matrix that differs
+    blind = pycheck_mea.Mea(pycheck_mea.exact_arcs(left, right, prot), p1, 0.5)
+    assert blind.objective == m1.objective and np.isfinite(blind.A[1, 1, M])
+
+
+def test_the_table_builders_conditions_hold(oracle):
+    """tests/fb_tables.py without a device: the tables are asymmetric and have one-sided zeros (the builders assert it), every
+    leaf pair has the width its decode instance needs, the graph and codon pairs build, the host's codon table is the oracle's,
+    and the zeros decide the matrix on the two cheapest zero-table pairs (the wider ones are held to the same condition by
+    test_mea_gpu.py's fixture).  R1024z: a 1,024-entry window would serve wrong states, the 2,048 of the 1,024-thread instance
+    none; the 513-wide pairs would not tell the two apart."""
+    import fb_tables
+    leaves = fb_tables.leaf_pairs()
+    shapes = fb_tables.check_shapes(leaves)
+    assert {v[2] for v in shapes.values()} == {64, 512, 1024}
+    pairs = dict(leaves, **fb_tables.graph_pairs())
+    k = fb_tables.codon_leaf_pair(oracle)
+    assert k.mp.n_states == 1892 and not np.array_equal(k.mp.score, k.mp.score.T)
+    for name in ("Q64z", "G211z"):
+        p = pairs[name]
+        if name == "G211z":
+            ex = pycheck_fb.Exact(*p.args())
+            post = ex.posterior()
+        else:
+            ex = pycheck_mea.exact_arcs(*p.args())
+            lf, _lb, post, _logf = oracle.fb(p.left, p.right, p.mp, band=p.band)
+            assert np.isfinite(lf)
+        mea = pycheck_mea.Mea(ex, post, 0.5)
+        assert mea.status == 0
+        counts = fb_tables.zeros_bite(p, pycheck_mea.exact_arcs(p.left, p.right, p.before, p.band), mea)
+        assert min(counts) >= 1
+        # the objective is NOT what the zeros move, behind a band and on graphs as little as in a full matrix of two sequences
+        blind = pycheck_mea.Mea(pycheck_mea.exact_arcs(p.left, p.right, p.before, p.band), post, 0.5)
+        assert abs(blind.objective - mea.objective) <= fb_tables.bound(mea.objective, mea.visited.shape[0] + 1), name
+    w = fb_tables.wide_zero_pair()
+    assert (w.Lx, w.Ly) == (1024, 1300) and fb_tables.widest_diagonal(w)[0] == 1024
+    assert fb_tables.stale_window_cells(w.Lx, w.Ly, 1024) > 10000 and fb_tables.stale_window_cells(w.Lx, w.Ly, 2048) == 0
+    for name in ("R513z", "Q513z"):
+        assert fb_tables.stale_window_cells(leaves[name].Lx, leaves[name].Ly, 1024) == 0
+
+
 NEW_DP = ["pagan_fb_decode_batch","pagan_fb_decode", "pagan_fb_decoded_summary", "pagan_fb_decoded_visited", "pagan_fb_decoded_result",
           "pagan_fb_decoded_dump", "pagan_fb_decoded_ms", "pagan_fb_debug_decode_route", "pagan_fb_decode_predict_bytes",
           "pagan_fb_decoded_destroy"]

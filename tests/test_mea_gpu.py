@@ -17,10 +17,11 @@ import pytest
 import pagan2_msa_amd as pgm
 from pagan2_msa_amd import abi, host, synth
 
-import fb_testlib
+import fb_tables
 import pycheck_fb
 import pycheck_mea
 import test_fb_exact_gpu as fx
+from fb_tables import widest_diagonal
 from fb_testlib import random_tunnel
 
 pytestmark = pytest.mark.gpu
@@ -69,13 +70,48 @@ def cases(pg, oracle):
         p = fx.Pair(name, gl, gr, mp, band, host.dna_model(BF, 0.2)[0])
         _lf, _lb, opost, _ologf = oracle.fb(gl, gr, mp, band=band)
         out[name] = Case(p, pycheck_mea.exact_arcs(gl, gr, mp, band), opost)
+    # asymmetric tables, tables with zeros, 211 and 1892 states, 512 and 1,024 threads (fb_tables.py): the leaf pairs on the
+    # oracle's posterior, the 71 x 67 graph pairs on the exact reading's
+    leaves = fb_tables.leaf_pairs()
+    fb_tables.check_shapes(leaves)
+    leaves["K1892"] = fb_tables.codon_leaf_pair(oracle)
+    # the root jobs of a four-leaf protein and a four-leaf codon walk: graph against graph, ancestral states (>= 20, > 61)
+    leaves["G211w"], leaves["K1892g"] = fb_tables.walk_root_pair(2), fb_tables.walk_root_pair(3, oracle)
+    for name, p in leaves.items():
+        lf, _lb, opost, _ologf = oracle.fb(p.left, p.right, p.mp, band=p.band)
+        assert np.isfinite(lf), name
+        out[name] = Case(p, pycheck_mea.exact_arcs(p.left, p.right, p.mp, p.band), opost)
+    for name, p in fb_tables.graph_pairs().items():
+        ex = pycheck_fb.Exact(*p.args())
+        assert np.isfinite(ex.log_fwd), name
+        out[name] = Case(p, ex, ex.posterior())
+    for name, c in out.items():
+        if getattr(c.p, "before", None) is not None:             # the zeros decide the result (fb_tables.zeros_bite)
+            counts = fb_tables.zeros_bite(c.p, pycheck_mea.exact_arcs(c.p.left, c.p.right, c.p.before, c.p.band), c.mea(0.5))
+            print("%s: zero entries that a skipped / transposed (-inf, finite) lookup shows, transposed zeros on the path: %s" % (name, counts))
     return out
 
 
-def widest_diagonal(p):
-    inb = fb_testlib.in_band(p.Lx, p.Ly, p.band)
-    i, j = np.nonzero(inb)
-    return int(np.bincount(i + j).max()), p.Lx + p.Ly - 1
+# pair -> (threads of the decode's workgroup, the instance looks the table up (TAB), the table is in LDS): what
+# pagan_fb_decode_batch must launch, asserted against the host-only plan and the table
+INSTANCES = {"R257": (512, False, True), "R512z": (512, True, True), "R513": (1024, False, True), "R513z": (1024, True, True),
+             "Q64z": (64, True, False), "Q257z": (512, True, False), "Q513z": (1024, True, False), "K1892": (64, False, False)}
+
+
+def check_instance(name, p, fb):
+    """the instance from what the library reports: the launch's threads and lookup flag (pagan_fb_decoded_launch), the plan's
+    decode_block and table_in_lds"""
+    block, tab, lds = INSTANCES[name]
+    mw, _nd = widest_diagonal(p)
+    plan = pgm.fb_plan(p.left, p.right, p.band, p.mp.n_states)
+    dec = fb.decode(0.5)
+    threads, looked = dec.launch()
+    dec.close()
+    assert threads == plan["decode_block"] and tab == bool((p.mp.score == 0).any())
+    got = (threads, looked, bool(plan["table_in_lds"]))
+    print("%s: widest diagonal %d, pg_fb_ring_decode<%d, %s> with %d threads, table in %s"
+          % (name, mw, 1024 if got[0] > 512 else 512, "true" if got[1] else "false", got[0], "LDS" if got[2] else "memory"))
+    assert plan["decode_route"] == 1 and got == (block, tab, lds) and block == fb_tables.block_for(mw), (name, got, mw)
 
 
 def check_decode(case, g, fb, schedule, what):
@@ -129,6 +165,13 @@ CASES = [
     ("P6a", "default", 0, None, 0, (0.5,)), ("P6b", "default", 0, None, 0, (0.5,)),
     ("R64", "default", 2, None, 1, (0.5,)), ("R64", "default", 2, "0", 0, (0.5,)),
     ("R40", "default", 2, None, 1, (0.5,)), ("R256", "default", 2, None, 1, (0.5,)),
+    ("R257", "default", 2, None, 1, (0.5,)), ("R512z", "default", 2, None, 1, (0.5,)),
+    ("R513", "default", 2, None, 1, (0.5,)), ("R513z", "default", 2, None, 1, (0.5,)), ("R513z", "default", 2, "0", 0, (0.5,)),
+    ("Q64z", "default", 2, None, 1, (0.5,)), ("Q64z", "default", 2, "0", 0, (0.5,)),
+    ("Q257z", "default", 2, None, 1, (0.5,)), ("Q513z", "default", 2, None, 1, (0.5,)),
+    ("G211", "default", 0, None, 0, (0.5,)), ("G211z", "default", 0, None, 0, (0.5, 0.0, 1.0)),
+    ("K1892", "default", 0, None, 1, (0.5,)),
+    ("G211w", "default", 0, None, 0, (0.5,)), ("K1892g", "default", 0, None, 0, (0.5,)),
 ]
 
 
@@ -152,8 +195,12 @@ def test_decode_against_the_second_reading(pg, cases, monkeypatch, name, env, sw
         assert 128 < mw <= 256 and nd > 512, (mw, nd)
     if name == "P3t":
         assert case.mea(0.5).status == 1
+    if name.startswith("G211"):
+        assert p.mp.n_states == 211 and case.mea(0.5).status == 0
     fb = pgm.FullProbability(*p.args())
     assert fb.schedule == sweep, (name, env, fb.schedule)
+    if name in INSTANCES and ring is None:
+        check_instance(name, p, fb)
     assert np.allclose(fb.posterior(), case.post, rtol=1e-7, atol=1e-12)       # (what the bound rests on)
     for g in gs:
         check_decode(case, g, fb, schedule, "%s after the %s sweeps" % (name, env))
@@ -161,8 +208,9 @@ def test_decode_against_the_second_reading(pg, cases, monkeypatch, name, env, sw
 
 
 def test_ring_and_fill_agree(pg, cases, monkeypatch):
-    """P5t and the 300 x 290 pair on both routes: equal -inf sets, objectives within the bound of one another."""
-    for name in ("P5t", "R64"):
+    """P5t, the 300 x 290 pair, and the zero tables from memory and on 1,024 threads, on both routes: equal -inf sets,
+    objectives within the bound of one another."""
+    for name in ("P5t", "R64", "Q64z", "R513z"):
         p = cases[name].p
         fx.set_env(monkeypatch, "default")
         fb = pgm.FullProbability(*p.args())
@@ -180,6 +228,38 @@ def test_ring_and_fill_agree(pg, cases, monkeypatch):
         for d in (ring, fill):
             d.close()
         fb.close()
+
+
+def test_the_1024_thread_windows_on_a_full_workgroup(pg, monkeypatch):
+    """R1024z: 1,024 x 1,300 cells under the DNA zero table -- every thread of pg_fb_ring_decode<1024, true> has a row, and the
+    row and column windows' live span (the diagonal's width + FB_RG_REFILL + 1 entries at a refill) passes 1,024 entries, which
+    no pair narrower than 769 cells, nor any whose longer side stays below 1,024 + the window's first column, can show
+    (fb_tables.stale_window_cells counts the cells a 1,024-entry window would serve a wrong state: test_mea_cpu.py).  No second
+    reading of 1.3 M cells: the ring against the PAGAN_FB_DECODE_RING=0 fill, which reads no window and whose lookup the 71 x 67
+    and 513-wide cases hold to the reading, within the bound; and the match scores finite exactly where the table's entry is
+    above 0 -- in a full matrix every cell is reached through gaps, so the lookup alone decides."""
+    p = fb_tables.wide_zero_pair()
+    assert (p.Lx, p.Ly) == (1024, 1300) and widest_diagonal(p)[0] == 1024
+    fx.set_env(monkeypatch, "default")
+    fb = pgm.FullProbability(*p.args())
+    monkeypatch.delenv(DECODE_ENV, raising=False)
+    ring = fb.decode(0.5, keep_matrix=True)
+    monkeypatch.setenv(DECODE_ENV, "0")
+    fill = fb.decode(0.5, keep_matrix=True)
+    a, b = ring.summary(), fill.summary()
+    assert (a["schedule"], b["schedule"]) == (1, 0) and a["status"] == b["status"] == 0 and ring.launch() == (1024, True)
+    assert abs(a["objective"] - b["objective"]) <= bound(b["objective"], b["n_steps"] + 1)
+    A, B = ring.matrix(), fill.matrix()
+    entry = fb_tables.entries(p)
+    for name, mat in (("ring", A), ("fill", B)):
+        assert np.array_equal(np.isfinite(mat[1:, 1:, 2]), entry[1:, 1:] > 0), name
+        assert np.isfinite(mat[1:, :, 0]).all() and np.isfinite(mat[:, 1:, 1]).all(), name
+    fin = np.isfinite(B)
+    assert np.array_equal(np.isfinite(A), fin)
+    assert np.all(np.abs(A[fin] - B[fin]) <= bound(B[fin], p.Lx + p.Ly))
+    for d in (ring, fill):
+        d.close()
+    fb.close()
 
 
 def _bytes(d):
@@ -210,6 +290,19 @@ def test_batch_equals_single(pg, cases, monkeypatch):
     assert _bytes(batch[1]) == want and batch[1].result().status == 0
     for b in batch:
         b.close()
+    # the fill and five ring launch keys -- <512, false> at 64 and at 512 threads, <512, true> at 64, <1024, false>, <1024, true>
+    # twice --; the call's order has the pair with the lookup behind the one without at 1,024 threads and in front of it at 64
+    names = ["R513", "Q64z", "R513z", "P1t", "R257", "Q513z", "K1892"]
+    fbs = [pgm.FullProbability(*cases[n].p.args()) for n in names]
+    batch = pgm.decode_batch(fbs, 0.5, keep_matrix=True)
+    assert [b.summary()["schedule"] for b in batch] == [1, 1, 1, 0, 1, 1, 1]
+    assert all(b.summary()["status"] == 0 for b in batch)
+    for n, fb, b in zip(names, fbs, batch):
+        single = fb.decode(0.5, keep_matrix=True)
+        assert _bytes(single) == _bytes(b), n
+        single.close()
+    for x in batch + fbs:
+        x.close()
 
 
 def test_arguments(pg, cases):
@@ -309,3 +402,37 @@ def test_the_walk_decodes_every_node(pg):
     with pytest.raises(pgm.PaganError) as e:
         both.align()
     assert e.value.code == abi.PAGAN_E_ARG
+
+
+@pytest.mark.parametrize("data_type", [2, 3])
+def test_the_walk_decodes_every_node_under_the_large_tables(pg, data_type):
+    """Four protein leaves of ~60 residues, four codon leaves of ~40 codons, posterior_decode=1: every node is the stand-alone
+    FullProbability -> decode chain on node_job(k) and node_model_prob(k) (211 and 1892 states: the table read from memory by
+    the ring at the leaves, by the fill and the trace above them), as test_the_walk_decodes_every_node has it for DNA."""
+    if data_type == 2:
+        names, seqs, nwk = synth.evolve_balanced(4, 60, branch=0.08, sub=0.1, indel_start=0.03, mean_len=3, seed=57, alphabet=fb_tables.AA)
+    else:
+        names, seqs, nwk = fb_tables.evolve_codons(4, 40, seed=58, branch=0.08, sub=0.1, indel_start=0.03, mean_len=2)
+    walk = host.Msa(names, seqs, nwk, posterior_decode=1, decode_gap_weight=0.5, data_type=data_type, use_anchors=0).align()
+    assert walk.n_internal == 3 and walk.data_type == data_type
+    schedules, top = set(), 0
+    for k in range(walk.n_internal):
+        left, right, _model, band = walk.node_job(k)
+        mp = walk.node_model_prob(k)
+        assert mp.n_states == (211 if data_type == 2 else 1892)
+        top = max(top, int(left.state[1:-1].max()), int(right.state[1:-1].max()))
+        fb = pgm.FullProbability(left, right, mp, band)
+        dec = fb.decode(0.5)
+        want, sm = dec.result(), dec.summary()
+        schedules.add(sm["schedule"])
+        got = walk.node_result(k)
+        assert sm["status"] == 0 and got.status == 0 and np.array_equal(got.cols, want.cols), k
+        assert np.array_equal(got.left_used, want.left_used) and np.array_equal(got.right_used, want.right_used), k
+        obj, steps, ms = walk.node_decode(k)
+        assert obj == sm["objective"] and steps == sm["n_steps"] and ms >= 0, k
+        assert walk.node_info(k).score == fb.log_fwd == walk.node_fb(k)[0]
+        assert walk.node_support(k).tobytes() == fb.path_support(want.cols).tobytes(), k
+        dec.close()
+        fb.close()
+    assert schedules == {0, 1}                                   # (the leaf pairs on the ring, the root on the fill)
+    assert top >= (20 if data_type == 2 else 62)                 # (an ancestral state entered the root's pair)

@@ -147,7 +147,7 @@ def _pass_bytes(msa, k, kw):
     """(what the forward/backward pass of node k takes under the mode: the sum the walk cuts by, the node's Viterbi batch)"""
     left, right, _model, band = msa.node_job(k)
     l, r = left.n_sites, right.n_sites
-    need = pgm.fb_predict_bytes(l, r, band)
+    need = pgm.fb_predict_bytes(l, r, band, n_states=msa.node_model_prob(k).n_states)
     if kw.get("posterior_decode"):
         need += pgm.fb_decode_predict_bytes(l, r, band)
     elif kw.get("sample_on_device"):
@@ -192,3 +192,31 @@ def test_a_budget_for_one_node_at_a_time_changes_nothing(pg, cut_tree, mode):
         # the decoder's time is booked at a sub-batch's first node: the cut walk has a sub-batch per leaf-level node, the uncut one
         assert all(tight.node_decode(k)[2] > 0 for k in leaf_level)
         assert sorted(whole.node_decode(k)[2] > 0 for k in leaf_level) == [False, True]
+
+
+def test_a_codon_walk_is_cut_by_its_tables(pg):
+    """Four codon leaves of ~40 codons with full_probability=1: a pair's arena is its score table (8 * 1892^2 B = 28.6 MB of logs)
+    and little else.  Under a budget that holds one leaf-level pass and not two the walk must take the two leaf-level nodes in a
+    sub-batch each -- a one-workgroup pair's sweeps are timed only when it is its call's one pair, so the cut walk books a time at
+    both and the uncut one at neither -- and give the uncut walk's bytes."""
+    import fb_tables
+    names, seqs, nwk = fb_tables.evolve_codons(4, 40, seed=96, branch=0.05, sub=0.08, indel_start=0.01, mean_len=2)
+    kw = {"data_type": 3, "full_probability": 1, "use_anchors": 0}
+    whole = host.Msa(names, seqs, nwk, **kw).align()
+    assert whole.n_internal == 3 and whole.data_type == 3
+    leaf_level = [k for k in range(3) if whole.node_info(k).level == whole.node_info(0).level]
+    assert leaf_level == [0, 1]
+    table = 8 * 1892 * 1892
+    needs = [_pass_bytes(whole, k, kw) for k in range(3)]
+    budget = max(fb + dp for fb, dp in needs) + 1
+    assert all(fb >= table for fb, _dp in needs) and table < budget < 2 * table
+    tight = host.Msa(names, seqs, nwk, device_mem_budget=budget, **kw).align()
+    assert tight.alignment_all() == whole.alignment_all()
+    for k in range(3):
+        a, b = whole.node_result(k), tight.node_result(k)
+        assert a.same_alignment(b) and a.status == b.status == 0, k
+        assert np.float64(whole.node_info(k).score).tobytes() == np.float64(tight.node_info(k).score).tobytes(), k
+        assert np.array(whole.node_fb(k)[:2]).tobytes() == np.array(tight.node_fb(k)[:2]).tobytes(), k
+        assert whole.node_support(k).tobytes() == tight.node_support(k).tobytes(), k
+    print("sweep ms booked: uncut %s, cut %s" % ([whole.node_fb(k)[2] for k in range(3)], [tight.node_fb(k)[2] for k in range(3)]))
+    assert all(tight.node_fb(k)[2] > 0 for k in leaf_level) and not any(whole.node_fb(k)[2] > 0 for k in leaf_level)
